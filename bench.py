@@ -11,6 +11,11 @@ per-GPU batch fixed, global batch 16*N, gradients all-reduced over RCCL inside t
 Rank 0 prints ONE JSON line.  See DESIGN.md "Measurement" for the roofline / cpu_baseline / parity_check definitions.
 `python bench.py --gpus N` without a launcher environment starts the N ranks itself (torch.distributed.run as a child
 process, before this process touches a GPU); it exits non-zero rather than report fewer GPUs than asked for.
+
+A plain run sets up, warms up, times --steps steps and prints the headline line.  Everything else it can measure or check
+(CPU baseline and parity check, side measurements, roofline kernel events, the matrix-pipe tally, host enqueue time,
+per-collective and exposed-communication timing, the peer-copy engine probe, the replica check) runs only with --full.
+--dump-outputs DIR writes what the last timed step computed (losses, and the networks' state after it) as .npy files.
 """
 import argparse
 import json
@@ -138,6 +143,45 @@ def host_cores() -> int:
     return n
 
 
+DUMP_SAMPLE = 1 << 16           # --dump-outputs: elements kept per tensor (larger ones: a fixed, seeded sample)
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_sample(t, name, n=DUMP_SAMPLE):
+    """float32 numpy copy of `t` flattened: all of it, or `n` elements at positions drawn from a generator seeded by `name`
+    (sorted; the same positions in every run)."""
+    import zlib
+    flat = t.detach().reshape(-1)
+    if flat.numel() > n:
+        g = torch.Generator().manual_seed(zlib.crc32(name.encode()))
+        idx = torch.randint(0, flat.numel(), (n,), generator=g).sort().values
+        flat = flat[idx.to(flat.device)]
+    return flat.float().cpu().numpy()
+
+
+def dump_outputs(path, arrays):
+    """arrays: [(name, numpy array)] -> path/<name>.npy; refuses to write more than DUMP_LIMIT_BYTES in all."""
+    import numpy as np
+    total = sum(a.nbytes for _, a in arrays)
+    if total > DUMP_LIMIT_BYTES:
+        raise SystemExit(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES} byte limit")
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays:
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
+def step_outputs(logs, nets):
+    """What a caller of the train step receives from its last call: the losses (float64 scalars, `loss_<key>`) and the networks'
+    state after it (`<net>.<state_dict key>`, float32, sampled by dump_sample)."""
+    import numpy as np
+    out = [(f"loss_{k}", np.asarray(float(v), dtype=np.float64)) for k, v in logs.items()]
+    for tag, net in nets:
+        if net is not None:
+            out += [(f"{tag}.{k}", dump_sample(v, f"{tag}.{k}")) for k, v in net.state_dict().items() if v.is_floating_point()]
+    return out
+
+
 def snapshot_state(G, D, vgg):
     """CPU copies of the three state dicts (taken BEFORE the first GPU step, for the oracle's parity step)."""
     f = lambda m: {k: v.detach().cpu().clone() for k, v in m.state_dict().items()} if m is not None else None
@@ -218,6 +262,8 @@ def bench_infer512(args, device):
             y = G(x)
         torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / args.steps
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, [("sr", dump_sample(y, "sr", 1 << 22))])
     tf = 105.3875 / dt
     bf16 = args.precision == "bf16"
     peak = PEAK_BF16_MFMA_TFLOPS if bf16 else PEAK_F32_MFMA_TFLOPS
@@ -279,6 +325,13 @@ def main():
                          "white-noise HR crops from an untrained Generator's output within ~15 steps: its loss falls to 1e-15 and its "
                          "backward pass then runs on zeros, whatever the batch (measured with 4 rotating batches).  The work of a step "
                          "does not depend on the value, so the default keeps the losses O(0.1 .. 1) for the whole run instead")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: the CPU oracle (cpu_baseline, parity_check), the side measurements, "
+                         "roofline kernel events, the matrix-pipe tally, host enqueue time and, with N > 1, per-collective and exposed-"
+                         "communication timing, the peer-copy engine probe and the replica check.  Off: set up, warm up, time the steps")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one computed to DIR/<name>.npy (rank 0): the losses and the "
+                         "networks' state after it, tensors above %d elements as a fixed, seeded sample" % DUMP_SAMPLE)
     args = ap.parse_args()
 
     under_launcher = "RANK" in os.environ and "MASTER_PORT" in os.environ
@@ -324,7 +377,8 @@ def main():
     lr, hr = batches[0]
     eager_step = trainer.gan_step if args.workload == "gan" else trainer.pretrain_step
     step = eager_step
-    want_cpu = not args.no_cpu_baseline and world == 1
+    full = args.full
+    want_cpu = full and not args.no_cpu_baseline and world == 1
     state0 = snapshot_state(G, D, vgg) if want_cpu else None
     nstep = [0]
 
@@ -336,11 +390,12 @@ def main():
     def run(fn):
         return fn(*next_batch())
 
-    # step 0 (always eager, on batch 0): its losses go to the parity check as host floats, and the matrix-pipe work of one
-    # step is tallied while it runs
-    ops.FLOPS.start()
+    # step 0 (always eager, on batch 0): its losses go to the parity check as host floats, and (--full) the matrix-pipe work of
+    # one step is tallied while it runs
+    if full:
+        ops.FLOPS.start()
     first_log = {k: float(v) for k, v in run(eager_step).items()}
-    flops = ops.FLOPS.stop()
+    flops = ops.FLOPS.stop() if full else None
     use_graph = args.hip_graph and args.workload in ("gan", "pretrain")
     optims = [o for o in (trainer.optim_D, trainer.optim_G) if o is not None]
     dp_on = all(o.buckets.enabled for o in optims)      # world > 1, or PESR_FORCE_DP=1 over a one-rank group
@@ -370,14 +425,14 @@ def main():
         step = trainer.capture_gan_step(lr, hr) if args.workload == "gan" else trainer.capture_pretrain_step(lr, hr)
         run(step)                                   # first replay outside the timed region (graph upload)
         torch.cuda.synchronize()
-    if not use_graph and not args.no_kernel_events:
+    if full and not use_graph and not args.no_kernel_events:
         ops.KERNEL_EVENTS.enable(shape=watch, every=args.event_every)
     for o in optims:
-        o.buckets.measure_exposed = not use_graph
+        o.buckets.measure_exposed = full and not use_graph
     dp_transports = trainer._transports() if dp_on else []
     for t_ in dp_transports:
         t_.collective_times()                      # (drop whatever the warm-up left)
-        t_.time_collectives = not use_graph         # HIP events on the communication stream around every all-reduce of the timed steps
+        t_.time_collectives = full and not use_graph    # HIP events on the communication stream around every all-reduce of the timed steps
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
@@ -390,6 +445,8 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     elapsed = my_elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:    # before anything below runs another step on these networks
+        dump_outputs(args.dump_outputs, step_outputs(logs, (("G", G), ("D", D))))
     exposed = [o.buckets.exposed_ms() for o in optims]
     for o in optims:
         o.buckets.measure_exposed = False
@@ -399,28 +456,30 @@ def main():
         coll += t_.collective_times()
     # which engine moved the peer copies (only the peer-memory transport has any), and: are the replicas still identical?
     peer_engine = None
-    if dp_transports and dp_transports[0].name == "peer-copy" and world > 1:
+    if full and dp_transports and dp_transports[0].name == "peer-copy" and world > 1:
         peer_engine = dp_transports[0].copy_engine_probe(optims[-1].flat.flat_g)
     replica_check = None
-    if world > 1:
+    if full and world > 1:
         sums = torch.stack([o.flat.flat_p.double().sum() for o in optims] + [o.flat.flat_p.double().abs().sum() for o in optims])
         lo, hi = sums.clone(), sums.clone()
         dist.all_reduce(lo, op=dist.ReduceOp.MIN)
         dist.all_reduce(hi, op=dist.ReduceOp.MAX)
         replica_check = {"identical": bool(torch.equal(lo, hi)), "what": "sum and abs-sum (float64) of every optimizer's flat parameter buffer after the "
                          "timed steps: MIN over ranks == MAX over ranks (replicas that received different gradient sums diverge)"}
-    if use_graph and not args.no_kernel_events:     # events cannot be read back from inside a graph: two eager steps for them
+    if full and use_graph and not args.no_kernel_events:     # events cannot be read back from inside a graph: two eager steps for them
         ops.KERNEL_EVENTS.enable(shape=watch)
         for _ in range(2):
             run(eager_step)
     kern = ops.KERNEL_EVENTS.drain()
-    # host cost of ONE eager step: enqueue three steps on an idle GPU without waiting for it (python + launches only)
-    torch.cuda.synchronize()
-    th = time.perf_counter()
-    for _ in range(3):
-        run(eager_step)
-    host_enqueue_ms = 1e3 * (time.perf_counter() - th) / 3
-    torch.cuda.synchronize()
+    host_enqueue_ms = None
+    if full:
+        # host cost of ONE eager step: enqueue three steps on an idle GPU without waiting for it (python + launches only)
+        torch.cuda.synchronize()
+        th = time.perf_counter()
+        for _ in range(3):
+            run(eager_step)
+        host_enqueue_ms = 1e3 * (time.perf_counter() - th) / 3
+        torch.cuda.synchronize()
     per_rank = None
     if world > 1:
         t = torch.tensor([elapsed], device=device, dtype=torch.float64)
@@ -428,9 +487,10 @@ def main():
         dist.all_gather(gathered, t)
         per_rank = [float(g.item()) for g in gathered]
         elapsed = max(per_rank)
-        hh = torch.tensor([host_enqueue_ms, host_done], device=device, dtype=torch.float64)
-        dist.all_reduce(hh, op=dist.ReduceOp.MAX)
-        host_enqueue_ms, host_done = float(hh[0]), float(hh[1])
+        if full:
+            hh = torch.tensor([host_enqueue_ms, host_done], device=device, dtype=torch.float64)
+            dist.all_reduce(hh, op=dist.ReduceOp.MAX)
+            host_enqueue_ms, host_done = float(hh[0]), float(hh[1])
     if rank != 0:
         from pesr_amd import comm
         comm.close_transports()
@@ -465,12 +525,6 @@ def main():
         # ALGORITHMIC flops / time / peak: may exceed 1 because the Winograd kernels issue 1/2 .. 2/3 of them
         "step_frac_of_mfma_peak": round(value / world * flop_patch / (peak * 1e12), 4),
         "mfma_peak_tflops": peak,
-        # flops the step's kernels really ISSUE on the matrix pipe (tallied per launch during step 0) / time / peak: the honest
-        # whole-step hardware fraction
-        "step_issued_frac": round(flops["issued"] / (1e3 * elapsed / args.steps) / 1e9 / peak, 4),
-        "step_flops": {"algorithmic_tflop_counted": round(flops["algorithmic"] / 1e12, 3), "issued_tflop": round(flops["issued"] / 1e12, 3),
-                       "by_kernel_family_tflop": {k: [round(a / 1e12, 3), round(b / 1e12, 3)] for k, (a, b) in flops["by_kernel_family"].items()},
-                       "note": "per family: [algorithmic, issued on the matrix pipe]; counted from the launches of step 0"},
         "losses": {k: float(v) for k, v in logs.items()},
         "losses_step0": first_log,
         "batches_rotated": len(batches), "lr": args.lr,
@@ -479,13 +533,23 @@ def main():
                     "on zeros); the work of a step does not depend on the value.  `--lr 5e-5` reproduces the reference's flag (same box, "
                     "same build: 216.2 vs 216.9 patches/s, DESIGN.md 6)") if args.lr != 5e-5 else None,
         "hip_graph": bool(use_graph),
-        # host side: time to ENQUEUE one eager step (python + launches, GPU idle at start, no waiting) and the moment the host
-        # had enqueued all K timed steps relative to their completion (max over ranks)
-        "host_enqueue_ms": round(host_enqueue_ms, 2),
-        "host_enqueue_frac_of_step": round(host_enqueue_ms / (1e3 * elapsed / args.steps), 3),
-        "host_done_ms_before_gpu": round(1e3 * (my_elapsed - host_done), 1),
         "force_dp": os.environ.get("PESR_FORCE_DP") == "1",
+        "full": full,
     }
+    if full:
+        out.update({
+            # flops the step's kernels really ISSUE on the matrix pipe (tallied per launch during step 0) / time / peak: the honest
+            # whole-step hardware fraction
+            "step_issued_frac": round(flops["issued"] / (1e3 * elapsed / args.steps) / 1e9 / peak, 4),
+            "step_flops": {"algorithmic_tflop_counted": round(flops["algorithmic"] / 1e12, 3), "issued_tflop": round(flops["issued"] / 1e12, 3),
+                           "by_kernel_family_tflop": {k: [round(a / 1e12, 3), round(b / 1e12, 3)] for k, (a, b) in flops["by_kernel_family"].items()},
+                           "note": "per family: [algorithmic, issued on the matrix pipe]; counted from the launches of step 0"},
+            # host side: time to ENQUEUE one eager step (python + launches, GPU idle at start, no waiting) and the moment the host
+            # had enqueued all K timed steps relative to their completion (max over ranks)
+            "host_enqueue_ms": round(host_enqueue_ms, 2),
+            "host_enqueue_frac_of_step": round(host_enqueue_ms / (1e3 * elapsed / args.steps), 3),
+            "host_done_ms_before_gpu": round(1e3 * (my_elapsed - host_done), 1),
+        })
     if share_gpu:
         out["test_hook"] = f"{world} ranks time-sharing cuda:0 over {backend}: exercises the multi-rank code path, NOT a measurement"
     if dp_info is not None:
@@ -547,7 +611,7 @@ def main():
             out["parity_check"]["oracle_one_ulp_noise_floor"] = floor
             if inconclusive:
                 out["parity_check"]["verdict"] = f"inconclusive: 3 x the oracle's own one-ulp noise floor exceeds the cap {BF16_TOL_CAP}"
-    if args.workload == "gan" and world == 1 and not args.no_side and not bf16 and not split:
+    if full and args.workload == "gan" and world == 1 and not args.no_side and not bf16 and not split:
         out["side"] = side_measurements(args, trainer, G, batches, device)
     print(json.dumps(out), flush=True)
     if dist.is_initialized():

@@ -4,6 +4,7 @@
 #   scripts/full_rehearsal.sh <ranks> <peer|torch> [extra bench.py flags]
 # Writes gpurun_out/full<N>_<transport>.{out,err,json}.
 N=${1:-8}; TR=${2:-peer}; shift; shift
+set -- --full "$@"      # the collectives, peer-copy engine and replica figures printed below are --full fields
 cd "$(dirname "$0")/.."
 mkdir -p gpurun_out
 export PESR_DP_BACKEND=gloo PESR_DP_SHARE_GPU=1 HSA_ENABLE_IPC_MODE_LEGACY=0 PESR_DUMP_STACKS_AFTER=${PESR_DUMP_STACKS_AFTER:-500} PESR_DP_TRANSPORT=$TR

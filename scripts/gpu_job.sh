@@ -16,13 +16,13 @@ R=$PWD; O=$R/gpurun_out/${TAG:-job}; mkdir -p $O
 job=$1; shift
 case $job in
   tests)  cd $R; timeout 1500 python3 -m pytest tests -m gpu -x -q "$@" > $O/tests.log 2>&1; echo "tests rc=$?"; tail -5 $O/tests.log ;;
-  bench)  n=$1; shift; cd /tmp; timeout 900 python3 $R/bench.py "$@" 2> $O/$n.err | tail -1 > $O/$n.json; cut -c1-400 $O/$n.json; echo; tail -3 $O/$n.err ;;
+  bench)  n=$1; shift; cd /tmp; timeout 900 python3 $R/bench.py --full "$@" 2> $O/$n.err | tail -1 > $O/$n.json; cut -c1-400 $O/$n.json; echo; tail -3 $O/$n.err ;;
   dp1)    n=$1; shift; cd /tmp
           PESR_FORCE_DP=1 timeout 600 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node 1 --master-addr 127.0.0.1 --master-port 29521 \
-              $R/bench.py --gpus 1 "$@" 2> $O/$n.err | tail -1 > $O/$n.json; cut -c1-400 $O/$n.json; echo; tail -3 $O/$n.err ;;
-  stats)  cd /tmp; timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o run -- python3 $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-side "$@" > $O/stats.log 2>&1
+              $R/bench.py --full --gpus 1 "$@" 2> $O/$n.err | tail -1 > $O/$n.json; cut -c1-400 $O/$n.json; echo; tail -3 $O/$n.err ;;
+  stats)  cd /tmp; timeout 400 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -o run -- python3 $R/bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-side "$@" > $O/stats.log 2>&1
           cp $(find $O/stats -name "*kernel_stats.csv") $O/kernel_stats.csv 2>/dev/null; rm -rf $O/stats; head -25 $O/kernel_stats.csv ;;
-  trace)  cd /tmp; timeout 400 rocprofv3 --kernel-trace --output-format csv -d $O/single -o run -- python3 $R/bench.py --steps 3 --warmup 2 --no-cpu-baseline --no-kernel-events --no-side > $O/single.log 2>&1
+  trace)  cd /tmp; timeout 400 rocprofv3 --kernel-trace --output-format csv -d $O/single -o run -- python3 $R/bench.py --full --steps 3 --warmup 2 --no-cpu-baseline --no-kernel-events --no-side > $O/single.log 2>&1
           cd $R; python3 scripts/summarize_profiles.py trace $(find $O/single -name "*kernel_trace.csv") 6 $O/kernel_trace_by_grid.csv 2
           rm -rf $O/single; head -40 $O/kernel_trace_by_grid.csv ;;
   pmc)    n=$1; s=$2; cd /tmp

@@ -147,36 +147,23 @@ def test_product_focal_loss_matches_reference_values_and_q4_gradient():
 
 
 def test_seeded_construction_matches_the_reference_when_it_is_available():
-    """Build container only (skipped where /root/reference does not exist): torch.manual_seed(s) + construction gives
-    bit-identical parameters and the same state_dict key order as the reference's modules."""
-    import subprocess, sys
-    import pytest
-    if not os.path.isdir("/root/reference/model"):
-        pytest.skip("reference not present (GPU box)")
-    code = r'''
-import sys, types, torch
-sys.path.insert(0, %r)
-from model import Generator, Discriminator
-torch.manual_seed(3)
-G = Generator({'depth': 2, 'num_channels': 16, 'res_scale': 0.1}); D = Discriminator({'patch_size': 8, 'spectral_norm': False})
-mine = [(k, v.clone()) for k, v in list(G.state_dict().items()) + list(D.state_dict().items())]
-for k in [k for k in list(sys.modules) if k == 'model' or k.startswith('model.')]:
-    del sys.modules[k]
-sys.path.remove(%r)
-tv, tvm = types.ModuleType('torchvision'), types.ModuleType('torchvision.models')
-tvm.vgg19 = lambda pretrained=False, **k: None; tv.models = tvm
-sys.modules['torchvision'] = tv; sys.modules['torchvision.models'] = tvm
-sys.path.insert(0, '/root/reference')
-import model as R
-torch.manual_seed(3)
-Gr = R.Generator({'depth': 2, 'num_channels': 16, 'res_scale': 0.1}); Dr = R.Discriminator({'patch_size': 8, 'spectral_norm': False})
-ref = list(Gr.state_dict().items()) + list(Dr.state_dict().items())
-assert [k for k, _ in mine] == [k for k, _ in ref]
-assert all(torch.equal(a, b) for (_, a), (_, b) in zip(mine, ref))
-print("identical")
-''' % (ROOT, ROOT)
-    out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300)
-    assert out.returncode == 0 and "identical" in out.stdout, out.stderr[-2000:]
+    """torch.manual_seed(s) + construction gives bit-identical parameters and the same state_dict key order as the
+    reference's modules: against golden GV13 (tests/golden/make_golden_seeded.py) - the reference's own
+    construction under the same seed, every entry's dtype, shape and sha256, the small ones' values too."""
+    import hashlib
+    from model import Discriminator, Generator
+    g = load_golden("gv13_seeded_construction")
+    with torch.random.fork_rng(devices=[]):
+        torch.manual_seed(int(g["seed"]))
+        G = Generator({'depth': 2, 'num_channels': 16, 'res_scale': 0.1}); D = Discriminator({'patch_size': 8, 'spectral_norm': False})
+    mine = [(f"G|{k}", v) for k, v in G.state_dict().items()] + [(f"D|{k}", v) for k, v in D.state_dict().items()]
+    assert [k for k, _ in mine] == list(g["keys"])
+    for (k, v), dt, shape, digest in zip(mine, g["dtypes"], g["shapes"], g["sha256"]):
+        a = v.detach().contiguous().numpy()
+        assert str(a.dtype) == dt and list(a.shape) == [s for s in shape if s >= 0], k
+        if k in g.files:
+            assert np.array_equal(a, g[k]), k
+        assert hashlib.sha256(a.tobytes()).hexdigest() == digest, k
 
 
 def test_lr_schedule_order_matches_reference_under_its_pinned_torch():
@@ -294,6 +281,37 @@ def test_bench_refuses_stale_pmc_summary(tmp_path, monkeypatch):
     (src / "conv3x3_wino4.hip").write_text("// kernel v2\n")               # the kernel changed after the counters were taken
     by, name, why = B.k1_hbm_traffic_bytes("conv3x3_wino4_kernel")
     assert by is None and "stale" in why
+
+
+def test_bench_dump_outputs_are_seeded_and_bounded(tmp_path):
+    """bench.py --dump-outputs: the losses as float64 scalars, every floating state_dict entry of the networks as float32 (tensors
+    above DUMP_SAMPLE elements at the same seeded positions in every call), and a refusal above the 64 MB limit."""
+    from model import Discriminator, Generator
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    B = importlib.util.module_from_spec(spec); spec.loader.exec_module(B)
+    with torch.random.fork_rng(devices=[]):
+        torch.manual_seed(0)
+        opt = {"patch_size": 8, "num_channels": 16, "depth": 2, "res_scale": 0.1, "spectral_norm": False}
+        G, D = Generator(opt), Discriminator(opt)
+    logs = {"l1": torch.tensor(0.5), "d": torch.tensor(0.25)}
+    a = B.step_outputs(logs, (("G", G), ("D", D)))
+    b = B.step_outputs(logs, (("G", G), ("D", D)))
+    names = [n for n, _ in a]
+    assert names[:2] == ["loss_l1", "loss_d"] and float(a[0][1]) == 0.5 and a[0][1].dtype == np.float64
+    assert {"G.embed.weight", "D.classifier.0.weight", "D.features.1.1.running_var"} <= set(names)
+    assert all(np.array_equal(x, y) for (_, x), (_, y) in zip(a, b))
+    sd = {**{f"G.{k}": v for k, v in G.state_dict().items()}, **{f"D.{k}": v for k, v in D.state_dict().items()}}
+    for n, arr in a[2:]:
+        assert arr.dtype == np.float32 and arr.size == min(sd[n].numel(), B.DUMP_SAMPLE), n
+        if sd[n].numel() <= B.DUMP_SAMPLE:
+            assert np.array_equal(arr, sd[n].reshape(-1).numpy()), n
+        else:                                                              # a sample: every value is one of the tensor's
+            assert np.isin(arr, sd[n].reshape(-1).numpy()).all(), n
+    B.dump_outputs(str(tmp_path / "out"), a)
+    assert sorted(os.listdir(tmp_path / "out")) == sorted(n + ".npy" for n in names)
+    assert np.array_equal(np.load(tmp_path / "out" / "G.embed.weight.npy"), dict(a)["G.embed.weight"])
+    with pytest.raises(SystemExit):
+        B.dump_outputs(str(tmp_path / "big"), [("x", np.zeros(B.DUMP_LIMIT_BYTES // 4 + 1, np.float32))])
 
 
 def test_comm_torch_group_single_rank_gloo():

@@ -335,6 +335,40 @@ print("ENTRY_OK")
     assert any(not torch.equal(sdg[k], sd[k]) for k in sd)                  # it trained
 
 
+def test_bench_py_plain_full_and_dumped_outputs(tmp_path):
+    """bench.py at a toy size, in fresh interpreters: a plain run times exactly --steps steps and reports the headline only;
+    --dump-outputs gives the same arrays in a second plain run and in a --full run (which adds the CPU oracle's parity check,
+    kernel events and the matrix-pipe tally without changing what the steps compute)."""
+    import json, subprocess, sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    toy = ["--gpus", "1", "--steps", "3", "--warmup", "2", "--batch", "4", "--patch_size", "16", "--num_channels", "64", "--num_blocks", "2"]
+
+    def bench(tag, *extra):
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py")] + toy + ["--dump-outputs", str(tmp_path / tag)] + list(extra),
+                           capture_output=True, text=True, timeout=600, cwd=str(tmp_path))
+        assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+        return json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+
+    a, b, f = bench("a"), bench("b"), bench("f", "--full", "--no-side")
+    for d in (a, b, f):
+        assert d["steps"] == 3 and d["warmup"] == 2 and d["unit"] == "patches/s" and d["higher_is_better"] is True and d["dtype"] == "f32"
+        assert abs(d["value"] - 4 * 1e3 / d["ms_per_step"]) < 1e-3 * d["value"]
+    for k in ("cpu_baseline", "parity_check", "roofline", "step_flops", "host_enqueue_ms", "side"):
+        assert k not in a, k
+    assert f["parity_check"]["ok"] and "cpu_baseline" in f and "step_flops" in f and "host_enqueue_ms" in f
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(os.listdir(tmp_path / "b")) == sorted(os.listdir(tmp_path / "f"))
+    assert {"loss_d.npy", "loss_g.npy", "G.body.0.body.0.weight.npy", "D.classifier.0.weight.npy"} <= set(names)
+    assert sum(os.path.getsize(tmp_path / "a" / n) for n in names) <= 64 << 20
+    for n in names:
+        x = np.load(tmp_path / "a" / n)
+        assert x.dtype in (np.float32, np.float64) and np.isfinite(x).all(), n
+        for other in ("b", "f"):
+            y = np.load(tmp_path / other / n)
+            np.testing.assert_allclose(y, x, rtol=1e-6, atol=1e-6 * max(1.0, float(np.abs(x).max(initial=0.0))), err_msg=f"{other}/{n}")
+    assert float(np.load(tmp_path / "a" / "loss_d.npy")) == a["losses"]["d"]
+
+
 def test_config5_large_tiles_64bit_indexing():
     """BASELINE config 5: G forward on 4 x 512x512 LR tiles (256 ch x 32 blocks).  The 256ch @ 2048^2 x 4 tensor has
     4.29e9 elements (> 2^31), so this exercises the 64-bit offsets.  Size-independent property: every output pixel
