@@ -1,7 +1,8 @@
 """Minimal data harness so that train.py / test.py run (the reference's data.py - PNG->npy cache, DIV2K/PIRM layout -
 is OUT OF SCOPE; benchmarks use synthetic crops).  Two datasets with the reference's sample contract
 (reference data.py:79-126): `(lr, hr)` float CHW tensors holding raw 0..255 values, hr = 4x lr, 8-way flip/transpose
-augmentation, random LR-aligned crops.
+augmentation, random LR-aligned crops.  hr = scale x lr with scale 4 by default (the reference's only setting) and 2 or 3 as
+an extension (docs/modes.md section 4e).
 """
 import glob
 import os
@@ -11,7 +12,7 @@ import numpy as np
 import torch
 from torch.utils.data import Dataset
 
-SCALE = 4
+SCALE = 4           # the default scale
 
 
 def augment(lr, hr, idx):
@@ -32,8 +33,8 @@ def to_tensor(a):
 class SyntheticSRDataset(Dataset):
     """DIV2K-shaped random crops: iid integers 0..255.  Deterministic per index."""
 
-    def __init__(self, length, patch_size, seed=1234):
-        self.length, self.ps, self.seed = length, patch_size, seed
+    def __init__(self, length, patch_size, seed=1234, scale=SCALE):
+        self.length, self.ps, self.seed, self.scale = length, patch_size, seed, scale
 
     def __len__(self):
         return self.length
@@ -41,21 +42,22 @@ class SyntheticSRDataset(Dataset):
     def __getitem__(self, i):
         g = torch.Generator().manual_seed(self.seed + i)
         lr = torch.randint(0, 256, (3, self.ps, self.ps), generator=g).float()
-        hr = torch.randint(0, 256, (3, SCALE * self.ps, SCALE * self.ps), generator=g).float()
+        hr = torch.randint(0, 256, (3, self.scale * self.ps, self.scale * self.ps), generator=g).float()
         return lr, hr
 
 
 class FolderSRDataset(Dataset):
-    """<root>/LR/*.png with matching <root>/HR/*.png (PIL); random crop + augmentation when patch_size is given."""
+    """<root>/LR/*.png with matching <root>/HR/*.png (PIL); random crop + augmentation when patch_size is given.  Every HR image
+    must be exactly scale x its LR image (ValueError naming the file otherwise)."""
 
-    def __init__(self, root, patch_size=None, num_repeats=1, is_aug=False, fixed_length=None):
+    def __init__(self, root, patch_size=None, num_repeats=1, is_aug=False, fixed_length=None, scale=SCALE):
         from PIL import Image
         self._open = Image.open
         self.lr_paths = sorted(glob.glob(os.path.join(root, "LR", "*.png")))
         if fixed_length:
             self.lr_paths = self.lr_paths[:fixed_length]
         self.hr_paths = [os.path.join(root, "HR", os.path.basename(p)) for p in self.lr_paths]
-        self.ps, self.rep, self.aug = patch_size, num_repeats, is_aug
+        self.ps, self.rep, self.aug, self.scale = patch_size, num_repeats, is_aug, scale
 
     def __len__(self):
         return len(self.lr_paths) * self.rep
@@ -64,11 +66,15 @@ class FolderSRDataset(Dataset):
         i %= len(self.lr_paths)
         lr = np.asarray(self._open(self.lr_paths[i]).convert("RGB"))
         hr = np.asarray(self._open(self.hr_paths[i]).convert("RGB"))
+        s = self.scale
+        if hr.shape[:2] != (s * lr.shape[0], s * lr.shape[1]):
+            raise ValueError(f"{self.hr_paths[i]}: HR image is {hr.shape[1]}x{hr.shape[0]}, expected {s} x the LR image "
+                             f"{lr.shape[1]}x{lr.shape[0]} = {s * lr.shape[1]}x{s * lr.shape[0]} (scale {s})")
         if self.ps:
             y = random.randint(0, lr.shape[0] - self.ps)
             x = random.randint(0, lr.shape[1] - self.ps)
             lr = lr[y:y + self.ps, x:x + self.ps]
-            hr = hr[SCALE * y:SCALE * (y + self.ps), SCALE * x:SCALE * (x + self.ps)]
+            hr = hr[s * y:s * (y + self.ps), s * x:s * (x + self.ps)]
         if self.aug:
             lr, hr = augment(lr, hr, random.randint(0, 7))
         return to_tensor(lr), to_tensor(hr)

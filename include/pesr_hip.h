@@ -207,6 +207,13 @@ int pesr_meanshift_bwd(const float* dy, const float* x, const float* w, float* d
 int pesr_pixel_shuffle_fwd(const float* x, float* y, int N, int H, int W, int C, void* stream);
 int pesr_pixel_shuffle_bwd(const float* dy, float* dx, int N, int H, int W, int C, void* stream);
 
+/* ---- nn.PixelShuffle(r) standalone for r = 2 or 3 (the x2 / x3 Upsampler), bit-exact indexing --- */
+/* x [N][H][W][r*r*C] -> y [N][r*H][r*W][C]:  y[n][r*h+i][r*w+j][c] = x[n][h][w][c*r*r + i*r + j];  bwd is the inverse
+ * (dy [N][r*H][r*W][C] -> dx [N][H][W][r*r*C]).  Any C >= 1; r outside {2, 3} -> PESR_EINVAL.  r = 2 gives the bits of
+ * pesr_pixel_shuffle_fwd / _bwd.  64-bit offsets; no workspace. */
+int pesr_pixel_shuffle_r_fwd(const float* x, float* y, int N, int H, int W, int C, int r, void* stream);
+int pesr_pixel_shuffle_r_bwd(const float* dy, float* dx, int N, int H, int W, int C, int r, void* stream);
+
 /* out = (ref > 0 ? alpha*g : slope*alpha*g) + add : ReLU (slope 0) / LeakyReLU backward (+ residual fan-in);
  * ref/add may be NULL */
 int pesr_relu_mask(const float* g, const float* ref, const float* add, float* out, long n, float alpha, float slope,

@@ -147,6 +147,12 @@ PESR_API int pesr_pixel_shuffle_fwd(const float* x, float* y, int N, int H, int 
 PESR_API int pesr_pixel_shuffle_bwd(const float* dy, float* dx, int N, int H, int W, int C, void* stream) {
     return pesr_pixel_shuffle_launch(dy, dx, N, H, W, C, 1, (hipStream_t)stream);
 }
+PESR_API int pesr_pixel_shuffle_r_fwd(const float* x, float* y, int N, int H, int W, int C, int r, void* stream) {
+    return pesr_pixel_shuffle_r_launch(x, y, N, H, W, C, r, 0, (hipStream_t)stream);
+}
+PESR_API int pesr_pixel_shuffle_r_bwd(const float* dy, float* dx, int N, int H, int W, int C, int r, void* stream) {
+    return pesr_pixel_shuffle_r_launch(dy, dx, N, H, W, C, r, 1, (hipStream_t)stream);
+}
 PESR_API int pesr_relu_mask(const float* g, const float* ref, const float* add, float* out, long n, float alpha, float slope,
                             void* stream) {
     return pesr_relu_mask_launch(g, ref, add, out, n, alpha, slope, (hipStream_t)stream);

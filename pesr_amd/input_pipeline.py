@@ -12,18 +12,19 @@ import torch
 
 from . import _lib
 
-SCALE = 4
+SCALE = 4           # the default scale (2 and 3 are extensions, docs/modes.md section 4e)
 
 
 class GpuPatchSampler:
-    def __init__(self, lr_images: Sequence[np.ndarray], hr_images: Sequence[np.ndarray], device: torch.device):
+    def __init__(self, lr_images: Sequence[np.ndarray], hr_images: Sequence[np.ndarray], device: torch.device, scale: int = SCALE):
         assert len(lr_images) == len(hr_images) and len(lr_images) > 0
-        self.device = device
+        assert scale in (2, 3, 4), scale
+        self.device, self.scale = device, scale
         self.n = len(lr_images)
         self.lr_shapes = [im.shape for im in lr_images]
         for l, h in zip(lr_images, hr_images):
             assert l.dtype == np.uint8 and h.dtype == np.uint8 and l.shape[2] == 3
-            assert h.shape[0] == SCALE * l.shape[0] and h.shape[1] == SCALE * l.shape[1], "HR must be 4x the LR image"
+            assert h.shape[0] == scale * l.shape[0] and h.shape[1] == scale * l.shape[1], f"HR must be {scale}x the LR image"
         self.lr_pool, self.lr_off = self._pool(lr_images)
         self.hr_pool, self.hr_off = self._pool(hr_images)
 
@@ -56,18 +57,18 @@ class GpuPatchSampler:
         return picks
 
     def assemble(self, picks: List[tuple], patch: int, nhwc: bool = False):
-        """-> (lr [B,3,P,P], hr [B,3,4P,4P]) fp32 on the device (logical NCHW; channels_last memory when nhwc)."""
-        B = len(picks)
+        """-> (lr [B,3,P,P], hr [B,3,sP,sP]) fp32 on the device, s = self.scale (logical NCHW; channels_last memory when nhwc)."""
+        B, S = len(picks), self.scale
         dl = np.empty((B, 3), dtype=np.int64)
         dh = np.empty((B, 3), dtype=np.int64)
         for b, (i, y, x, aug) in enumerate(picks):
             w = self.lr_shapes[i][1]
             dl[b] = (self.lr_off[i], w | (y << 32), x | (aug << 32))
-            dh[b] = (self.hr_off[i], (SCALE * w) | ((SCALE * y) << 32), (SCALE * x) | (aug << 32))
+            dh[b] = (self.hr_off[i], (S * w) | ((S * y) << 32), (S * x) | (aug << 32))
         L = _lib.lib()
         s = torch.cuda.current_stream(self.device).cuda_stream
         outs = []
-        for pool, d, P in ((self.lr_pool, dl, patch), (self.hr_pool, dh, SCALE * patch)):
+        for pool, d, P in ((self.lr_pool, dl, patch), (self.hr_pool, dh, S * patch)):
             desc = torch.from_numpy(d).to(self.device)
             out = torch.empty((B, P, P, 3) if nhwc else (B, 3, P, P), dtype=torch.float32, device=self.device)
             _lib.check(L.pesr_crop_augment(pool.data_ptr(), desc.data_ptr(), out.data_ptr(), B, P, int(nhwc), s), "pesr_crop_augment")

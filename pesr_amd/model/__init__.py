@@ -7,8 +7,8 @@ import torch.nn.functional as F
 
 from .basic import BasicBlock, Conv, MeanShift, PixelShuffle, ResBlock, Upsampler
 from .focal_loss import FocalLoss
-from .pesr import Discriminator, Generator
+from .pesr import Discriminator, Generator, scale_of_state_dict
 from .vgg import VGG
 
 __all__ = ["Generator", "Discriminator", "VGG", "FocalLoss", "Conv", "MeanShift", "BasicBlock", "ResBlock",
-           "Upsampler", "PixelShuffle", "nn", "torch", "F"]
+           "Upsampler", "PixelShuffle", "scale_of_state_dict", "nn", "torch", "F"]

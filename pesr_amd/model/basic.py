@@ -100,15 +100,19 @@ class MeanShift(nn.Module):
 
 
 class PixelShuffle(nn.Module):
-    """nn.PixelShuffle(2) as a standalone kernel (Upsampler fuses it into the conv epilogue instead)."""
+    """nn.PixelShuffle(r), r = 2 or 3, as a standalone kernel (the x4 / x2 Upsampler fuses r = 2 into the conv epilogue
+    instead; the x3 Upsampler runs this module's r = 3 kernel)."""
 
     def __init__(self, upscale_factor=2):
         super().__init__()
-        assert upscale_factor == 2
+        if upscale_factor not in (2, 3):
+            raise ValueError(f"PixelShuffle: upscale_factor {upscale_factor}; the HIP kernels implement 2 and 3")
         self.upscale_factor = upscale_factor
 
     def forward(self, x):
-        return nchw(_PixelShuffleFn.apply(nhwc(x)))
+        if self.upscale_factor == 2:
+            return nchw(_PixelShuffleFn.apply(nhwc(x)))
+        return nchw(_PixelShuffleRFn.apply(nhwc(x), self.upscale_factor))
 
 
 class _PixelShuffleFn(torch.autograd.Function):
@@ -119,6 +123,19 @@ class _PixelShuffleFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gy):
         return ops.pixel_shuffle_bwd(gy.contiguous())
+
+
+class _PixelShuffleRFn(torch.autograd.Function):
+    """NHWC [N,H,W,r*r*C] -> [N,r*H,r*W,C] on pixel_shuffle_r.hip; the backward is the same kernel's inverse."""
+
+    @staticmethod
+    def forward(ctx, x, r):
+        ctx.r = r
+        return ops.pixel_shuffle_r_fwd(x.contiguous(), r)
+
+    @staticmethod
+    def backward(ctx, gy):
+        return ops.pixel_shuffle_r_bwd(gy.contiguous(), ctx.r), None
 
 
 def _act_slope(act):
@@ -243,19 +260,44 @@ class ResBlock(nn.Module):
         return nchw(PF.ScaleAddFn.apply(r, h, float(self.res_scale)))
 
 
-class Upsampler(nn.Sequential):
-    """conv C->4C, PixelShuffle(2), conv C->4C, PixelShuffle(2), conv C->3 (reference model/basic.py:54-60).
-    Both PixelShuffles are fused into the conv epilogue (forward) and the dgrad/wgrad loaders (backward)."""
+SCALES = (2, 3, 4)
 
-    def __init__(self, n_feats):
-        super().__init__(Conv(n_feats, 4 * n_feats, 3), PixelShuffle(2), Conv(n_feats, 4 * n_feats, 3), PixelShuffle(2),
-                         Conv(n_feats, 3, 3))
-        self[0].packed = PF.PackedConvWeights(ps=True)
-        self[2].packed = PF.PackedConvWeights(ps=True)
+
+class Upsampler(nn.Sequential):
+    """The EDSR-style sub-pixel upsampler (reference model/basic.py:54-60 is the x4 one).
+      x4: conv C->4C, PixelShuffle(2), conv C->4C, PixelShuffle(2), conv C->3 - both PixelShuffles fused into the conv
+          epilogue (forward) and the dgrad/wgrad loaders (backward);
+      x2: conv C->4C, PixelShuffle(2), conv C->3 - the same fused r = 2 store and loaders;
+      x3: conv C->9C, PixelShuffle(3), conv C->3 - a plain conv, the standalone r = 3 kernel on its NHWC output, then the C->3
+          conv (docs/modes.md section 4e).
+    The convs are constructed (and draw their initialisation) in module order."""
+
+    def __init__(self, n_feats, scale=4):
+        if scale not in SCALES:
+            raise ValueError(f"Upsampler: scale {scale}; supported scales are {SCALES}")
+        if scale == 4:
+            super().__init__(Conv(n_feats, 4 * n_feats, 3), PixelShuffle(2), Conv(n_feats, 4 * n_feats, 3), PixelShuffle(2),
+                             Conv(n_feats, 3, 3))
+            self[0].packed = PF.PackedConvWeights(ps=True)
+            self[2].packed = PF.PackedConvWeights(ps=True)
+        else:
+            super().__init__(Conv(n_feats, scale * scale * n_feats, 3), PixelShuffle(scale), Conv(n_feats, 3, 3))
+            if scale == 2:
+                self[0].packed = PF.PackedConvWeights(ps=True)
+        self.scale = scale
 
     def forward(self, x):
+        if self.scale != 4:
+            return self._forward_x2_x3(x)
         h = nhwc(x)
         h = PF.conv3x3(h, self[0].weight, self[0].bias, self[0].packed)   # -> [N, 2H, 2W, C]
         h = PF.conv3x3(h, self[2].weight, self[2].bias, self[2].packed)   # -> [N, 4H, 4W, C]
         h = PF.conv3x3(h, self[4].weight, self[4].bias, self[4].packed)   # -> [N, 4H, 4W, 3]
+        return nchw(h)
+
+    def _forward_x2_x3(self, x):
+        h = PF.conv3x3(nhwc(x), self[0].weight, self[0].bias, self[0].packed)  # x2: -> [N, 2H, 2W, C] (fused); x3: -> [N, H, W, 9C]
+        if self.scale == 3:
+            h = _PixelShuffleRFn.apply(h, 3)                                 # -> [N, 3H, 3W, C]
+        h = PF.conv3x3(h, self[2].weight, self[2].bias, self[2].packed)     # -> [N, sH, sW, 3]
         return nchw(h)

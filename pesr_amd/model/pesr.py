@@ -1,4 +1,4 @@
-"""Generator (EDSR-style trunk + x4 sub-pixel upsampler) and Discriminator (strided VGG-style stack + 2 Linear layers)
+"""Generator (EDSR-style trunk + sub-pixel upsampler: x4 as in the reference, x2 / x3 as an extension) and Discriminator (strided VGG-style stack + 2 Linear layers)
 on the HIP kernels, API- and checkpoint-compatible with reference model/pesr.py: same `opt` keys, same attribute names
 (`sub_mean, embed, body, upsample, add_mean` / `features, classifier`), hence the same state_dict keys and shapes, and the
 same order of parameter-initialisation RNG draws.
@@ -8,7 +8,7 @@ import torch.nn as nn
 
 from .. import functional as PF
 from .. import ops
-from .basic import BasicBlock, Conv, MeanShift, ResBlock, Upsampler, nchw, nhwc
+from .basic import SCALES, BasicBlock, Conv, MeanShift, ResBlock, Upsampler, nchw, nhwc
 
 _DIV2K_MEAN = (0.4488, 0.4371, 0.4040)      # reference model/pesr.py:13
 _UNIT_STD = (1.0, 1.0, 1.0)
@@ -27,17 +27,35 @@ def discriminator_plan(first_width=64, stages=7):
     return plan
 
 
+def scale_of_state_dict(sd):
+    """-> 2, 3 or 4: the upscaling factor of a Generator state_dict, read from its upsampler (Upsampler's table of keys and
+    shapes); ValueError for anything else."""
+    prefix = "module." if "module.upsample.0.weight" in sd else ""
+    w0 = sd.get(prefix + "upsample.0.weight")
+    if w0 is None or w0.dim() != 4:
+        raise ValueError("not a Generator state_dict: no upsample.0.weight")
+    if prefix + "upsample.4.weight" in sd:
+        return 4
+    ratio, rem = divmod(w0.shape[0], w0.shape[1])
+    if rem == 0 and ratio in (4, 9) and prefix + "upsample.2.weight" in sd and sd[prefix + "upsample.2.weight"].shape[0] == 3:
+        return 2 if ratio == 4 else 3
+    raise ValueError(f"upsampler of unknown scale: upsample.0.weight {tuple(w0.shape)}")
+
+
 class Generator(nn.Module):
     def __init__(self, opt):
         super().__init__()
         width, depth, res_scale = opt['num_channels'], opt['depth'], opt['res_scale']
+        scale = opt.get('scale', 4)        # an extension: the reference's Generator is x4 only (docs/modes.md section 4e)
+        if scale not in SCALES:
+            raise ValueError(f"Generator: scale {scale}; supported scales are {SCALES}")
         # The reference builds the trunk before everything else (RNG order) but registers it third (state_dict order).
         trunk = [ResBlock(width, 3, act=nn.ReLU(True), res_scale=res_scale) for _ in range(depth)]
         trunk.append(Conv(width, width, 3))
         self.sub_mean = MeanShift(255, _DIV2K_MEAN, _UNIT_STD)
         self.embed = Conv(3, width, 3)
         self.body = nn.Sequential(*trunk)
-        self.upsample = Upsampler(width)
+        self.upsample = Upsampler(width, scale)
         self.add_mean = MeanShift(255, _DIV2K_MEAN, _UNIT_STD, 1)
 
     def forward(self, x):
@@ -62,7 +80,7 @@ class Discriminator(nn.Module):
         self.features = nn.Sequential(*blocks)
         # the last block emits NCHW-contiguous so that .view(B, -1) has the reference's column order (c, y, x)
         self.features[-1].flatten_output = True
-        side = (opt['patch_size'] * 4) // 16                 # four stride-2 stages on the HR patch
+        side = (opt['patch_size'] * opt.get('scale', 4)) // 16   # four stride-2 stages on the HR patch (scale x the LR patch)
         self.classifier = nn.Sequential(nn.Linear(512 * side * side, 1024), lrelu, nn.Linear(1024, 1))
 
     def forward_features(self, x):

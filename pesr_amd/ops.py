@@ -729,6 +729,29 @@ def pixel_shuffle_bwd(dy: torch.Tensor) -> torch.Tensor:
     return dx
 
 
+def pixel_shuffle_r_fwd(x: torch.Tensor, r: int) -> torch.Tensor:
+    """nn.PixelShuffle(r), r in {2, 3}, NHWC: x [N,H,W,r*r*C] -> y [N,r*H,r*W,C] (torch's channel order)."""
+    _chk(x, "pixel_shuffle_r_fwd.x")
+    N, H, W, Crr = x.shape
+    if r not in (2, 3) or Crr % (r * r):
+        raise _lib.PesrHipError(f"pixel_shuffle_r_fwd: r = {r} with {Crr} channels (r must be 2 or 3, channels a multiple of r*r)")
+    C = Crr // (r * r)
+    y = torch.empty((N, r * H, r * W, C), dtype=torch.float32, device=x.device)
+    _lib.check(_lib.lib().pesr_pixel_shuffle_r_fwd(_p(x), _p(y), N, H, W, C, r, _stream()), f"pesr_pixel_shuffle_r_fwd[r={r}]")
+    return y
+
+
+def pixel_shuffle_r_bwd(dy: torch.Tensor, r: int) -> torch.Tensor:
+    """Its backward (nn.PixelUnshuffle(r)): dy [N,r*H,r*W,C] -> dx [N,H,W,r*r*C]."""
+    _chk(dy, "pixel_shuffle_r_bwd.dy")
+    N, HR, WR, C = dy.shape
+    if r not in (2, 3) or HR % r or WR % r:
+        raise _lib.PesrHipError(f"pixel_shuffle_r_bwd: r = {r} with a {HR}x{WR} gradient (r must be 2 or 3 and divide both sizes)")
+    dx = torch.empty((N, HR // r, WR // r, r * r * C), dtype=torch.float32, device=dy.device)
+    _lib.check(_lib.lib().pesr_pixel_shuffle_r_bwd(_p(dy), _p(dx), N, HR // r, WR // r, C, r, _stream()), f"pesr_pixel_shuffle_r_bwd[r={r}]")
+    return dx
+
+
 def relu_mask(g: torch.Tensor, ref: Optional[torch.Tensor] = None, add: Optional[torch.Tensor] = None,
               alpha: float = 1.0, slope: float = 0.0) -> torch.Tensor:
     _chk(g, "relu_mask.g")

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
-"""x4 SR inference entry point (counterpart of reference test.py): perceptual model, optional PSNR model with x8
+"""SR inference entry point (counterpart of reference test.py): perceptual model, optional PSNR model with x8
 self-ensemble, image-space blend `alpha*out + (1-alpha)*out_psnr`, PNG output.  Same flags as the reference
-(test.py:13-33); device-agnostic plumbing; the Generator itself runs on the MI355X kernels.
+(test.py:13-33) plus --precision and --scale; device-agnostic plumbing; the Generator itself runs on the MI355X kernels.
 """
 import argparse
 import glob
@@ -27,14 +27,37 @@ _FLAGS = [
 
 
 def build_parser():
-    parser = argparse.ArgumentParser(description="x4 super-resolution of a folder of LR images")
+    parser = argparse.ArgumentParser(description="x4 (or x2 / x3) super-resolution of a folder of LR images")
     for name, typ, default, text in _FLAGS:
         parser.add_argument("--" + name, type=typ, default=default, help=text)
     # an addition (not a reference flag): the optional bf16-operand mode of the build, DESIGN.md section 4c
     parser.add_argument("--precision", type=str, default="fp32", choices=["fp32", "bf16", "split-bf16"],
                         help="bf16: the generator's 3x3 convs round their operands to bf16 (fp32 accumulation and tensors): ~3x faster, "
                              "pixel values differ from the fp32 result by <= 1 grey level on a small fraction of pixels")
+    # an addition (not a reference flag): the upscaling factor of the checkpoints, docs/modes.md section 4e
+    parser.add_argument("--scale", type=int, default=4, choices=[2, 3, 4],
+                        help="upscaling factor of the generator checkpoints (4: the reference's; 2 / 3: EDSR-style upsamplers)")
     return parser
+
+
+def check_checkpoint_scale(sd, scale, path):
+    """A checkpoint whose upsampler belongs to another scale than --scale: SystemExit naming both (instead of load_state_dict's
+    size-mismatch dump)."""
+    from pesr_amd.model import scale_of_state_dict
+    try:
+        found = scale_of_state_dict(sd)
+    except ValueError as e:
+        raise SystemExit(f"test.py: {path}: {e}")
+    if found != scale:
+        raise SystemExit(f"test.py: {path} is a x{found} generator, but --scale is {scale}; pass --scale {found}")
+    return sd
+
+
+def load_generator(opt, path, scale):
+    from model import Generator
+    model = Generator(dict(opt, scale=scale))
+    model.load_state_dict(check_checkpoint_scale(torch.load(path, map_location="cpu"), scale, path))
+    return model
 
 
 # the three generators of the 8-element dihedral group, in the reference's order (test.py:58-60), as tensor ops
@@ -80,22 +103,19 @@ def _write_png(path, img):
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
-    from model import Generator
+    if args.scale != 4 and args.precision != "fp32":
+        raise SystemExit(f"test.py: --precision {args.precision} is checked for --scale 4 only; use --precision fp32 with --scale {args.scale}")
     if args.precision != "fp32":
         from pesr_amd import ops as _ops
         _ops.set_precision(args.precision)
     device = default_device()
     lr_paths = sorted(glob.glob(os.path.join("data/origin/test/", args.dataset, "LR", "*.png")))
     opt = {"num_channels": args.num_channels, "depth": args.num_blocks, "res_scale": args.res_scale}
-    model = Generator(opt)
-    model.load_state_dict(torch.load(args.perceptual_model, map_location="cpu"))
-    model = model.to(device)
+    model = load_generator(opt, args.perceptual_model, args.scale).to(device)
     print("Number of parameters:", sum(p.nelement() for p in model.parameters()))
     model_psnr = None
     if args.alpha != 1:
-        model_psnr = Generator(opt)
-        model_psnr.load_state_dict(torch.load(args.psnr_model, map_location="cpu"))
-        model_psnr = model_psnr.to(device)
+        model_psnr = load_generator(opt, args.psnr_model, args.scale).to(device)
     save_path = os.path.join(args.save_path, args.dataset)
     os.makedirs(save_path, exist_ok=True)
     with torch.no_grad():

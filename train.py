@@ -25,7 +25,8 @@ def str2bool(x):
 
 def build_parser():
     p = argparse.ArgumentParser(description="PIRM 2018")
-    p.add_argument("--scale", type=int, default=4)
+    p.add_argument("--scale", type=int, default=4,
+                   help="interpolation scale: 4 (the reference's), or 2 / 3 (an extension: EDSR-style upsamplers, docs/modes.md section 4e)")
     p.add_argument("--train_dataset", type=str, default="DIV2K")
     p.add_argument("--valid_dataset", type=str, default="PIRM")
     p.add_argument("--num_valids", type=int, default=10)
@@ -86,12 +87,14 @@ def make_loaders(args, rank, world, need_train=True):
     from data import FolderSRDataset, SyntheticSRDataset
     train_set = None
     if args.synthetic:
-        train_set = SyntheticSRDataset(args.synthetic, args.patch_size)
-        val_set = SyntheticSRDataset(min(args.num_valids, 2), args.patch_size, seed=99)
+        train_set = SyntheticSRDataset(args.synthetic, args.patch_size, scale=args.scale)
+        val_set = SyntheticSRDataset(min(args.num_valids, 2), args.patch_size, seed=99, scale=args.scale)
     else:
         if need_train:      # (the GPU input pipeline replaces the host training loader altogether)
-            train_set = FolderSRDataset(os.path.join("data/origin/train", args.train_dataset), args.patch_size, args.num_repeats, True)
-        val_set = FolderSRDataset(os.path.join("data/origin/valid", args.valid_dataset), None, 1, False, fixed_length=10)
+            train_set = FolderSRDataset(os.path.join("data/origin/train", args.train_dataset), args.patch_size, args.num_repeats, True,
+                                        scale=args.scale)
+        val_set = FolderSRDataset(os.path.join("data/origin/valid", args.valid_dataset), None, 1, False, fixed_length=10,
+                                  scale=args.scale)
     sampler = train_loader = None
     if train_set is not None:
         sampler = DistributedSampler(train_set, world, rank, shuffle=True, drop_last=True) if world > 1 else None
@@ -144,7 +147,7 @@ def make_gpu_loader(args, rank, world, device):
     lr_paths = sorted(glob.glob(os.path.join(root, "LR", "*.png")))
     lrs = [np.asarray(Image.open(p).convert("RGB")) for p in lr_paths]
     hrs = [np.asarray(Image.open(os.path.join(root, "HR", os.path.basename(p))).convert("RGB")) for p in lr_paths]
-    return GpuLoader(GpuPatchSampler(lrs, hrs, device), args.batch_size // world, args.patch_size, len(lrs), args.num_repeats,
+    return GpuLoader(GpuPatchSampler(lrs, hrs, device, scale=args.scale), args.batch_size // world, args.patch_size, len(lrs), args.num_repeats,
                      rank, world)
 
 
@@ -199,9 +202,18 @@ def check_limits(args, world):
     """Shape limits of the HIP path, checked up front with a clear message instead of a PESR_EINVAL deep inside a step."""
     if args.batch_size % world:
         raise SystemExit(f"train.py: --batch_size {args.batch_size} must be a multiple of the {world} ranks")
-    if args.phase != "pretrain" and args.patch_size % 4:
+    if args.scale not in (2, 3, 4):
+        raise SystemExit(f"train.py: --scale {args.scale} is not supported; the upsamplers are x2, x3 and x4")
+    if args.scale != 4 and args.precision != "fp32":
+        raise SystemExit(f"train.py: --precision {args.precision} is checked for --scale 4 only; use --precision fp32 with --scale "
+                         f"{args.scale}")
+    if args.phase != "pretrain" and args.scale == 4 and args.patch_size % 4:
         raise SystemExit("train.py: the GAN phase needs --patch_size % 4 == 0 (HR patches must survive four stride-2 stages and "
                          "VGG's four 2x2 max-pools, which this implementation does for even sizes only)")
+    if args.phase != "pretrain" and (args.patch_size * args.scale) % 16:
+        raise SystemExit(f"train.py: the GAN phase needs (--patch_size * --scale) % 16 == 0, here {args.patch_size} * {args.scale} = "
+                         f"{args.patch_size * args.scale} (HR patches must survive four stride-2 stages and VGG's four 2x2 max-pools, "
+                         "which this implementation does for even sizes only)")
 
 
 def main(argv=None):
@@ -240,7 +252,7 @@ def main(argv=None):
     if gpu_pipe:
         train_loader = sampler = make_gpu_loader(args, rank, world, device)      # (it has set_epoch like a DistributedSampler)
     opt = {"patch_size": args.patch_size, "num_channels": args.num_channels, "depth": args.num_blocks,
-           "res_scale": args.res_scale, "spectral_norm": args.spectral_norm}
+           "res_scale": args.res_scale, "spectral_norm": args.spectral_norm, "scale": args.scale}
     G = Generator(opt)
     if args.pretrained_model:
         G.load_state_dict(torch.load(args.pretrained_model, map_location="cpu"))
