@@ -2,7 +2,7 @@
 is OUT OF SCOPE; benchmarks use synthetic crops).  Two datasets with the reference's sample contract
 (reference data.py:79-126): `(lr, hr)` float CHW tensors holding raw 0..255 values, hr = 4x lr, 8-way flip/transpose
 augmentation, random LR-aligned crops.  hr = scale x lr with scale 4 by default (the reference's only setting) and 2 or 3 as
-an extension (docs/modes.md section 4e).
+an extension (docs/modes.md section 4e).  FolderSRDataset(lr_from_hr=callable) builds its LR images from HR/ alone (section 4f).
 """
 import glob
 import os
@@ -48,24 +48,44 @@ class SyntheticSRDataset(Dataset):
 
 class FolderSRDataset(Dataset):
     """<root>/LR/*.png with matching <root>/HR/*.png (PIL); random crop + augmentation when patch_size is given.  Every HR image
-    must be exactly scale x its LR image (ValueError naming the file otherwise)."""
+    must be exactly scale x its LR image (ValueError naming the file otherwise).
+    With a callable `lr_from_hr(hr uint8 HWC array) -> lr uint8 HWC array`, LR/ is not consulted: the file list comes from
+    HR/*.png, every HR image is cropped at the top-left to multiples of `scale` and its LR image is made ONCE, here, and kept in
+    host memory (HR is still read per item).  The dataset holds no GPU code: the caller supplies the resize (train.py: the device
+    bicubic of docs/modes.md section 4f, called in the parent process before the loader's workers fork)."""
 
-    def __init__(self, root, patch_size=None, num_repeats=1, is_aug=False, fixed_length=None, scale=SCALE):
+    def __init__(self, root, patch_size=None, num_repeats=1, is_aug=False, fixed_length=None, scale=SCALE, lr_from_hr=None):
         from PIL import Image
         self._open = Image.open
+        self.ps, self.rep, self.aug, self.scale = patch_size, num_repeats, is_aug, scale
+        self.lr_images = None
+        if lr_from_hr is not None:
+            self.hr_paths = sorted(glob.glob(os.path.join(root, "HR", "*.png")))
+            if fixed_length:
+                self.hr_paths = self.hr_paths[:fixed_length]
+            self.lr_paths = self.hr_paths                     # (one entry per sample; never opened)
+            self.lr_images = [np.ascontiguousarray(lr_from_hr(self._read_hr(p))) for p in self.hr_paths]
+            return
         self.lr_paths = sorted(glob.glob(os.path.join(root, "LR", "*.png")))
         if fixed_length:
             self.lr_paths = self.lr_paths[:fixed_length]
         self.hr_paths = [os.path.join(root, "HR", os.path.basename(p)) for p in self.lr_paths]
-        self.ps, self.rep, self.aug, self.scale = patch_size, num_repeats, is_aug, scale
+
+    def _read_hr(self, path):
+        hr = np.asarray(self._open(path).convert("RGB"))
+        s = self.scale
+        return np.ascontiguousarray(hr[:hr.shape[0] - hr.shape[0] % s, :hr.shape[1] - hr.shape[1] % s])
 
     def __len__(self):
         return len(self.lr_paths) * self.rep
 
     def __getitem__(self, i):
         i %= len(self.lr_paths)
-        lr = np.asarray(self._open(self.lr_paths[i]).convert("RGB"))
-        hr = np.asarray(self._open(self.hr_paths[i]).convert("RGB"))
+        if self.lr_images is not None:
+            lr, hr = self.lr_images[i], self._read_hr(self.hr_paths[i])
+        else:
+            lr = np.asarray(self._open(self.lr_paths[i]).convert("RGB"))
+            hr = np.asarray(self._open(self.hr_paths[i]).convert("RGB"))
         s = self.scale
         if hr.shape[:2] != (s * lr.shape[0], s * lr.shape[1]):
             raise ValueError(f"{self.hr_paths[i]}: HR image is {hr.shape[1]}x{hr.shape[0]}, expected {s} x the LR image "

@@ -290,6 +290,19 @@ int pesr_mse_fwd_bwd(const float* a, const float* b, float* grad, float* out1, l
  * transpose, applied transpose -> vflip -> hflip as the reference).  out: [B][3][P][P] fp32 (nhwc = 0) or [B][P][P][3]. */
 int pesr_crop_augment(const unsigned char* pool, const long long* desc, float* out, int B, int P, int nhwc, void* stream);
 
+/* ---- bicubic resize of uint8 HWC images by s in {2, 3, 4}: MATLAB's imresize for uint8 input (docs/modes.md section 4f) ------- */
+/* One pass along one axis (0 = height, 1 = width) over n_images images of a device-resident pool.  Descriptor: n_images rows of
+ * 4 int64 {source byte offset in src, destination byte offset in dst, H, W}, H and W being the size of the pass's INPUT image; the
+ * output is H/s (up = 0) or s*H (up = 1) rows of W pixels for axis 0, H rows of W/s or s*W pixels for axis 1.  desc_host and
+ * desc_dev hold the same rows: the host copy is checked and sizes the grid, the kernel reads the device copy.  weights_host: 16
+ * doubles on the host, copied by value - up = 0: the 8 / 11 / 16 tap weights in ascending tap order; up = 1: [s][4], one row per
+ * output phase (pesr_amd/resize.py resize_weights); the rest ignored.  float64 accumulation in ascending tap order without fused
+ * multiply-add, clamp, round half up: bit-identical to the float64 host restatement.  A full resize is axis 0 into an
+ * intermediate pool, then axis 1.  PESR_EINVAL (nothing launched): s outside {2, 3, 4}, H or W < 1, the pass's axis length not a
+ * multiple of s when up = 0, a negative offset.  64-bit offsets; no workspace. */
+int pesr_imresize_u8_pass(const unsigned char* src, unsigned char* dst, const long long* desc_host, const long long* desc_dev,
+                          int n_images, int axis, int s, int up, const double* weights_host, void* stream);
+
 /* ---- validation PSNR on the Y channel (reference utils.py:32-41 compute_PSNR), one image pair [1][3][H][W] ------- */
 /* a_nhwc / b_nhwc: the tensor is stored [H][W][3] instead of [3][H][W].  out2 (device doubles): {mse, psnr dB}; all
  * arithmetic in double on integer-valued terms -> bit-identical to the reference's numpy path.  workspace >= 2 KiB. */

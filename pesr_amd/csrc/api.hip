@@ -331,6 +331,11 @@ PESR_API int pesr_crop_augment(const unsigned char* pool, const long long* desc,
     return pesr_crop_augment_launch(pool, desc, out, B, P, nhwc, (hipStream_t)stream);
 }
 
+PESR_API int pesr_imresize_u8_pass(const unsigned char* src, unsigned char* dst, const long long* desc_host, const long long* desc_dev,
+                                   int n_images, int axis, int s, int up, const double* weights_host, void* stream) {
+    return pesr_imresize_u8_pass_launch(src, dst, desc_host, desc_dev, n_images, axis, s, up, weights_host, (hipStream_t)stream);
+}
+
 PESR_API int pesr_psnr_y(const float* a, const float* b, double* out2, int H, int W, int a_nhwc, int b_nhwc, void* workspace,
                          size_t ws_bytes, void* stream) {
     return pesr_psnr_y_launch(a, b, out2, H, W, a_nhwc, b_nhwc, workspace, ws_bytes, (hipStream_t)stream);

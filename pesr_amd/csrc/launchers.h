@@ -174,5 +174,9 @@ int pesr_spectral_norm_bwd_launch(const float* G, const float* w_hat, const floa
 
 int pesr_crop_augment_launch(const unsigned char* pool, const long long* desc, float* out, int B, int P, int nhwc, hipStream_t stream);
 
+// bicubic resize of a pool of uint8 HWC images, one pass along one axis (resize.hip)
+int pesr_imresize_u8_pass_launch(const unsigned char* src, unsigned char* dst, const long long* desc_host, const long long* desc_dev,
+                                 int n_images, int axis, int s, int up, const double* weights_host, hipStream_t stream);
+
 int pesr_psnr_y_launch(const float* a, const float* b, double* out2, int H, int W, int a_nhwc, int b_nhwc, void* ws, size_t ws_bytes,
                        hipStream_t stream);

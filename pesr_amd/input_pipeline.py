@@ -28,6 +28,23 @@ class GpuPatchSampler:
         self.lr_pool, self.lr_off = self._pool(lr_images)
         self.hr_pool, self.hr_off = self._pool(hr_images)
 
+    @classmethod
+    def from_hr(cls, hr_images: Sequence[np.ndarray], device: torch.device, scale: int = SCALE):
+        """A sampler from HR images alone: each is mod-cropped to multiples of `scale`, the HR pool is uploaded once and the LR pool
+        is made from it on the device (pesr_amd.resize: MATLAB's bicubic imresize, docs/modes.md section 4f) in two launches.
+        From there on it is the sampler the constructor would build from (LR, HR)."""
+        from .resize import imresize_pool_u8, modcrop
+        assert len(hr_images) > 0 and scale in (2, 3, 4), scale
+        self = cls.__new__(cls)
+        self.device, self.scale, self.n = device, scale, len(hr_images)
+        hrs = [modcrop(im, scale) for im in hr_images]
+        for h in hrs:
+            assert h.dtype == np.uint8 and h.ndim == 3 and h.shape[2] == 3 and h.shape[0] >= scale and h.shape[1] >= scale
+        self.hr_pool, self.hr_off = self._pool(hrs)
+        self.lr_pool, self.lr_off, lr_hw = imresize_pool_u8(self.hr_pool, self.hr_off, [h.shape[:2] for h in hrs], scale, up=False)
+        self.lr_shapes = [(h, w, 3) for h, w in lr_hw]
+        return self
+
     def _pool(self, images):
         offs, total = [], 0
         for im in images:

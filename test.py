@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """SR inference entry point (counterpart of reference test.py): perceptual model, optional PSNR model with x8
 self-ensemble, image-space blend `alpha*out + (1-alpha)*out_psnr`, PNG output.  Same flags as the reference
-(test.py:13-33) plus --precision and --scale; device-agnostic plumbing; the Generator itself runs on the MI355X kernels.
+(test.py:13-33) plus --precision, --scale and --from_hr (a test set that ships HR images only: LR made on the device, PSNR-Y of the
+result and of the bicubic baseline printed); device-agnostic plumbing; the Generator itself runs on the MI355X kernels.
 """
 import argparse
 import glob
@@ -10,12 +11,12 @@ import os
 import numpy as np
 import torch
 
-from utils import default_device, imgs_to_tensors, tensors_to_imgs
+from utils import compute_PSNR, default_device, imgs_to_tensors, tensors_to_imgs
 
 
 # (flag, type, default, help) - the reference's flags and defaults (reference test.py:15-33)
 _FLAGS = [
-    ("dataset", str, "Set5", "folder under data/origin/test/ with an LR/ sub-folder of PNGs"),
+    ("dataset", str, "Set5", "folder under data/origin/test/ with an LR/ sub-folder of PNGs (HR/ with --from_hr true)"),
     ("perceptual_model", str, "check_point/PESR/train/PERC_model.pt", "GAN-phase generator checkpoint"),
     ("psnr_model", str, "check_point/PESR/pretrain/PSNR_model.pt", "L1-pretrained generator checkpoint (used when alpha != 1)"),
     ("num_channels", int, 256, "generator width"),
@@ -37,6 +38,10 @@ def build_parser():
     # an addition (not a reference flag): the upscaling factor of the checkpoints, docs/modes.md section 4e
     parser.add_argument("--scale", type=int, default=4, choices=[2, 3, 4],
                         help="upscaling factor of the generator checkpoints (4: the reference's; 2 / 3: EDSR-style upsamplers)")
+    # an addition (not a reference flag): a test set that ships HR images only, docs/modes.md section 4f
+    parser.add_argument("--from_hr", type=lambda x: str(x).lower() == "true", default=False,
+                        help="read data/origin/test/<dataset>/HR/*.png instead of LR/: crop each to multiples of --scale, make its LR image on "
+                             "the GPU by MATLAB-style bicubic resize, and print PSNR-Y of the result and of the bicubic baseline against HR")
     return parser
 
 
@@ -101,6 +106,16 @@ def _write_png(path, img):
     Image.fromarray(img).save(path)
 
 
+def lr_from_hr(hr_img, scale, device):
+    """--from_hr: uint8 HWC HR array -> (LR, mod-cropped HR, bicubic x`scale` of the LR) as [1,3,H,W] float tensors on the device;
+    both resizes run there (pesr_amd.resize, docs/modes.md section 4f)."""
+    from pesr_amd.resize import imresize_u8, modcrop
+    hr = torch.from_numpy(np.array(modcrop(hr_img, scale))).to(device)
+    lr = imresize_u8(hr, scale, up=False)
+    bic = imresize_u8(lr, scale, up=True)
+    return tuple(t.permute(2, 0, 1)[None].float().contiguous() for t in (lr, hr, bic))
+
+
 def main(argv=None):
     args = build_parser().parse_args(argv)
     if args.scale != 4 and args.precision != "fp32":
@@ -109,7 +124,7 @@ def main(argv=None):
         from pesr_amd import ops as _ops
         _ops.set_precision(args.precision)
     device = default_device()
-    lr_paths = sorted(glob.glob(os.path.join("data/origin/test/", args.dataset, "LR", "*.png")))
+    lr_paths = sorted(glob.glob(os.path.join("data/origin/test/", args.dataset, "HR" if args.from_hr else "LR", "*.png")))
     opt = {"num_channels": args.num_channels, "depth": args.num_blocks, "res_scale": args.res_scale}
     model = load_generator(opt, args.perceptual_model, args.scale).to(device)
     print("Number of parameters:", sum(p.nelement() for p in model.parameters()))
@@ -118,15 +133,26 @@ def main(argv=None):
         model_psnr = load_generator(opt, args.psnr_model, args.scale).to(device)
     save_path = os.path.join(args.save_path, args.dataset)
     os.makedirs(save_path, exist_ok=True)
+    psnrs = []
     with torch.no_grad():
         for i, lr_path in enumerate(lr_paths):
-            [inp] = imgs_to_tensors([_read_png(lr_path)], device)
+            if args.from_hr:
+                inp, hr, bic = lr_from_hr(_read_png(lr_path), args.scale, device)
+            else:
+                [inp] = imgs_to_tensors([_read_png(lr_path)], device)
             out = model(inp)
             if model_psnr is not None:
                 out = args.alpha * out + (1 - args.alpha) * x8_forward(inp, model_psnr)
             [img] = tensors_to_imgs([out])
             _write_png(os.path.join(save_path, os.path.basename(lr_path)), img)
+            if args.from_hr:
+                # the PSNR of what was SAVED: the uint8 image back on the device (compute_PSNR rounds the same way itself)
+                [sr] = imgs_to_tensors([img], device)
+                psnrs.append((compute_PSNR(sr, hr), compute_PSNR(bic, hr)))
+                print("%s: PSNR-Y %.10f dB, bicubic %.10f dB" % ((os.path.basename(lr_path),) + psnrs[-1]))
             print("Tested %d img(s)" % (i + 1))
+    if args.from_hr and psnrs:
+        print("Mean PSNR-Y %.10f dB, bicubic %.10f dB" % (float(np.mean([p[0] for p in psnrs])), float(np.mean([p[1] for p in psnrs]))))
     print("Finish")
 
 

@@ -80,21 +80,32 @@ def build_parser():
                         "multiply (hi / lo operand split): 4e-6 of the output maximum, inside the fp32 kernels' own tolerances")
     p.add_argument("--gpu_pipeline", type=str2bool, default=False,
                    help="keep the uint8 training images in HBM and crop/augment on the GPU (pesr_amd.input_pipeline)")
+    p.add_argument("--lr_from_hr", type=str2bool, default=False,
+                   help="build the training and validation sets from their HR/ folders alone: every HR image is cropped to multiples "
+                        "of --scale and its LR image is made on the GPU by MATLAB-style bicubic resize (docs/modes.md section 4f)")
     return p
 
 
-def make_loaders(args, rank, world, need_train=True):
+def device_lr_from_hr(scale, device):
+    """The callable FolderSRDataset(lr_from_hr=...) wants, on the device resize: uint8 HWC array -> uint8 HWC array."""
+    from pesr_amd.resize import imresize_u8
+    return lambda hr: imresize_u8(torch.from_numpy(np.array(hr)).to(device), scale, up=False).cpu().numpy()
+
+
+def make_loaders(args, rank, world, need_train=True, device=None):
     from data import FolderSRDataset, SyntheticSRDataset
     train_set = None
+    # (the LR images are made here, in the parent process, before any loader worker is forked)
+    from_hr = device_lr_from_hr(args.scale, device) if args.lr_from_hr and not args.synthetic else None
     if args.synthetic:
         train_set = SyntheticSRDataset(args.synthetic, args.patch_size, scale=args.scale)
         val_set = SyntheticSRDataset(min(args.num_valids, 2), args.patch_size, seed=99, scale=args.scale)
     else:
         if need_train:      # (the GPU input pipeline replaces the host training loader altogether)
             train_set = FolderSRDataset(os.path.join("data/origin/train", args.train_dataset), args.patch_size, args.num_repeats, True,
-                                        scale=args.scale)
+                                        scale=args.scale, lr_from_hr=from_hr)
         val_set = FolderSRDataset(os.path.join("data/origin/valid", args.valid_dataset), None, 1, False, fixed_length=10,
-                                  scale=args.scale)
+                                  scale=args.scale, lr_from_hr=from_hr)
     sampler = train_loader = None
     if train_set is not None:
         sampler = DistributedSampler(train_set, world, rank, shuffle=True, drop_last=True) if world > 1 else None
@@ -144,6 +155,10 @@ def make_gpu_loader(args, rank, world, device):
     from PIL import Image
     from pesr_amd.input_pipeline import GpuPatchSampler
     root = os.path.join("data/origin/train", args.train_dataset)
+    if args.lr_from_hr:
+        hrs = [np.asarray(Image.open(p).convert("RGB")) for p in sorted(glob.glob(os.path.join(root, "HR", "*.png")))]
+        return GpuLoader(GpuPatchSampler.from_hr(hrs, device, scale=args.scale), args.batch_size // world, args.patch_size, len(hrs),
+                         args.num_repeats, rank, world)
     lr_paths = sorted(glob.glob(os.path.join(root, "LR", "*.png")))
     lrs = [np.asarray(Image.open(p).convert("RGB")) for p in lr_paths]
     hrs = [np.asarray(Image.open(os.path.join(root, "HR", os.path.basename(p))).convert("RGB")) for p in lr_paths]
@@ -248,7 +263,7 @@ def main(argv=None):
     from utils import compute_PSNR
 
     gpu_pipe = args.gpu_pipeline and not args.synthetic
-    train_loader, val_loader, sampler = make_loaders(args, rank, world, need_train=not gpu_pipe)
+    train_loader, val_loader, sampler = make_loaders(args, rank, world, need_train=not gpu_pipe, device=device)
     if gpu_pipe:
         train_loader = sampler = make_gpu_loader(args, rank, world, device)      # (it has set_epoch like a DistributedSampler)
     opt = {"patch_size": args.patch_size, "num_channels": args.num_channels, "depth": args.num_blocks,
