@@ -309,6 +309,18 @@ int pesr_imresize_u8_pass(const unsigned char* src, unsigned char* dst, const lo
 int pesr_psnr_y(const float* a, const float* b, double* out2, int H, int W, int a_nhwc, int b_nhwc, void* workspace,
                 size_t ws_bytes, void* stream);
 
+/* ---- SSIM on the Y channel with a border shave (docs/modes.md section 4g), N image pairs [N][3][H][W] ------- */
+/* The SSIM of Wang et al.'s ssim_index.m on the Y image of the PSNR-Y above: rows and columns [shave, H-shave) x [shave, W-shave),
+ * 11 x 11 Gaussian window of sigma 1.5 applied separably (height, then width) over the "valid" region, K1 = 0.01, K2 = 0.03,
+ * L = 255; float64 without fused multiply-add, bit-identical to the float64 host restatement.  a_nhwc / b_nhwc: that tensor is
+ * stored [N][H][W][3].  out: N device doubles, the mean of each pair's map.  map_or_null: when non-null the
+ * [N][H-2*shave-10][W-2*shave-10] double map is written too.  The workspace holds one double per workgroup:
+ * 8 * N * ceil((H-2*shave-10)/16) * ceil((W-2*shave-10)/16) bytes are enough for every tile size the library may be built with,
+ * less -> PESR_EWORKSPACE.  PESR_EINVAL (nothing launched): N < 1, shave < 0, H-2*shave or W-2*shave below 11 (no smaller window is
+ * substituted), N > 65535.  No atomics: the result is the same bits on every run.  64-bit offsets. */
+int pesr_ssim_y(const float* a, const float* b, double* out, int N, int H, int W, int a_nhwc, int b_nhwc, int shave,
+                double* map_or_null, void* workspace, size_t ws_bytes, void* stream);
+
 /* ---- GAN losses on the [B][1] logits (reference train.py:132-133,210-213,244-253; model/focal_loss.py:9-13), value and both
  * gradients in one launch.  gan_type 0 SGAN, 1 RSGAN, 2 RaSGAN (an extension: batch means over the B samples given);
  * side 0 = discriminator loss (BCE), 1 = generator loss (BCE, or the reference's FocalLoss when focal = 1, with the torch-0.4

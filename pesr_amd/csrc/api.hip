@@ -341,6 +341,11 @@ PESR_API int pesr_psnr_y(const float* a, const float* b, double* out2, int H, in
     return pesr_psnr_y_launch(a, b, out2, H, W, a_nhwc, b_nhwc, workspace, ws_bytes, (hipStream_t)stream);
 }
 
+PESR_API int pesr_ssim_y(const float* a, const float* b, double* out, int N, int H, int W, int a_nhwc, int b_nhwc, int shave,
+                         double* map_or_null, void* workspace, size_t ws_bytes, void* stream) {
+    return pesr_ssim_y_launch(a, b, out, N, H, W, a_nhwc, b_nhwc, shave, map_or_null, workspace, ws_bytes, (hipStream_t)stream);
+}
+
 PESR_API size_t pesr_spectral_norm_workspace_bytes(int O, int K) { return pesr_spectral_norm_ws_bytes(O, K); }
 PESR_API int pesr_spectral_norm_fwd(const float* w, float* u, float* v, float* w_hat, float* sigma, int O, int K, int update, float eps,
                                     void* workspace, size_t ws_bytes, void* stream) {

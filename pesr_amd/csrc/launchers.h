@@ -180,3 +180,7 @@ int pesr_imresize_u8_pass_launch(const unsigned char* src, unsigned char* dst, c
 
 int pesr_psnr_y_launch(const float* a, const float* b, double* out2, int H, int W, int a_nhwc, int b_nhwc, void* ws, size_t ws_bytes,
                        hipStream_t stream);
+
+// SSIM on the Y channel with a border shave (ssim.hip)
+int pesr_ssim_y_launch(const float* a, const float* b, double* out, int N, int H, int W, int a_nhwc, int b_nhwc, int shave,
+                       double* map, void* ws, size_t ws_bytes, hipStream_t stream);

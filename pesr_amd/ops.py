@@ -1121,6 +1121,43 @@ def psnr_y(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     return out
 
 
+# g[k] = exp(-(k-5)^2 / 4.5) / sum, k = 0..10: the SSIM window (docs/modes.md section 4g).  ssim.hip carries these doubles as literals;
+# utils.compute_SSIM's host path filters with them.
+SSIM_WINDOW = (0.00102838008447911, 0.007598758135239185, 0.03600077212843083, 0.10936068950970002, 0.2130055377112537,
+               0.26601172486179436, 0.2130055377112537, 0.10936068950970002, 0.03600077212843083, 0.007598758135239185,
+               0.00102838008447911)
+
+
+def ssim_y(a: torch.Tensor, b: torch.Tensor, shave: int = 0, return_map: bool = False):
+    """Y-channel SSIM of N image pairs [N, 3, H, W] (each NCHW-contiguous or channels_last), a border of `shave` pixels ignored
+    -> device double [N], the mean of each pair's map; with return_map also the [N, H-2*shave-10, W-2*shave-10] double map."""
+    outs = []
+    for t in (a, b):
+        if not torch.is_tensor(t) or not t.is_cuda or t.dtype != torch.float32 or t.dim() != 4 or t.shape[0] < 1 or t.shape[1] != 3:
+            raise _lib.PesrHipError("ssim_y: expected [N, 3, H, W] float32 GPU tensors")
+        if t.is_contiguous():
+            outs.append((t, 0))
+        elif t.is_contiguous(memory_format=torch.channels_last):
+            outs.append((t, 1))
+        else:
+            outs.append((t.contiguous(), 0))
+    (ta, la), (tb, lb) = outs
+    if ta.shape != tb.shape:
+        raise ValueError(f"ssim_y: the two tensors differ in shape: {tuple(ta.shape)} and {tuple(tb.shape)}")
+    shave = int(shave)
+    N, H, W = ta.shape[0], ta.shape[2], ta.shape[3]
+    Ho, Wo = H - 2 * shave - 10, W - 2 * shave - 10
+    if shave < 0 or Ho < 1 or Wo < 1:
+        raise ValueError(f"ssim_y: a {H} x {W} image with shave {shave} leaves less than the 11 x 11 window")
+    out = torch.empty(N, dtype=torch.float64, device=ta.device)
+    smap = torch.empty((N, Ho, Wo), dtype=torch.float64, device=ta.device) if return_map else None
+    ws = workspace(8 * N * ((Ho + 15) // 16) * ((Wo + 15) // 16), ta.device)
+    rc = _lib.lib().pesr_ssim_y(ta.data_ptr(), tb.data_ptr(), out.data_ptr(), N, H, W, la, lb, shave,
+                                smap.data_ptr() if return_map else None, ws.data_ptr(), ws.numel(), _stream())
+    _lib.check(rc, "pesr_ssim_y")
+    return (out, smap) if return_map else out
+
+
 # ------------------------------------------------------------------------------------------------
 # spectral normalisation (reference model/basic.py:25; torch.nn.utils.spectral_norm semantics)
 # ------------------------------------------------------------------------------------------------

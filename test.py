@@ -2,7 +2,8 @@
 """SR inference entry point (counterpart of reference test.py): perceptual model, optional PSNR model with x8
 self-ensemble, image-space blend `alpha*out + (1-alpha)*out_psnr`, PNG output.  Same flags as the reference
 (test.py:13-33) plus --precision, --scale and --from_hr (a test set that ships HR images only: LR made on the device, PSNR-Y of the
-result and of the bicubic baseline printed); device-agnostic plumbing; the Generator itself runs on the MI355X kernels.
+result and of the bicubic baseline printed; --ssim adds SSIM-Y, --shave drops a border before both); device-agnostic plumbing; the
+Generator itself runs on the MI355X kernels.
 """
 import argparse
 import glob
@@ -11,7 +12,7 @@ import os
 import numpy as np
 import torch
 
-from utils import compute_PSNR, default_device, imgs_to_tensors, tensors_to_imgs
+from utils import compute_PSNR, compute_SSIM, default_device, imgs_to_tensors, tensors_to_imgs
 
 
 # (flag, type, default, help) - the reference's flags and defaults (reference test.py:15-33)
@@ -42,6 +43,13 @@ def build_parser():
     parser.add_argument("--from_hr", type=lambda x: str(x).lower() == "true", default=False,
                         help="read data/origin/test/<dataset>/HR/*.png instead of LR/: crop each to multiples of --scale, make its LR image on "
                              "the GPU by MATLAB-style bicubic resize, and print PSNR-Y of the result and of the bicubic baseline against HR")
+    # additions (not reference flags): the other half of a super-resolution table entry, docs/modes.md section 4g
+    parser.add_argument("--ssim", type=lambda x: str(x).lower() == "true", default=False,
+                        help="with --from_hr true: also print SSIM-Y (11 x 11 Gaussian window, measured on the GPU) of the result and of "
+                             "the bicubic baseline")
+    parser.add_argument("--shave", type=int, default=0,
+                        help="with --from_hr true: drop a border of this many pixels before PSNR-Y and SSIM-Y are measured; -1 means "
+                             "--scale, the convention of the published tables")
     return parser
 
 
@@ -123,6 +131,11 @@ def main(argv=None):
     if args.precision != "fp32":
         from pesr_amd import ops as _ops
         _ops.set_precision(args.precision)
+    if args.ssim and not args.from_hr:
+        raise SystemExit("test.py: --ssim true needs --from_hr true: without the HR images there is nothing to compare the result with")
+    if args.shave < -1:
+        raise SystemExit(f"test.py: --shave is a border width in pixels (or -1 for --scale), got {args.shave}")
+    shave = args.scale if args.shave == -1 else args.shave
     device = default_device()
     lr_paths = sorted(glob.glob(os.path.join("data/origin/test/", args.dataset, "HR" if args.from_hr else "LR", "*.png")))
     opt = {"num_channels": args.num_channels, "depth": args.num_blocks, "res_scale": args.res_scale}
@@ -133,7 +146,7 @@ def main(argv=None):
         model_psnr = load_generator(opt, args.psnr_model, args.scale).to(device)
     save_path = os.path.join(args.save_path, args.dataset)
     os.makedirs(save_path, exist_ok=True)
-    psnrs = []
+    psnrs, ssims = [], []
     with torch.no_grad():
         for i, lr_path in enumerate(lr_paths):
             if args.from_hr:
@@ -148,11 +161,18 @@ def main(argv=None):
             if args.from_hr:
                 # the PSNR of what was SAVED: the uint8 image back on the device (compute_PSNR rounds the same way itself)
                 [sr] = imgs_to_tensors([img], device)
-                psnrs.append((compute_PSNR(sr, hr), compute_PSNR(bic, hr)))
-                print("%s: PSNR-Y %.10f dB, bicubic %.10f dB" % ((os.path.basename(lr_path),) + psnrs[-1]))
+                psnrs.append((compute_PSNR(sr, hr, shave), compute_PSNR(bic, hr, shave)))
+                line = "%s: PSNR-Y %.10f dB, bicubic %.10f dB" % ((os.path.basename(lr_path),) + psnrs[-1])
+                if args.ssim:
+                    ssims.append((compute_SSIM(sr, hr, shave), compute_SSIM(bic, hr, shave)))
+                    line += ", SSIM-Y %.10f, bicubic %.10f" % ssims[-1]
+                print(line)
             print("Tested %d img(s)" % (i + 1))
     if args.from_hr and psnrs:
-        print("Mean PSNR-Y %.10f dB, bicubic %.10f dB" % (float(np.mean([p[0] for p in psnrs])), float(np.mean([p[1] for p in psnrs]))))
+        line = "Mean PSNR-Y %.10f dB, bicubic %.10f dB" % (float(np.mean([p[0] for p in psnrs])), float(np.mean([p[1] for p in psnrs])))
+        if ssims:
+            line += ", SSIM-Y %.10f, bicubic %.10f" % (float(np.mean([q[0] for q in ssims])), float(np.mean([q[1] for q in ssims])))
+        print(line)
     print("Finish")
 
 

@@ -83,6 +83,11 @@ def build_parser():
     p.add_argument("--lr_from_hr", type=str2bool, default=False,
                    help="build the training and validation sets from their HR/ folders alone: every HR image is cropped to multiples "
                         "of --scale and its LR image is made on the GPU by MATLAB-style bicubic resize (docs/modes.md section 4f)")
+    p.add_argument("--valid_ssim", type=str2bool, default=False,
+                   help="validation also averages SSIM-Y (measured on the GPU, docs/modes.md section 4g) and prints it in a line of its "
+                        "own; the best model is still chosen by PSNR")
+    p.add_argument("--valid_shave", type=int, default=0,
+                   help="drop a border of this many pixels before the validation PSNR (and SSIM) is measured")
     return p
 
 
@@ -260,7 +265,7 @@ def main(argv=None):
     _ops.set_precision(args.precision)
     from pesr_amd.optim import FlatAdam
     from pesr_amd.step import Trainer
-    from utils import compute_PSNR
+    from utils import compute_PSNR, compute_SSIM
 
     gpu_pipe = args.gpu_pipeline and not args.synthetic
     train_loader, val_loader, sampler = make_loaders(args, rank, world, need_train=not gpu_pipe, device=device)
@@ -389,15 +394,23 @@ def main(argv=None):
 
         # validation on rank 0 (full images, batch 1, no_grad), reference train.py:281-295
         if rank == 0:
-            psnr = []
+            psnr, ssim = [], []
             with torch.no_grad():
                 for lr_img, hr_img in val_loader:
                     sr = G(lr_img.to(device))
-                    psnr.append(compute_PSNR(hr_img.to(device), sr))
+                    hr_img = hr_img.to(device)
+                    psnr.append(compute_PSNR(hr_img, sr, args.valid_shave))
+                    if args.valid_ssim:
+                        ssim.append(compute_SSIM(hr_img, sr, args.valid_shave))
             val_psnr = float(np.mean(psnr)) if psnr else 0.0
             print("Finish valid [%d/%d]. PSNR: %.4fdB" % (epoch, args.num_epochs, val_psnr))
             if tb is not None:
                 tb.add_scalar("Validate PSNR", val_psnr, epoch)
+            if args.valid_ssim:
+                val_ssim = float(np.mean(ssim)) if ssim else 0.0
+                print("Finish valid [%d/%d]. SSIM: %.6f" % (epoch, args.num_epochs, val_ssim))
+                if tb is not None:
+                    tb.add_scalar("Validate SSIM", val_ssim, epoch)
             if not gan and val_psnr > best_psnr:
                 best_psnr = val_psnr
                 torch.save(G.state_dict(), os.path.join(check_point, "best_model.pt"))

@@ -1,4 +1,5 @@
-"""Image <-> tensor helpers and the Y-channel PSNR of the reference (reference utils.py:10-41), device-agnostic.
+"""Image <-> tensor helpers, the Y-channel PSNR of the reference (reference utils.py:10-41) and the Y-channel SSIM beside it
+(docs/modes.md section 4g), device-agnostic.
 
 Tensors carry raw 0..255 values (no /255 anywhere).  Metrics run in numpy on the host exactly as the
 reference does; nothing here is on the hot path.
@@ -40,9 +41,19 @@ def normalize(tensors):
     return [t.clamp(0, 255) / 255 for t in tensors]
 
 
-def compute_PSNR(out, lbl):
+def _shaved(t, shave):
+    shave = int(shave)
+    if shave < 0 or 2 * shave >= min(t.shape[-2], t.shape[-1]):
+        raise ValueError(f"shave {shave} leaves nothing of a {t.shape[-2]} x {t.shape[-1]} image")
+    return t[..., shave:t.shape[-2] - shave, shave:t.shape[-1] - shave]
+
+
+def compute_PSNR(out, lbl, shave=0):
     """PSNR on the rounded Y channel of two [1,3,H,W] tensors (reference utils.py:32-41).  GPU tensors are measured on the
-    device (pesr_amd.ops.psnr_y, bit-identical: integer-valued terms in double); only the scalar comes back."""
+    device (pesr_amd.ops.psnr_y, bit-identical: integer-valued terms in double); only the scalar comes back.  shave > 0 drops a
+    border of that many pixels from both images first (the convention of the super-resolution tables: shave = scale)."""
+    if shave:
+        out, lbl = _shaved(out, shave), _shaved(lbl, shave)
     if torch.is_tensor(out) and torch.is_tensor(lbl) and out.is_cuda and lbl.is_cuda and out.dtype == torch.float32 \
             and lbl.dtype == torch.float32 and out.dim() == 4 and out.shape[0] == 1 and out.shape == lbl.shape:
         from pesr_amd import ops
@@ -52,6 +63,58 @@ def compute_PSNR(out, lbl):
     yl = np.clip(rgb2y(l), 0, 255).round()
     rmse = np.sqrt(np.mean((yo - yl) ** 2))
     return 20 * np.log10(255 / rmse)
+
+
+def _ssim_luma(t):
+    """[1,3,H,W] or [3,H,W] tensor / array -> the integer-valued float64 Y image of the PSNR-Y, [H, W]."""
+    a = t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
+    if a.ndim == 4 and a.shape[0] == 1:
+        a = a[0]
+    if a.ndim != 3 or a.shape[0] != 3:
+        raise ValueError(f"compute_SSIM: expected a [1, 3, H, W] or [3, H, W] image, got {tuple(a.shape)}")
+    rgb = np.rint(np.clip(a.astype(np.float64), 0.0, 255.0))
+    y = ((rgb[0] * _Y_COEF[0] + rgb[1] * _Y_COEF[1]) + rgb[2] * _Y_COEF[2]) + 16.0
+    return np.rint(np.clip(y, 0.0, 255.0))
+
+
+def _ssim_filter(v, g):
+    """[M, H, W] -> [M, H-10, W-10]: the 11-tap window along the height, then along the width, "valid" region, taps ascending."""
+    ho, wo = v.shape[1] - 10, v.shape[2] - 10
+    acc = np.zeros((v.shape[0], ho, v.shape[2]))
+    for k in range(11):
+        acc = acc + g[k] * v[:, k:k + ho, :]
+    out = np.zeros((v.shape[0], ho, wo))
+    for k in range(11):
+        out = out + g[k] * acc[:, :, k:k + wo]
+    return out
+
+
+def compute_SSIM(out, lbl, shave=0):
+    """SSIM on the rounded Y channel of two images (docs/modes.md section 4g): Wang et al.'s ssim_index.m as the super-resolution
+    tables use it - 11 x 11 Gaussian window of sigma 1.5, "valid" region, K1 = 0.01, K2 = 0.03, L = 255, a border of `shave`
+    pixels dropped first.  float32 GPU tensors [N,3,H,W] are measured on the device (pesr_amd.ops.ssim_y; the mean over the N pairs
+    comes back); anything else ([1,3,H,W] / [3,H,W] tensors or arrays) goes through numpy in float64 with the same definition.
+    ValueError when the shaved image is smaller than the window or the shapes differ."""
+    shave = int(shave)
+    if shave < 0:
+        raise ValueError(f"compute_SSIM: shave must be >= 0, got {shave}")
+    if tuple(out.shape) != tuple(lbl.shape):
+        raise ValueError(f"compute_SSIM: the two images differ in shape: {tuple(out.shape)} and {tuple(lbl.shape)}")
+    if min(out.shape[-2], out.shape[-1]) - 2 * shave < 11:
+        raise ValueError(f"compute_SSIM: a {out.shape[-2]} x {out.shape[-1]} image with shave {shave} leaves less than the 11 x 11 "
+                         "window")
+    if torch.is_tensor(out) and torch.is_tensor(lbl) and out.is_cuda and lbl.is_cuda and out.dtype == torch.float32 \
+            and lbl.dtype == torch.float32 and out.dim() == 4 and out.shape[1] == 3:
+        from pesr_amd import ops
+        return float(ops.ssim_y(out.detach(), lbl.detach(), shave).mean())
+    from pesr_amd.ops import SSIM_WINDOW
+    x, y = _shaved(_ssim_luma(out), shave), _shaved(_ssim_luma(lbl), shave)
+    mx, my, xx, yy, xy = _ssim_filter(np.stack([x, y, x * x, y * y, x * y]), SSIM_WINDOW)
+    c1, c2 = (0.01 * 255) * (0.01 * 255), (0.03 * 255) * (0.03 * 255)
+    mxmx, mymy, mxmy = mx * mx, my * my, mx * my
+    num = (2.0 * mxmy + c1) * (2.0 * (xy - mxmy) + c2)
+    den = ((mxmx + mymy) + c1) * (((xx - mxmx) + (yy - mymy)) + c2)
+    return float(np.mean(num / den))
 
 
 def update_tensorboard(epoch, tb, img_idx, inp, out, lbl):
