@@ -321,6 +321,28 @@ int pesr_psnr_y(const float* a, const float* b, double* out2, int H, int W, int 
 int pesr_ssim_y(const float* a, const float* b, double* out, int N, int H, int W, int a_nhwc, int b_nhwc, int shave,
                 double* map_or_null, void* workspace, size_t ws_bytes, void* stream);
 
+/* ---- tiled inference (docs/modes.md section 4h): tiles of one LR image -> a batch, a batch's outputs -> the image ------- */
+/* Gather.  src: the LR image, fp32 [3][H][W] (src_u8 = 0) or uint8 [H][W][3] (src_u8 = 1).  desc: n rows of 3 int32 {y0, x0, m}:
+ * tile origin and ensemble member m in 0..7 = entry m of test.py:x8_forward's inputs (bit 0 reverses the W axis, then bit 1 the H
+ * axis, then bit 2 transposes).  dst: fp32 [n][3][oh][ow]; the tile read for an entry is oh x ow (m < 4) or ow x oh (m >= 4).
+ * Values are copied exactly.  desc_host is checked here, desc_dev (the same rows on the device) is what the kernel reads.
+ * PESR_EINVAL (nothing launched): a tile outside the image, m outside 0..7, n < 1 or n > 65535. */
+int pesr_tile_gather(const void* src, int src_u8, int H, int W, float* dst, const int* desc_host, const int* desc_dev, int n,
+                     int oh, int ow, void* stream);
+/* Scatter.  n entries, E = 1 or 8 consecutive ones per tile, each the Generator's fp32 output [3][s*th][s*tw] of a th x tw tile
+ * (members 4-7: [3][s*tw][s*th]), stored channel-first (t_nhwc = 0) or channel-last (1).  t_hi = NULL: t_lo holds every entry
+ * (E = 8 needs th == tw then); else t_lo holds members 0-3 and t_hi members 4-7 of every tile, four entries per tile each.
+ * desc: n / E rows of 6 int32 {y0, x0, oy, ox, oh, ow}: the tile's origin and the rectangle of LR pixels it owns (origin, rows,
+ * columns; image coordinates).  For every owned output pixel: undo each member's transform (transpose, then H, then W),
+ * v = t0 or (((((((t0+t1)+t2)+t3)+t4)+t5)+t6)+t7)/8, out = v or wa*p + wb*v (p_or_null: [n/E][3][s*th][s*tw], layout p_nhwc), fp32,
+ * no fused multiply-add.  out_f32: [3][s*H][s*W]; out_u8: [s*H][s*W][3], clamped to 0..255 and rounded half to even; either may be
+ * NULL.  The owned rectangles must not overlap (not checked): each pixel is then written once, no atomics, same bits every run.
+ * PESR_EINVAL (nothing launched): E not 1 or 8, n not a multiple of E, s outside 2..4, a tile outside the image, an owned rectangle
+ * outside its tile or empty, both outputs NULL, more than 65535 tiles. */
+int pesr_tile_scatter(const float* t_lo, const float* t_hi, int t_nhwc, const float* p_or_null, int p_nhwc, float wa, float wb,
+                      const int* desc_host, const int* desc_dev, int n, int E, int th, int tw, int s, int H, int W,
+                      float* out_f32_or_null, unsigned char* out_u8_or_null, void* stream);
+
 /* ---- GAN losses on the [B][1] logits (reference train.py:132-133,210-213,244-253; model/focal_loss.py:9-13), value and both
  * gradients in one launch.  gan_type 0 SGAN, 1 RSGAN, 2 RaSGAN (an extension: batch means over the B samples given);
  * side 0 = discriminator loss (BCE), 1 = generator loss (BCE, or the reference's FocalLoss when focal = 1, with the torch-0.4

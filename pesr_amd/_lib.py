@@ -90,6 +90,9 @@ SIGNATURES.update({
     "pesr_imresize_u8_pass": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, _P, _P]),
     "pesr_psnr_y": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, _P, c_size_t, _P]),
     "pesr_ssim_y": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, c_size_t, _P]),
+    "pesr_tile_gather": (c_int, [_P, c_int, c_int, c_int, _P, _P, _P, c_int, c_int, c_int, _P]),
+    "pesr_tile_scatter": (c_int, [_P, _P, c_int, _P, c_int, c_float, c_float, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
+                                  _P, _P, _P]),
     "pesr_adam_step": (c_int, [_P, _P, _P, _P, c_long, c_float, c_float, c_float, c_float, c_int, c_float, _P]),
     "pesr_adam_step_dev": (c_int, [_P, _P, _P, _P, c_long, _P, c_float, c_float, c_float, c_float, _P]),
     "pesr_conv3x3_bn_rows": (c_long, [c_int, c_int, c_int, c_int, c_int, c_int, c_int]),

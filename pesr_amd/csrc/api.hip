@@ -346,6 +346,18 @@ PESR_API int pesr_ssim_y(const float* a, const float* b, double* out, int N, int
     return pesr_ssim_y_launch(a, b, out, N, H, W, a_nhwc, b_nhwc, shave, map_or_null, workspace, ws_bytes, (hipStream_t)stream);
 }
 
+PESR_API int pesr_tile_gather(const void* src, int src_u8, int H, int W, float* dst, const int* desc_host, const int* desc_dev, int n,
+                             int oh, int ow, void* stream) {
+    return pesr_tile_gather_launch(src, src_u8, H, W, dst, desc_host, desc_dev, n, oh, ow, (hipStream_t)stream);
+}
+
+PESR_API int pesr_tile_scatter(const float* t_lo, const float* t_hi, int t_nhwc, const float* p_or_null, int p_nhwc, float wa, float wb,
+                              const int* desc_host, const int* desc_dev, int n, int E, int th, int tw, int s, int H, int W,
+                              float* out_f32_or_null, unsigned char* out_u8_or_null, void* stream) {
+    return pesr_tile_scatter_launch(t_lo, t_hi, t_nhwc, p_or_null, p_nhwc, wa, wb, desc_host, desc_dev, n, E, th, tw, s, H, W,
+                                    out_f32_or_null, out_u8_or_null, (hipStream_t)stream);
+}
+
 PESR_API size_t pesr_spectral_norm_workspace_bytes(int O, int K) { return pesr_spectral_norm_ws_bytes(O, K); }
 PESR_API int pesr_spectral_norm_fwd(const float* w, float* u, float* v, float* w_hat, float* sigma, int O, int K, int update, float eps,
                                     void* workspace, size_t ws_bytes, void* stream) {

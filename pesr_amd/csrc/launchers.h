@@ -184,3 +184,10 @@ int pesr_psnr_y_launch(const float* a, const float* b, double* out2, int H, int 
 // SSIM on the Y channel with a border shave (ssim.hip)
 int pesr_ssim_y_launch(const float* a, const float* b, double* out, int N, int H, int W, int a_nhwc, int b_nhwc, int shave,
                        double* map, void* ws, size_t ws_bytes, hipStream_t stream);
+
+// tiled inference: tiles of one image -> a batch, and a batch's outputs -> the owned pixels of the image (tile.hip)
+int pesr_tile_gather_launch(const void* src, int src_u8, int H, int W, float* dst, const int* desc_host, const int* desc_dev, int n,
+                            int oh, int ow, hipStream_t stream);
+int pesr_tile_scatter_launch(const float* t_lo, const float* t_hi, int t_nhwc, const float* p, int p_nhwc, float wa, float wb,
+                             const int* desc_host, const int* desc_dev, int n, int E, int th, int tw, int s, int H, int W,
+                             float* out_f32, unsigned char* out_u8, hipStream_t stream);

@@ -1159,6 +1159,89 @@ def ssim_y(a: torch.Tensor, b: torch.Tensor, shave: int = 0, return_map: bool = 
 
 
 # ------------------------------------------------------------------------------------------------
+# tiled inference (docs/modes.md section 4h; the plan and the driver are pesr_amd/tile.py)
+# ------------------------------------------------------------------------------------------------
+def _tile_desc(desc, cols: int, device):
+    """Descriptor rows as a C-contiguous int32 host array (what the library checks) and its copy on the device (what the kernel
+    reads)."""
+    import numpy as np
+    host = np.ascontiguousarray(np.asarray(desc, dtype=np.int32).reshape(-1, cols))
+    return host, torch.from_numpy(host).to(device)
+
+
+def _entry_layout(t: torch.Tensor, name: str):
+    """[n, 3, h, w] fp32 device tensor -> (tensor, 0 if NCHW-contiguous / 1 if channels_last).  A tensor in neither layout is copied
+    by torch first (the Generator's outputs and their leading slices are in one of the two: the driver never takes that copy)."""
+    if not torch.is_tensor(t) or not t.is_cuda or t.dtype != torch.float32 or t.dim() != 4 or t.shape[1] != 3:
+        raise _lib.PesrHipError(f"tile_scatter: {name}: expected an [n, 3, h, w] float32 GPU tensor")
+    if t.is_contiguous():
+        return t, 0
+    if t.is_contiguous(memory_format=torch.channels_last):
+        return t, 1
+    return t.contiguous(), 0
+
+
+def tile_gather(src: torch.Tensor, desc, oh: int, ow: int) -> torch.Tensor:
+    """Tiles of one LR image as a batch.  src: fp32 [3, H, W] or uint8 [H, W, 3] device tensor; desc: rows {y0, x0, member};
+    -> fp32 [n, 3, oh, ow], entry i = member desc[i][2] (entry of test.py:x8_forward's inputs) of the tile at (y0, x0)."""
+    if not (torch.is_tensor(src) and src.is_cuda):
+        raise _lib.PesrHipError("tile_gather needs a device tensor: pesr_amd has no CPU fallback")
+    if src.dtype == torch.uint8 and src.dim() == 3 and src.shape[2] == 3:
+        u8, H, W = 1, int(src.shape[0]), int(src.shape[1])
+    elif src.dtype == torch.float32 and src.dim() == 3 and src.shape[0] == 3:
+        u8, H, W = 0, int(src.shape[1]), int(src.shape[2])
+    else:
+        raise _lib.PesrHipError("tile_gather: expected a float32 [3, H, W] or a uint8 [H, W, 3] image")
+    src = src.contiguous()
+    host, dev = _tile_desc(desc, 3, src.device)
+    n = host.shape[0]
+    out = torch.empty((n, 3, int(oh), int(ow)), dtype=torch.float32, device=src.device)
+    rc = _lib.lib().pesr_tile_gather(src.data_ptr(), u8, H, W, out.data_ptr(), host.ctypes.data, dev.data_ptr(), n, int(oh), int(ow),
+                                     _stream())
+    _lib.check(rc, "pesr_tile_gather")
+    return out
+
+
+def tile_scatter(t_lo: torch.Tensor, t_hi: Optional[torch.Tensor], desc, E: int, th: int, tw: int, s: int, H: int, W: int,
+                 out_f32: Optional[torch.Tensor] = None, out_u8: Optional[torch.Tensor] = None, p: Optional[torch.Tensor] = None,
+                 wa: float = 1.0, wb: float = 0.0) -> None:
+    """The owned pixels of n / E tiles into the fp32 [3, s*H, s*W] and / or uint8 [s*H, s*W, 3] image.  t_lo: the Generator's outputs
+    [n, 3, s*th, s*tw] (with t_hi: members 0-3 there, members 4-7 [n, 3, s*tw, s*th] in t_hi); desc: rows {y0, x0, oy, ox, oh, ow};
+    p: the E = 1 outputs of a second model for the blend wa * p + wb * v (wa, wb are rounded to fp32 here)."""
+    import numpy as np
+    t_lo, lay = _entry_layout(t_lo, "t_lo")
+    n = int(t_lo.shape[0])
+    if t_hi is not None:
+        t_hi, lay_hi = _entry_layout(t_hi, "t_hi")
+        if lay_hi != lay:
+            t_lo, t_hi, lay = t_lo.contiguous(), t_hi.contiguous(), 0
+        if tuple(t_hi.shape) != (n, 3, s * tw, s * th):
+            raise ValueError(f"tile_scatter: t_hi is {tuple(t_hi.shape)}, expected {(n, 3, s * tw, s * th)}")
+        n *= 2
+    if tuple(t_lo.shape[1:]) != (3, s * th, s * tw):
+        raise ValueError(f"tile_scatter: t_lo is {tuple(t_lo.shape)}, expected [n, 3, {s * th}, {s * tw}]")
+    lay_p = 0
+    if p is not None:
+        p, lay_p = _entry_layout(p, "p")
+        if tuple(p.shape) != (n // max(int(E), 1), 3, s * th, s * tw):
+            raise ValueError(f"tile_scatter: p is {tuple(p.shape)}, expected {(n // max(int(E), 1), 3, s * th, s * tw)}")
+    if out_f32 is not None:
+        if not (out_f32.is_cuda and out_f32.dtype == torch.float32 and out_f32.is_contiguous() and tuple(out_f32.shape) == (3, s * H, s * W)):
+            raise ValueError(f"tile_scatter: out_f32 must be a contiguous float32 GPU tensor [3, {s * H}, {s * W}]")
+    if out_u8 is not None:
+        if not (out_u8.is_cuda and out_u8.dtype == torch.uint8 and out_u8.is_contiguous() and tuple(out_u8.shape) == (s * H, s * W, 3)):
+            raise ValueError(f"tile_scatter: out_u8 must be a contiguous uint8 GPU tensor [{s * H}, {s * W}, 3]")
+    host, dev = _tile_desc(desc, 6, t_lo.device)
+    if host.shape[0] * int(E) != n:
+        raise ValueError(f"tile_scatter: {host.shape[0]} descriptor rows for {n} entries with E = {E}")
+    rc = _lib.lib().pesr_tile_scatter(t_lo.data_ptr(), None if t_hi is None else t_hi.data_ptr(), lay, None if p is None else p.data_ptr(),
+                                      lay_p, float(np.float32(wa)), float(np.float32(wb)), host.ctypes.data, dev.data_ptr(), n, int(E),
+                                      int(th), int(tw), int(s), int(H), int(W), None if out_f32 is None else out_f32.data_ptr(),
+                                      None if out_u8 is None else out_u8.data_ptr(), _stream())
+    _lib.check(rc, "pesr_tile_scatter")
+
+
+# ------------------------------------------------------------------------------------------------
 # spectral normalisation (reference model/basic.py:25; torch.nn.utils.spectral_norm semantics)
 # ------------------------------------------------------------------------------------------------
 def spectral_norm_fwd(w: torch.Tensor, u: torch.Tensor, v: torch.Tensor, update: bool, eps: float = 1e-12):

@@ -2,7 +2,8 @@
 """SR inference entry point (counterpart of reference test.py): perceptual model, optional PSNR model with x8
 self-ensemble, image-space blend `alpha*out + (1-alpha)*out_psnr`, PNG output.  Same flags as the reference
 (test.py:13-33) plus --precision, --scale and --from_hr (a test set that ships HR images only: LR made on the device, PSNR-Y of the
-result and of the bicubic baseline printed; --ssim adds SSIM-Y, --shave drops a border before both); device-agnostic plumbing; the
+result and of the bicubic baseline printed; --ssim adds SSIM-Y, --shave drops a border before both) and --tile (every image as
+batches of fixed-size tiles, docs/modes.md section 4h); device-agnostic plumbing; the
 Generator itself runs on the MI355X kernels.
 """
 import argparse
@@ -50,6 +51,15 @@ def build_parser():
     parser.add_argument("--shave", type=int, default=0,
                         help="with --from_hr true: drop a border of this many pixels before PSNR-Y and SSIM-Y are measured; -1 means "
                              "--scale, the convention of the published tables")
+    # additions (not reference flags): tiled inference, docs/modes.md section 4h
+    parser.add_argument("--tile", type=int, default=0,
+                        help="run every image as batches of overlapping tiles of one fixed shape on the GPU: the side of the square of "
+                             "LR pixels a tile owns; 0 (default) = off, one Generator call on the whole image")
+    parser.add_argument("--tile_halo", type=int, default=-1,
+                        help="with --tile: LR pixels of context around a tile's owned square; -1 = 2 * num_blocks + 4, from which on the "
+                             "result equals the whole-image forward up to fp32 summation order; a smaller halo is an approximation")
+    parser.add_argument("--tile_batch", type=int, default=16,
+                        help="with --tile: tiles per Generator call (entries per call for the x8 ensemble: rounded down to a multiple of 8)")
     return parser
 
 
@@ -136,6 +146,9 @@ def main(argv=None):
     if args.shave < -1:
         raise SystemExit(f"test.py: --shave is a border width in pixels (or -1 for --scale), got {args.shave}")
     shave = args.scale if args.shave == -1 else args.shave
+    from pesr_amd import tile as _tile
+    tile_halo = _tile.check_flags("test.py", ("--tile", "--tile_halo", "--tile_batch"), args.tile, args.tile_halo, args.tile_batch,
+                                  args.num_blocks, args.scale)
     device = default_device()
     lr_paths = sorted(glob.glob(os.path.join("data/origin/test/", args.dataset, "HR" if args.from_hr else "LR", "*.png")))
     opt = {"num_channels": args.num_channels, "depth": args.num_blocks, "res_scale": args.res_scale}
@@ -147,16 +160,27 @@ def main(argv=None):
     save_path = os.path.join(args.save_path, args.dataset)
     os.makedirs(save_path, exist_ok=True)
     psnrs, ssims = [], []
+    if args.tile:
+        print(_tile.describe(args.tile, tile_halo, _tile.receptive_halo(args.num_blocks, args.scale)))
     with torch.no_grad():
         for i, lr_path in enumerate(lr_paths):
             if args.from_hr:
                 inp, hr, bic = lr_from_hr(_read_png(lr_path), args.scale, device)
             else:
                 [inp] = imgs_to_tensors([_read_png(lr_path)], device)
-            out = model(inp)
-            if model_psnr is not None:
-                out = args.alpha * out + (1 - args.alpha) * x8_forward(inp, model_psnr)
-            [img] = tensors_to_imgs([out])
+            if args.tile:
+                # [gather, G, scatter] per batch of tiles; the blend and the uint8 conversion happen in the scatter kernel
+                if model_psnr is not None:
+                    _, img = _tile.tiled_forward(model_psnr, inp, args.scale, args.tile, tile_halo, args.tile_batch, ensemble=True,
+                                                 blend_model=model, alpha=args.alpha, f32=False, u8=True)
+                else:
+                    _, img = _tile.tiled_forward(model, inp, args.scale, args.tile, tile_halo, args.tile_batch, f32=False, u8=True)
+                img = img.cpu().numpy()
+            else:
+                out = model(inp)
+                if model_psnr is not None:
+                    out = args.alpha * out + (1 - args.alpha) * x8_forward(inp, model_psnr)
+                [img] = tensors_to_imgs([out])
             _write_png(os.path.join(save_path, os.path.basename(lr_path)), img)
             if args.from_hr:
                 # the PSNR of what was SAVED: the uint8 image back on the device (compute_PSNR rounds the same way itself)

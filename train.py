@@ -88,6 +88,11 @@ def build_parser():
                         "own; the best model is still chosen by PSNR")
     p.add_argument("--valid_shave", type=int, default=0,
                    help="drop a border of this many pixels before the validation PSNR (and SSIM) is measured")
+    p.add_argument("--valid_tile", type=int, default=0,
+                   help="validate every image as batches of overlapping tiles (docs/modes.md section 4h): the side of the square of LR "
+                        "pixels a tile owns; 0 (default) = off, one Generator call on the whole image")
+    p.add_argument("--valid_tile_halo", type=int, default=-1,
+                   help="with --valid_tile: LR pixels of context around a tile; -1 = 2 * num_blocks + 4, the exact one")
     return p
 
 
@@ -227,6 +232,8 @@ def check_limits(args, world):
     if args.scale != 4 and args.precision != "fp32":
         raise SystemExit(f"train.py: --precision {args.precision} is checked for --scale 4 only; use --precision fp32 with --scale "
                          f"{args.scale}")
+    from pesr_amd.tile import check_flags
+    check_flags("train.py", ("--valid_tile", "--valid_tile_halo"), args.valid_tile, args.valid_tile_halo, 1, args.num_blocks, args.scale)
     if args.phase != "pretrain" and args.scale == 4 and args.patch_size % 4:
         raise SystemExit("train.py: the GAN phase needs --patch_size % 4 == 0 (HR patches must survive four stride-2 stages and "
                          "VGG's four 2x2 max-pools, which this implementation does for even sizes only)")
@@ -266,6 +273,10 @@ def main(argv=None):
     from pesr_amd.optim import FlatAdam
     from pesr_amd.step import Trainer
     from utils import compute_PSNR, compute_SSIM
+    from pesr_amd.tile import describe, receptive_halo, tiled_forward
+    valid_halo = receptive_halo(args.num_blocks, args.scale) if args.valid_tile_halo == -1 else args.valid_tile_halo
+    if args.valid_tile and rank == 0:
+        print(describe(args.valid_tile, valid_halo, receptive_halo(args.num_blocks, args.scale)))
 
     gpu_pipe = args.gpu_pipeline and not args.synthetic
     train_loader, val_loader, sampler = make_loaders(args, rank, world, need_train=not gpu_pipe, device=device)
@@ -397,7 +408,10 @@ def main(argv=None):
             psnr, ssim = [], []
             with torch.no_grad():
                 for lr_img, hr_img in val_loader:
-                    sr = G(lr_img.to(device))
+                    if args.valid_tile:
+                        sr, _ = tiled_forward(G, lr_img.to(device), args.scale, args.valid_tile, valid_halo)
+                    else:
+                        sr = G(lr_img.to(device))
                     hr_img = hr_img.to(device)
                     psnr.append(compute_PSNR(hr_img, sr, args.valid_shave))
                     if args.valid_ssim:
