@@ -363,6 +363,16 @@ int pesr_adam_step(float* p, const float* g, float* m, float* v, long n, float l
 int pesr_adam_step_dev(float* p, const float* g, float* m, float* v, long n, float* state, float beta1, float beta2, float eps,
                        float grad_scale, void* stream);
 
+/* Both forms of the step with an exponential moving average of the parameters kept in the same launch (an extension: the
+ * ema_decay of ESRGAN-style trainers): after p' is formed, ema' = ema + (p' - ema) * (1 - ema_decay), in fp32, with (1 - ema_decay)
+ * formed once on the host.  p, m, v come out bit-identical to pesr_adam_step / pesr_adam_step_dev on the same inputs.  ema has n
+ * floats.  PESR_EINVAL, with nothing launched, for n % 4 != 0, ema == NULL, ema_decay outside (0, 1), and as for the plain forms
+ * step < 1 / state == NULL. */
+int pesr_adam_ema_step(float* p, const float* g, float* m, float* v, long n, float lr, float beta1, float beta2, float eps,
+                       int step, float grad_scale, float* ema, float ema_decay, void* stream);
+int pesr_adam_ema_step_dev(float* p, const float* g, float* m, float* v, long n, float* state, float beta1, float beta2, float eps,
+                           float grad_scale, float* ema, float ema_decay, void* stream);
+
 /* ---- convs whose epilogue leaves the BatchNorm sums (round 6, ABI 18): SURVEY K10 for the Discriminator's BasicBlocks (reference
  * model/basic.py:26-30: conv -> BatchNorm2d(train) -> LeakyReLU).  Replaces aten::native_batch_norm's statistics pass and
  * aten::native_batch_norm_backward's reduction pass: the conv kernel that WRITES a tensor also leaves, per pixel tile, the per-channel sums the

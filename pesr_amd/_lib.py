@@ -95,6 +95,8 @@ SIGNATURES.update({
                                   _P, _P, _P]),
     "pesr_adam_step": (c_int, [_P, _P, _P, _P, c_long, c_float, c_float, c_float, c_float, c_int, c_float, _P]),
     "pesr_adam_step_dev": (c_int, [_P, _P, _P, _P, c_long, _P, c_float, c_float, c_float, c_float, _P]),
+    "pesr_adam_ema_step": (c_int, [_P, _P, _P, _P, c_long, c_float, c_float, c_float, c_float, c_int, c_float, _P, c_float, _P]),
+    "pesr_adam_ema_step_dev": (c_int, [_P, _P, _P, _P, c_long, _P, c_float, c_float, c_float, c_float, _P, c_float, _P]),
     "pesr_conv3x3_bn_rows": (c_long, [c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
     "pesr_conv3x3_fwd_bn": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P, c_size_t, _P, _P]),
     "pesr_conv3x3_dgrad_bn": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P, c_size_t, _P, _P]),

@@ -2,6 +2,9 @@
 // eps 1e-8, no weight decay, no amsgrad).  Follows torch's single-tensor update order:
 //   m = lerp(m, g, 1-b1) ; v = b2*v + (1-b2)*g*g ; p -= (lr/bc1) * m / (sqrt(v)/sqrt(bc2) + eps)
 // HBM-bound: reads p, g, m, v and writes p, m, v once (28 B per parameter).
+// The *_ema_* forms also keep an exponential moving average of p in a fourth read-write stream (36 B per parameter): it is
+// updated from the new p while that is still in registers.  They are kernels of their own, so the plain forms stay the code
+// they were, and they share adam_update, so p, m, v come out bit-identical with the average on or off.
 #include "common.h"
 #include "launchers.h"
 
@@ -93,5 +96,62 @@ int pesr_adam_dev_launch(float* p, const float* g, float* m, float* v, long n, f
     hipLaunchKernelGGL(adam_tick_kernel, dim3(1), dim3(64), 0, stream, state, b1, b2);
     hipLaunchKernelGGL(adam_dev_kernel, dim3(grid), dim3(256), 0, stream, (f32x4*)p, (const f32x4*)g, (f32x4*)m, (f32x4*)v, n4, 1.0f - b1, b2,
                        1.0f - b2, (const float*)state, eps, gscale);
+    return pesr_launch_status();
+}
+
+// ---- Adam + EMA of the parameters: e' = e + (p' - e) * (1 - decay), both forms of the step ------------------------------------
+// DEV = false: step_size / bc2_sqrt are kernel arguments (pesr_adam_ema_step); DEV = true: they are read from state[2..3]
+// (pesr_adam_ema_step_dev, hipGraph replay).  e is loaded and stored like m and v: read once per step like the gradient, but it
+// is written back, and a line about to be rewritten gains nothing from a non-temporal read.
+__device__ __forceinline__ void ema_update(f32x4& ee, const f32x4& pp, float one_minus_d) { ee = ee + (pp - ee) * one_minus_d; }
+template <bool DEV>
+__global__ void adam_ema_kernel(f32x4* __restrict__ p, const f32x4* __restrict__ g, f32x4* __restrict__ m, f32x4* __restrict__ v,
+                                f32x4* __restrict__ ema, long n4, float one_minus_b1, float b2, float one_minus_b2, float step_size_arg,
+                                float bc2_sqrt_arg, const float* __restrict__ state, float eps, float gscale, float one_minus_d) {
+    const float step_size = DEV ? state[2] : step_size_arg, bc2_sqrt = DEV ? state[3] : bc2_sqrt_arg;
+    const long stride = (long)gridDim.x * blockDim.x;
+    long e = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    for (; e + stride < n4; e += 2 * stride) {
+        const long e1 = e + stride;
+        f32x4 g0 = __builtin_nontemporal_load(g + e), g1 = __builtin_nontemporal_load(g + e1);
+        f32x4 m0 = m[e], v0 = v[e], p0 = p[e], a0 = ema[e], m1 = m[e1], v1 = v[e1], p1 = p[e1], a1 = ema[e1];
+        adam_update(p0, m0, v0, g0, one_minus_b1, b2, one_minus_b2, step_size, bc2_sqrt, eps, gscale);
+        adam_update(p1, m1, v1, g1, one_minus_b1, b2, one_minus_b2, step_size, bc2_sqrt, eps, gscale);
+        ema_update(a0, p0, one_minus_d);
+        ema_update(a1, p1, one_minus_d);
+        p[e] = p0; m[e] = m0; v[e] = v0; ema[e] = a0; p[e1] = p1; m[e1] = m1; v[e1] = v1; ema[e1] = a1;
+    }
+    for (; e < n4; e += stride) {
+        f32x4 mm = m[e], vv = v[e], pp = p[e], aa = ema[e];
+        adam_update(pp, mm, vv, g[e], one_minus_b1, b2, one_minus_b2, step_size, bc2_sqrt, eps, gscale);
+        ema_update(aa, pp, one_minus_d);
+        p[e] = pp; m[e] = mm; v[e] = vv; ema[e] = aa;
+    }
+}
+
+static inline bool ema_args_ok(long n, const float* ema, float decay) { return n % 4 == 0 && ema && decay > 0.0f && decay < 1.0f; }
+
+int pesr_adam_ema_launch(float* p, const float* g, float* m, float* v, float* ema, long n, float lr, float b1, float b2, float eps, int step,
+                         float gscale, float decay, hipStream_t stream) {
+    if (!ema_args_ok(n, ema, decay) || step < 1) return PESR_EINVAL;
+    const double bc1 = 1.0 - pow((double)b1, (double)step);
+    const double bc2 = 1.0 - pow((double)b2, (double)step);
+    const float step_size = (float)((double)lr / bc1);
+    const float bc2_sqrt = (float)sqrt(bc2);
+    const long n4 = n / 4;
+    const int grid = (int)((n4 + 255) / 256 < 8192 ? (n4 + 255) / 256 : 8192);
+    hipLaunchKernelGGL(adam_ema_kernel<false>, dim3(grid), dim3(256), 0, stream, (f32x4*)p, (const f32x4*)g, (f32x4*)m, (f32x4*)v, (f32x4*)ema,
+                       n4, 1.0f - b1, b2, 1.0f - b2, step_size, bc2_sqrt, (const float*)nullptr, eps, gscale, 1.0f - decay);
+    return pesr_launch_status();
+}
+
+int pesr_adam_ema_dev_launch(float* p, const float* g, float* m, float* v, float* ema, long n, float* state, float b1, float b2, float eps,
+                             float gscale, float decay, hipStream_t stream) {
+    if (!ema_args_ok(n, ema, decay) || !state) return PESR_EINVAL;
+    const long n4 = n / 4;
+    const int grid = (int)((n4 + 255) / 256 < 8192 ? (n4 + 255) / 256 : 8192);
+    hipLaunchKernelGGL(adam_tick_kernel, dim3(1), dim3(64), 0, stream, state, b1, b2);
+    hipLaunchKernelGGL(adam_ema_kernel<true>, dim3(grid), dim3(256), 0, stream, (f32x4*)p, (const f32x4*)g, (f32x4*)m, (f32x4*)v, (f32x4*)ema,
+                       n4, 1.0f - b1, b2, 1.0f - b2, 0.0f, 0.0f, (const float*)state, eps, gscale, 1.0f - decay);
     return pesr_launch_status();
 }

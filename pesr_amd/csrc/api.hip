@@ -236,6 +236,16 @@ PESR_API int pesr_adam_step_dev(float* p, const float* g, float* m, float* v, lo
     return pesr_adam_dev_launch(p, g, m, v, n, state, beta1, beta2, eps, grad_scale, (hipStream_t)stream);
 }
 
+PESR_API int pesr_adam_ema_step(float* p, const float* g, float* m, float* v, long n, float lr, float beta1, float beta2, float eps,
+                                int step, float grad_scale, float* ema, float ema_decay, void* stream) {
+    return pesr_adam_ema_launch(p, g, m, v, ema, n, lr, beta1, beta2, eps, step, grad_scale, ema_decay, (hipStream_t)stream);
+}
+
+PESR_API int pesr_adam_ema_step_dev(float* p, const float* g, float* m, float* v, long n, float* state, float beta1, float beta2,
+                                    float eps, float grad_scale, float* ema, float ema_decay, void* stream) {
+    return pesr_adam_ema_dev_launch(p, g, m, v, ema, n, state, beta1, beta2, eps, grad_scale, ema_decay, (hipStream_t)stream);
+}
+
 PESR_API int pesr_conv3x3_rgb_fwd(const float* x, const float* w, const float* bias, float* y, int N, int H, int W, int Cout,
                                   int act, float slope, void* stream) {
     return pesr_conv_rgb_in_launch(x, w, bias, y, N, H, W, Cout, act, slope, (hipStream_t)stream);

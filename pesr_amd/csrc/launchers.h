@@ -90,6 +90,10 @@ int pesr_loss_mse_launch(const float* a, const float* b, float* grad, float* out
                          hipStream_t stream);
 int pesr_gan_loss_launch(const float* pred_real, const float* pred_fake, int B, int gan, int side, int focal, float gamma, float scale,
                          float* out, float* d_real, float* d_fake, hipStream_t stream);
+int pesr_adam_ema_launch(float* p, const float* g, float* m, float* v, float* ema, long n, float lr, float b1, float b2, float eps, int step,
+                         float gscale, float decay, hipStream_t stream);
+int pesr_adam_ema_dev_launch(float* p, const float* g, float* m, float* v, float* ema, long n, float* state, float b1, float b2, float eps,
+                             float gscale, float decay, hipStream_t stream);
 int pesr_adam_dev_launch(float* p, const float* g, float* m, float* v, long n, float* state, float b1, float b2, float eps, float gscale,
                          hipStream_t stream);
 int pesr_adam_launch(float* p, const float* g, float* m, float* v, long n, float lr, float b1, float b2, float eps, int step,

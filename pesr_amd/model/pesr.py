@@ -45,6 +45,7 @@ def scale_of_state_dict(sd):
 class Generator(nn.Module):
     def __init__(self, opt):
         super().__init__()
+        self.opt = dict(opt)               # (what a second Generator of this shape is built from: FlatAdam.ema_module)
         width, depth, res_scale = opt['num_channels'], opt['depth'], opt['res_scale']
         scale = opt.get('scale', 4)        # an extension: the reference's Generator is x4 only (docs/modes.md section 4e)
         if scale not in SCALES:

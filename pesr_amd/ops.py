@@ -1099,6 +1099,26 @@ def adam_step_dev(p, g, m, v, state, beta1, beta2, eps, grad_scale=1.0):
     _lib.check(rc, "pesr_adam_step_dev")
 
 
+def adam_ema_step(p, g, m, v, ema, ema_decay, lr, beta1, beta2, eps, step, grad_scale=1.0):
+    """adam_step plus ema += (p_new - ema) * (1 - ema_decay) in the same launch; p, m, v exactly as adam_step leaves them."""
+    for t, n in ((p, "p"), (g, "g"), (m, "m"), (v, "v"), (ema, "ema")):
+        _chk(t, f"adam_ema_step.{n}")
+    assert ema.numel() == p.numel()
+    rc = _lib.lib().pesr_adam_ema_step(_p(p), _p(g), _p(m), _p(v), p.numel(), lr, beta1, beta2, eps, step, grad_scale, _p(ema),
+                                       ema_decay, _stream())
+    _lib.check(rc, "pesr_adam_ema_step")
+
+
+def adam_ema_step_dev(p, g, m, v, ema, ema_decay, state, beta1, beta2, eps, grad_scale=1.0):
+    """adam_step_dev plus the moving average of adam_ema_step: capturable, the average is updated inside the replayed launch."""
+    for t, n in ((p, "p"), (g, "g"), (m, "m"), (v, "v"), (ema, "ema"), (state, "state")):
+        _chk(t, f"adam_ema_step_dev.{n}")
+    assert state.numel() == 6 and ema.numel() == p.numel()
+    rc = _lib.lib().pesr_adam_ema_step_dev(_p(p), _p(g), _p(m), _p(v), p.numel(), _p(state), beta1, beta2, eps, grad_scale, _p(ema),
+                                           ema_decay, _stream())
+    _lib.check(rc, "pesr_adam_ema_step_dev")
+
+
 def psnr_y(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     """Y-channel PSNR of two [1, 3, H, W] image tensors (NCHW-contiguous or channels_last) -> device double [mse, psnr]."""
     outs = []

@@ -206,9 +206,16 @@ class FlatAdam(torch.optim.Optimizer):
 
     A torch.optim.Optimizer subclass so lr_scheduler.StepLR (reference train.py:127-128) drives
     param_groups[0]['lr'] unchanged.  zero_grad() zeroes (never sets to None): like the reference's torch 0.4,
-    a parameter that received no gradient still takes a (zero-gradient) Adam step."""
+    a parameter that received no gradient still takes a (zero-gradient) Adam step.
 
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, process_group=None, bucket_bytes=32 << 20):
+    ema_decay > 0 keeps an exponential moving average of the parameters in `flat_ema` (same layout as `flat_p`, started as a copy
+    of it): ema += (p_new - ema) * (1 - ema_decay) inside the Adam kernel of every step (36 instead of 28 B per parameter, no
+    launch of its own, and part of a captured step).  ema_module() gives a network that reads the averaged weights.
+
+    state_dict() / load_state_dict() speak torch.optim.Adam's schema (per-parameter step / exp_avg / exp_avg_sq in the parameters'
+    own shapes), so either optimizer loads the other's state; with the average on, `ema` and `ema_decay` are added at top level."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, process_group=None, bucket_bytes=32 << 20, ema_decay=0.0):
         params = [p for p in params]
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps))
         assert len(self.param_groups) == 1
@@ -220,6 +227,11 @@ class FlatAdam(torch.optim.Optimizer):
         self.dev_state = None        # use_device_state(): lr and step count in device memory (hipGraph replay)
         self._dev_lr = None
         self.last_scale = 1.0        # the 1/world factor of the latest step (flat_g holds the SUM over ranks)
+        if not 0.0 <= ema_decay < 1.0:
+            raise ValueError(f"FlatAdam: ema_decay must be 0 (off) or in (0, 1), got {ema_decay}")
+        self.ema_decay = float(ema_decay)
+        self.flat_ema = self.flat.flat_p.clone() if self.ema_decay > 0 else None
+        self._ema_params = []        # the parameters ema_module() made: views into flat_ema (refresh_ema)
         PF.bump_weight_epoch(self.flat.params)
 
     def zero_grad(self, set_to_none: bool = False) -> None:  # noqa: ARG002 (kept for API compatibility)
@@ -229,15 +241,20 @@ class FlatAdam(torch.optim.Optimizer):
     def use_device_state(self) -> torch.Tensor:
         """Move the step-dependent Adam scalars to device memory (include/pesr_hip.h pesr_adam_step_dev): from now on step()
         launches nothing whose kernel arguments change from step to step, so a captured step can be replayed.  The host keeps
-        counting in self.steps (state_dict, logging); a replay that runs without step() must add to it itself."""
+        counting in self.steps, which is what state_dict() records as every parameter's `step`; a replay that runs without
+        step() must add to it itself (Trainer._replay does).  load_state_dict() rewrites the device copy of the count."""
         if self.dev_state is None:
-            st = torch.zeros(6, dtype=torch.float32, device=self.flat.flat_p.device)
-            st.view(torch.int32)[4] = self.steps & 0x7fffffff
-            st.view(torch.int32)[5] = self.steps >> 31
-            assert self.steps < (1 << 31)
-            self.dev_state = st
+            self.dev_state = torch.zeros(6, dtype=torch.float32, device=self.flat.flat_p.device)
+            self._write_dev_count()
             self.sync_lr_to_device()
         return self.dev_state
+
+    def _write_dev_count(self) -> None:
+        """self.steps into the two 32-bit halves of the device state (include/pesr_hip.h pesr_adam_step_dev)."""
+        assert 0 <= self.steps < (1 << 31)
+        halves = self.dev_state.view(torch.int32)
+        halves[4] = self.steps
+        halves[5] = 0
 
     def sync_lr_to_device(self) -> None:
         """Write param_groups[0]['lr'] (StepLR) into the device state; a no-op while it is unchanged.  NOT capturable - call it
@@ -260,10 +277,127 @@ class FlatAdam(torch.optim.Optimizer):
         if self.dev_state is not None:
             if not torch.cuda.is_current_stream_capturing():
                 self.sync_lr_to_device()
-            ops.adam_step_dev(self.flat.flat_p, self.flat.flat_g, self.exp_avg, self.exp_avg_sq, self.dev_state, g["betas"][0],
-                              g["betas"][1], g["eps"], scale)
+            if self.flat_ema is not None:
+                ops.adam_ema_step_dev(self.flat.flat_p, self.flat.flat_g, self.exp_avg, self.exp_avg_sq, self.flat_ema, self.ema_decay,
+                                      self.dev_state, g["betas"][0], g["betas"][1], g["eps"], scale)
+            else:
+                ops.adam_step_dev(self.flat.flat_p, self.flat.flat_g, self.exp_avg, self.exp_avg_sq, self.dev_state, g["betas"][0],
+                                  g["betas"][1], g["eps"], scale)
+        elif self.flat_ema is not None:
+            ops.adam_ema_step(self.flat.flat_p, self.flat.flat_g, self.exp_avg, self.exp_avg_sq, self.flat_ema, self.ema_decay, g["lr"],
+                              g["betas"][0], g["betas"][1], g["eps"], self.steps, scale)
         else:
             ops.adam_step(self.flat.flat_p, self.flat.flat_g, self.exp_avg, self.exp_avg_sq, g["lr"], g["betas"][0],
                           g["betas"][1], g["eps"], self.steps, scale)
         PF.bump_weight_epoch(self.flat.params)   # this optimizer's packed conv weights are now stale ...
         PF.repack_all(self.flat.params)          # ... and are refreshed here in one batched launch
+
+    # ---- state in torch.optim.Adam's schema ------------------------------------------------------------------------------------
+    def _per_param(self, flat: torch.Tensor):
+        """Copies of the parameters' slices of a flat buffer, in the parameters' shapes (the alignment padding stays behind)."""
+        return [flat[o:o + p.numel()].view(p.shape).clone() for p, o in zip(self.flat.params, self.flat.offsets)]
+
+    def state_dict(self):
+        g = self.param_groups[0]
+        m, v = self._per_param(self.exp_avg), self._per_param(self.exp_avg_sq)
+        group = {k: (list(range(len(self.flat.params))) if k == "params" else val) for k, val in g.items()}
+        # torch.optim.Adam's remaining options at the values this optimizer implements (no weight decay, no amsgrad, ...): a
+        # torch.optim.Adam that loaded this state takes its groups from it and must find them to step
+        for k, val in torch.optim.Adam([torch.zeros(1)]).defaults.items():
+            group.setdefault(k, val)
+        sd = {"state": {}, "param_groups": [group]}
+        if self.steps > 0:                 # (torch.optim.Adam has no state before its first step either)
+            for i in range(len(self.flat.params)):
+                sd["state"][i] = {"step": torch.tensor(float(self.steps)), "exp_avg": m[i], "exp_avg_sq": v[i]}
+        if self.flat_ema is not None:
+            sd["ema"] = self._per_param(self.flat_ema)
+            sd["ema_decay"] = self.ema_decay
+        return sd
+
+    @torch.no_grad()
+    def load_state_dict(self, state_dict) -> None:
+        params = self.flat.params
+        groups = state_dict["param_groups"]
+        if len(groups) != 1 or len(groups[0]["params"]) != len(params):
+            raise ValueError(f"FlatAdam.load_state_dict: the state has {sum(len(g['params']) for g in groups)} parameters in "
+                             f"{len(groups)} group(s), this optimizer has {len(params)} in one")
+        ids = list(groups[0]["params"])
+        state = state_dict["state"]
+        ema = state_dict.get("ema")
+        if (ema is not None) != (self.flat_ema is not None):
+            raise ValueError("FlatAdam.load_state_dict: the state was saved %s a moving average (ema) and this optimizer runs %s one"
+                             % (("with", "without") if ema is not None else ("without", "with")))
+        if ema is not None and len(ema) != len(params):
+            raise ValueError(f"FlatAdam.load_state_dict: ema has {len(ema)} tensors for {len(params)} parameters")
+        for i, p in enumerate(params):      # every shape is checked before anything is written
+            for what, t in (("exp_avg", state.get(ids[i], {}).get("exp_avg")), ("exp_avg_sq", state.get(ids[i], {}).get("exp_avg_sq")),
+                            ("ema", None if ema is None else ema[i])):
+                if t is not None and tuple(t.shape) != tuple(p.shape):
+                    raise ValueError(f"FlatAdam.load_state_dict: parameter {i}: {what} has shape {tuple(t.shape)} in the state, the "
+                                     f"parameter has {tuple(p.shape)}")
+        steps = {int(float(state[k]["step"])) for k in ids if k in state}
+        if len(steps) > 1:
+            raise ValueError(f"FlatAdam.load_state_dict: one step count for the whole flat buffer, the state has {sorted(steps)}")
+        if state and len([k for k in ids if k in state]) != len(params):
+            raise ValueError("FlatAdam.load_state_dict: the state covers only some of the parameters")
+        for i, (p, o) in enumerate(zip(params, self.flat.offsets)):
+            n = p.numel()
+            st = state.get(ids[i])
+            for flat, t in ((self.exp_avg, None if st is None else st["exp_avg"]), (self.exp_avg_sq, None if st is None else st["exp_avg_sq"])):
+                if t is None:
+                    flat[o:o + n].zero_()
+                else:
+                    flat[o:o + n].copy_(t.reshape(-1))
+            if ema is not None:
+                self.flat_ema[o:o + n].copy_(ema[i].reshape(-1))
+        self.steps = steps.pop() if steps else 0
+        g = self.param_groups[0]
+        for k, val in groups[0].items():    # lr, betas, eps (and StepLR's initial_lr); torch.optim.Adam's other options are not ours
+            if k != "params" and (k in g or k == "initial_lr"):
+                g[k] = val
+        if self.dev_state is not None:
+            self._write_dev_count()
+            self._dev_lr = None
+            self.sync_lr_to_device()
+        PF.bump_weight_epoch(params)
+        self.refresh_ema()
+
+    # ---- the averaged weights as a network ---------------------------------------------------------------------------------------
+    def ema_module(self, template: torch.nn.Module, fresh: Optional[torch.nn.Module] = None) -> torch.nn.Module:
+        """A module of the template's class whose parameters are requires_grad=False views into flat_ema, at the offsets of the
+        template's (live) parameters in flat_p; parameters and buffers of the template that this optimizer does not own are
+        copied.  `fresh` is a newly constructed module of that class (default: type(template)(template.opt)) - never a deepcopy:
+        the live parameters carry flat-gradient registrations and packed-weight caches that must not be shared.  Its weights
+        change through raw pointers: call refresh_ema() before running it."""
+        if self.flat_ema is None:
+            raise ValueError("FlatAdam.ema_module: this optimizer keeps no moving average (ema_decay = 0)")
+        if fresh is None:
+            rng = torch.random.get_rng_state()      # the construction draws an initialisation nobody uses
+            fresh = type(template)(template.opt)
+            torch.random.set_rng_state(rng)
+        fresh = fresh.to(self.flat_ema.device)
+        where = {id(p): (o, p.numel()) for p, o in zip(self.flat.params, self.flat.offsets)}
+        live = dict(template.named_parameters())
+        mine = dict(fresh.named_parameters())
+        if list(live) != list(mine):
+            raise ValueError("FlatAdam.ema_module: the fresh module's parameters are not the template's")
+        with torch.no_grad():
+            for name, q in mine.items():
+                p = live[name]
+                if id(p) in where:
+                    o, n = where[id(p)]
+                    q.data = self.flat_ema[o:o + n].view(p.shape)
+                    self._ema_params.append(q)
+                else:
+                    q.data = p.detach().clone()
+                q.requires_grad_(False)
+            for (_, b), (_, a) in zip(fresh.named_buffers(), template.named_buffers()):
+                b.copy_(a)
+        fresh.eval()
+        PF.bump_weight_epoch(self._ema_params)
+        return fresh
+
+    def refresh_ema(self) -> None:
+        """The steps since the last call rewrote flat_ema through raw pointers (graph replays included): mark the packed layouts
+        of the ema_module() weights stale.  Once before a validation pass, not per step - they are rebuilt only when used."""
+        PF.bump_weight_epoch(self._ema_params)

@@ -5,7 +5,8 @@ Same flags and defaults as the reference (train.py:21-77) plus `--synthetic N` (
 the DIV2K cache, which is out of scope here).  One process per GPU: run plainly for one GPU, or under
 `python -m torch.distributed.run --nproc-per-node N train.py ...` for N (RCCL gradient all-reduce inside the
 optimizers replaces nn.DataParallel; --batch_size stays the GLOBAL batch as in the reference, each rank takes 1/N).
-tensorboardX is optional.  Checkpoints keep the reference's format: torch.save(G.state_dict()).
+tensorboardX is optional.  Checkpoints keep the reference's format: torch.save(G.state_dict()).  --save_state_every / --resume
+add a full training state file next to them (pesr_amd/checkpoint.py), --ema_decay a moving average of G's weights.
 """
 import argparse
 import json
@@ -15,7 +16,7 @@ import numpy as np
 import torch
 import torch.distributed as dist
 import torch.optim.lr_scheduler as lr_scheduler
-from torch.utils.data import DataLoader
+from torch.utils.data import DataLoader, RandomSampler
 from torch.utils.data.distributed import DistributedSampler
 
 
@@ -93,6 +94,15 @@ def build_parser():
                         "pixels a tile owns; 0 (default) = off, one Generator call on the whole image")
     p.add_argument("--valid_tile_halo", type=int, default=-1,
                    help="with --valid_tile: LR pixels of context around a tile; -1 = 2 * num_blocks + 4, the exact one")
+    p.add_argument("--save_state_every", type=int, default=0,
+                   help="at the end of every N-th epoch write <check_point>/<phase>/train_state.pt: both networks, both optimizers, the "
+                        "schedulers, the epoch, the random streams (docs/modes.md section 4i); 0 (default) = never")
+    p.add_argument("--resume", type=str, default="",
+                   help="a training state file to continue from (with the epoch after the one it records), or 'auto': this run's own "
+                        "<check_point>/<phase>/train_state.pt if it exists, a fresh start otherwise")
+    p.add_argument("--ema_decay", type=float, default=0.0,
+                   help="keep an exponential moving average of the Generator's weights with this decay (typical: 0.999), updated inside "
+                        "the Adam kernel; validation and the saved models then use the averaged weights.  0 (default) = off")
     return p
 
 
@@ -100,6 +110,13 @@ def device_lr_from_hr(scale, device):
     """The callable FolderSRDataset(lr_from_hr=...) wants, on the device resize: uint8 HWC array -> uint8 HWC array."""
     from pesr_amd.resize import imresize_u8
     return lambda hr: imresize_u8(torch.from_numpy(np.array(hr)).to(device), scale, up=False).cpu().numpy()
+
+
+def spawn_generator():
+    """A generator of its own, started from torch's global stream (so torch.manual_seed still decides everything)."""
+    g = torch.Generator()
+    g.manual_seed(int(torch.empty((), dtype=torch.int64).random_().item()))
+    return g
 
 
 def make_loaders(args, rank, world, need_train=True, device=None):
@@ -119,7 +136,13 @@ def make_loaders(args, rank, world, need_train=True, device=None):
     sampler = train_loader = None
     if train_set is not None:
         sampler = DistributedSampler(train_set, world, rank, shuffle=True, drop_last=True) if world > 1 else None
-        train_loader = DataLoader(train_set, batch_size=args.batch_size // world, shuffle=sampler is None, sampler=sampler,
+        # The shuffle (one GPU; DistributedSampler's is a function of the epoch) and the seed of the loader's workers are drawn from
+        # generators of their own.  The iterator draws its workers' seed when it is CREATED - in the first epoch of a process, not in
+        # the later ones, which reuse the workers -, so on torch's global stream a resumed run would be one draw ahead of the run that
+        # was never stopped.  The shuffle generator is part of the training state (main: checkpoint.rng_snapshot).
+        train_loader = DataLoader(train_set, batch_size=args.batch_size // world,
+                                  sampler=sampler if sampler is not None else RandomSampler(train_set, generator=spawn_generator()),
+                                  generator=spawn_generator(),
                                   num_workers=4, pin_memory=True, drop_last=True, persistent_workers=True)   # (forked once: a fork of a
         # process with a GPU context's mappings takes seconds, and without this flag every epoch forks its four workers anew)
     val_loader = DataLoader(val_set, batch_size=1, shuffle=False, num_workers=1, pin_memory=True)
@@ -234,6 +257,10 @@ def check_limits(args, world):
                          f"{args.scale}")
     from pesr_amd.tile import check_flags
     check_flags("train.py", ("--valid_tile", "--valid_tile_halo"), args.valid_tile, args.valid_tile_halo, 1, args.num_blocks, args.scale)
+    if not 0.0 <= args.ema_decay < 1.0:
+        raise SystemExit(f"train.py: --ema_decay {args.ema_decay} must be 0 (off) or inside (0, 1)")
+    if args.save_state_every < 0:
+        raise SystemExit(f"train.py: --save_state_every {args.save_state_every} must be 0 (never) or a number of epochs")
     if args.phase != "pretrain" and args.scale == 4 and args.patch_size % 4:
         raise SystemExit("train.py: the GAN phase needs --patch_size % 4 == 0 (HR patches must survive four stride-2 stages and "
                          "VGG's four 2x2 max-pools, which this implementation does for even sizes only)")
@@ -284,18 +311,29 @@ def main(argv=None):
         train_loader = sampler = make_gpu_loader(args, rank, world, device)      # (it has set_epoch like a DistributedSampler)
     opt = {"patch_size": args.patch_size, "num_channels": args.num_channels, "depth": args.num_blocks,
            "res_scale": args.res_scale, "spectral_norm": args.spectral_norm, "scale": args.scale}
+    from pesr_amd import checkpoint
+    resume_path = checkpoint.resolve_resume(args.resume, args.check_point, args.phase)
+    state = None
+    if resume_path is not None:
+        state = checkpoint.load_state(resume_path)          # (every rank reads the file)
+        checkpoint.check_flags(state, args, resume_path)
+    elif args.resume and rank == 0:
+        print("resume: no %s yet, starting fresh" % checkpoint.state_path(args.check_point, args.phase))
     G = Generator(opt)
-    if args.pretrained_model:
+    if args.pretrained_model and state is None:
         G.load_state_dict(torch.load(args.pretrained_model, map_location="cpu"))
     G = G.to(device)
     gan = args.phase != "pretrain"
     D = Discriminator(opt).to(device) if gan else None
     vgg = build_vgg(args, device, rank, world) if gan else None
 
-    optim_G = FlatAdam([p for p in G.parameters() if p.requires_grad], lr=args.learning_rate, betas=(0.9, 0.999))
+    optim_G = FlatAdam([p for p in G.parameters() if p.requires_grad], lr=args.learning_rate, betas=(0.9, 0.999),
+                       ema_decay=args.ema_decay)
     optim_D = FlatAdam(D.parameters(), lr=args.learning_rate, betas=(0.9, 0.999)) if gan else None
     if world > 1:  # replicas start identical
         dist.broadcast(optim_G.flat.flat_p, 0)
+        if optim_G.flat_ema is not None:
+            optim_G.flat_ema.copy_(optim_G.flat.flat_p)      # (the average starts from the weights every replica now holds)
         if gan:
             dist.broadcast(optim_D.flat.flat_p, 0)
     scheduler_G = lr_scheduler.StepLR(optim_G, step_size=args.lr_step, gamma=0.5)
@@ -305,6 +343,9 @@ def main(argv=None):
                       world_size=world, gradient_penalty=args.GP)
 
     check_point = os.path.join(args.check_point, args.phase)
+    # what checkpoint.rng_snapshot / rng_restore get besides the process-wide streams: the GPU input pipeline's crop stream, or the
+    # host loader's shuffle generator (one GPU)
+    rng_extra = {"gpu_loader": train_loader} if gpu_pipe else {"shuffle": getattr(train_loader.sampler, "generator", None)}
     tb = None
     if rank == 0:
         os.makedirs(check_point, exist_ok=True)
@@ -314,6 +355,19 @@ def main(argv=None):
         except ImportError:
             pass
     best_psnr = 0.0
+    first_epoch = 1
+    if state is not None:
+        checkpoint.restore(state, G, D, optim_G, optim_D, scheduler_G, scheduler_D)
+        best_psnr, first_epoch = state["best_psnr"], state["epoch"] + 1
+        if rank == 0:
+            print("resume: %s, epoch %d done, going on with epoch %d at lr %g (--pretrained_model, --learning_rate and --lr_step are "
+                  "the state's)" % (resume_path, state["epoch"], first_epoch, optim_G.param_groups[0]["lr"]))
+            if state["world"] != world:
+                print("resume: the state was saved by %d rank(s), this run has %d: model, optimizer and schedule state are exact, the "
+                      "random streams start fresh" % (state["world"], world))
+    # with --ema_decay the averaged weights are what is validated and saved (the raw ones live in the state file)
+    G_eval = optim_G.ema_module(G) if args.ema_decay > 0 else G
+    ema_tag = " (EMA)" if args.ema_decay > 0 else ""
     keys = ("l1", "vgg", "g", "tv", "d") if gan else ("l1",)
     graphed, graph_shapes, eager_at_shape = None, None, 0
     use_graph = device.type == "cuda" and (world == 1 if args.hip_graph == "auto" else str2bool(args.hip_graph))
@@ -322,13 +376,29 @@ def main(argv=None):
     dp_calibrate = dp_on and args.dp_policy == "auto"
     if dp_on and args.dp_policy != "auto":
         trainer.set_dp_policy(args.dp_policy)
+    elif dp_calibrate and state is not None and state["world"] == world and state["dp"]["policy"] is not None:
+        # the first run measured (and its measurement consumed training steps): a resumed run takes that schedule, it does not re-time
+        dp_calibrate = False
+        trainer.set_dp_policy(state["dp"]["policy"])
+        use_graph = use_graph or bool(state["dp"].get("graph"))
+        if rank == 0:
+            now = [type(t).__name__ for t in trainer._transports()]
+            print("data-parallel schedule: '%s' as recorded in the state (not measured again)%s" % (
+                trainer.dp_policy, "" if not now or now[0] == state["dp"]["transport"] else
+                "; gradient exchange over %s, the state's run used %s" % (now[0], state["dp"]["transport"])))
     CALIB_STEPS = 3
     peer_cand = str2bool(args.dp_peer_candidate) and world > 1
     # iterations the calibration consumes at most (its own worst-case count: eager candidates, the peer-memory candidate, the capture's
     # batch and the replays - ADVICE r05: the peer candidate was not counted and the calibration could run off the end of an epoch)
     calib_need = Trainer.calibration_batches("gan" if gan else "pretrain", CALIB_STEPS, graph=args.hip_graph == "auto", peer_candidate=peer_cand) + 2
 
+    if state is not None and state["world"] == world:
+        # last of all: nothing between here and the first batch draws from these streams
+        checkpoint.rng_restore(state["rng"][rank], device, **rng_extra)
+    state = None        # (its tensors are loaded; drop the host copy)
     for epoch in range(1, args.num_epochs + 1):
+        if epoch < first_epoch:     # --resume: the state holds these epochs
+            continue
         # The reference calls scheduler.step() at epoch START (train.py:156,185-186); under its pinned torch 0.4 the
         # constructor leaves last_epoch = -1, so epoch e trains at lr*0.5^((e-1)//lr_step) (first halving: epoch lr_step+1).
         # On torch >= 1.1 the constructor already counts one step, so the same schedule is: step at the END of every epoch.
@@ -406,18 +476,20 @@ def main(argv=None):
         # validation on rank 0 (full images, batch 1, no_grad), reference train.py:281-295
         if rank == 0:
             psnr, ssim = [], []
+            if G_eval is not G:
+                optim_G.refresh_ema()       # the steps of this epoch rewrote the averaged weights through raw pointers
             with torch.no_grad():
                 for lr_img, hr_img in val_loader:
                     if args.valid_tile:
-                        sr, _ = tiled_forward(G, lr_img.to(device), args.scale, args.valid_tile, valid_halo)
+                        sr, _ = tiled_forward(G_eval, lr_img.to(device), args.scale, args.valid_tile, valid_halo)
                     else:
-                        sr = G(lr_img.to(device))
+                        sr = G_eval(lr_img.to(device))
                     hr_img = hr_img.to(device)
                     psnr.append(compute_PSNR(hr_img, sr, args.valid_shave))
                     if args.valid_ssim:
                         ssim.append(compute_SSIM(hr_img, sr, args.valid_shave))
             val_psnr = float(np.mean(psnr)) if psnr else 0.0
-            print("Finish valid [%d/%d]. PSNR: %.4fdB" % (epoch, args.num_epochs, val_psnr))
+            print("Finish valid [%d/%d]. PSNR: %.4fdB%s" % (epoch, args.num_epochs, val_psnr, ema_tag))
             if tb is not None:
                 tb.add_scalar("Validate PSNR", val_psnr, epoch)
             if args.valid_ssim:
@@ -427,12 +499,19 @@ def main(argv=None):
                     tb.add_scalar("Validate SSIM", val_ssim, epoch)
             if not gan and val_psnr > best_psnr:
                 best_psnr = val_psnr
-                torch.save(G.state_dict(), os.path.join(check_point, "best_model.pt"))
+                torch.save(G_eval.state_dict(), os.path.join(check_point, "best_model.pt"))
             elif gan and epoch % args.snapshot_every == 0:
-                torch.save(G.state_dict(), os.path.join(check_point, "model_%d.pt" % epoch))
+                torch.save(G_eval.state_dict(), os.path.join(check_point, "model_%d.pt" % epoch))
         scheduler_G.step()
         if gan:
             scheduler_D.step()
+        if args.save_state_every and epoch % args.save_state_every == 0:
+            # after validation and the scheduler steps: the file describes the run as epoch + 1 will find it
+            rngs = checkpoint.gather_rng(checkpoint.rng_snapshot(device, **rng_extra), rank, world)
+            if rank == 0:
+                st = checkpoint.build_state(args, epoch, best_psnr, G, D, optim_G, optim_D, scheduler_G, scheduler_D, trainer, world, rngs)
+                st["dp"]["graph"] = graphed is not None
+                checkpoint.atomic_save(st, checkpoint.state_path(args.check_point, args.phase))
         if world > 1:
             dist.barrier()
     if world > 1:
