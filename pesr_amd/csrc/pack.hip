@@ -15,8 +15,8 @@
 
 // R (reduction channels) is zero-padded to a multiple of 16 and Nn ("n" channels) to 16 (if <= 16) or a multiple of 64, so
 // the 3-channel RGB layers run on the same MFMA kernels.
-__global__ void pack_conv3x3_kernel(const float* __restrict__ w, float* __restrict__ out, int O, int I, int mode, int ps,
-                                    int R, int Nn) {
+__device__ __forceinline__ void pack_conv3x3_direct(const float* __restrict__ w, float* __restrict__ out, int O, int I, int mode, int ps,
+                                                    int R, int Nn) {
     const long total = 9L * R * Nn;
     const int C = O >> 2;
     for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
@@ -33,16 +33,23 @@ __global__ void pack_conv3x3_kernel(const float* __restrict__ w, float* __restri
     }
 }
 
+__global__ void pack_conv3x3_kernel(const float* __restrict__ w, float* __restrict__ out, int O, int I, int mode, int ps,
+                                    int R, int Nn) {
+    pack_conv3x3_direct(w, out, O, I, mode, ps, R, Nn);
+}
+
 // Batched form: one launch packs many convs (all of a network's, right after its optimizer step).  desc[d] (8 int64):
-// {src ptr, dst ptr, O, I, mode, ps, R, Nn}; blockIdx.y = d.  mode 2 / 3: the Winograd F(2,3) packing of mode 0 / 1, 4 / 5: F(4,3),
-// 7 / 8: bf16, 9 / 10: split-bf16 (hi plane + lo plane).
+// {src ptr, dst ptr, O, I, mode, ps, R, Nn}; blockIdx.y = d.  mode = the family's base number (the `mode` field of its record in
+// pesr_amd/ops.py _FAMILIES) for the forward packing, + 1 for the dgrad one.  The transformed and bf16 packings below restate the
+// single-pack kernels that live with their conv kernels; tests/test_conv_gpu.py pins the two copies to each other bit for bit.
 __global__ void pack_conv3x3_batched_kernel(const long long* __restrict__ desc) {
     const long long* d = desc + (size_t)blockIdx.y * 8;
     const float* __restrict__ w = (const float*)d[0];
     float* __restrict__ out = (float*)d[1];
     const int O = (int)d[2], I = (int)d[3], mode = (int)d[4], ps = (int)d[5], R = (int)d[6], Nn = (int)d[7];
-    if (mode >= 7) {   // bf16 packing (conv3x3_bf16.hip): mode 7 = forward, 8 = dgrad; out[t][c][n][k], 32-channel chunks;
-        //                    9 / 10: the split-bf16 packing (conv3x3_bf16x3.hip): a hi plane (= modes 7 / 8) and a lo plane behind it
+    switch (mode) {
+    case 7: case 8:     // "bf16" (conv3x3_bf16.hip): out[t][c][n][k], 32-channel chunks
+    case 9: case 10: {  // "split-bf16" (conv3x3_bf16x3.hip): a hi plane (= modes 7 / 8) and a lo plane behind it
         const bool split = mode >= 9;
         const int m = split ? mode - 9 : mode - 7;
         const int Rr = m == 0 ? I : O, Nr = m == 0 ? O : I;
@@ -65,7 +72,7 @@ __global__ void pack_conv3x3_batched_kernel(const long long* __restrict__ desc) 
         }
         return;
     }
-    if (mode >= 4) {   // Winograd F(4,3) packing (conv3x3_wino4.hip): mode 4 = forward, 5 = dgrad
+    case 4: case 5: {   // "F(4,3)" (conv3x3_wino4.hip)
         // One thread per (n, k) of a 16 x 16 tile of (output row n, reduction channel 16c + k): it reads the nine taps of its
         // (o, i) pair once (36 contiguous bytes; a tile row is 576 contiguous bytes) and writes all 18 transformed values, each
         // into a slab where the tile's 256 (n, k) entries are ONE contiguous KiB.  (One thread per output element read every
@@ -100,25 +107,14 @@ __global__ void pack_conv3x3_batched_kernel(const long long* __restrict__ desc) 
         }
         return;
     }
-    if (mode >= 2) {   // Winograd packing (conv3x3_wino.hip): mode 2 = forward, 3 = dgrad
+    case 2: case 3: {   // "F(2,3)" (conv3x3_wino.hip)
         const long total_w = 12L * O * I;
         for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < total_w; e += (long)gridDim.x * blockDim.x)
             out[e] = pesr_wino_pack_elem(w, O, I, mode - 2, ps, e);
         return;
     }
-    const long total = 9L * R * Nn;
-    const int C = O >> 2;
-    for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
-        const int k = (int)(e & 15);
-        long rest = e >> 4;
-        const int n = (int)(rest % Nn); rest /= Nn;
-        const int c = (int)(rest % (R >> 4));
-        const int t = (int)(rest / (R >> 4));
-        const int red = c * 16 + k;
-        int o = mode == 0 ? n : red;
-        const int i = mode == 0 ? red : n;
-        if (ps) { const int sub = o / C, cc = o - sub * C; o = 4 * cc + sub; }
-        out[e] = (o < O && i < I) ? w[((long)o * I + i) * 9 + t] : 0.f;
+    default:            // 0 / 1: "direct"
+        pack_conv3x3_direct(w, out, O, I, mode, ps, R, Nn);
     }
 }
 

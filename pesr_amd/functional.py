@@ -6,6 +6,10 @@ arithmetic in torch except scalar-sized glue (gradient fan-in adds are autograd'
 """
 from __future__ import annotations
 
+import os
+import threading
+import weakref
+
 import torch
 from torch.autograd import Function
 
@@ -87,28 +91,27 @@ _ALL_PACKS = []   # weak registry of every PackedConvWeights (for the batched re
 
 
 class _PackSlot:
-    """The packed layouts of one weight tensor ON ONE DEVICE."""
-    __slots__ = ("fwd", "dgrad", "bias", "wfwd", "wdgrad", "w4fwd", "w4dgrad", "bfwd", "bdgrad", "sfwd", "sdgrad", "kf", "kd", "kb", "kwf",
-                 "kwd", "k4f", "k4d", "kbf", "kbd", "ksf", "ksd", "wref", "bref")
+    """The packed layouts of one weight tensor ON ONE DEVICE: packs[mode] = [packed, key of the tensor it was built from], under the
+    batched re-pack's mode numbers (csrc/pack.hip) - family.mode of ops._FAMILIES for the forward packing, + 1 for the dgrad one."""
+    __slots__ = ("packs", "wref", "bref")
 
     def __init__(self):
-        self.fwd = self.dgrad = self.bias = self.wfwd = self.wdgrad = self.w4fwd = self.w4dgrad = self.bfwd = self.bdgrad = None
-        self.sfwd = self.sdgrad = None
-        self.kf = self.kd = self.kb = self.kwf = self.kwd = self.k4f = self.k4d = self.kbf = self.kbd = self.ksf = self.ksd = None
+        self.packs = {}
         self.wref = None            # weakref to the weight tensor this slot was last built from
-        self.bref = None            # ... and to the bias tensor of its PixelShuffle-permuted copy
+        self.bref = None            # ... and to the bias tensor of its PixelShuffle-permuted copy (packs[_BIAS])
+
+
+_BIAS = 6       # the slot of the PixelShuffle-permuted bias: no mode of the batched kernel, a number in this bookkeeping only
 
 
 class PackedConvWeights:
-    """Per-module cache of the kernel-side weight layouts (forward / dgrad packing, PS-permuted bias).
+    """Per-module cache of the kernel-side weight layouts (forward / dgrad packing of each kernel family used, PS-permuted bias).
 
     One slot per device: nn.DataParallel's replicas are shallow copies that SHARE this object while their weights live
     on different GPUs and their forwards run on concurrent threads (SURVEY 8b "Threading") - every replica works on its
     own device's slot, and the lock makes the check-then-pack step atomic."""
 
     def __init__(self, ps: bool = False):
-        import threading
-        import weakref
         self.ps = ps
         self._slots = {}            # device index -> _PackSlot
         self._lock = threading.Lock()
@@ -127,102 +130,47 @@ class PackedConvWeights:
     def _key(t: torch.Tensor):
         return (t.data_ptr(), t._version, weight_epoch(t))
 
-    def _slot(self, w) -> _PackSlot:
-        idx = w.device.index if w.is_cuda else -1
+    def _slot(self, t) -> _PackSlot:
+        idx = t.device.index if t.is_cuda else -1
         sl = self._slots.get(idx)
         if sl is None:
             sl = self._slots[idx] = _PackSlot()
-        if sl.wref is None or sl.wref() is not w:
-            import weakref
-            sl.wref = weakref.ref(w)
         return sl
 
-    def _get(self, w, field, keyf, build):
+    def _get(self, w, family, dgrad: int):
+        assert tuple(w.shape[2:]) == (3, 3), f"PackedConvWeights: 3x3 kernels only, got a weight of shape {tuple(w.shape)}"
+        mode = family.mode + dgrad
         with self._lock:
             sl = self._slot(w)
+            if sl.wref is None or sl.wref() is not w:
+                sl.wref = weakref.ref(w)
             k = self._key(w)
-            if getattr(sl, keyf) != k:
-                setattr(sl, field, build())
-                setattr(sl, keyf, k)
-            return getattr(sl, field)
-
-    def fwd(self, w: torch.Tensor) -> torch.Tensor:
-        return self._get(w, "fwd", "kf", lambda: ops.pack_conv3x3(w.detach(), 0, self.ps))
-
-    def dgrad(self, w: torch.Tensor) -> torch.Tensor:
-        return self._get(w, "dgrad", "kd", lambda: ops.pack_conv3x3(w.detach(), 1, self.ps))
-
-    def wino_fwd(self, w: torch.Tensor):
-        return self._get(w, "wfwd", "kwf", lambda: ops.pack_conv3x3_wino(w.detach(), 0, self.ps))
-
-    def wino_dgrad(self, w: torch.Tensor):
-        return self._get(w, "wdgrad", "kwd", lambda: ops.pack_conv3x3_wino(w.detach(), 1, self.ps))
-
-    def wino4_fwd(self, w: torch.Tensor):
-        return self._get(w, "w4fwd", "k4f", lambda: ops.pack_conv3x3_wino4(w.detach(), 0, self.ps))
-
-    def wino4_dgrad(self, w: torch.Tensor):
-        return self._get(w, "w4dgrad", "k4d", lambda: ops.pack_conv3x3_wino4(w.detach(), 1, self.ps))
-
-    def bf16_fwd(self, w: torch.Tensor):
-        return self._get(w, "bfwd", "kbf", lambda: ops.pack_conv3x3_bf16(w.detach(), 0, self.ps))
-
-    def bf16_dgrad(self, w: torch.Tensor):
-        return self._get(w, "bdgrad", "kbd", lambda: ops.pack_conv3x3_bf16(w.detach(), 1, self.ps))
-
-    def bf16x3_fwd(self, w: torch.Tensor):
-        return self._get(w, "sfwd", "ksf", lambda: ops.pack_conv3x3_bf16x3(w.detach(), 0, self.ps))
-
-    def bf16x3_dgrad(self, w: torch.Tensor):
-        return self._get(w, "sdgrad", "ksd", lambda: ops.pack_conv3x3_bf16x3(w.detach(), 1, self.ps))
+            e = sl.packs.get(mode)
+            if e is None or e[1] != k:
+                e = sl.packs[mode] = [ops._pack(family, w.detach(), dgrad, self.ps), k]
+            return e[0]
 
     def for_fwd(self, w: torch.Tensor, x_shape, stride: int = 1):
-        """Packed weights for y = conv(x, w): Winograd F(4,3) where that kernel applies and fills the chip, else F(2,3)
-        where THAT applies, else the direct packing.  (ops.PRECISION == "bf16": the bf16 kernel where IT applies, first.)"""
-        N, H, W, Cin = x_shape
-        assert tuple(w.shape[2:]) == (3, 3), f"PackedConvWeights: 3x3 kernels only, got a weight of shape {tuple(w.shape)}"
-        if ops.bf16x3_eligible(N, H, W, Cin, w.shape[0], stride, ps_out=self.ps):
-            return self.bf16x3_fwd(w)
-        if ops.bf16_eligible(N, H, W, Cin, w.shape[0], stride, ps_out=self.ps):
-            return self.bf16_fwd(w)
-        if ops.wino4_eligible(N, H, W, Cin, w.shape[0], stride, ps_out=self.ps):
-            return self.wino4_fwd(w)
-        if ops.wino_eligible(N, H, W, Cin, w.shape[0], stride):
-            return self.wino_fwd(w)
-        return self.fwd(w)
+        """Packed weights for y = conv(x, w) with x of NHWC shape x_shape: of the first kernel family in ops._FAMILIES that applies and
+        fills the chip."""
+        return self._get(w, ops.conv3x3_family_fwd(*x_shape, w.shape[0], stride, self.ps), 0)
 
     def for_dgrad(self, w: torch.Tensor, x_shape, stride: int = 1):
-        """Packed weights for dx of y = conv(x, w) with x of NHWC shape x_shape."""
-        N, H, W, Cin = x_shape
-        assert tuple(w.shape[2:]) == (3, 3), f"PackedConvWeights: 3x3 kernels only, got a weight of shape {tuple(w.shape)}"
-        if stride == 1 and ops.bf16x3_eligible(N, H, W, w.shape[0], Cin, 1, ps_in=self.ps):
-            return self.bf16x3_dgrad(w)
-        if stride == 1 and ops.bf16_eligible(N, H, W, w.shape[0], Cin, 1, ps_in=self.ps):
-            return self.bf16_dgrad(w)
-        if stride == 2 and not self.ps and ops.bf16_s2_dgrad_eligible(N, H, W, w.shape[0], Cin):
-            return self.bf16_dgrad(w)
-        if ops.wino4_eligible(N, H, W, w.shape[0], Cin, stride):
-            return self.wino4_dgrad(w)
-        if ops.wino_eligible(N, H, W, w.shape[0], Cin, stride):
-            return self.wino_dgrad(w)
-        return self.dgrad(w)
+        """Packed weights for dx of that conv."""
+        return self._get(w, ops.conv3x3_family_dgrad(*x_shape, w.shape[0], stride, self.ps), 1)
 
     def bias(self, b):
         if b is None or not self.ps:
             return None if b is None else b.detach()
         with self._lock:
-            idx = b.device.index if b.is_cuda else -1
-            sl = self._slots.get(idx)
-            if sl is None:
-                sl = self._slots[idx] = _PackSlot()
+            sl = self._slot(b)
             k = self._key(b)
-            if sl.kb != k:
-                sl.bias = ops.pack_bias_ps(b.detach())
-                sl.kb = k
+            e = sl.packs.get(_BIAS)
+            if e is None or e[1] != k:
+                e = sl.packs[_BIAS] = [ops.pack_bias_ps(b.detach()), k]
             if sl.bref is None or sl.bref() is not b:
-                import weakref
                 sl.bref = weakref.ref(b)
-            return sl.bias
+            return e[0]
 
 
 # Optional side stream for the weight-gradient kernels (off by default, DESIGN.md 3b): in a backward chain the dgrad kernels
@@ -232,7 +180,7 @@ class PackedConvWeights:
 _SIDE = {}
 # PESR_SIDE_STREAM: "0" everything on one stream, "1" every conv block's wgrad on the side stream, "g" only the blocks
 # without BatchNorm (the Generator's), "d" only the conv+BN blocks (the Discriminator's)
-SIDE_MODE = __import__("os").environ.get("PESR_SIDE_STREAM", "0")
+SIDE_MODE = os.environ.get("PESR_SIDE_STREAM", "0")
 USE_SIDE_STREAM = SIDE_MODE != "0"
 _SIDE_OFF = SIDE_MODE == "0"     # (in-place second-use accumulation assumes every weight gradient is written on ONE stream)
 
@@ -305,35 +253,23 @@ _REPACK_TABLES_MAX = 8
 # the packings the replayed launch refreshed.
 _REPACK_RECORD = None
 
-_SLOT_FIELD = {0: ("fwd", "kf"), 1: ("dgrad", "kd"), 2: ("wfwd", "kwf"), 3: ("wdgrad", "kwd"), 4: ("w4fwd", "k4f"), 5: ("w4dgrad", "k4d"),
-               6: ("bias", "kb"), 7: ("bfwd", "kbf"), 8: ("bdgrad", "kbd"), 9: ("sfwd", "ksf"), 10: ("sdgrad", "ksd")}      # 6: the PixelShuffle-permuted bias (its source tensor is the slot's bref, not wref)
-
-
-def _slot_buffer(sl, mode):
-    b = getattr(sl, _SLOT_FIELD[mode][0])
-    return b if (b is None or torch.is_tensor(b)) else b.t
-
-
 def stamp_repacked(jobs) -> None:
     """Mark the packings of `jobs` (as recorded by repack_all) as built from their weights' CURRENT contents.  A packing whose
     buffer is no longer the recorded one (an eager rebuild replaced it) is left alone: its key then misses and it is rebuilt
     on next use."""
     for sl, wref, mode, ptr in jobs:
-        w = wref()          # (mode 6: the bias tensor)
-        buf = _slot_buffer(sl, mode)
-        if w is None or buf is None or buf.data_ptr() != ptr:
-            continue
-        setattr(sl, _SLOT_FIELD[mode][1], PackedConvWeights._key(w))
+        w = wref()          # (mode _BIAS: the bias tensor)
+        e = sl.packs.get(mode)
+        if w is not None and e is not None and e[0].data_ptr() == ptr:
+            e[1] = PackedConvWeights._key(w)
 
 
 def repack_all(params) -> None:
     """Refresh, in ONE kernel launch, every packed layout that already exists for the given parameters (called by
     FlatAdam.step right after its Adam kernel, instead of ~2 small pack launches per conv on the next forward/backward)."""
-    import weakref
-
     import numpy as np
     ids = {id(p) for p in params}
-    jobs = []
+    jobs, bias_rec = [], []
     for ref in list(_ALL_PACKS):
         c = ref()
         if c is None:
@@ -341,37 +277,23 @@ def repack_all(params) -> None:
             continue
         for sl in list(c._slots.values()):
             w = sl.wref() if sl.wref is not None else None
-            if w is None or id(w) not in ids or not w.is_cuda:
-                continue
-            O, I = w.shape[0], w.shape[1]
-            for mode, buf in ((0, sl.fwd), (1, sl.dgrad)):
-                if buf is None:
-                    continue
-                R, Nn = (I, O) if mode == 0 else (O, I)
-                jobs.append((sl, w, mode, (w.data_ptr(), buf.data_ptr(), O, I, mode, int(c.ps), (R + 15) // 16 * 16, 16 if Nn <= 16 else (Nn + 63) // 64 * 64)))
-            # Winograd packings (batched kernel modes 2 / 3: F(2,3), 4 / 5: F(4,3))
-            for mode, wpk in ((2, sl.wfwd), (3, sl.wdgrad), (4, sl.w4fwd), (5, sl.w4dgrad), (7, sl.bfwd), (8, sl.bdgrad), (9, sl.sfwd),
-                              (10, sl.sdgrad)):
-                if wpk is not None:
-                    fwd_like = mode in (2, 4, 7, 9)
-                    jobs.append((sl, w, mode, (w.data_ptr(), wpk.t.data_ptr(), O, I, mode, int(c.ps), I if fwd_like else O, O if fwd_like else I)))
-    # PixelShuffle-permuted biases of these parameters: refreshed in place too (two tiny launches for the Generator).  Left to the
-    # lazy per-forward check they were re-packed on every forward - and a captured step whose capture happened to find the key
-    # current (a forward between the last optimizer step and the capture) would never refresh them at all.
-    bias_rec = []
-    for ref in list(_ALL_PACKS):
-        c = ref()
-        if c is None:
-            continue
-        for sl in list(c._slots.values()):
             b = sl.bref() if sl.bref is not None else None
-            if b is None or sl.bias is None or id(b) not in ids or not b.is_cuda:
-                continue
-            ops.pack_bias_ps(b.detach(), out=sl.bias)
-            bias_rec.append((sl, sl.bref, 6, sl.bias.data_ptr()))
+            for mode, (packed, _) in sorted(sl.packs.items()):
+                if mode == _BIAS:
+                    # PixelShuffle-permuted biases of these parameters: refreshed in place too (two tiny launches for the Generator).
+                    # Left to the lazy per-forward check they were re-packed on every forward - and a captured step whose capture
+                    # happened to find the key current (a forward between the last optimizer step and the capture) would never
+                    # refresh them at all.
+                    if b is not None and id(b) in ids and b.is_cuda:
+                        ops.pack_bias_ps(b.detach(), out=packed)
+                        bias_rec.append((sl, sl.bref, _BIAS, packed.data_ptr()))
+                elif w is not None and id(w) in ids and w.is_cuda:
+                    O, I = w.shape[0], w.shape[1]
+                    f = ops._conv_family(packed)
+                    jobs.append((sl, w, mode, (w.data_ptr(), packed.data_ptr(), O, I, mode, int(c.ps), *f.dims(O, I, mode - f.mode))))
     if bias_rec:
         if _REPACK_RECORD is not None:
-            _REPACK_RECORD.append((bias_rec, None, [sl.bias for sl, _, _, _ in bias_rec]))
+            _REPACK_RECORD.append((bias_rec, None, [sl.packs[_BIAS][0] for sl, _, _, _ in bias_rec]))
         stamp_repacked(bias_rec)
     if not jobs:
         return
@@ -392,7 +314,7 @@ def repack_all(params) -> None:
     rec = [(sl, weakref.ref(w), mode, d[1]) for sl, w, mode, d in jobs]
     if _REPACK_RECORD is not None:
         # under capture nothing ran: the record (it also pins the table and the packed buffers) is used at replay time
-        _REPACK_RECORD.append((rec, table, [_slot_buffer(sl, mode) for sl, _, mode, _ in jobs]))
+        _REPACK_RECORD.append((rec, table, [sl.packs[mode][0] for sl, _, mode, _ in jobs]))
     stamp_repacked(rec)
 
 

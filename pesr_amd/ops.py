@@ -7,7 +7,9 @@ There is no CPU path: a CPU tensor raises.
 """
 from __future__ import annotations
 
-from typing import Optional
+import ctypes
+import os
+from typing import NamedTuple, Optional
 
 import torch
 
@@ -33,32 +35,29 @@ def _stream() -> int:
     return torch.cuda.current_stream().cuda_stream
 
 
-class _KernelEvents:
-    """Optional HIP-event bracket around every launch of ONE conv shape (bench.py's live roofline figures), kept per kind
-    ("fwd", "dgrad", "wgrad").  Events are recorded on the stream the kernel is launched on (torch's current stream).
-    Not inside a captured step: an event recorded under capture is only a dependency and cannot be timed, and recording it as an
-    external event node (hipEventRecordWithFlags(hipEventRecordExternal)) is refused under capture by this ROCm runtime
-    (hipErrorInvalidValue; tried in round 3) - bench.py --hip-graph takes its kernel times from eager steps."""
+class _Events:
+    """Optional HIP-event brackets around kernel launches, recorded on the stream the kernel is launched on (torch's current stream);
+    off unless enabled.  enable(shape) watches the launches whose begin() names that shape, and keeps their times per begin() key."""
 
     def __init__(self):
         self.shape, self.pairs, self.every, self._n = None, {}, 1, {}
 
-    def enable(self, shape, every=1):
-        """Watch launches of `shape`; bracket every `every`-th launch of each kind (two event records per bracket are not free:
+    def enable(self, shape=(), every=1):
+        """Watch launches of `shape`; bracket every `every`-th launch of each key (two event records per bracket are not free:
         bracketing all ~200 watched launches of a GAN step cost 2 % of the step)."""
         self.shape, self.pairs, self.every, self._n = tuple(shape), {}, max(1, int(every)), {}
 
-    def begin(self, kind, N, H, W, Cin, Cout, stride):
+    def begin(self, key, *shape):
         """-> an open bracket (or None when this launch is not the watched shape / not sampled); close it with end()."""
-        if self.shape is None or self.shape != (N, H, W, Cin, Cout, stride):
+        if self.shape is None or self.shape != shape:
             return None
-        n = self._n.get(kind, 0)
-        self._n[kind] = n + 1
+        n = self._n.get(key, 0)
+        self._n[key] = n + 1
         if n % self.every:
             return None
         e0 = torch.cuda.Event(enable_timing=True)
         e0.record()
-        return (kind, e0)
+        return (key, e0)
 
     def end(self, br):
         if br is not None:
@@ -67,7 +66,7 @@ class _KernelEvents:
             self.pairs.setdefault(br[0], []).append((br[1], e1))
 
     def drain(self):
-        """-> {kind: (average milliseconds per launch, launches)}; disables recording."""
+        """-> {key: (average milliseconds per launch, launches)}; disables recording."""
         pairs, self.pairs, self.shape = self.pairs, {}, None
         if not pairs:
             return {}
@@ -75,42 +74,14 @@ class _KernelEvents:
         return {k: (sum(a.elapsed_time(b) for a, b in v) / len(v), len(v)) for k, v in pairs.items()}
 
 
-KERNEL_EVENTS = _KernelEvents()
-
-
-class _OpEvents:
-    """Optional HIP-event brackets around the HBM-bound ops that have no conv shape key (bench.py's config-5 side measurement:
-    the C -> 3 and 3 -> C convs, MeanShift), recorded on the launch stream; off unless enabled."""
-
-    def __init__(self):
-        self.on, self.pairs = False, {}
-
-    def enable(self):
-        self.on, self.pairs = True, {}
-
-    def begin(self, name):
-        if not self.on:
-            return None
-        e0 = torch.cuda.Event(enable_timing=True)
-        e0.record()
-        return (name, e0)
-
-    def end(self, br):
-        if br is not None:
-            e1 = torch.cuda.Event(enable_timing=True)
-            e1.record()
-            self.pairs.setdefault(br[0], []).append((br[1], e1))
-
-    def drain(self):
-        """-> {name: (mean milliseconds per launch, launches)}; disables recording."""
-        pairs, self.pairs, self.on = self.pairs, {}, False
-        if not pairs:
-            return {}
-        torch.cuda.synchronize()
-        return {k: (sum(a.elapsed_time(b) for a, b in v) / len(v), len(v)) for k, v in pairs.items()}
-
-
-OP_EVENTS = _OpEvents()
+# Every launch of ONE conv shape (N, H, W, Cin, Cout, stride), kept per kind "fwd" / "dgrad" / "wgrad": bench.py's live roofline figures.
+# Not inside a captured step: an event recorded under capture is only a dependency and cannot be timed, and recording it as an
+# external event node (hipEventRecordWithFlags(hipEventRecordExternal)) is refused under capture by this ROCm runtime
+# (hipErrorInvalidValue; tried in round 3) - bench.py --hip-graph takes its kernel times from eager steps.
+KERNEL_EVENTS = _Events()
+# The HBM-bound ops that have no conv shape key, kept per op name (bench.py's config-5 side measurement: the C -> 3 and 3 -> C convs,
+# MeanShift): enable() without a shape watches them all.
+OP_EVENTS = _Events()
 
 
 class _FlopCount:
@@ -140,17 +111,6 @@ class _FlopCount:
 FLOPS = _FlopCount()
 
 
-def _conv_family(wp):
-    if isinstance(wp, Bf16x3Packed):
-        return 3.0, "split-bf16 (3 bf16 products per multiply)"
-    if isinstance(wp, Bf16Packed):
-        return 1.0, "bf16"
-    if isinstance(wp, Wino4Packed):
-        return 0.5, "F(4,3)"
-    if isinstance(wp, WinoPacked):
-        return 2.0 / 3.0, "F(2,3)"
-    return 1.0, "direct"
-
 _workspaces = {}
 
 
@@ -164,45 +124,26 @@ def workspace(nbytes: int, device: torch.device) -> torch.Tensor:
     return ws
 
 
-# ------------------------------------------------------------------------------------------------
-# weight packing
-# ------------------------------------------------------------------------------------------------
-def pack_conv3x3(w: torch.Tensor, mode: int, ps: bool = False) -> torch.Tensor:
-    """OIHW [O, I, 3, 3] -> packed [9, R/16, Nn, 16] (mode 0: forward, mode 1: dgrad)."""
-    _chk(w, "pack_conv3x3.w")
-    O, I = w.shape[0], w.shape[1]
-    assert tuple(w.shape[2:]) == (3, 3), f"pack_conv3x3: a 3x3 kernel is required, got {tuple(w.shape)}"
-    R, Nn = (I, O) if mode == 0 else (O, I)
-    nn_pad = 16 if Nn <= 16 else (Nn + 63) // 64 * 64
-    out = torch.empty(9 * ((R + 15) // 16 * 16) * nn_pad, dtype=torch.float32, device=w.device)
-    _lib.check(_lib.lib().pesr_pack_conv3x3(_p(w), _p(out), O, I, mode, int(ps), _stream()), "pesr_pack_conv3x3")
-    return out
+_MEMO = {}
 
 
-def pack_bias_ps(b: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-    _chk(b, "pack_bias_ps.b")
-    if out is None:
-        out = torch.empty_like(b)
-    assert out.shape == b.shape and out.is_contiguous()
-    _lib.check(_lib.lib().pesr_pack_bias_ps(_p(b), _p(out), b.numel(), _stream()), "pesr_pack_bias_ps")
-    return out
+def _memo(fn: str, *args, cache=_MEMO):
+    """The library's host-only planner call `fn(*args)` (a score, a row count: pure functions of their arguments), asked once."""
+    key = (fn, *args)
+    v = cache.get(key)
+    if v is None:
+        v = cache[key] = int(getattr(_lib.lib(), fn)(*args))
+    return v
 
 
 # ------------------------------------------------------------------------------------------------
 # 3x3 conv family
 # ------------------------------------------------------------------------------------------------
-class WinoPacked:
-    """Weights packed for the Winograd F(2,3)-along-x kernel (pesr_pack_conv3x3_wino); conv3x3_fwd / conv3x3_dgrad dispatch on it."""
-    __slots__ = ("t",)
-
-    def __init__(self, t: torch.Tensor):
-        self.t = t
-
-
-USE_WINO = __import__("os").environ.get("PESR_WINO", "1") != "0"     # PESR_WINO=0: direct kernel everywhere
+USE_WINO = os.environ.get("PESR_WINO", "1") != "0"     # PESR_WINO=0: direct kernel everywhere
+USE_WINO4 = os.environ.get("PESR_WINO4", "1") != "0"   # PESR_WINO4=0: no F(4,3) kernel (F(2,3) / direct instead)
 # PESR_WGRAD_WINO=0: direct weight-gradient kernel everywhere (passed to the library as the explicit `algo` argument)
-USE_WGRAD_WINO = __import__("os").environ.get("PESR_WGRAD_WINO", "1") != "0"
-USE_WGRAD_WINO4 = __import__("os").environ.get("PESR_WGRAD_WINO4", "1") != "0"   # =0: F(2,3) weight gradient instead of F(4,3)
+USE_WGRAD_WINO = os.environ.get("PESR_WGRAD_WINO", "1") != "0"
+USE_WGRAD_WINO4 = os.environ.get("PESR_WGRAD_WINO4", "1") != "0"   # =0: F(2,3) weight gradient instead of F(4,3)
 
 
 def _wg4_plan_ok(N, H, W, Cin, Cout):
@@ -261,19 +202,6 @@ def wino_eligible(N: int, H: int, W: int, Cin: int, Cout: int, stride: int = 1) 
     return per_img * 144 <= 1.15 * H * (W // 2) and wgs * min(8, Cin // 64) >= 192
 
 
-class Wino4Packed:
-    """Weights packed for the Winograd F(4,3)-along-x kernel (pesr_pack_conv3x3_wino4)."""
-    __slots__ = ("t",)
-
-    def __init__(self, t: torch.Tensor):
-        self.t = t
-
-
-USE_WINO4 = __import__("os").environ.get("PESR_WINO4", "1") != "0"   # PESR_WINO4=0: no F(4,3) kernel (F(2,3) / direct instead)
-
-_W4_SCORE = {}
-
-
 def wino4_eligible(N: int, H: int, W: int, Cin: int, Cout: int, stride: int = 1, ps_out: bool = False) -> bool:
     """The F(4,3) kernel applies (stride 1, W % 4 == 0, Cin % 16 == 0, Cout % 64 == 0; Cout % 256 == 0 with a fused
     PixelShuffle store), its 576-pixel x 64-channel tiles (split-K included) give at least 192 workgroups, AND at least 78 %
@@ -281,47 +209,18 @@ def wino4_eligible(N: int, H: int, W: int, Cin: int, Cout: int, stride: int = 1,
     from ~0.75 of F(2,3)'s tile efficiency up.  Cin / Cout are those of the problem the kernel runs."""
     if not (USE_WINO and USE_WINO4) or stride != 1 or W % 4 or Cin % 16 or Cout % 64 or (ps_out and Cout % 256):
         return False
-    key = (N, H, W, Cin, Cout, ps_out)
-    sc = _W4_SCORE.get(key)
-    if sc is None:
-        sc = _W4_SCORE[key] = _lib.lib().pesr_conv3x3_wino4_score(N, H, W, Cin, Cout, 0 if ps_out else 1)
-    return sc >= 780
-
-
-def pack_conv3x3_wino4(w: torch.Tensor, mode: int, ps: bool = False) -> Wino4Packed:
-    """OIHW [O, I, 3, 3] -> transformed [18, R/16, Nn, 16] (mode 0: forward, mode 1: dgrad; ps: sub-pixel-major O order)."""
-    _chk(w, "pack_conv3x3_wino4.w")
-    O, I = w.shape[0], w.shape[1]
-    assert tuple(w.shape[2:]) == (3, 3), f"pack_conv3x3_wino4: a 3x3 kernel is required, got {tuple(w.shape)}"
-    out = torch.empty(18 * O * I, dtype=torch.float32, device=w.device)
-    rc = _lib.lib().pesr_pack_conv3x3_wino4(_p(w), _p(out), O, I, mode, int(ps), _stream())
-    _lib.check(rc, f"pesr_pack_conv3x3_wino4[{O}x{I},mode{mode}]")
-    return Wino4Packed(out)
-
-
-def pack_conv3x3_wino(w: torch.Tensor, mode: int, ps: bool = False) -> WinoPacked:
-    """OIHW [O, I, 3, 3] -> transformed [12, R/16, Nn, 16] (mode 0: forward, mode 1: dgrad; ps: sub-pixel-major O order)."""
-    _chk(w, "pack_conv3x3_wino.w")
-    O, I = w.shape[0], w.shape[1]
-    assert tuple(w.shape[2:]) == (3, 3), f"pack_conv3x3_wino: a 3x3 kernel is required, got {tuple(w.shape)}"
-    out = torch.empty(12 * O * I, dtype=torch.float32, device=w.device)
-    rc = _lib.lib().pesr_pack_conv3x3_wino(_p(w), _p(out), O, I, mode, int(ps), _stream())
-    _lib.check(rc, f"pesr_pack_conv3x3_wino[{O}x{I},mode{mode}]")
-    return WinoPacked(out)
+    return _memo("pesr_conv3x3_wino4_score", N, H, W, Cin, Cout, 0 if ps_out else 1) >= 780
 
 
 # ---- the OPTIONAL bf16-operand mode (SURVEY 8 f4) --------------------------------------------------------------------------------
 # PRECISION = "bf16" (set_precision / PESR_PRECISION / train.py --precision): the stride-1 convs with 32-multiple input and
 # 64-multiple output channels run on v_mfma_f32_16x16x32_bf16 - operands rounded to bf16, fp32 accumulation, fp32 tensors in HBM.
 # Everything else (and everything by default) stays on the fp32 kernels.
-PRECISION = __import__("os").environ.get("PESR_PRECISION", "fp32")
-_B16_SCORE = {}
-_BF16_NO_S2 = __import__("os").environ.get("PESR_BF16_NO_S2", "0") == "1"      # A/B switch of scripts/gpu_call51.sh: stride-2 forwards stay fp32
+PRECISION = os.environ.get("PESR_PRECISION", "fp32")
+_BF16_NO_S2 = os.environ.get("PESR_BF16_NO_S2", "0") == "1"      # A/B switch of scripts/gpu_call51.sh: stride-2 forwards stay fp32
 # layers whose bf16 launch would have fewer workgroups stay on the fp32 kernels (tests lower it; at 64 workgroups the 16x12x12x512
 # layers take 47 us against 89 on the F(4,3) kernel, scripts/bf16_small_time.py).  The env form is for A/B runs only.
-BF16_MIN_WGS = int(__import__("os").environ.get("PESR_BF16_MIN_WGS", "64"))
-
-
+BF16_MIN_WGS = int(os.environ.get("PESR_BF16_MIN_WGS", "64"))
 PRECISIONS = ("fp32", "bf16", "split-bf16")
 
 
@@ -332,54 +231,6 @@ def set_precision(p: str) -> None:
     PRECISION = p
 
 
-class Bf16Packed:
-    """Weights rounded to bf16 and packed for conv3x3_bf16_kernel (pesr_pack_conv3x3_bf16)."""
-    __slots__ = ("t",)
-
-    def __init__(self, t: torch.Tensor):
-        self.t = t
-
-
-# ---- the OPTIONAL split-bf16 mode (SURVEY 8 f4; round 4) ---------------------------------------------------------------------------
-# PRECISION = "split-bf16": forward and input gradient of the stride-1 convs with Cin % 32 == 0 and Cout % 128 == 0 run on the bf16
-# MFMA with every operand split into hi + lo bf16 terms and three products per multiply (conv3x3_bf16x3.hip): 3.6 .. 4.7e-6 of the
-# output maximum against fp64 - inside the fp32 kernels' own tolerances, so the mode is tested against the fp32 oracle.  Weight
-# gradients, stride-2 convs, 64-channel layers and everything else stay on the fp32 kernels.
-class Bf16x3Packed:
-    """Weights split into hi + lo bf16 planes and packed for conv3x3_bf16x3_kernel (pesr_pack_conv3x3_bf16x3)."""
-    __slots__ = ("t",)
-
-    def __init__(self, t: torch.Tensor):
-        self.t = t
-
-
-_B3_SCORE = {}
-BF16X3_MIN_WGS = 128
-
-
-def bf16x3_eligible(N: int, H: int, W: int, Cin: int, Cout: int, stride: int = 1, ps_out: bool = False, ps_in: bool = False) -> bool:
-    """PRECISION is "split-bf16" and the split kernel covers the problem it would run (an input gradient: Cin / Cout swapped)."""
-    # (ps_out: an n-tile - 256 or 128 channels, the planner's choice - must stay inside one of the four sub-pixel planes)
-    if PRECISION != "split-bf16" or stride != 1 or Cin % 32 or Cout % 128 or (ps_out and Cout % 1024) or (ps_in and Cin % 128):
-        return False
-    key = (N, H, W, Cin, Cout)
-    sc = _B3_SCORE.get(key)
-    if sc is None:
-        sc = _B3_SCORE[key] = _lib.lib().pesr_conv3x3_bf16x3_score(N, H, W, Cin, Cout, BF16X3_MIN_WGS)
-    return sc >= 780
-
-
-def pack_conv3x3_bf16x3(w: torch.Tensor, mode: int, ps: bool = False) -> Bf16x3Packed:
-    """OIHW [O, I, 3, 3] fp32 -> [2 (hi, lo)][9, R/32, Nn, 32] bf16 (mode 0: forward, mode 1: dgrad with flipped taps; ps: sub-pixel-major O)."""
-    _chk(w, "pack_conv3x3_bf16x3.w")
-    O, I = w.shape[0], w.shape[1]
-    assert tuple(w.shape[2:]) == (3, 3), f"pack_conv3x3_bf16x3: a 3x3 kernel is required, got {tuple(w.shape)}"
-    out = torch.empty(2 * 9 * O * I, dtype=torch.bfloat16, device=w.device)
-    rc = _lib.lib().pesr_pack_conv3x3_bf16x3(_p(w), _p(out), O, I, mode, int(ps), _stream())
-    _lib.check(rc, f"pesr_pack_conv3x3_bf16x3[{O}x{I},mode{mode}]")
-    return Bf16x3Packed(out)
-
-
 def bf16_eligible(N: int, H: int, W: int, Cin: int, Cout: int, stride: int = 1, ps_out: bool = False, ps_in: bool = False) -> bool:
     """PRECISION is "bf16" and the bf16 kernel covers the shape with at least 78 % of its tile area inside the image.
     Cin / Cout are those of the problem the kernel runs."""
@@ -388,57 +239,187 @@ def bf16_eligible(N: int, H: int, W: int, Cin: int, Cout: int, stride: int = 1, 
         return False
     if stride == 2 and (ps_out or ps_in or _BF16_NO_S2):
         return False
-    key = (N, H, W, Cin, Cout, BF16_MIN_WGS, stride)
-    sc = _B16_SCORE.get(key)
-    if sc is None:       # stride 2: the FORWARD kernel only (H, W: the input's size); its gradients stay on the fp32 kernels
-        score = _lib.lib().pesr_conv3x3_bf16_score if stride == 1 else _lib.lib().pesr_conv3x3_bf16_s2_score
-        sc = _B16_SCORE[key] = score(N, H, W, Cin, Cout, BF16_MIN_WGS)
-    return sc >= 780
+    # stride 2: the FORWARD kernel only (H, W: the input's size); its gradients stay on the fp32 kernels
+    return _memo("pesr_conv3x3_bf16_score" if stride == 1 else "pesr_conv3x3_bf16_s2_score", N, H, W, Cin, Cout, BF16_MIN_WGS) >= 780
 
 
 def bf16_s2_dgrad_eligible(N: int, H: int, W: int, Cout_fwd: int, Cin_fwd: int) -> bool:
     """PRECISION is "bf16" and the stride-2 input-gradient form of the bf16 kernel covers dx [N, H, W, Cin_fwd]."""
     if PRECISION != "bf16" or _BF16_NO_S2 or Cout_fwd % 32 or Cin_fwd % 64:
         return False
-    key = (N, H, W, Cout_fwd, Cin_fwd, BF16_MIN_WGS, "s2d")
-    sc = _B16_SCORE.get(key)
-    if sc is None:
-        sc = _B16_SCORE[key] = _lib.lib().pesr_conv3x3_bf16_s2_dgrad_score(N, H, W, Cout_fwd, Cin_fwd, BF16_MIN_WGS)
-    return sc >= 780
+    return _memo("pesr_conv3x3_bf16_s2_dgrad_score", N, H, W, Cout_fwd, Cin_fwd, BF16_MIN_WGS) >= 780
+
+
+# ---- the OPTIONAL split-bf16 mode (SURVEY 8 f4; round 4) ---------------------------------------------------------------------------
+# PRECISION = "split-bf16": forward and input gradient of the stride-1 convs with Cin % 32 == 0 and Cout % 128 == 0 run on the bf16
+# MFMA with every operand split into hi + lo bf16 terms and three products per multiply (conv3x3_bf16x3.hip): 3.6 .. 4.7e-6 of the
+# output maximum against fp64 - inside the fp32 kernels' own tolerances, so the mode is tested against the fp32 oracle.  Weight
+# gradients, stride-2 convs, 64-channel layers and everything else stay on the fp32 kernels.
+BF16X3_MIN_WGS = 128
+
+
+def bf16x3_eligible(N: int, H: int, W: int, Cin: int, Cout: int, stride: int = 1, ps_out: bool = False, ps_in: bool = False) -> bool:
+    """PRECISION is "split-bf16" and the split kernel covers the problem it would run (an input gradient: Cin / Cout swapped)."""
+    # (ps_out: an n-tile - 256 or 128 channels, the planner's choice - must stay inside one of the four sub-pixel planes)
+    if PRECISION != "split-bf16" or stride != 1 or Cin % 32 or Cout % 128 or (ps_out and Cout % 1024) or (ps_in and Cin % 128):
+        return False
+    return _memo("pesr_conv3x3_bf16x3_score", N, H, W, Cin, Cout, BF16X3_MIN_WGS) >= 780
+
+
+# ---- the kernel families: one record each.  Packing, the batched re-pack's mode numbers, the flop tally, the launch and the dispatch
+# priority (here and in functional.PackedConvWeights) all read this table. ---------------------------------------------------------
+class _Packed:
+    """Weights packed for one of the kernel families below: the buffer `.t` and, per subclass, its `.family` record.  (The direct
+    kernels' packing is a bare tensor.)  conv3x3_fwd / conv3x3_dgrad dispatch on it."""
+    __slots__ = ("t",)
+
+    def __init__(self, t: torch.Tensor):
+        self.t = t
+
+    def data_ptr(self) -> int:      # (as the bare tensor of the direct packing has it)
+        return self.t.data_ptr()
+
+
+class WinoPacked(_Packed):
+    """Weights packed for the Winograd F(2,3)-along-x kernel (pesr_pack_conv3x3_wino)."""
+    __slots__ = ()
+
+
+class Wino4Packed(_Packed):
+    """Weights packed for the Winograd F(4,3)-along-x kernel (pesr_pack_conv3x3_wino4)."""
+    __slots__ = ()
+
+
+class Bf16Packed(_Packed):
+    """Weights rounded to bf16 and packed for conv3x3_bf16_kernel (pesr_pack_conv3x3_bf16)."""
+    __slots__ = ()
+
+
+class Bf16x3Packed(_Packed):
+    """Weights split into hi + lo bf16 planes and packed for conv3x3_bf16x3_kernel (pesr_pack_conv3x3_bf16x3)."""
+    __slots__ = ()
+
+
+class _Family(NamedTuple):
+    name: str                   # as the dispatch tests and documents call it
+    mode: int                   # mode number of its forward packing in the batched re-pack (csrc/pack.hip); the dgrad packing is mode + 1
+    wrap: Optional[type]        # class of its packed weights; None: a bare tensor
+    pack: str                   # C entry point of the single pack
+    planes: int                 # packed elements per (reduction channel, "n" channel) pair
+    dtype: torch.dtype          # ... and their type
+    frac: float                 # flops issued on the matrix pipe per algorithmic flop ...
+    label: str                  # ... and the key FLOPS.add files them under
+    launch: Optional[str]       # C entry point _conv3x3_wino launches; None: conv3x3_fwd / conv3x3_dgrad launch the direct kernels themselves
+    splitk: bool                # the launch takes the split-K workspace
+    eligible: object            # (N, H, W, Cin, Cout, stride, ps_out, ps_in) of the problem the KERNEL would run -> it covers it and fills the chip
+
+    def dims(self, O: int, I: int, mode: int):
+        """(R, Nn): reduction and "n" channels of the packing, mode 0 forward / 1 dgrad.  The direct kernels' packing zero-pads R to
+        a multiple of 16 and Nn to 16 (if <= 16) or a multiple of 64, so the 3-channel RGB layers run on the same MFMA kernels."""
+        R, Nn = (I, O) if mode == 0 else (O, I)
+        if self.wrap is None:
+            R, Nn = (R + 15) // 16 * 16, 16 if Nn <= 16 else (Nn + 63) // 64 * 64
+        return R, Nn
+
+
+# In dispatch priority: the first family that is eligible runs.
+_FAMILIES = (
+    _Family("split-bf16", 9, Bf16x3Packed, "pesr_pack_conv3x3_bf16x3", 18, torch.bfloat16, 3.0, "split-bf16 (3 bf16 products per multiply)",
+            "pesr_conv3x3_bf16x3", False, bf16x3_eligible),
+    _Family("bf16", 7, Bf16Packed, "pesr_pack_conv3x3_bf16", 9, torch.bfloat16, 1.0, "bf16",
+            "pesr_conv3x3_bf16", False, bf16_eligible),
+    _Family("F(4,3)", 4, Wino4Packed, "pesr_pack_conv3x3_wino4", 18, torch.float32, 0.5, "F(4,3)",
+            "pesr_conv3x3_wino4", True, lambda N, H, W, Cin, Cout, s, po, pi: wino4_eligible(N, H, W, Cin, Cout, s, po)),
+    _Family("F(2,3)", 2, WinoPacked, "pesr_pack_conv3x3_wino", 12, torch.float32, 2.0 / 3.0, "F(2,3)",
+            "pesr_conv3x3_wino", True, lambda N, H, W, Cin, Cout, s, po, pi: wino_eligible(N, H, W, Cin, Cout, s)),
+    _Family("direct", 0, None, "pesr_pack_conv3x3", 9, torch.float32, 1.0, "direct",
+            None, True, lambda N, H, W, Cin, Cout, s, po, pi: True),
+)
+_BF16X3, _BF16, _WINO4, _WINO, _DIRECT = _FAMILIES
+for _f in _FAMILIES[:-1]:
+    _f.wrap.family = _f
+
+
+def _conv_family(wp) -> _Family:
+    return getattr(wp, "family", _DIRECT)
+
+
+def conv3x3_family_fwd(N: int, H: int, W: int, Cin: int, Cout: int, stride: int, ps: bool) -> _Family:
+    """The family that runs y = conv(x [N, H, W, Cin], w [Cout, Cin, 3, 3]); ps: with the PixelShuffle fused into its store."""
+    for f in _FAMILIES:
+        if f.eligible(N, H, W, Cin, Cout, stride, ps, False):
+            return f
+
+
+def conv3x3_family_dgrad(N: int, H: int, W: int, Cin: int, Cout: int, stride: int, ps: bool) -> _Family:
+    """The family that runs dx [N, H, W, Cin] of that conv: the stride-1 kernels on the problem with Cin and Cout swapped.  At stride 2
+    only the bf16 kernel has an input-gradient form besides the direct one (on the bf16 dgrad packing; none with a fused pixel-unshuffle)."""
+    if stride != 1:
+        return _BF16 if stride == 2 and not ps and bf16_s2_dgrad_eligible(N, H, W, Cout, Cin) else _DIRECT
+    for f in _FAMILIES:
+        if f.eligible(N, H, W, Cout, Cin, 1, False, ps):
+            return f
+
+
+def _pack(f: _Family, w: torch.Tensor, mode: int, ps: bool):
+    """OIHW [O, I, 3, 3] fp32 -> family f's packing (mode 0: forward, mode 1: dgrad; ps: sub-pixel-major O order)."""
+    name = f.pack[len("pesr_"):]
+    _chk(w, f"{name}.w")
+    O, I = w.shape[0], w.shape[1]
+    assert tuple(w.shape[2:]) == (3, 3), f"{name}: a 3x3 kernel is required, got {tuple(w.shape)}"
+    R, Nn = f.dims(O, I, mode)
+    out = torch.empty(f.planes * R * Nn, dtype=f.dtype, device=w.device)
+    rc = getattr(_lib.lib(), f.pack)(_p(w), _p(out), O, I, mode, int(ps), _stream())
+    _lib.check(rc, f.pack if f.wrap is None else f"{f.pack}[{O}x{I},mode{mode}]")
+    return out if f.wrap is None else f.wrap(out)
+
+
+def pack_conv3x3(w: torch.Tensor, mode: int, ps: bool = False) -> torch.Tensor:
+    """OIHW [O, I, 3, 3] -> packed [9, R/16, Nn, 16] (mode 0: forward, mode 1: dgrad)."""
+    return _pack(_DIRECT, w, mode, ps)
+
+
+def pack_conv3x3_wino(w: torch.Tensor, mode: int, ps: bool = False) -> WinoPacked:
+    """OIHW [O, I, 3, 3] -> transformed [12, R/16, Nn, 16] (mode 0: forward, mode 1: dgrad; ps: sub-pixel-major O order)."""
+    return _pack(_WINO, w, mode, ps)
+
+
+def pack_conv3x3_wino4(w: torch.Tensor, mode: int, ps: bool = False) -> Wino4Packed:
+    """OIHW [O, I, 3, 3] -> transformed [18, R/16, Nn, 16] (mode 0: forward, mode 1: dgrad; ps: sub-pixel-major O order)."""
+    return _pack(_WINO4, w, mode, ps)
 
 
 def pack_conv3x3_bf16(w: torch.Tensor, mode: int, ps: bool = False) -> Bf16Packed:
     """OIHW [O, I, 3, 3] fp32 -> [9, R/32, Nn, 32] bf16 (mode 0: forward, mode 1: dgrad with flipped taps; ps: sub-pixel-major O)."""
-    _chk(w, "pack_conv3x3_bf16.w")
-    O, I = w.shape[0], w.shape[1]
-    assert tuple(w.shape[2:]) == (3, 3), f"pack_conv3x3_bf16: a 3x3 kernel is required, got {tuple(w.shape)}"
-    out = torch.empty(9 * O * I, dtype=torch.bfloat16, device=w.device)
-    rc = _lib.lib().pesr_pack_conv3x3_bf16(_p(w), _p(out), O, I, mode, int(ps), _stream())
-    _lib.check(rc, f"pesr_pack_conv3x3_bf16[{O}x{I},mode{mode}]")
-    return Bf16Packed(out)
+    return _pack(_BF16, w, mode, ps)
+
+
+def pack_conv3x3_bf16x3(w: torch.Tensor, mode: int, ps: bool = False) -> Bf16x3Packed:
+    """OIHW [O, I, 3, 3] fp32 -> [2 (hi, lo)][9, R/32, Nn, 32] bf16 (mode 0: forward, mode 1: dgrad with flipped taps; ps: sub-pixel-major O)."""
+    return _pack(_BF16X3, w, mode, ps)
+
+
+def pack_bias_ps(b: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    _chk(b, "pack_bias_ps.b")
+    if out is None:
+        out = torch.empty_like(b)
+    assert out.shape == b.shape and out.is_contiguous()
+    _lib.check(_lib.lib().pesr_pack_bias_ps(_p(b), _p(out), b.numel(), _stream()), "pesr_pack_bias_ps")
+    return out
 
 
 def _conv3x3_wino(x, wp, bias, skip, mask, y, N, H, W, Cin, cout, alpha, act, slope, what, ps_out=False, ps_in=False):
-    """Both Winograd kernels (WinoPacked -> F(2,3), Wino4Packed -> F(4,3)) and the bf16 kernel (Bf16Packed): same arguments,
-    same fused epilogue."""
+    """Every family that is not the direct one (wp.family says which kernel): same arguments, same fused epilogue; the Winograd
+    kernels also take the split-K scratch for layers with few tiles."""
+    f = wp.family
     L = _lib.lib()
-    if isinstance(wp, Bf16x3Packed):
-        rc = L.pesr_conv3x3_bf16x3(_p(x), _p(wp.t), _p(bias), _p(skip), _p(mask), _p(y), N, H, W, Cin, cout, alpha, act, slope,
-                                   int(ps_out), int(ps_in), _stream())
-        _lib.check(rc, f"pesr_conv3x3_bf16x3[{what} {N}x{H}x{W}x{Cin}->{cout}]")
-        return
-    if isinstance(wp, Bf16Packed):
-        rc = L.pesr_conv3x3_bf16(_p(x), _p(wp.t), _p(bias), _p(skip), _p(mask), _p(y), N, H, W, Cin, cout, alpha, act, slope,
-                                 int(ps_out), int(ps_in), _stream())
-        _lib.check(rc, f"pesr_conv3x3_bf16[{what} {N}x{H}x{W}x{Cin}->{cout}]")
-        return
-    nws = L.pesr_conv3x3_workspace_bytes(N, H, W, cout) if not ps_out else 0     # split-K scratch for layers with few tiles
-    ws = workspace(nws, x.device) if nws else None
-    four = isinstance(wp, Wino4Packed)
-    fn = L.pesr_conv3x3_wino4 if four else L.pesr_conv3x3_wino
-    rc = fn(_p(x), _p(wp.t), _p(bias), _p(skip), _p(mask), _p(y), N, H, W, Cin, cout, alpha, act, slope,
-            int(ps_out), int(ps_in), _p(ws), nws, _stream())
-    _lib.check(rc, f"pesr_conv3x3_wino{'4' if four else ''}[{what} {N}x{H}x{W}x{Cin}->{cout}]")
+    ws_args = ()
+    if f.splitk:
+        nws = L.pesr_conv3x3_workspace_bytes(N, H, W, cout) if not ps_out else 0
+        ws_args = (_p(workspace(nws, x.device) if nws else None), nws)
+    rc = getattr(L, f.launch)(_p(x), _p(wp.t), _p(bias), _p(skip), _p(mask), _p(y), N, H, W, Cin, cout, alpha, act, slope,
+                              int(ps_out), int(ps_in), *ws_args, _stream())
+    _lib.check(rc, f"{f.launch}[{what} {N}x{H}x{W}x{Cin}->{cout}]")
 
 
 USE_RGB_OUT = True   # tests switch it off to compare with the implicit-GEMM kernel
@@ -484,14 +465,14 @@ def conv3x3_fwd(x: torch.Tensor, wp: torch.Tensor, bias: Optional[torch.Tensor],
         return y
     if callable(wp):
         wp = wp()
-    if FLOPS.on:
-        FLOPS.add(18.0 * N * OH * OW * Cin * cout, *_conv_family(wp))
+    fam = _conv_family(wp)
+    FLOPS.add(18.0 * N * OH * OW * Cin * cout, fam.frac, fam.label)
     br = KERNEL_EVENTS.begin("fwd", N, H, W, Cin, cout, stride)
     L = _lib.lib()
     if isinstance(wp, Bf16Packed) and stride == 2:
         assert not ps_out
         rc = L.pesr_conv3x3_bf16_s2(_p(x), _p(wp.t), _p(bias), _p(skip), _p(mask), _p(y), N, H, W, Cin, cout, alpha, act, slope, _stream())
-    elif isinstance(wp, (WinoPacked, Wino4Packed, Bf16Packed, Bf16x3Packed)):
+    elif fam is not _DIRECT:
         assert stride == 1
         _conv3x3_wino(x, wp, bias, skip, mask, y, N, H, W, Cin, cout, alpha, act, slope, "fwd", ps_out=ps_out)
         rc = 0
@@ -518,8 +499,8 @@ def conv3x3_dgrad(dy: torch.Tensor, wpd: torch.Tensor, in_shape, stride: int = 1
             _chk(t, f"conv3x3_dgrad.{n}")
             assert t.shape == dx.shape
     L = _lib.lib()
-    if FLOPS.on:
-        FLOPS.add(18.0 * N * ((H - 1) // stride + 1) * ((W - 1) // stride + 1) * Cin * cout, *_conv_family(wpd))
+    fam = _conv_family(wpd)
+    FLOPS.add(18.0 * N * ((H - 1) // stride + 1) * ((W - 1) // stride + 1) * Cin * cout, fam.frac, fam.label)
     br = KERNEL_EVENTS.begin("dgrad", N, H, W, Cin, cout, stride)
     if isinstance(wpd, Bf16Packed) and stride == 2:
         assert not ps_in
@@ -527,7 +508,7 @@ def conv3x3_dgrad(dy: torch.Tensor, wpd: torch.Tensor, in_shape, stride: int = 1
         KERNEL_EVENTS.end(br)
         _lib.check(rc, f"pesr_conv3x3_bf16_s2_dgrad[{N}x{H}x{W}x{Cin}<-{cout}]")
         return dx
-    if isinstance(wpd, (WinoPacked, Wino4Packed, Bf16Packed, Bf16x3Packed)):     # the input gradient is the conv of dy with the flipped, transposed kernel
+    if fam is not _DIRECT:     # the input gradient is the conv of dy with the flipped, transposed kernel
         assert stride == 1
         _conv3x3_wino(dy, wpd, None, skip, mask, dx, N, H, W, cout, Cin, alpha, ACT_NONE, 0.0, "dgrad", ps_in=ps_in)
         KERNEL_EVENTS.end(br)
@@ -586,9 +567,9 @@ def _out(t, shape, device):
 
 WGRAD_AUTO, WGRAD_DIRECT, WGRAD_WINO23, WGRAD_WINO4_16X16, WGRAD_WINO4_1D, WGRAD_WINO4_12W = 0, 1, 2, 3, 4, 5      # include/pesr_hip.h PESR_WGRAD_*
 # PESR_WGRAD_WINO4_16X16=1: round 2's 16x16x4-MFMA form of the F(4,3) weight gradient instead of the 32x32x2 form (A/B switch)
-USE_WGRAD_WINO4_16X16 = __import__("os").environ.get("PESR_WGRAD_WINO4_16X16", "0") == "1"
+USE_WGRAD_WINO4_16X16 = os.environ.get("PESR_WGRAD_WINO4_16X16", "0") == "1"
 # PESR_WGRAD_WINO4_1D=1: round 3's 1-D F(4,3) transform on the 32x32x2 kernel instead of the y-nested one (A/B switch)
-USE_WGRAD_WINO4_1D = __import__("os").environ.get("PESR_WGRAD_WINO4_1D", "0") == "1"
+USE_WGRAD_WINO4_1D = os.environ.get("PESR_WGRAD_WINO4_1D", "0") == "1"
 
 
 def wgrad_bf16_eligible(N: int, H: int, W: int, Cin: int, Cout: int, stride: int = 1, ps_in: bool = False) -> bool:
@@ -650,8 +631,8 @@ def conv3x3_wgrad(x: torch.Tensor, dy: torch.Tensor, stride: int = 1, alpha: flo
         name, frac = wgrad_kernel_for(N, H, W, Cin, cout) if (stride == 1 and algo != WGRAD_DIRECT) else ("conv3x3_wgrad_kernel", 1.0)
         if algo == WGRAD_WINO23 and frac == 0.5:
             frac = 2.0 / 3.0
-        FLOPS.add(18.0 * N * ((H - 1) // stride + 1) * ((W - 1) // stride + 1) * Cin * cout, frac,
-                  {0.5: "F(4,3)", 1.0: "direct", 1.0 / 3.0: "F(2,3)y x F(4,3)x"}.get(frac, "F(2,3)"))
+        label = next((f.label for f in (_WINO4, _WINO, _DIRECT) if f.frac == frac), "F(2,3)y x F(4,3)x")
+        FLOPS.add(18.0 * N * ((H - 1) // stride + 1) * ((W - 1) // stride + 1) * Cin * cout, frac, label)
     br = KERNEL_EVENTS.begin("wgrad", N, H, W, Cin, cout, stride)
     rc = L.pesr_conv3x3_wgrad(_p(x), _p(dy), _p(dw), _p(db), N, H, W, Cin, cout, stride, alpha, int(ps_in), algo, int(accumulate),
                               _p(ws), ws.numel(), _stream())
@@ -819,14 +800,14 @@ def conv_rgb_bn_lrelu_fwd(x, w_oihw, gamma, beta, running_mean, running_var, num
 
 
 # ---- convs whose epilogue leaves the BatchNorm sums (round 6; include/pesr_hip.h PesrBnFuse) -------------------------------------------
-class _BnFuse(__import__("ctypes").Structure):
-    _fields_ = [("mode", __import__("ctypes").c_int), ("rows", __import__("ctypes").c_int), ("part", __import__("ctypes").c_void_p),
-                ("z", __import__("ctypes").c_void_p), ("mean_invstd", __import__("ctypes").c_void_p), ("gamma", __import__("ctypes").c_void_p),
-                ("beta", __import__("ctypes").c_void_p), ("slope", __import__("ctypes").c_float)]
+class _BnFuse(ctypes.Structure):
+    _fields_ = [("mode", ctypes.c_int), ("rows", ctypes.c_int), ("part", ctypes.c_void_p),
+                ("z", ctypes.c_void_p), ("mean_invstd", ctypes.c_void_p), ("gamma", ctypes.c_void_p),
+                ("beta", ctypes.c_void_p), ("slope", ctypes.c_float)]
 
 
 BN_FWD_STATS, BN_BWD_MASK_SUMS = 1, 2
-USE_BN_FUSE = __import__("os").environ.get("PESR_BN_FUSE", "1") != "0"     # PESR_BN_FUSE=0: the un-fused BatchNorm passes everywhere (A/B switch)
+USE_BN_FUSE = os.environ.get("PESR_BN_FUSE", "1") != "0"     # PESR_BN_FUSE=0: the un-fused BatchNorm passes everywhere (A/B switch)
 _BN_ROWS = {}
 
 
@@ -835,11 +816,7 @@ def conv_bn_rows(which: int, N: int, H: int, W: int, Cin: int, Cout: int, stride
     2 = the F(4,3) kernel) leaves for this problem; 0: not covered (split-K layers, odd channel counts) - use the un-fused calls."""
     if not USE_BN_FUSE:
         return 0
-    key = (which, N, H, W, Cin, Cout, stride)
-    r = _BN_ROWS.get(key)
-    if r is None:
-        r = _BN_ROWS[key] = int(_lib.lib().pesr_conv3x3_bn_rows(which, N, H, W, Cin, Cout, stride))
-    return r
+    return _memo("pesr_conv3x3_bn_rows", which, N, H, W, Cin, Cout, stride, cache=_BN_ROWS)
 
 
 def _fuse_struct(mode, part, z=None, stats=None, gamma=None, beta=None, slope=0.0):
@@ -852,7 +829,6 @@ def _fuse_struct(mode, part, z=None, stats=None, gamma=None, beta=None, slope=0.
 def conv3x3_fwd_bn_stats(x: torch.Tensor, wp, bias: Optional[torch.Tensor], cout: int, stride: int = 1):
     """z = conv(x) (+ bias) with the per-pixel-tile sums of z and z^2 left by the kernel's epilogue -> (z, part [rows, 2, cout]) or None when
     the fused form does not cover this problem / packing (the caller then runs conv3x3_fwd + bn_lrelu_fwd)."""
-    import ctypes
     _chk(x, "conv3x3_fwd_bn_stats.x")
     N, H, W, Cin = x.shape
     four = isinstance(wp, Wino4Packed)
@@ -868,8 +844,8 @@ def conv3x3_fwd_bn_stats(x: torch.Tensor, wp, bias: Optional[torch.Tensor], cout
     f = _fuse_struct(BN_FWD_STATS, part)
     nws = L.pesr_conv3x3_workspace_bytes(N, OH, OW, cout)
     ws = workspace(nws, x.device) if nws else None
-    if FLOPS.on:
-        FLOPS.add(18.0 * N * OH * OW * Cin * cout, *_conv_family(wp))
+    fam = _conv_family(wp)
+    FLOPS.add(18.0 * N * OH * OW * Cin * cout, fam.frac, fam.label)
     br = KERNEL_EVENTS.begin("fwd", N, H, W, Cin, cout, stride)
     if four:
         rc = L.pesr_conv3x3_wino4_bn(_p(x), _p(wp.t), _p(bias), _p(z), N, H, W, Cin, cout, _p(ws), nws, ctypes.byref(f), _stream())
@@ -895,7 +871,6 @@ def bn_finalize_apply(z, part, gamma, beta, running_mean, running_var, num_batch
 def conv3x3_dgrad_bn_sums(dy: torch.Tensor, wpd, in_shape, stride, z, stats, gamma, beta, slope):
     """The input gradient dx of a conv whose INPUT was y = lrelu(bn(z)): the kernel stores g' = dx * lrelu'(bn(z)) and leaves the sums of g'
     and g' * xhat per pixel tile -> (g' [in_shape], part [rows, 2, C]) or None when the fused form does not cover the problem / packing."""
-    import ctypes
     _chk(dy, "conv3x3_dgrad_bn_sums.dy")
     N, H, W, Cin = in_shape
     cout = dy.shape[3]
@@ -912,8 +887,8 @@ def conv3x3_dgrad_bn_sums(dy: torch.Tensor, wpd, in_shape, stride, z, stats, gam
     f = _fuse_struct(BN_BWD_MASK_SUMS, part, z, stats, gamma, beta, slope)
     nws = L.pesr_conv3x3_workspace_bytes(N, H, W, Cin) if stride == 1 else 0
     ws = workspace(nws, dy.device) if nws else None
-    if FLOPS.on:
-        FLOPS.add(18.0 * N * ((H - 1) // stride + 1) * ((W - 1) // stride + 1) * Cin * cout, *_conv_family(wpd))
+    fam = _conv_family(wpd)
+    FLOPS.add(18.0 * N * ((H - 1) // stride + 1) * ((W - 1) // stride + 1) * Cin * cout, fam.frac, fam.label)
     br = KERNEL_EVENTS.begin("dgrad", N, H, W, Cin, cout, stride)
     if four:
         rc = L.pesr_conv3x3_wino4_bn(_p(dy), _p(wpd.t), None, _p(g), N, H, W, cout, Cin, _p(ws), nws, ctypes.byref(f), _stream())

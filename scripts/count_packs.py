@@ -13,13 +13,13 @@ for _ in range(2): trainer.gan_step(lr, hr)
 cnt = collections.Counter()
 def wrap(name):
     f = getattr(ops, name)
-    def g(w, *a, **k):
+    def g(*a, **k):
         st = traceback.extract_stack(limit=8)
         who = " < ".join(f"{os.path.basename(s.filename)}:{s.lineno}" for s in st[-5:-1])
-        cnt[(name, tuple(w.shape), a, who)] += 1
-        return f(w, *a, **k)
+        cnt[(name, tuple(x.name if isinstance(x, ops._Family) else tuple(x.shape) if torch.is_tensor(x) else x for x in a), who)] += 1
+        return f(*a, **k)
     setattr(ops, name, g)
-for n in ("pack_conv3x3", "pack_conv3x3_wino", "pack_conv3x3_wino4", "pack_bias_ps"): wrap(n)
+for n in ("_pack", "pack_bias_ps"): wrap(n)     # (every family's single pack goes through ops._pack)
 trainer.gan_step(lr, hr)
 torch.cuda.synchronize()
 for k, v in sorted(cnt.items(), key=lambda kv: -kv[1]): print(v, k)

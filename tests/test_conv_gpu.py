@@ -511,24 +511,107 @@ def test_conv3x3_s2_dgrad_256_channel_tiles_one_tap_class():
         assert torch.equal(dx, _nchw(ops.conv3x3_dgrad(_nhwc(dy), ops.pack_conv3x3(w.cuda(), 1), (N, H, W, Cin), 2)))
 
 
-@pytest.mark.parametrize("O,I,ps", [(64, 64, False), (256, 256, False), (128, 64, False), (64, 192, False), (1024, 256, True), (256, 64, True)])
-def test_batched_wino4_repack_equals_the_single_pack(O, I, ps):
-    """The one-launch re-pack behind every optimizer step (pesr_pack_conv3x3_batched, F(4,3) modes 4 / 5: one thread per
-    (row, channel) of a 16 x 16 tile) against the per-element packing the first forward uses (pesr_pack_conv3x3_wino4): bit-identical, forward and input-gradient
-    layouts, with and without the pixel-shuffle channel order; also from a weight tensor that sits 4 bytes off a 16-byte boundary."""
+# family -> (mode number of its forward packing in the batched re-pack, its single pack)
+_REPACK_FAMILIES = {"direct": (0, "pack_conv3x3"), "F(2,3)": (2, "pack_conv3x3_wino"), "F(4,3)": (4, "pack_conv3x3_wino4"),
+                    "bf16": (7, "pack_conv3x3_bf16"), "split-bf16": (9, "pack_conv3x3_bf16x3")}
+_REPACK_CASES = (
+    [("F(4,3)", O, I, ps) for O, I, ps in [(64, 64, False), (256, 256, False), (128, 64, False), (64, 192, False), (1024, 256, True), (256, 64, True)]]
+    + [("direct", 64, 64, False),
+       ("direct", 3, 64, False), ("direct", 64, 3, False),       # Nn <= 16 -> 16, R padded to 16, and the zero fill
+       ("direct", 128, 64, True), ("direct", 64, 16, True),      # pixel-shuffle channel order
+       ("F(2,3)", 128, 64, False), ("F(2,3)", 256, 64, True)]
+    + [(f, O, I, ps) for f in ("bf16", "split-bf16") for O, I, ps in [(64, 32, False), (32, 64, False), (128, 32, True)]])   # (ps: the pack wants O % 128)
+
+
+def _repack_buffer(ref):
+    """A buffer like the single pack's, every element a NaN (bf16: every byte 0xFF - a NaN too), and its view for a bit-wise comparison."""
+    buf = ref if torch.is_tensor(ref) else ref.t
+    out = torch.empty_like(buf)
+    out.view(torch.uint8).fill_(0xFF)
+    bits = (lambda t: t.view(torch.int16)) if buf.dtype == torch.bfloat16 else (lambda t: t)
+    assert bool(torch.isnan(out.float()).all())
+    return out, bits(buf), bits
+
+
+@pytest.mark.parametrize("family,O,I,ps", _REPACK_CASES,
+                         ids=[(f"{O}-{I}-{ps}" if f == "F(4,3)" else f"{f}-{O}-{I}-{ps}") for f, O, I, ps in _REPACK_CASES])
+def test_batched_wino4_repack_equals_the_single_pack(family, O, I, ps):
+    """The one-launch re-pack behind every optimizer step (pesr_pack_conv3x3_batched; its F(4,3) modes 4 / 5 work one thread per
+    (row, channel) of a 16 x 16 tile, where the single pack works per element) against the packing the first forward uses
+    (pesr_pack_conv3x3*), for every kernel family: bit-identical, forward and input-gradient layouts, with and without the
+    pixel-shuffle channel order, the direct packing's zero padding included; also from a weight tensor that sits 4 bytes off a
+    16-byte boundary.  The descriptor table carries the direct packing's jobs between the family's own: blockIdx.y picks the job."""
     import numpy as np
     from pesr_amd import ops, _lib
     for shift in (0, 1):
         base = torch.empty(O * I * 9 + 4, device="cuda")
         w = base[shift:shift + O * I * 9].view(O, I, 3, 3)
         w.copy_(_rand(O, I, 3, 3, seed=O + I + shift, scale=0.1))
-        jobs, outs = [], []
+        jobs, checks = [], []
         for mode in (0, 1):
-            out = torch.full((18 * O * I,), float("nan"), device="cuda")
-            outs.append(out)
-            jobs.append((w.data_ptr(), out.data_ptr(), O, I, 4 + mode, int(ps), I if mode == 0 else O, O if mode == 0 else I))
+            for fam in dict.fromkeys((family, "direct")):
+                mode0, pack = _REPACK_FAMILIES[fam]
+                out, ref, bits = _repack_buffer(getattr(ops, pack)(w, mode, ps=ps))
+                R, Nn = (I, O) if mode == 0 else (O, I)
+                if fam == "direct":
+                    R, Nn = (R + 15) // 16 * 16, 16 if Nn <= 16 else (Nn + 63) // 64 * 64
+                    assert out.numel() == 9 * R * Nn
+                jobs.append((w.data_ptr(), out.data_ptr(), O, I, mode0 + mode, int(ps), R, Nn))
+                checks.append((fam, mode, bits(out), ref))
         table = torch.from_numpy(np.array(jobs, dtype=np.int64)).cuda()
         _lib.check(_lib.lib().pesr_pack_conv3x3_batched(table.data_ptr(), len(jobs), torch.cuda.current_stream().cuda_stream), "batched pack")
-        for mode in (0, 1):
-            ref = ops.pack_conv3x3_wino4(w, mode, ps=ps).t
-            assert torch.equal(outs[mode], ref), (mode, shift)
+        for fam, mode, out, ref in checks:
+            if fam == "split-bf16":         # the hi plane and the lo plane behind it
+                assert out.numel() == 2 * 9 * O * I
+                assert torch.equal(out[:9 * O * I], ref[:9 * O * I]), (fam, "hi", mode, shift)
+                assert torch.equal(out[9 * O * I:], ref[9 * O * I:]), (fam, "lo", mode, shift)
+            else:
+                assert torch.equal(out, ref), (fam, mode, shift)
+
+
+def _packed_bits(packed):
+    buf = packed if torch.is_tensor(packed) else packed.t
+    return buf.view(torch.int16) if buf.dtype == torch.bfloat16 else buf
+
+
+@pytest.mark.parametrize("family", ["direct", "F(2,3)", "F(4,3)", "bf16", "split-bf16"])
+def test_packed_weight_cache_after_an_optimizer_step(family, monkeypatch):
+    """PackedConvWeights through an optimizer step, for every kernel family (the selection is pinned to the family; which shapes select
+    it is tests/test_conv_families_cpu.py's business): the weight is overwritten in place through .data and its epoch bumped - as the
+    fused Adam leaves it - and repack_all refreshes the existing forward / dgrad packings (and the PixelShuffle-permuted bias) IN
+    PLACE in its one batched launch, bit-equal to a fresh single pack, after which for_fwd / for_dgrad hand out the same objects
+    without packing; a weight that was not among the step's parameters keeps its stale packing and is re-packed on next use."""
+    from pesr_amd import functional as PF
+    from pesr_amd import ops
+    fam = next(f for f in ops._FAMILIES if f.name == family)
+    monkeypatch.setattr(ops, "conv3x3_family_fwd", lambda *a: fam)
+    monkeypatch.setattr(ops, "conv3x3_family_dgrad", lambda *a: fam)
+    single, packs = ops._pack, []
+    monkeypatch.setattr(ops, "_pack", lambda f, *a: packs.append(f.name) or single(f, *a))
+    for O, I, ps in ((128, 128, False), (256, 64, True)):
+        w, other = (torch.nn.Parameter(_rand(O, I, 3, 3, seed=s, scale=0.1).cuda()) for s in (1, 2))
+        b = torch.nn.Parameter(_rand(O, seed=3).cuda())
+        cache, cache_other, shape = PF.PackedConvWeights(ps=ps), PF.PackedConvWeights(ps=ps), (4, 24, 24, I)
+        pf, pd, qf = cache.for_fwd(w, shape), cache.for_dgrad(w, shape), cache_other.for_fwd(other, shape)
+        assert ops._conv_family(pf) is fam and ops._conv_family(pd) is fam and pf is not pd
+        pb = cache.bias(b)
+        assert (pb.data_ptr() != b.data_ptr()) == ps                    # (without the fused PixelShuffle: the bias itself)
+        ptrs = [_packed_bits(t).data_ptr() for t in (pf, pd, pb)]
+        before = [_packed_bits(t).clone() for t in (pf, pd, qf)]
+        for t, seed in ((w, 11), (other, 12), (b, 13)):
+            t.data.copy_(_rand(*t.shape, seed=seed, scale=0.1))         # raw writes: _version does not move, the epoch does
+        PF.bump_weight_epoch([w, other, b])
+        n = len(packs)
+        PF.repack_all([w, b])
+        assert cache.for_fwd(w, shape) is pf and cache.for_dgrad(w, shape) is pd and len(packs) == n, packs[n:]
+        assert [_packed_bits(t).data_ptr() for t in (pf, pd, pb)] == ptrs
+        for mode, t, old in ((0, pf, before[0]), (1, pd, before[1])):
+            assert not torch.equal(_packed_bits(t), old)
+            assert torch.equal(_packed_bits(t), _packed_bits(single(fam, w.detach(), mode, ps))), (family, mode, ps)
+        if ps:
+            assert cache.bias(b) is pb and torch.equal(pb, ops.pack_bias_ps(b.detach()))
+            assert not torch.equal(pb, b.detach())
+        assert torch.equal(_packed_bits(qf), before[2])                 # not in params: left as it was ...
+        q2 = cache_other.for_fwd(other, shape)                          # ... and its key misses: one single pack on next use
+        assert packs[n:] == [family] and q2 is not qf
+        assert torch.equal(_packed_bits(q2), _packed_bits(single(fam, other.detach(), 0, ps)))
