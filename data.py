@@ -52,9 +52,12 @@ class FolderSRDataset(Dataset):
     With a callable `lr_from_hr(hr uint8 HWC array) -> lr uint8 HWC array`, LR/ is not consulted: the file list comes from
     HR/*.png, every HR image is cropped at the top-left to multiples of `scale` and its LR image is made ONCE, here, and kept in
     host memory (HR is still read per item).  The dataset holds no GPU code: the caller supplies the resize (train.py: the device
-    bicubic of docs/modes.md section 4f, called in the parent process before the loader's workers fork)."""
+    bicubic of docs/modes.md section 4f, called in the parent process before the loader's workers fork).  With `lr_from_hr_index`
+    the callable is `lr_from_hr(hr, i)`, i the image's position in the sorted file list (the classical degradation of section 4j
+    gives every validation image parameters of its own that way)."""
 
-    def __init__(self, root, patch_size=None, num_repeats=1, is_aug=False, fixed_length=None, scale=SCALE, lr_from_hr=None):
+    def __init__(self, root, patch_size=None, num_repeats=1, is_aug=False, fixed_length=None, scale=SCALE, lr_from_hr=None,
+                 lr_from_hr_index=False):
         from PIL import Image
         self._open = Image.open
         self.ps, self.rep, self.aug, self.scale = patch_size, num_repeats, is_aug, scale
@@ -64,7 +67,8 @@ class FolderSRDataset(Dataset):
             if fixed_length:
                 self.hr_paths = self.hr_paths[:fixed_length]
             self.lr_paths = self.hr_paths                     # (one entry per sample; never opened)
-            self.lr_images = [np.ascontiguousarray(lr_from_hr(self._read_hr(p))) for p in self.hr_paths]
+            self.lr_images = [np.ascontiguousarray(lr_from_hr(self._read_hr(p), i) if lr_from_hr_index else lr_from_hr(self._read_hr(p)))
+                              for i, p in enumerate(self.hr_paths)]
             return
         self.lr_paths = sorted(glob.glob(os.path.join(root, "LR", "*.png")))
         if fixed_length:

@@ -303,6 +303,20 @@ int pesr_crop_augment(const unsigned char* pool, const long long* desc, float* o
 int pesr_imresize_u8_pass(const unsigned char* src, unsigned char* dst, const long long* desc_host, const long long* desc_dev,
                           int n_images, int axis, int s, int up, const double* weights_host, void* stream);
 
+/* ---- classical degradation LR = (HR (*) k) subsampled by s, plus noise (docs/modes.md section 4j) ------- */
+/* n entries in one launch.  Descriptor: n rows of 11 int64 {source byte offset in src, destination byte offset in dst (both at any
+ * alignment), H, W of the uint8 HWC source image (multiples of s), y0, x0, h, w of the window of its H/s x W/s LR grid that the
+ * entry produces, index of its blur kernel in the bank, sigma_n as float64 bits, noise stream number q}.  Entry i writes h*w*3 bytes,
+ * HWC, at its destination offset.  bank_dev: device doubles [n_kernels][K][K], row-major.  LR pixel (oy, ox) of the image reads HR
+ * rows s*oy + (s-K)/2 + i, i = 0 .. K-1 (columns likewise), an index outside the image clamped to the edge; float64 accumulation
+ * over i, then j, ascending, without fused multiply-add; sigma_n != 0 adds sigma_n * g(q, element of the window); clamp, round half
+ * up: bit-identical to the float64 host restatement.  desc_host and desc_dev hold the same rows: the host copy is checked and sizes
+ * the grid, the kernel reads the device copy.  PESR_EINVAL (nothing launched): s outside {2, 3, 4}, K outside 1..24 or K - s odd,
+ * H % s or W % s nonzero, an empty window or one outside the LR grid, a kernel index outside the bank, a negative or non-finite
+ * sigma_n, a negative offset, n < 1.  No workspace. */
+int pesr_degrade_u8(const unsigned char* src, unsigned char* dst, const long long* desc_host, const long long* desc_dev, int n, int s,
+                    int K, const double* bank_dev, int n_kernels, void* stream);
+
 /* ---- validation PSNR on the Y channel (reference utils.py:32-41 compute_PSNR), one image pair [1][3][H][W] ------- */
 /* a_nhwc / b_nhwc: the tensor is stored [H][W][3] instead of [3][H][W].  out2 (device doubles): {mse, psnr dB}; all
  * arithmetic in double on integer-valued terms -> bit-identical to the reference's numpy path.  workspace >= 2 KiB. */

@@ -88,6 +88,7 @@ SIGNATURES.update({
     "pesr_mse_fwd_bwd": (c_int, [_P, _P, _P, _P, c_long, c_float, _P, c_size_t, _P]),
     "pesr_crop_augment": (c_int, [_P, _P, _P, c_int, c_int, c_int, _P]),
     "pesr_imresize_u8_pass": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, _P, _P]),
+    "pesr_degrade_u8": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, _P, c_int, _P]),
     "pesr_psnr_y": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, _P, c_size_t, _P]),
     "pesr_ssim_y": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, c_size_t, _P]),
     "pesr_tile_gather": (c_int, [_P, c_int, c_int, c_int, _P, _P, _P, c_int, c_int, c_int, _P]),

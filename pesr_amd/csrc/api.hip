@@ -346,6 +346,11 @@ PESR_API int pesr_imresize_u8_pass(const unsigned char* src, unsigned char* dst,
     return pesr_imresize_u8_pass_launch(src, dst, desc_host, desc_dev, n_images, axis, s, up, weights_host, (hipStream_t)stream);
 }
 
+PESR_API int pesr_degrade_u8(const unsigned char* src, unsigned char* dst, const long long* desc_host, const long long* desc_dev, int n,
+                             int s, int K, const double* bank_dev, int n_kernels, void* stream) {
+    return pesr_degrade_u8_launch(src, dst, desc_host, desc_dev, n, s, K, bank_dev, n_kernels, (hipStream_t)stream);
+}
+
 PESR_API int pesr_psnr_y(const float* a, const float* b, double* out2, int H, int W, int a_nhwc, int b_nhwc, void* workspace,
                          size_t ws_bytes, void* stream) {
     return pesr_psnr_y_launch(a, b, out2, H, W, a_nhwc, b_nhwc, workspace, ws_bytes, (hipStream_t)stream);

@@ -182,6 +182,10 @@ int pesr_crop_augment_launch(const unsigned char* pool, const long long* desc, f
 int pesr_imresize_u8_pass_launch(const unsigned char* src, unsigned char* dst, const long long* desc_host, const long long* desc_dev,
                                  int n_images, int axis, int s, int up, const double* weights_host, hipStream_t stream);
 
+// classical degradation (blur, subsample, noise) of windows of a pool of uint8 HWC images (degrade.hip)
+int pesr_degrade_u8_launch(const unsigned char* src, unsigned char* dst, const long long* desc_host, const long long* desc_dev, int n,
+                           int s, int K, const double* bank_dev, int n_kernels, hipStream_t stream);
+
 int pesr_psnr_y_launch(const float* a, const float* b, double* out2, int H, int W, int a_nhwc, int b_nhwc, void* ws, size_t ws_bytes,
                        hipStream_t stream);
 

@@ -60,7 +60,37 @@ def build_parser():
                              "result equals the whole-image forward up to fp32 summation order; a smaller halo is an approximation")
     parser.add_argument("--tile_batch", type=int, default=16,
                         help="with --tile: tiles per Generator call (entries per call for the x8 ensemble: rounded down to a multiple of 8)")
+    # additions (not reference flags): a fixed non-bicubic test degradation, docs/modes.md section 4j
+    parser.add_argument("--degradation", type=str, default="bicubic", choices=["bicubic", "classical"],
+                        help="with --from_hr true: how the LR image is made.  classical: LR = (HR blurred by a Gaussian kernel) subsampled, "
+                             "plus noise, the same kernel for every image (the BD / DN rows of the published tables, by this project's "
+                             "own definition)")
+    parser.add_argument("--blur_sigma", type=str, default="0",
+                        help="with --degradation classical: S, the Gaussian's standard deviation in HR pixels, or S1,S2,THETA for an "
+                             "anisotropic one; 0 (default) = no blur, the narrowest legal kernel with equal weights")
+    parser.add_argument("--noise_sigma", type=float, default=0.0,
+                        help="with --degradation classical: standard deviation of the added noise in grey levels; 0 (default) = none")
+    parser.add_argument("--degrade_seed", type=int, default=0,
+                        help="with --degradation classical: the noise stream number (image i of the sorted folder takes stream seed + i)")
     return parser
+
+
+def classical_kernel(args):
+    """--degradation classical -> its blur kernel (None for bicubic); SystemExit naming the flags.  No GPU is touched."""
+    if args.degradation != "classical":
+        return None
+    if not args.from_hr:
+        raise SystemExit("test.py: --degradation classical degrades HR images: it needs --from_hr true")
+    from pesr_amd.degrade import delta_kernel, gaussian_kernel, kernel_size, parse_sigma_list
+    vals = parse_sigma_list(args.blur_sigma, "test.py", "--blur_sigma", (1, 3))
+    s1, s2, theta = vals if len(vals) == 3 else (vals[0], vals[0], 0.0)
+    if not (args.noise_sigma >= 0 and np.isfinite(args.noise_sigma)):
+        raise SystemExit(f"test.py: --noise_sigma {args.noise_sigma} must be >= 0")
+    if s1 == 0 and s2 == 0:
+        return delta_kernel(args.scale)
+    if not (s1 > 0 and s2 > 0 and np.isfinite(s1) and np.isfinite(s2)):
+        raise SystemExit(f"test.py: --blur_sigma {args.blur_sigma}: positive standard deviations (or a single 0) expected")
+    return gaussian_kernel(kernel_size(args.scale, max(s1, s2)), s1, s2, theta)
 
 
 def check_checkpoint_scale(sd, scale, path):
@@ -124,12 +154,17 @@ def _write_png(path, img):
     Image.fromarray(img).save(path)
 
 
-def lr_from_hr(hr_img, scale, device):
+def lr_from_hr(hr_img, scale, device, kernel=None, noise_sigma=0.0, noise_stream=0):
     """--from_hr: uint8 HWC HR array -> (LR, mod-cropped HR, bicubic x`scale` of the LR) as [1,3,H,W] float tensors on the device;
-    both resizes run there (pesr_amd.resize, docs/modes.md section 4f)."""
+    both resizes run there (pesr_amd.resize, docs/modes.md section 4f).  With a blur kernel the LR image is the classical
+    degradation of section 4j instead of the bicubic one."""
     from pesr_amd.resize import imresize_u8, modcrop
     hr = torch.from_numpy(np.array(modcrop(hr_img, scale))).to(device)
-    lr = imresize_u8(hr, scale, up=False)
+    if kernel is not None:
+        from pesr_amd.degrade import degrade_u8
+        lr = degrade_u8(hr, scale, kernel, noise_sigma, noise_stream)
+    else:
+        lr = imresize_u8(hr, scale, up=False)
     bic = imresize_u8(lr, scale, up=True)
     return tuple(t.permute(2, 0, 1)[None].float().contiguous() for t in (lr, hr, bic))
 
@@ -146,6 +181,7 @@ def main(argv=None):
     if args.shave < -1:
         raise SystemExit(f"test.py: --shave is a border width in pixels (or -1 for --scale), got {args.shave}")
     shave = args.scale if args.shave == -1 else args.shave
+    kernel = classical_kernel(args)
     from pesr_amd import tile as _tile
     tile_halo = _tile.check_flags("test.py", ("--tile", "--tile_halo", "--tile_batch"), args.tile, args.tile_halo, args.tile_batch,
                                   args.num_blocks, args.scale)
@@ -165,7 +201,7 @@ def main(argv=None):
     with torch.no_grad():
         for i, lr_path in enumerate(lr_paths):
             if args.from_hr:
-                inp, hr, bic = lr_from_hr(_read_png(lr_path), args.scale, device)
+                inp, hr, bic = lr_from_hr(_read_png(lr_path), args.scale, device, kernel, args.noise_sigma, args.degrade_seed + i)
             else:
                 [inp] = imgs_to_tensors([_read_png(lr_path)], device)
             if args.tile:

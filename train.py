@@ -84,6 +84,19 @@ def build_parser():
     p.add_argument("--lr_from_hr", type=str2bool, default=False,
                    help="build the training and validation sets from their HR/ folders alone: every HR image is cropped to multiples "
                         "of --scale and its LR image is made on the GPU by MATLAB-style bicubic resize (docs/modes.md section 4f)")
+    p.add_argument("--degradation", type=str, default="bicubic", choices=["bicubic", "classical"],
+                   help="how --lr_from_hr makes the LR images.  bicubic (default): the resize of section 4f.  classical: blind training "
+                        "on LR = (HR blurred by a Gaussian kernel) subsampled, plus noise (docs/modes.md section 4j): every training "
+                        "sample gets a kernel and a noise level of its own, made on the GPU each step; needs --lr_from_hr true "
+                        "--gpu_pipeline true and no --synthetic")
+    p.add_argument("--blur_sigma", type=str, default="",
+                   help="with --degradation classical: LO,HI, the range of the Gaussian's standard deviation in HR pixels; default "
+                        "0.2*scale,0.8*scale")
+    p.add_argument("--blur_aniso", type=str2bool, default=False,
+                   help="with --degradation classical: anisotropic kernels - a second sigma in [LO, the first] and an angle in [0, pi)")
+    p.add_argument("--noise_sigma", type=float, default=0.0,
+                   help="with --degradation classical: every sample gets noise of a standard deviation drawn from [0, this] grey levels; "
+                        "0 (default) = no noise")
     p.add_argument("--valid_ssim", type=str2bool, default=False,
                    help="validation also averages SSIM-Y (measured on the GPU, docs/modes.md section 4g) and prints it in a line of its "
                         "own; the best model is still chosen by PSNR")
@@ -112,6 +125,35 @@ def device_lr_from_hr(scale, device):
     return lambda hr: imresize_u8(torch.from_numpy(np.array(hr)).to(device), scale, up=False).cpu().numpy()
 
 
+VALID_DEGRADE_SEED = 20240229      # --degradation classical: the validation images' kernels and noise never change
+
+
+def degradation_spec(args):
+    """--degradation classical -> its DegradationSpec (None for bicubic); SystemExit naming the flags it needs.  No GPU is touched."""
+    if args.degradation != "classical":
+        return None
+    if not (args.lr_from_hr and args.gpu_pipeline) or args.synthetic:
+        raise SystemExit("train.py: --degradation classical makes every LR patch on the GPU from the HR pool: it needs --lr_from_hr true "
+                         "--gpu_pipeline true and no --synthetic")
+    from pesr_amd.degrade import DegradationSpec, parse_sigma_list
+    lo, hi = parse_sigma_list(args.blur_sigma, "train.py", "--blur_sigma", (2,)) if args.blur_sigma else (0.2 * args.scale, 0.8 * args.scale)
+    return DegradationSpec(lo, hi, bool(args.blur_aniso), float(args.noise_sigma)).check("train.py: --blur_sigma / --noise_sigma")
+
+
+def device_degrade_from_hr(scale, spec, device):
+    """The callable FolderSRDataset(lr_from_hr=..., lr_from_hr_index=True) wants under --degradation classical: image i of the sorted
+    folder is degraded whole, with parameters drawn from a stream that only VALID_DEGRADE_SEED and i decide - the validation PSNR
+    is comparable across epochs and across a resume."""
+    import random
+    from pesr_amd.degrade import degrade_u8, gaussian_kernel, kernel_size
+    K = kernel_size(scale, spec.sigma_hi)
+
+    def make(hr, i):
+        s1, s2, theta, sigma_n, q = spec.draw(random.Random(VALID_DEGRADE_SEED * 1000003 + i))
+        return degrade_u8(torch.from_numpy(np.array(hr)).to(device), scale, gaussian_kernel(K, s1, s2, theta), sigma_n, q).cpu().numpy()
+    return make
+
+
 def spawn_generator():
     """A generator of its own, started from torch's global stream (so torch.manual_seed still decides everything)."""
     g = torch.Generator()
@@ -124,6 +166,9 @@ def make_loaders(args, rank, world, need_train=True, device=None):
     train_set = None
     # (the LR images are made here, in the parent process, before any loader worker is forked)
     from_hr = device_lr_from_hr(args.scale, device) if args.lr_from_hr and not args.synthetic else None
+    spec = degradation_spec(args)
+    if spec is not None:      # (the training set is the GPU loader's; this serves the validation set)
+        from_hr = device_degrade_from_hr(args.scale, spec, device)
     if args.synthetic:
         train_set = SyntheticSRDataset(args.synthetic, args.patch_size, scale=args.scale)
         val_set = SyntheticSRDataset(min(args.num_valids, 2), args.patch_size, seed=99, scale=args.scale)
@@ -132,7 +177,7 @@ def make_loaders(args, rank, world, need_train=True, device=None):
             train_set = FolderSRDataset(os.path.join("data/origin/train", args.train_dataset), args.patch_size, args.num_repeats, True,
                                         scale=args.scale, lr_from_hr=from_hr)
         val_set = FolderSRDataset(os.path.join("data/origin/valid", args.valid_dataset), None, 1, False, fixed_length=10,
-                                  scale=args.scale, lr_from_hr=from_hr)
+                                  scale=args.scale, lr_from_hr=from_hr, lr_from_hr_index=spec is not None)
     sampler = train_loader = None
     if train_set is not None:
         sampler = DistributedSampler(train_set, world, rank, shuffle=True, drop_last=True) if world > 1 else None
@@ -190,7 +235,7 @@ def make_gpu_loader(args, rank, world, device):
     root = os.path.join("data/origin/train", args.train_dataset)
     if args.lr_from_hr:
         hrs = [np.asarray(Image.open(p).convert("RGB")) for p in sorted(glob.glob(os.path.join(root, "HR", "*.png")))]
-        return GpuLoader(GpuPatchSampler.from_hr(hrs, device, scale=args.scale), args.batch_size // world, args.patch_size, len(hrs),
+        return GpuLoader(GpuPatchSampler.from_hr(hrs, device, scale=args.scale, degradation=degradation_spec(args)), args.batch_size // world, args.patch_size, len(hrs),
                          args.num_repeats, rank, world)
     lr_paths = sorted(glob.glob(os.path.join(root, "LR", "*.png")))
     lrs = [np.asarray(Image.open(p).convert("RGB")) for p in lr_paths]
@@ -272,6 +317,7 @@ def check_limits(args, world):
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
+    degradation_spec(args)      # (refuses a classical run without its companion flags before anything else starts)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
