@@ -335,6 +335,23 @@ int pesr_psnr_y(const float* a, const float* b, double* out2, int H, int W, int 
 int pesr_ssim_y(const float* a, const float* b, double* out, int N, int H, int W, int a_nhwc, int b_nhwc, int shave,
                 double* map_or_null, void* workspace, size_t ws_bytes, void* stream);
 
+/* ---- NIQE block statistics (docs/modes.md section 4k), N images [N][3][H][W] (nhwc: [N][H][W][3]) ------- */
+/* The device half of the no-reference score of Mittal et al. as section 4k restates it.  RGB clipped to 0..255 and rounded; luma
+ * 0 = MATLAB's rgb2gray, floor(((r*0.298936021293775 + g*0.587043074451121) + b*0.114020904255103) + 0.5), luma 1 = the Y of the
+ * PSNR-Y above; `shave` pixels dropped on each side, then a top-left crop to Hc = B*floor((H-2*shave)/B), Wc likewise: nby x nbx
+ * blocks.  Scale 1 is that luma, scale 2 its x0.5 antialiased bicubic resize (pesr_imresize_u8_pass's x2-down weights and border
+ * rule, height then width, never rounded or clamped), with blocks of B/2.  Per scale the MSCN map (I - mu) / (sigma + 1), mu and
+ * sigma from the 7-tap Gaussian window of sigma 7/6 applied separably with replicated edges.  stats: double [N][2][nby*nbx][26], per
+ * block and scale: for the map m and for m * circshift(m, d), d = (0,1), (1,0), (1,1), (1,-1), the shift wrapping inside the block,
+ * {sum of x*x over x < 0, count of x < 0, sum of x*x over x > 0, count of x > 0, sum of |x|}; the 26th value is the sum of sigma.
+ * mscn1_or_null / mscn2_or_null: when non-null the maps [N][Hc][Wc] and [N][Hc/2][Wc/2] are written there.  float64 without fused
+ * multiply-add: both maps are bit-identical to the float64 host restatement; the sums are taken in a fixed order without atomics,
+ * the same bits on every run.  Workspace: 30 * N * Hc * Wc bytes (luma, sigma and MSCN map of both scales, 8-byte aligned), whether
+ * or not the maps are asked for; less -> PESR_EWORKSPACE.  PESR_EINVAL (nothing launched): B odd or outside 8..96, shave < 0,
+ * fewer than 2 blocks, N < 1 or N > 65535, luma not 0 or 1.  64-bit offsets. */
+int pesr_niqe_stats(const float* img, int N, int H, int W, int nhwc, int shave, int B, int luma, double* stats,
+                    double* mscn1_or_null, double* mscn2_or_null, void* workspace, size_t ws_bytes, void* stream);
+
 /* ---- tiled inference (docs/modes.md section 4h): tiles of one LR image -> a batch, a batch's outputs -> the image ------- */
 /* Gather.  src: the LR image, fp32 [3][H][W] (src_u8 = 0) or uint8 [H][W][3] (src_u8 = 1).  desc: n rows of 3 int32 {y0, x0, m}:
  * tile origin and ensemble member m in 0..7 = entry m of test.py:x8_forward's inputs (bit 0 reverses the W axis, then bit 1 the H

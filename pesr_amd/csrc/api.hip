@@ -361,6 +361,12 @@ PESR_API int pesr_ssim_y(const float* a, const float* b, double* out, int N, int
     return pesr_ssim_y_launch(a, b, out, N, H, W, a_nhwc, b_nhwc, shave, map_or_null, workspace, ws_bytes, (hipStream_t)stream);
 }
 
+PESR_API int pesr_niqe_stats(const float* img, int N, int H, int W, int nhwc, int shave, int B, int luma, double* stats,
+                             double* mscn1_or_null, double* mscn2_or_null, void* workspace, size_t ws_bytes, void* stream) {
+    return pesr_niqe_stats_launch(img, N, H, W, nhwc, shave, B, luma, stats, mscn1_or_null, mscn2_or_null, workspace, ws_bytes,
+                                  (hipStream_t)stream);
+}
+
 PESR_API int pesr_tile_gather(const void* src, int src_u8, int H, int W, float* dst, const int* desc_host, const int* desc_dev, int n,
                              int oh, int ow, void* stream) {
     return pesr_tile_gather_launch(src, src_u8, H, W, dst, desc_host, desc_dev, n, oh, ow, (hipStream_t)stream);

@@ -2,7 +2,8 @@
 """SR inference entry point (counterpart of reference test.py): perceptual model, optional PSNR model with x8
 self-ensemble, image-space blend `alpha*out + (1-alpha)*out_psnr`, PNG output.  Same flags as the reference
 (test.py:13-33) plus --precision, --scale and --from_hr (a test set that ships HR images only: LR made on the device, PSNR-Y of the
-result and of the bicubic baseline printed; --ssim adds SSIM-Y, --shave drops a border before both) and --tile (every image as
+result and of the bicubic baseline printed; --ssim adds SSIM-Y, --shave drops a border before both), --niqe (the no-reference NIQE
+of every saved image against a pristine model, with or without --from_hr; docs/modes.md section 4k) and --tile (every image as
 batches of fixed-size tiles, docs/modes.md section 4h); device-agnostic plumbing; the
 Generator itself runs on the MI355X kernels.
 """
@@ -13,7 +14,7 @@ import os
 import numpy as np
 import torch
 
-from utils import compute_PSNR, compute_SSIM, default_device, imgs_to_tensors, tensors_to_imgs
+from utils import compute_NIQE, compute_PSNR, compute_SSIM, default_device, imgs_to_tensors, tensors_to_imgs
 
 
 # (flag, type, default, help) - the reference's flags and defaults (reference test.py:15-33)
@@ -51,6 +52,11 @@ def build_parser():
     parser.add_argument("--shave", type=int, default=0,
                         help="with --from_hr true: drop a border of this many pixels before PSNR-Y and SSIM-Y are measured; -1 means "
                              "--scale, the convention of the published tables")
+    # an addition (not a reference flag): the no-reference half of the Perceptual Index, docs/modes.md section 4k
+    parser.add_argument("--niqe", type=str, default="",
+                        help="a NIQE pristine model (.npz from `python -m pesr_amd.niqe fit`, or the standard .mat): also print the NIQE "
+                             "of every saved image (measured on the GPU, --shave applied), and of the bicubic baseline with --from_hr "
+                             "true; needs no HR images")
     # additions (not reference flags): tiled inference, docs/modes.md section 4h
     parser.add_argument("--tile", type=int, default=0,
                         help="run every image as batches of overlapping tiles of one fixed shape on the GPU: the side of the square of "
@@ -169,6 +175,13 @@ def lr_from_hr(hr_img, scale, device, kernel=None, noise_sigma=0.0, noise_stream
     return tuple(t.permute(2, 0, 1)[None].float().contiguous() for t in (lr, hr, bic))
 
 
+def _niqe_of(img, model, shave, path):
+    try:
+        return compute_NIQE(img, model, shave)
+    except ValueError as e:
+        raise ValueError(f"{os.path.basename(path)}: {e}") from None
+
+
 def main(argv=None):
     args = build_parser().parse_args(argv)
     if args.scale != 4 and args.precision != "fp32":
@@ -182,11 +195,22 @@ def main(argv=None):
         raise SystemExit(f"test.py: --shave is a border width in pixels (or -1 for --scale), got {args.shave}")
     shave = args.scale if args.shave == -1 else args.shave
     kernel = classical_kernel(args)
+    niqe_model = None
+    if args.niqe:
+        from pesr_amd import niqe as _niqe
+        niqe_model = _niqe.load_model_flag("test.py", "--niqe", args.niqe)
     from pesr_amd import tile as _tile
     tile_halo = _tile.check_flags("test.py", ("--tile", "--tile_halo", "--tile_batch"), args.tile, args.tile_halo, args.tile_batch,
                                   args.num_blocks, args.scale)
     device = default_device()
     lr_paths = sorted(glob.glob(os.path.join("data/origin/test/", args.dataset, "HR" if args.from_hr else "LR", "*.png")))
+    if niqe_model is not None:                # (the size comes from the PNG header: still no GPU)
+        from PIL import Image
+        for path in lr_paths:
+            with Image.open(path) as im:
+                w, h = im.size
+            h, w = (h - h % args.scale, w - w % args.scale) if args.from_hr else (h * args.scale, w * args.scale)
+            _niqe.check_fits_flag("test.py", "--niqe / --shave", niqe_model, h, w, shave, os.path.basename(path))
     opt = {"num_channels": args.num_channels, "depth": args.num_blocks, "res_scale": args.res_scale}
     model = load_generator(opt, args.perceptual_model, args.scale).to(device)
     print("Number of parameters:", sum(p.nelement() for p in model.parameters()))
@@ -195,7 +219,7 @@ def main(argv=None):
         model_psnr = load_generator(opt, args.psnr_model, args.scale).to(device)
     save_path = os.path.join(args.save_path, args.dataset)
     os.makedirs(save_path, exist_ok=True)
-    psnrs, ssims = [], []
+    psnrs, ssims, niqes = [], [], []
     if args.tile:
         print(_tile.describe(args.tile, tile_halo, _tile.receptive_halo(args.num_blocks, args.scale)))
     with torch.no_grad():
@@ -226,13 +250,25 @@ def main(argv=None):
                 if args.ssim:
                     ssims.append((compute_SSIM(sr, hr, shave), compute_SSIM(bic, hr, shave)))
                     line += ", SSIM-Y %.10f, bicubic %.10f" % ssims[-1]
+                if niqe_model is not None:
+                    niqes.append((_niqe_of(sr, niqe_model, shave, lr_path), _niqe_of(bic, niqe_model, shave, lr_path)))
+                    line += ", NIQE %.10f, bicubic %.10f" % niqes[-1]
                 print(line)
+            elif niqe_model is not None:
+                # an LR-only set: the NIQE of what was saved needs nothing else
+                [sr] = imgs_to_tensors([img], device)
+                niqes.append((_niqe_of(sr, niqe_model, shave, lr_path),))
+                print("%s: NIQE %.10f" % (os.path.basename(lr_path), niqes[-1][0]))
             print("Tested %d img(s)" % (i + 1))
     if args.from_hr and psnrs:
         line = "Mean PSNR-Y %.10f dB, bicubic %.10f dB" % (float(np.mean([p[0] for p in psnrs])), float(np.mean([p[1] for p in psnrs])))
         if ssims:
             line += ", SSIM-Y %.10f, bicubic %.10f" % (float(np.mean([q[0] for q in ssims])), float(np.mean([q[1] for q in ssims])))
+        if niqes:
+            line += ", NIQE %.10f, bicubic %.10f" % (float(np.mean([q[0] for q in niqes])), float(np.mean([q[1] for q in niqes])))
         print(line)
+    elif niqes:
+        print("Mean NIQE %.10f" % float(np.mean([q[0] for q in niqes])))
     print("Finish")
 
 

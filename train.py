@@ -101,7 +101,11 @@ def build_parser():
                    help="validation also averages SSIM-Y (measured on the GPU, docs/modes.md section 4g) and prints it in a line of its "
                         "own; the best model is still chosen by PSNR")
     p.add_argument("--valid_shave", type=int, default=0,
-                   help="drop a border of this many pixels before the validation PSNR (and SSIM) is measured")
+                   help="drop a border of this many pixels before the validation PSNR (and SSIM, NIQE) is measured")
+    p.add_argument("--valid_niqe", type=str, default="",
+                   help="a NIQE pristine model (.npz from `python -m pesr_amd.niqe fit`, or the standard .mat): validation also averages "
+                        "the NIQE of the results (measured on the GPU, docs/modes.md section 4k) and prints it in a line of its own; "
+                        "the best model is still chosen by PSNR")
     p.add_argument("--valid_tile", type=int, default=0,
                    help="validate every image as batches of overlapping tiles (docs/modes.md section 4h): the side of the square of LR "
                         "pixels a tile owns; 0 (default) = off, one Generator call on the whole image")
@@ -315,9 +319,23 @@ def check_limits(args, world):
                          "which this implementation does for even sizes only)")
 
 
+def niqe_model_of(args):
+    """--valid_niqe -> its model (None without the flag); SystemExit naming the flags.  No GPU is touched."""
+    if not args.valid_niqe:
+        return None
+    from pesr_amd import niqe as _niqe
+    model = _niqe.load_model_flag("train.py", "--valid_niqe", args.valid_niqe)
+    if args.synthetic:          # (the synthetic validation images are patch-sized; a folder's sizes are known when it is read)
+        side = args.patch_size * args.scale
+        _niqe.check_fits_flag("train.py", "--valid_niqe / --valid_shave / --patch_size", model, side, side, args.valid_shave,
+                              "the synthetic validation images")
+    return model
+
+
 def main(argv=None):
     args = build_parser().parse_args(argv)
     degradation_spec(args)      # (refuses a classical run without its companion flags before anything else starts)
+    niqe_model = niqe_model_of(args)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -345,7 +363,7 @@ def main(argv=None):
     _ops.set_precision(args.precision)
     from pesr_amd.optim import FlatAdam
     from pesr_amd.step import Trainer
-    from utils import compute_PSNR, compute_SSIM
+    from utils import compute_NIQE, compute_PSNR, compute_SSIM
     from pesr_amd.tile import describe, receptive_halo, tiled_forward
     valid_halo = receptive_halo(args.num_blocks, args.scale) if args.valid_tile_halo == -1 else args.valid_tile_halo
     if args.valid_tile and rank == 0:
@@ -521,7 +539,7 @@ def main(argv=None):
 
         # validation on rank 0 (full images, batch 1, no_grad), reference train.py:281-295
         if rank == 0:
-            psnr, ssim = [], []
+            psnr, ssim, niqe = [], [], []
             if G_eval is not G:
                 optim_G.refresh_ema()       # the steps of this epoch rewrote the averaged weights through raw pointers
             with torch.no_grad():
@@ -534,6 +552,11 @@ def main(argv=None):
                     psnr.append(compute_PSNR(hr_img, sr, args.valid_shave))
                     if args.valid_ssim:
                         ssim.append(compute_SSIM(hr_img, sr, args.valid_shave))
+                    if niqe_model is not None:
+                        try:
+                            niqe.append(compute_NIQE(sr, niqe_model, args.valid_shave))
+                        except ValueError as e:
+                            raise SystemExit(f"train.py: --valid_niqe / --valid_shave: a validation image: {e}")
             val_psnr = float(np.mean(psnr)) if psnr else 0.0
             print("Finish valid [%d/%d]. PSNR: %.4fdB%s" % (epoch, args.num_epochs, val_psnr, ema_tag))
             if tb is not None:
@@ -543,6 +566,11 @@ def main(argv=None):
                 print("Finish valid [%d/%d]. SSIM: %.6f" % (epoch, args.num_epochs, val_ssim))
                 if tb is not None:
                     tb.add_scalar("Validate SSIM", val_ssim, epoch)
+            if niqe_model is not None:
+                val_niqe = float(np.mean(niqe)) if niqe else 0.0
+                print("Finish valid [%d/%d]. NIQE: %.6f" % (epoch, args.num_epochs, val_niqe))
+                if tb is not None:
+                    tb.add_scalar("Validate NIQE", val_niqe, epoch)
             if not gan and val_psnr > best_psnr:
                 best_psnr = val_psnr
                 torch.save(G_eval.state_dict(), os.path.join(check_point, "best_model.pt"))

@@ -1,5 +1,5 @@
-"""Image <-> tensor helpers, the Y-channel PSNR of the reference (reference utils.py:10-41) and the Y-channel SSIM beside it
-(docs/modes.md section 4g), device-agnostic.
+"""Image <-> tensor helpers, the Y-channel PSNR of the reference (reference utils.py:10-41), the Y-channel SSIM beside it
+(docs/modes.md section 4g) and the no-reference NIQE (section 4k), device-agnostic.
 
 Tensors carry raw 0..255 values (no /255 anywhere).  Metrics run in numpy on the host exactly as the
 reference does; nothing here is on the hot path.
@@ -115,6 +115,18 @@ def compute_SSIM(out, lbl, shave=0):
     num = (2.0 * mxmy + c1) * (2.0 * (xy - mxmy) + c2)
     den = ((mxmx + mymy) + c1) * (((xx - mxmx) + (yy - mymy)) + c2)
     return float(np.mean(num / den))
+
+
+def compute_NIQE(out, model, shave=0):
+    """NIQE of an image against a pristine model (a pesr_amd.niqe.NiqeModel or the path of one; docs/modes.md section 4k), a border
+    of `shave` pixels dropped first.  No second image is needed.  float32 GPU tensors [N,3,H,W] are measured on the device
+    (pesr_amd.niqe.niqe_stats; the mean over the N images comes back); anything else ([1,3,H,W] / [3,H,W] tensors or arrays) goes
+    through numpy in float64 with the same definition.  ValueError when the shaved image holds the model's block less than twice or
+    fewer than two blocks have finite features."""
+    from pesr_amd import niqe as _niqe
+    if not isinstance(model, _niqe.NiqeModel):
+        model = _niqe.NiqeModel.load(model)
+    return float(np.mean(_niqe.niqe(out, model, int(shave))))
 
 
 def update_tensorboard(epoch, tb, img_idx, inp, out, lbl):
