@@ -317,6 +317,24 @@ int pesr_imresize_u8_pass(const unsigned char* src, unsigned char* dst, const lo
 int pesr_degrade_u8(const unsigned char* src, unsigned char* dst, const long long* desc_host, const long long* desc_dev, int n, int s,
                     int K, const double* bank_dev, int n_kernels, void* stream);
 
+/* ---- JPEG round trip of uint8 HWC RGB windows: encoder at quality q, then decoder (docs/modes.md section 4l) ------- */
+/* n entries in one call (two launches).  Descriptor: n rows of 8 int64 {source byte offset in src, source row stride in pixels,
+ * destination byte offset in dst, destination row stride in pixels (offsets at any alignment), h, w of the window, quality q in
+ * 1 .. 100, byte offset of the entry's planes in the workspace = the workspace bytes of the entries before it}.  Entry i reads the
+ * h x w pixels at its source offset and writes h x w pixels at its destination offset; the entries' windows must not overlap, but
+ * dst may be src (in place).  chroma: 420 (chroma planes of ceil(h/2) x ceil(w/2): 2 x 2 mean, back up with the 9/3/3/1 triangle
+ * filter) or 444.  dct_dev: 64 device doubles, T[u][x] = 0.5 c(u) cos((2x+1) u pi / 16); quant_dev: device doubles [100][2][64], the
+ * luminance and chrominance tables of q = 1 .. 100 in row-major (vertical frequency first) order (pesr_amd/jpeg.py makes both).
+ * The 8 x 8 block grid starts at the window's origin; planes are extended by replication.  float64 without fused multiply-add, sums
+ * in ascending order: bit-identical to the float64 host restatement.  Workspace: an entry needs h*w + 2*ceil(h/2)*ceil(w/2) bytes
+ * at 420, 3*h*w at 444; pesr_jpeg_workspace_bytes adds them up (0 if the descriptors are not valid).  desc_host and desc_dev hold
+ * the same rows: the host copy is checked and sizes the grid, the kernels read the device copy.  PESR_EINVAL (nothing launched): q
+ * outside 1 .. 100, h or w < 1, a stride below w, a negative offset, a workspace offset that is not the running sum, n < 1, chroma
+ * not 420 or 444, a workspace smaller than pesr_jpeg_workspace_bytes.  No atomics: the same bits on every run. */
+size_t pesr_jpeg_workspace_bytes(const long long* desc_host, int n, int chroma);
+int pesr_jpeg_u8(const unsigned char* src, unsigned char* dst, const long long* desc_host, const long long* desc_dev, int n,
+                 int chroma, const double* dct_dev, const double* quant_dev, void* workspace, size_t ws_bytes, void* stream);
+
 /* ---- validation PSNR on the Y channel (reference utils.py:32-41 compute_PSNR), one image pair [1][3][H][W] ------- */
 /* a_nhwc / b_nhwc: the tensor is stored [H][W][3] instead of [3][H][W].  out2 (device doubles): {mse, psnr dB}; all
  * arithmetic in double on integer-valued terms -> bit-identical to the reference's numpy path.  workspace >= 2 KiB. */

@@ -89,6 +89,8 @@ SIGNATURES.update({
     "pesr_crop_augment": (c_int, [_P, _P, _P, c_int, c_int, c_int, _P]),
     "pesr_imresize_u8_pass": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, _P, _P]),
     "pesr_degrade_u8": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, _P, c_int, _P]),
+    "pesr_jpeg_workspace_bytes": (c_size_t, [_P, c_int, c_int]),
+    "pesr_jpeg_u8": (c_int, [_P, _P, _P, _P, c_int, c_int, _P, _P, _P, c_size_t, _P]),
     "pesr_psnr_y": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, _P, c_size_t, _P]),
     "pesr_ssim_y": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, c_size_t, _P]),
     "pesr_niqe_stats": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, c_size_t, _P]),

@@ -351,6 +351,15 @@ PESR_API int pesr_degrade_u8(const unsigned char* src, unsigned char* dst, const
     return pesr_degrade_u8_launch(src, dst, desc_host, desc_dev, n, s, K, bank_dev, n_kernels, (hipStream_t)stream);
 }
 
+PESR_API size_t pesr_jpeg_workspace_bytes(const long long* desc_host, int n, int chroma) {
+    return pesr_jpeg_workspace_bytes_host(desc_host, n, chroma);
+}
+
+PESR_API int pesr_jpeg_u8(const unsigned char* src, unsigned char* dst, const long long* desc_host, const long long* desc_dev, int n,
+                          int chroma, const double* dct_dev, const double* quant_dev, void* workspace, size_t ws_bytes, void* stream) {
+    return pesr_jpeg_u8_launch(src, dst, desc_host, desc_dev, n, chroma, dct_dev, quant_dev, workspace, ws_bytes, (hipStream_t)stream);
+}
+
 PESR_API int pesr_psnr_y(const float* a, const float* b, double* out2, int H, int W, int a_nhwc, int b_nhwc, void* workspace,
                          size_t ws_bytes, void* stream) {
     return pesr_psnr_y_launch(a, b, out2, H, W, a_nhwc, b_nhwc, workspace, ws_bytes, (hipStream_t)stream);

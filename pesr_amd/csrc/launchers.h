@@ -186,6 +186,11 @@ int pesr_imresize_u8_pass_launch(const unsigned char* src, unsigned char* dst, c
 int pesr_degrade_u8_launch(const unsigned char* src, unsigned char* dst, const long long* desc_host, const long long* desc_dev, int n,
                            int s, int K, const double* bank_dev, int n_kernels, hipStream_t stream);
 
+// JPEG round trip (colour, chroma subsampling, 8 x 8 DCT, quantisation and back) of windows of a pool of uint8 HWC images (jpeg.hip)
+size_t pesr_jpeg_workspace_bytes_host(const long long* desc_host, int n, int chroma);
+int pesr_jpeg_u8_launch(const unsigned char* src, unsigned char* dst, const long long* desc_host, const long long* desc_dev, int n,
+                        int chroma, const double* dct_dev, const double* quant_dev, void* ws, size_t ws_bytes, hipStream_t stream);
+
 int pesr_psnr_y_launch(const float* a, const float* b, double* out2, int H, int W, int a_nhwc, int b_nhwc, void* ws, size_t ws_bytes,
                        hipStream_t stream);
 

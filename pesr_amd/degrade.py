@@ -120,17 +120,32 @@ def degrade_u8(img: torch.Tensor, s: int, kernel, noise_sigma: float = 0.0, nois
     return out.view(ho, wo, 3)
 
 
-class DegradationSpec(NamedTuple):
-    """The ranges a blind-training sample's degradation is drawn from: blur sigma in [sigma_lo, sigma_hi] (HR pixels), a second
-    sigma and an angle when `aniso`, a noise level in [0, noise_hi] (grey levels) when noise_hi > 0."""
+class _BlurNoise(NamedTuple):
     sigma_lo: float
     sigma_hi: float
     aniso: bool = False
     noise_hi: float = 0.0
 
+
+class DegradationSpec(_BlurNoise):
+    """The ranges a blind-training sample's degradation is drawn from: blur sigma in [sigma_lo, sigma_hi] (HR pixels), a second
+    sigma and an angle when `aniso`, a noise level in [0, noise_hi] (grey levels) when noise_hi > 0, a JPEG quality in
+    jpeg_lo .. jpeg_hi (docs/modes.md section 4l; 4:2:0 chroma unless `jpeg_420` is false) when jpeg_hi > 0.  As a tuple it is the
+    four blur and noise values, as it was before JPEG; jpeg_lo, jpeg_hi and jpeg_420 are trailing constructor arguments with
+    defaults and plain attributes."""
+
+    def __new__(cls, sigma_lo, sigma_hi, aniso=False, noise_hi=0.0, jpeg_lo=0, jpeg_hi=0, jpeg_420=True):
+        self = super().__new__(cls, sigma_lo, sigma_hi, aniso, noise_hi)
+        self.jpeg_lo, self.jpeg_hi, self.jpeg_420 = int(jpeg_lo), int(jpeg_hi), bool(jpeg_420)
+        return self
+
+    def __repr__(self):
+        return f"DegradationSpec{tuple(self) + (self.jpeg_lo, self.jpeg_hi, self.jpeg_420)!r}"
+
     def draw(self, rng):
         """-> (sigma1, sigma2, theta, sigma_n, q) from `rng` (a random.Random) alone, in this fixed order: sigma1; if aniso, sigma2 in
-        [sigma_lo, sigma1], then theta in [0, pi); if noise_hi > 0, sigma_n; always q = 64 random bits."""
+        [sigma_lo, sigma1], then theta in [0, pi); if noise_hi > 0, sigma_n; always q = 64 random bits; if jpeg_hi > 0, a sixth value
+        after q: the JPEG quality, an integer in jpeg_lo .. jpeg_hi."""
         sigma1 = rng.uniform(self.sigma_lo, self.sigma_hi)
         sigma2, theta, sigma_n = sigma1, 0.0, 0.0
         if self.aniso:
@@ -138,13 +153,16 @@ class DegradationSpec(NamedTuple):
             theta = rng.uniform(0.0, math.pi)
         if self.noise_hi > 0:
             sigma_n = rng.uniform(0.0, self.noise_hi)
-        return sigma1, sigma2, theta, sigma_n, rng.getrandbits(64)
+        drawn = (sigma1, sigma2, theta, sigma_n, rng.getrandbits(64))
+        return drawn + (rng.randint(self.jpeg_lo, self.jpeg_hi),) if self.jpeg_hi else drawn
 
     def check(self, who: str = "DegradationSpec"):
         if not (0 < self.sigma_lo <= self.sigma_hi and math.isfinite(self.sigma_hi)):
             raise SystemExit(f"{who}: the blur range {self.sigma_lo},{self.sigma_hi} must be 0 < LO <= HI")
         if not (self.noise_hi >= 0 and math.isfinite(self.noise_hi)):
             raise SystemExit(f"{who}: the noise level {self.noise_hi} must be >= 0")
+        if (self.jpeg_lo or self.jpeg_hi) and not 1 <= self.jpeg_lo <= self.jpeg_hi <= 100:
+            raise SystemExit(f"{who}: the JPEG quality range {self.jpeg_lo},{self.jpeg_hi} must be 1 <= LO <= HI <= 100")
         return self
 
 

@@ -68,12 +68,12 @@ class GpuPatchSampler:
     def _pick(self, i, patch, rng, augment):
         h, w, _ = self.lr_shapes[i]
         pick = (i, rng.randint(0, h - patch), rng.randint(0, w - patch), rng.randint(0, 7) if augment else 0)
-        # (sigma1, sigma2, theta, sigma_n, q), drawn after the crop and from the same stream
+        # (sigma1, sigma2, theta, sigma_n, q[, JPEG quality]), drawn after the crop and from the same stream
         return pick if self.degradation is None else pick + self.degradation.draw(rng)
 
     def draw(self, batch: int, patch: int, rng: Optional[random.Random] = None, augment: bool = True):
         """Host-side random choices, as the reference's random.randint calls: (image, y, x, aug) per sample; with a degradation
-        spec (image, y, x, aug, sigma1, sigma2, theta, sigma_n, q)."""
+        spec (image, y, x, aug, sigma1, sigma2, theta, sigma_n, q), and the JPEG quality as a tenth value when the spec has one."""
         rng = rng or random
         return [self._pick(rng.randrange(self.n), patch, rng, augment) for _ in range(batch)]
 
@@ -84,12 +84,19 @@ class GpuPatchSampler:
         return [self._pick(i, patch, rng, augment) for i in images]
 
     def _degraded_patches(self, picks, patch):
-        """The step's LR patches, unaugmented, as a scratch uint8 pool of B patches of patch x patch pixels: one kernel per pick."""
+        """The step's LR patches, unaugmented, as a scratch uint8 pool of B patches of patch x patch pixels: one kernel per pick.
+        A spec with a JPEG range then compresses every patch in place at its pick's quality (docs/modes.md section 4l), the block
+        grid starting at the patch's own origin."""
         from .degrade import degrade_pool_u8, gaussian_kernel
         bank = np.stack([gaussian_kernel(self.kernel_size, p[4], p[5], p[6]) for p in picks])
         out, _, _ = degrade_pool_u8(self.hr_pool, [self.hr_off[p[0]] for p in picks], [self.hr_shapes[p[0]] for p in picks], self.scale, bank,
                                     range(len(picks)), [p[7] for p in picks], [p[8] for p in picks],
                                     windows=[(p[1], p[2], patch, patch) for p in picks])
+        if self.degradation.jpeg_hi:
+            from .jpeg import jpeg_pool_u8
+            B = len(picks)
+            jpeg_pool_u8(out, [3 * patch * patch * b for b in range(B)], [(patch, patch)] * B, [patch] * B, [p[9] for p in picks],
+                         self.degradation.jpeg_420, out=out)
         return out
 
     def assemble(self, picks: List[tuple], patch: int, nhwc: bool = False):

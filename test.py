@@ -78,7 +78,23 @@ def build_parser():
                         help="with --degradation classical: standard deviation of the added noise in grey levels; 0 (default) = none")
     parser.add_argument("--degrade_seed", type=int, default=0,
                         help="with --degradation classical: the noise stream number (image i of the sorted folder takes stream seed + i)")
+    # additions (not reference flags): JPEG compression of the LR image, docs/modes.md section 4l
+    parser.add_argument("--jpeg_quality", type=str, default="",
+                        help="with --from_hr true: Q in 1 .. 100 - the LR image (bicubic or classical) goes through a JPEG round trip on the "
+                             "GPU at this quality before the Generator sees it; default: no compression")
+    parser.add_argument("--jpeg_chroma", type=str, default="420", choices=["420", "444"],
+                        help="with --jpeg_quality: chroma at half resolution in both directions (420, default) or at full resolution (444)")
     return parser
+
+
+def jpeg_quality(args):
+    """--jpeg_quality -> its integer (0: no compression); SystemExit naming the flags.  No GPU is touched."""
+    if not args.jpeg_quality:
+        return 0
+    if not args.from_hr:
+        raise SystemExit("test.py: --jpeg_quality compresses the LR image made from an HR image: it needs --from_hr true")
+    from pesr_amd.jpeg import parse_quality
+    return parse_quality(args.jpeg_quality, "test.py", "--jpeg_quality", 1)[0]
 
 
 def classical_kernel(args):
@@ -160,10 +176,11 @@ def _write_png(path, img):
     Image.fromarray(img).save(path)
 
 
-def lr_from_hr(hr_img, scale, device, kernel=None, noise_sigma=0.0, noise_stream=0):
+def lr_from_hr(hr_img, scale, device, kernel=None, noise_sigma=0.0, noise_stream=0, jpeg_q=0, jpeg_420=True):
     """--from_hr: uint8 HWC HR array -> (LR, mod-cropped HR, bicubic x`scale` of the LR) as [1,3,H,W] float tensors on the device;
     both resizes run there (pesr_amd.resize, docs/modes.md section 4f).  With a blur kernel the LR image is the classical
-    degradation of section 4j instead of the bicubic one."""
+    degradation of section 4j instead of the bicubic one; with jpeg_q the LR image, however made, then goes through the JPEG round
+    trip of section 4l, and the bicubic baseline is the upscale of the compressed image."""
     from pesr_amd.resize import imresize_u8, modcrop
     hr = torch.from_numpy(np.array(modcrop(hr_img, scale))).to(device)
     if kernel is not None:
@@ -171,6 +188,9 @@ def lr_from_hr(hr_img, scale, device, kernel=None, noise_sigma=0.0, noise_stream
         lr = degrade_u8(hr, scale, kernel, noise_sigma, noise_stream)
     else:
         lr = imresize_u8(hr, scale, up=False)
+    if jpeg_q:
+        from pesr_amd.jpeg import jpeg_u8
+        lr = jpeg_u8(lr, jpeg_q, jpeg_420)
     bic = imresize_u8(lr, scale, up=True)
     return tuple(t.permute(2, 0, 1)[None].float().contiguous() for t in (lr, hr, bic))
 
@@ -195,6 +215,7 @@ def main(argv=None):
         raise SystemExit(f"test.py: --shave is a border width in pixels (or -1 for --scale), got {args.shave}")
     shave = args.scale if args.shave == -1 else args.shave
     kernel = classical_kernel(args)
+    jpeg_q = jpeg_quality(args)
     niqe_model = None
     if args.niqe:
         from pesr_amd import niqe as _niqe
@@ -225,7 +246,8 @@ def main(argv=None):
     with torch.no_grad():
         for i, lr_path in enumerate(lr_paths):
             if args.from_hr:
-                inp, hr, bic = lr_from_hr(_read_png(lr_path), args.scale, device, kernel, args.noise_sigma, args.degrade_seed + i)
+                inp, hr, bic = lr_from_hr(_read_png(lr_path), args.scale, device, kernel, args.noise_sigma, args.degrade_seed + i,
+                                          jpeg_q, args.jpeg_chroma == "420")
             else:
                 [inp] = imgs_to_tensors([_read_png(lr_path)], device)
             if args.tile:

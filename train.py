@@ -97,6 +97,13 @@ def build_parser():
     p.add_argument("--noise_sigma", type=float, default=0.0,
                    help="with --degradation classical: every sample gets noise of a standard deviation drawn from [0, this] grey levels; "
                         "0 (default) = no noise")
+    p.add_argument("--jpeg_quality", type=str, default="",
+                   help="with --degradation classical: LO,HI - every training sample's LR patch goes through a JPEG round trip on the GPU "
+                        "at a quality drawn from LO .. HI (1 .. 100), after the noise and before the flips (docs/modes.md section 4l); "
+                        "every validation image is compressed once at a quality of its own; needs --degradation classical "
+                        "--lr_from_hr true --gpu_pipeline true; default: no compression")
+    p.add_argument("--jpeg_chroma", type=str, default="420", choices=["420", "444"],
+                   help="with --jpeg_quality: chroma at half resolution in both directions (420, default) or at full resolution (444)")
     p.add_argument("--valid_ssim", type=str2bool, default=False,
                    help="validation also averages SSIM-Y (measured on the GPU, docs/modes.md section 4g) and prints it in a line of its "
                         "own; the best model is still chosen by PSNR")
@@ -134,6 +141,9 @@ VALID_DEGRADE_SEED = 20240229      # --degradation classical: the validation ima
 
 def degradation_spec(args):
     """--degradation classical -> its DegradationSpec (None for bicubic); SystemExit naming the flags it needs.  No GPU is touched."""
+    if args.jpeg_quality and not (args.degradation == "classical" and args.lr_from_hr and args.gpu_pipeline and not args.synthetic):
+        raise SystemExit("train.py: --jpeg_quality compresses the LR patches the GPU makes from the HR pool: it needs --degradation classical "
+                         "--lr_from_hr true --gpu_pipeline true and no --synthetic")
     if args.degradation != "classical":
         return None
     if not (args.lr_from_hr and args.gpu_pipeline) or args.synthetic:
@@ -141,20 +151,30 @@ def degradation_spec(args):
                          "--gpu_pipeline true and no --synthetic")
     from pesr_amd.degrade import DegradationSpec, parse_sigma_list
     lo, hi = parse_sigma_list(args.blur_sigma, "train.py", "--blur_sigma", (2,)) if args.blur_sigma else (0.2 * args.scale, 0.8 * args.scale)
-    return DegradationSpec(lo, hi, bool(args.blur_aniso), float(args.noise_sigma)).check("train.py: --blur_sigma / --noise_sigma")
+    jlo = jhi = 0
+    if args.jpeg_quality:
+        from pesr_amd.jpeg import parse_quality
+        jlo, jhi = parse_quality(args.jpeg_quality, "train.py", "--jpeg_quality", 2)
+    return DegradationSpec(lo, hi, bool(args.blur_aniso), float(args.noise_sigma), jlo, jhi, args.jpeg_chroma == "420").check(
+        "train.py: --blur_sigma / --noise_sigma / --jpeg_quality")
 
 
 def device_degrade_from_hr(scale, spec, device):
     """The callable FolderSRDataset(lr_from_hr=..., lr_from_hr_index=True) wants under --degradation classical: image i of the sorted
     folder is degraded whole, with parameters drawn from a stream that only VALID_DEGRADE_SEED and i decide - the validation PSNR
-    is comparable across epochs and across a resume."""
+    is comparable across epochs and across a resume.  A spec with a JPEG range compresses the image at a quality the same stream
+    gives after the other values (docs/modes.md section 4l)."""
     import random
     from pesr_amd.degrade import degrade_u8, gaussian_kernel, kernel_size
     K = kernel_size(scale, spec.sigma_hi)
 
     def make(hr, i):
-        s1, s2, theta, sigma_n, q = spec.draw(random.Random(VALID_DEGRADE_SEED * 1000003 + i))
-        return degrade_u8(torch.from_numpy(np.array(hr)).to(device), scale, gaussian_kernel(K, s1, s2, theta), sigma_n, q).cpu().numpy()
+        s1, s2, theta, sigma_n, q, *quality = spec.draw(random.Random(VALID_DEGRADE_SEED * 1000003 + i))
+        lr = degrade_u8(torch.from_numpy(np.array(hr)).to(device), scale, gaussian_kernel(K, s1, s2, theta), sigma_n, q)
+        if quality:
+            from pesr_amd.jpeg import jpeg_u8
+            lr = jpeg_u8(lr, quality[0], spec.jpeg_420)
+        return lr.cpu().numpy()
     return make
 
 
