@@ -335,6 +335,23 @@ size_t pesr_jpeg_workspace_bytes(const long long* desc_host, int n, int chroma);
 int pesr_jpeg_u8(const unsigned char* src, unsigned char* dst, const long long* desc_host, const long long* desc_dev, int n,
                  int chroma, const double* dct_dev, const double* quant_dev, void* workspace, size_t ws_bytes, void* stream);
 
+/* ---- resize of uint8 HWC RGB windows from any size to any size, one pass (docs/modes.md section 4m) ------- */
+/* n entries in one launch; axis 0 resizes the height (w_out must equal w_in), axis 1 the width (h_out must equal h_in); a resize is
+ * the height pass into an intermediate uint8 image, then the width pass.  Descriptor: n rows of 12 int64 {source byte offset in
+ * src, source row stride in pixels, destination byte offset in dst, destination row stride in pixels (offsets at any alignment),
+ * h_in, w_in, h_out, w_out, offset of the entry's table in tables_dev in 8-byte words, taps T, the float64 bits of the noise level
+ * sigma_n (grey levels; 0 = none; width pass only), noise stream}.  An entry may be a window of a larger image: the symmetric
+ * reflection is at the window's own border.  Table of an axis with n_out outputs (pesr_amd/resize.py makes it): (T + 1) * n_out
+ * words, tap-major - word [o] the unreflected first tap of output o as an int64, word [(1 + k) * n_out + o] the float64 weight k of
+ * output o, rows with fewer than T taps ending in 0.0; entries may share a table.  out[o] = sum over k ascending of w[k][o] *
+ * in[reflect(first[o] + k)] in float64 without fused multiply-add, then section 4j's noise, clamp, round half up: bit-identical to
+ * the float64 host restatement.  desc_host and desc_dev hold the same rows: the host copy is checked and sizes the grid, the kernel
+ * reads the device copy.  PESR_EINVAL (nothing launched): n < 1, a side < 1, the pass's axis beyond 8:1 or 1:8, the other axis
+ * changed, a stride below the width, a negative offset, T outside 1 .. 32, a table that does not lie inside table_words, a negative,
+ * NaN or infinite sigma_n, a nonzero sigma_n on the height pass, an axis other than 0 or 1.  No workspace, no atomics. */
+int pesr_resize_to_u8_pass(const unsigned char* src, unsigned char* dst, const long long* desc_host, const long long* desc_dev, int n,
+                           int axis, const void* tables_dev, long table_words, void* stream);
+
 /* ---- validation PSNR on the Y channel (reference utils.py:32-41 compute_PSNR), one image pair [1][3][H][W] ------- */
 /* a_nhwc / b_nhwc: the tensor is stored [H][W][3] instead of [3][H][W].  out2 (device doubles): {mse, psnr dB}; all
  * arithmetic in double on integer-valued terms -> bit-identical to the reference's numpy path.  workspace >= 2 KiB. */

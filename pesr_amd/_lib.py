@@ -91,6 +91,7 @@ SIGNATURES.update({
     "pesr_degrade_u8": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, _P, c_int, _P]),
     "pesr_jpeg_workspace_bytes": (c_size_t, [_P, c_int, c_int]),
     "pesr_jpeg_u8": (c_int, [_P, _P, _P, _P, c_int, c_int, _P, _P, _P, c_size_t, _P]),
+    "pesr_resize_to_u8_pass": (c_int, [_P, _P, _P, _P, c_int, c_int, _P, c_long, _P]),
     "pesr_psnr_y": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, _P, c_size_t, _P]),
     "pesr_ssim_y": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, c_size_t, _P]),
     "pesr_niqe_stats": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, c_size_t, _P]),

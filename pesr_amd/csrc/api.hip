@@ -360,6 +360,11 @@ PESR_API int pesr_jpeg_u8(const unsigned char* src, unsigned char* dst, const lo
     return pesr_jpeg_u8_launch(src, dst, desc_host, desc_dev, n, chroma, dct_dev, quant_dev, workspace, ws_bytes, (hipStream_t)stream);
 }
 
+PESR_API int pesr_resize_to_u8_pass(const unsigned char* src, unsigned char* dst, const long long* desc_host, const long long* desc_dev,
+                                    int n, int axis, const void* tables_dev, long table_words, void* stream) {
+    return pesr_resize_to_u8_pass_launch(src, dst, desc_host, desc_dev, n, axis, tables_dev, table_words, (hipStream_t)stream);
+}
+
 PESR_API int pesr_psnr_y(const float* a, const float* b, double* out2, int H, int W, int a_nhwc, int b_nhwc, void* workspace,
                          size_t ws_bytes, void* stream) {
     return pesr_psnr_y_launch(a, b, out2, H, W, a_nhwc, b_nhwc, workspace, ws_bytes, (hipStream_t)stream);

@@ -191,6 +191,10 @@ size_t pesr_jpeg_workspace_bytes_host(const long long* desc_host, int n, int chr
 int pesr_jpeg_u8_launch(const unsigned char* src, unsigned char* dst, const long long* desc_host, const long long* desc_dev, int n,
                         int chroma, const double* dct_dev, const double* quant_dev, void* ws, size_t ws_bytes, hipStream_t stream);
 
+// resize of windows of a pool of uint8 HWC images from any size to any size, one pass (axis 0: height, 1: width) (resize_to.hip)
+int pesr_resize_to_u8_pass_launch(const unsigned char* src, unsigned char* dst, const long long* desc_host, const long long* desc_dev,
+                                  int n, int axis, const void* tables_dev, long table_words, hipStream_t stream);
+
 int pesr_psnr_y_launch(const float* a, const float* b, double* out2, int H, int W, int a_nhwc, int b_nhwc, void* ws, size_t ws_bytes,
                        hipStream_t stream);
 

@@ -130,22 +130,40 @@ class _BlurNoise(NamedTuple):
 class DegradationSpec(_BlurNoise):
     """The ranges a blind-training sample's degradation is drawn from: blur sigma in [sigma_lo, sigma_hi] (HR pixels), a second
     sigma and an angle when `aniso`, a noise level in [0, noise_hi] (grey levels) when noise_hi > 0, a JPEG quality in
-    jpeg_lo .. jpeg_hi (docs/modes.md section 4l; 4:2:0 chroma unless `jpeg_420` is false) when jpeg_hi > 0.  As a tuple it is the
-    four blur and noise values, as it was before JPEG; jpeg_lo, jpeg_hi and jpeg_420 are trailing constructor arguments with
-    defaults and plain attributes."""
+    jpeg_lo .. jpeg_hi (docs/modes.md section 4l; 4:2:0 chroma unless `jpeg_420` is false) when jpeg_hi > 0, a resize jitter
+    (section 4m: a round trip through an intermediate size of r times the sides, r in [jitter_lo, jitter_hi], with a random filter
+    each way) when jitter_hi > 0.  As a tuple it is the four blur and noise values, as it was before JPEG; jpeg_lo, jpeg_hi,
+    jpeg_420, jitter_lo and jitter_hi are trailing constructor arguments with defaults and plain attributes."""
 
-    def __new__(cls, sigma_lo, sigma_hi, aniso=False, noise_hi=0.0, jpeg_lo=0, jpeg_hi=0, jpeg_420=True):
+    def __new__(cls, sigma_lo, sigma_hi, aniso=False, noise_hi=0.0, jpeg_lo=0, jpeg_hi=0, jpeg_420=True, jitter_lo=0.0, jitter_hi=0.0):
         self = super().__new__(cls, sigma_lo, sigma_hi, aniso, noise_hi)
         self.jpeg_lo, self.jpeg_hi, self.jpeg_420 = int(jpeg_lo), int(jpeg_hi), bool(jpeg_420)
+        self.jitter_lo, self.jitter_hi = float(jitter_lo), float(jitter_hi)
         return self
 
     def __repr__(self):
-        return f"DegradationSpec{tuple(self) + (self.jpeg_lo, self.jpeg_hi, self.jpeg_420)!r}"
+        return f"DegradationSpec{tuple(self) + (self.jpeg_lo, self.jpeg_hi, self.jpeg_420, self.jitter_lo, self.jitter_hi)!r}"
+
+    def fields(self):
+        """The names of the values draw() returns, in its order: what is at which position depends on the spec."""
+        names = ("sigma1", "sigma2", "theta", "sigma_n", "q")
+        if self.jpeg_hi:
+            names += ("jpeg_quality",)
+        if self.jitter_hi:
+            names += ("jitter_r", "jitter_m1", "jitter_m2")
+        return names
+
+    def named(self, drawn):
+        """A drawn tuple (or the tail of a sampler's pick that holds one) as a dict by field name."""
+        names = self.fields()
+        assert len(drawn) == len(names), (len(drawn), names)
+        return dict(zip(names, drawn))
 
     def draw(self, rng):
         """-> (sigma1, sigma2, theta, sigma_n, q) from `rng` (a random.Random) alone, in this fixed order: sigma1; if aniso, sigma2 in
         [sigma_lo, sigma1], then theta in [0, pi); if noise_hi > 0, sigma_n; always q = 64 random bits; if jpeg_hi > 0, a sixth value
-        after q: the JPEG quality, an integer in jpeg_lo .. jpeg_hi."""
+        after q: the JPEG quality, an integer in jpeg_lo .. jpeg_hi; if jitter_hi > 0, three more after everything else: r in
+        [jitter_lo, jitter_hi] and the two filters, indices into pesr_amd.resize.METHODS.  fields() names what was drawn."""
         sigma1 = rng.uniform(self.sigma_lo, self.sigma_hi)
         sigma2, theta, sigma_n = sigma1, 0.0, 0.0
         if self.aniso:
@@ -154,7 +172,11 @@ class DegradationSpec(_BlurNoise):
         if self.noise_hi > 0:
             sigma_n = rng.uniform(0.0, self.noise_hi)
         drawn = (sigma1, sigma2, theta, sigma_n, rng.getrandbits(64))
-        return drawn + (rng.randint(self.jpeg_lo, self.jpeg_hi),) if self.jpeg_hi else drawn
+        if self.jpeg_hi:
+            drawn += (rng.randint(self.jpeg_lo, self.jpeg_hi),)
+        if self.jitter_hi:
+            drawn += (rng.uniform(self.jitter_lo, self.jitter_hi), rng.randrange(3), rng.randrange(3))
+        return drawn
 
     def check(self, who: str = "DegradationSpec"):
         if not (0 < self.sigma_lo <= self.sigma_hi and math.isfinite(self.sigma_hi)):
@@ -163,7 +185,54 @@ class DegradationSpec(_BlurNoise):
             raise SystemExit(f"{who}: the noise level {self.noise_hi} must be >= 0")
         if (self.jpeg_lo or self.jpeg_hi) and not 1 <= self.jpeg_lo <= self.jpeg_hi <= 100:
             raise SystemExit(f"{who}: the JPEG quality range {self.jpeg_lo},{self.jpeg_hi} must be 1 <= LO <= HI <= 100")
+        if (self.jitter_lo or self.jitter_hi) and not 0.125 <= self.jitter_lo <= self.jitter_hi <= 8:
+            raise SystemExit(f"{who}: the resize-jitter range {self.jitter_lo},{self.jitter_hi} must be 0.125 <= LO <= HI <= 8")
         return self
+
+
+def jitter_size(n: int, r: float) -> int:
+    """Q(n) = min(8n, max(ceil(n / 8), floor(r n + 0.5))): the intermediate length of the resize jitter, kept inside section 4m's limits."""
+    return min(8 * n, max(-(-n // 8), int(math.floor(r * n + 0.5))))
+
+
+def resize_jitter_pool_u8(pool: torch.Tensor, offsets: Sequence[int], shapes: Sequence[Tuple[int, int]], r: Sequence[float],
+                          m1: Sequence[int], m2: Sequence[int], noise_sigma=None, noise_stream=None, strides=None):
+    """The resize-jitter round trip of docs/modes.md section 4m for n windows of a device-resident uint8 pool: entry i goes from
+    h x w to Q(h) x Q(w) with filter METHODS[m1[i]] and back to h x w with METHODS[m2[i]], the noise in the second resize's width
+    pass: two pooled resizes, four launches.  -> (out_pool, out_offsets, out_shapes), the results back to back."""
+    from .resize import METHODS, imresize_to_pool_u8
+    shapes = [(int(h), int(w)) for h, w in shapes]
+    mids = [(jitter_size(h, ri), jitter_size(w, ri)) for (h, w), ri in zip(shapes, r)]
+    mid, mid_off, _ = imresize_to_pool_u8(pool, offsets, shapes, mids, [METHODS[i] for i in m1], strides=strides)
+    return imresize_to_pool_u8(mid, mid_off, mids, shapes, [METHODS[i] for i in m2], noise_sigma=noise_sigma, noise_stream=noise_stream)
+
+
+def resize_jitter_u8(img: torch.Tensor, r: float, m1: int = 0, m2: int = 0, noise_sigma: float = 0.0, noise_stream: int = 0) -> torch.Tensor:
+    """uint8 HWC device tensor -> the same size, after the resize-jitter round trip through Q(h) x Q(w)."""
+    if not (torch.is_tensor(img) and img.is_cuda):
+        raise _lib.PesrHipError("resize_jitter_u8 needs a device tensor: pesr_amd has no CPU fallback")
+    assert img.dtype == torch.uint8 and img.dim() == 3 and img.shape[2] == 3, "uint8 [H][W][3] expected"
+    h, w = int(img.shape[0]), int(img.shape[1])
+    out, _, _ = resize_jitter_pool_u8(img.contiguous().view(-1), [0], [(h, w)], [r], [m1], [m2], [noise_sigma], [noise_stream])
+    return out.view(h, w, 3)
+
+
+def parse_resize_jitter(text: str, who: str):
+    """test.py's 'R[,M1[,M2]]' -> (r, m1, m2), the filters as indices into pesr_amd.resize.METHODS (default bicubic); SystemExit
+    naming the flag for a bad number, a ratio outside 0.125 .. 8 or an unknown filter name."""
+    from .resize import METHODS
+    parts = str(text).split(",")
+    try:
+        r = float(parts[0])
+    except ValueError:
+        raise SystemExit(f"{who}: --resize_jitter {text!r}: R[,M1[,M2]] expected, R a number")
+    if not (0.125 <= r <= 8) or len(parts) > 3:
+        raise SystemExit(f"{who}: --resize_jitter {text!r}: R[,M1[,M2]] expected, 0.125 <= R <= 8")
+    names = parts[1:] + ["bicubic"] * (3 - len(parts))
+    for m in names:
+        if m not in METHODS:
+            raise SystemExit(f"{who}: --resize_jitter {text!r}: filter {m!r} is not one of {', '.join(METHODS)}")
+    return r, METHODS.index(names[0]), METHODS.index(names[1])
 
 
 def parse_sigma_list(text: str, who: str, flag: str, counts: Sequence[int]):

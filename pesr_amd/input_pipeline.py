@@ -68,12 +68,13 @@ class GpuPatchSampler:
     def _pick(self, i, patch, rng, augment):
         h, w, _ = self.lr_shapes[i]
         pick = (i, rng.randint(0, h - patch), rng.randint(0, w - patch), rng.randint(0, 7) if augment else 0)
-        # (sigma1, sigma2, theta, sigma_n, q[, JPEG quality]), drawn after the crop and from the same stream
+        # the spec's draw (DegradationSpec.fields() names its values), after the crop and from the same stream
         return pick if self.degradation is None else pick + self.degradation.draw(rng)
 
     def draw(self, batch: int, patch: int, rng: Optional[random.Random] = None, augment: bool = True):
         """Host-side random choices, as the reference's random.randint calls: (image, y, x, aug) per sample; with a degradation
-        spec (image, y, x, aug, sigma1, sigma2, theta, sigma_n, q), and the JPEG quality as a tenth value when the spec has one."""
+        spec (image, y, x, aug, sigma1, sigma2, theta, sigma_n, q), then the JPEG quality when the spec has one, then the resize
+        jitter's (r, m1, m2) when it has one: DegradationSpec.named(pick[4:]) names them."""
         rng = rng or random
         return [self._pick(rng.randrange(self.n), patch, rng, augment) for _ in range(batch)]
 
@@ -85,18 +86,25 @@ class GpuPatchSampler:
 
     def _degraded_patches(self, picks, patch):
         """The step's LR patches, unaugmented, as a scratch uint8 pool of B patches of patch x patch pixels: one kernel per pick.
+        A spec with a resize jitter then sends every patch through its pick's intermediate size and back (section 4m: two pooled
+        resizes, reflection at the patch's own border), and the noise moves from the degrade launch into the second resize.
         A spec with a JPEG range then compresses every patch in place at its pick's quality (docs/modes.md section 4l), the block
         grid starting at the patch's own origin."""
-        from .degrade import degrade_pool_u8, gaussian_kernel
-        bank = np.stack([gaussian_kernel(self.kernel_size, p[4], p[5], p[6]) for p in picks])
-        out, _, _ = degrade_pool_u8(self.hr_pool, [self.hr_off[p[0]] for p in picks], [self.hr_shapes[p[0]] for p in picks], self.scale, bank,
-                                    range(len(picks)), [p[7] for p in picks], [p[8] for p in picks],
-                                    windows=[(p[1], p[2], patch, patch) for p in picks])
-        if self.degradation.jpeg_hi:
+        from .degrade import degrade_pool_u8, gaussian_kernel, resize_jitter_pool_u8
+        spec, B = self.degradation, len(picks)
+        drawn = [spec.named(p[4:]) for p in picks]
+        bank = np.stack([gaussian_kernel(self.kernel_size, d["sigma1"], d["sigma2"], d["theta"]) for d in drawn])
+        sigma_n, q = [d["sigma_n"] for d in drawn], [d["q"] for d in drawn]
+        out, offs, shapes = degrade_pool_u8(self.hr_pool, [self.hr_off[p[0]] for p in picks], [self.hr_shapes[p[0]] for p in picks], self.scale,
+                                            bank, range(B), [0.0] * B if spec.jitter_hi else sigma_n, q,
+                                            windows=[(p[1], p[2], patch, patch) for p in picks])
+        if spec.jitter_hi:
+            out, _, _ = resize_jitter_pool_u8(out, offs, shapes, [d["jitter_r"] for d in drawn], [d["jitter_m1"] for d in drawn],
+                                              [d["jitter_m2"] for d in drawn], sigma_n, q)
+        if spec.jpeg_hi:
             from .jpeg import jpeg_pool_u8
-            B = len(picks)
-            jpeg_pool_u8(out, [3 * patch * patch * b for b in range(B)], [(patch, patch)] * B, [patch] * B, [p[9] for p in picks],
-                         self.degradation.jpeg_420, out=out)
+            jpeg_pool_u8(out, [3 * patch * patch * b for b in range(B)], [(patch, patch)] * B, [patch] * B,
+                         [d["jpeg_quality"] for d in drawn], spec.jpeg_420, out=out)
         return out
 
     def assemble(self, picks: List[tuple], patch: int, nhwc: bool = False):

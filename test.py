@@ -84,7 +84,22 @@ def build_parser():
                              "GPU at this quality before the Generator sees it; default: no compression")
     parser.add_argument("--jpeg_chroma", type=str, default="420", choices=["420", "444"],
                         help="with --jpeg_quality: chroma at half resolution in both directions (420, default) or at full resolution (444)")
+    # addition (not a reference flag): a fixed resize jitter of the LR image, docs/modes.md section 4m
+    parser.add_argument("--resize_jitter", type=str, default="",
+                        help="with --degradation classical: R[,M1[,M2]] - every LR image is resized to R times its sides (0.125 .. 8) with "
+                             "filter M1 and back with filter M2 (bicubic, bilinear or box; default bicubic) on the GPU, the noise added "
+                             "after the resize, before the JPEG round trip; default: none")
     return parser
+
+
+def resize_jitter(args):
+    """--resize_jitter -> (r, m1, m2) (None: no jitter); SystemExit naming the flags.  No GPU is touched."""
+    if not args.resize_jitter:
+        return None
+    if args.degradation != "classical":
+        raise SystemExit("test.py: --resize_jitter is a step of the classical degradation: it needs --from_hr true --degradation classical")
+    from pesr_amd.degrade import parse_resize_jitter
+    return parse_resize_jitter(args.resize_jitter, "test.py")
 
 
 def jpeg_quality(args):
@@ -176,16 +191,20 @@ def _write_png(path, img):
     Image.fromarray(img).save(path)
 
 
-def lr_from_hr(hr_img, scale, device, kernel=None, noise_sigma=0.0, noise_stream=0, jpeg_q=0, jpeg_420=True):
+def lr_from_hr(hr_img, scale, device, kernel=None, noise_sigma=0.0, noise_stream=0, jpeg_q=0, jpeg_420=True, jitter=None):
     """--from_hr: uint8 HWC HR array -> (LR, mod-cropped HR, bicubic x`scale` of the LR) as [1,3,H,W] float tensors on the device;
     both resizes run there (pesr_amd.resize, docs/modes.md section 4f).  With a blur kernel the LR image is the classical
     degradation of section 4j instead of the bicubic one; with jpeg_q the LR image, however made, then goes through the JPEG round
-    trip of section 4l, and the bicubic baseline is the upscale of the compressed image."""
+    trip of section 4l, and the bicubic baseline is the upscale of the compressed image.  With jitter = (r, m1, m2) the classical
+    LR image goes through the resize round trip of section 4m before that, its noise added in the second resize; the baseline is
+    then the upscale of the jittered (or jittered and compressed) image."""
     from pesr_amd.resize import imresize_u8, modcrop
     hr = torch.from_numpy(np.array(modcrop(hr_img, scale))).to(device)
     if kernel is not None:
-        from pesr_amd.degrade import degrade_u8
-        lr = degrade_u8(hr, scale, kernel, noise_sigma, noise_stream)
+        from pesr_amd.degrade import degrade_u8, resize_jitter_u8
+        lr = degrade_u8(hr, scale, kernel, 0.0 if jitter else noise_sigma, noise_stream)
+        if jitter:
+            lr = resize_jitter_u8(lr, jitter[0], jitter[1], jitter[2], noise_sigma, noise_stream)
     else:
         lr = imresize_u8(hr, scale, up=False)
     if jpeg_q:
@@ -216,6 +235,7 @@ def main(argv=None):
     shave = args.scale if args.shave == -1 else args.shave
     kernel = classical_kernel(args)
     jpeg_q = jpeg_quality(args)
+    jitter = resize_jitter(args)
     niqe_model = None
     if args.niqe:
         from pesr_amd import niqe as _niqe
@@ -247,7 +267,7 @@ def main(argv=None):
         for i, lr_path in enumerate(lr_paths):
             if args.from_hr:
                 inp, hr, bic = lr_from_hr(_read_png(lr_path), args.scale, device, kernel, args.noise_sigma, args.degrade_seed + i,
-                                          jpeg_q, args.jpeg_chroma == "420")
+                                          jpeg_q, args.jpeg_chroma == "420", jitter)
             else:
                 [inp] = imgs_to_tensors([_read_png(lr_path)], device)
             if args.tile:

@@ -104,6 +104,12 @@ def build_parser():
                         "--lr_from_hr true --gpu_pipeline true; default: no compression")
     p.add_argument("--jpeg_chroma", type=str, default="420", choices=["420", "444"],
                    help="with --jpeg_quality: chroma at half resolution in both directions (420, default) or at full resolution (444)")
+    p.add_argument("--resize_jitter", type=str, default="",
+                   help="with --degradation classical: LO,HI (0.125 .. 8) - every training sample's LR patch is resized to r times its "
+                        "sides, r drawn from [LO, HI], and back, each way with a filter drawn from bicubic, bilinear and box, on the GPU "
+                        "(docs/modes.md section 4m); the noise then comes after the resize, the JPEG round trip last; every validation "
+                        "image gets one such round trip of its own; needs --degradation classical --lr_from_hr true --gpu_pipeline true; "
+                        "default: none")
     p.add_argument("--valid_ssim", type=str2bool, default=False,
                    help="validation also averages SSIM-Y (measured on the GPU, docs/modes.md section 4g) and prints it in a line of its "
                         "own; the best model is still chosen by PSNR")
@@ -144,6 +150,9 @@ def degradation_spec(args):
     if args.jpeg_quality and not (args.degradation == "classical" and args.lr_from_hr and args.gpu_pipeline and not args.synthetic):
         raise SystemExit("train.py: --jpeg_quality compresses the LR patches the GPU makes from the HR pool: it needs --degradation classical "
                          "--lr_from_hr true --gpu_pipeline true and no --synthetic")
+    if args.resize_jitter and not (args.degradation == "classical" and args.lr_from_hr and args.gpu_pipeline and not args.synthetic):
+        raise SystemExit("train.py: --resize_jitter resizes the LR patches the GPU makes from the HR pool: it needs --degradation classical "
+                         "--lr_from_hr true --gpu_pipeline true and no --synthetic")
     if args.degradation != "classical":
         return None
     if not (args.lr_from_hr and args.gpu_pipeline) or args.synthetic:
@@ -155,25 +164,32 @@ def degradation_spec(args):
     if args.jpeg_quality:
         from pesr_amd.jpeg import parse_quality
         jlo, jhi = parse_quality(args.jpeg_quality, "train.py", "--jpeg_quality", 2)
-    return DegradationSpec(lo, hi, bool(args.blur_aniso), float(args.noise_sigma), jlo, jhi, args.jpeg_chroma == "420").check(
-        "train.py: --blur_sigma / --noise_sigma / --jpeg_quality")
+    rlo, rhi = parse_sigma_list(args.resize_jitter, "train.py", "--resize_jitter", (2,)) if args.resize_jitter else (0.0, 0.0)
+    if args.resize_jitter and not 0.125 <= rlo <= rhi <= 8:      # (NaN too; check() alone would take 0,0 for "off")
+        raise SystemExit(f"train.py: --resize_jitter {args.resize_jitter!r}: the range must be 0.125 <= LO <= HI <= 8")
+    return DegradationSpec(lo, hi, bool(args.blur_aniso), float(args.noise_sigma), jlo, jhi, args.jpeg_chroma == "420", rlo, rhi).check(
+        "train.py: --blur_sigma / --noise_sigma / --jpeg_quality / --resize_jitter")
 
 
 def device_degrade_from_hr(scale, spec, device):
     """The callable FolderSRDataset(lr_from_hr=..., lr_from_hr_index=True) wants under --degradation classical: image i of the sorted
     folder is degraded whole, with parameters drawn from a stream that only VALID_DEGRADE_SEED and i decide - the validation PSNR
-    is comparable across epochs and across a resume.  A spec with a JPEG range compresses the image at a quality the same stream
-    gives after the other values (docs/modes.md section 4l)."""
+    is comparable across epochs and across a resume.  A spec with a resize jitter sends the image through the round trip of section
+    4m (the noise then in its second resize), a spec with a JPEG range compresses it last (section 4l): both take their values from
+    the same stream, after the other values."""
     import random
-    from pesr_amd.degrade import degrade_u8, gaussian_kernel, kernel_size
+    from pesr_amd.degrade import degrade_u8, gaussian_kernel, kernel_size, resize_jitter_u8
     K = kernel_size(scale, spec.sigma_hi)
 
     def make(hr, i):
-        s1, s2, theta, sigma_n, q, *quality = spec.draw(random.Random(VALID_DEGRADE_SEED * 1000003 + i))
-        lr = degrade_u8(torch.from_numpy(np.array(hr)).to(device), scale, gaussian_kernel(K, s1, s2, theta), sigma_n, q)
-        if quality:
+        d = spec.named(spec.draw(random.Random(VALID_DEGRADE_SEED * 1000003 + i)))
+        lr = degrade_u8(torch.from_numpy(np.array(hr)).to(device), scale, gaussian_kernel(K, d["sigma1"], d["sigma2"], d["theta"]),
+                        0.0 if spec.jitter_hi else d["sigma_n"], d["q"])
+        if spec.jitter_hi:
+            lr = resize_jitter_u8(lr, d["jitter_r"], d["jitter_m1"], d["jitter_m2"], d["sigma_n"], d["q"])
+        if spec.jpeg_hi:
             from pesr_amd.jpeg import jpeg_u8
-            lr = jpeg_u8(lr, quality[0], spec.jpeg_420)
+            lr = jpeg_u8(lr, d["jpeg_quality"], spec.jpeg_420)
         return lr.cpu().numpy()
     return make
 
