@@ -1,6 +1,6 @@
 // Classical degradation of uint8 HWC images, LR = (HR (*) k) subsampled by s, plus noise, as pinned in docs/modes.md section 4j:
 // a K x K float64 blur kernel (1 <= K <= 24, K of the parity of s) centred on the s x s block of every LR pixel, replicate clamp at
-// the IMAGE border, Gaussian-like noise made from integers, clamp to [0, 255], floor(acc + 0.5).  One launch serves n entries through
+// the IMAGE border, Gaussian-like noise made from integers, clamp to [0, 255], round half up.  One launch serves n entries through
 // a descriptor array; an entry is a window (y0, x0, h, w) of the LR grid of one image of the pool, so a training crop reads the real
 // image around it and only the image border is special.
 //   acc = 0; for i ascending, for j ascending: acc = acc + k[i][j] * hr[clamp(s*oy + (s-K)/2 + i)][clamp(s*ox + (s-K)/2 + j)]
@@ -12,48 +12,12 @@
 #pragma clang fp contract(off)
 #include "common.h"
 #include "launchers.h"
+#include "exact_u8.h"
 
 constexpr int DEGRADE_THREADS = 256;
 constexpr int DEGRADE_TILE = 16;                           // LR pixels per workgroup and axis
 constexpr int DEGRADE_MAX_K = 24;
 constexpr int DEGRADE_DESC = 11;                           // int64 words per entry (include/pesr_hip.h)
-
-// oracle/detrand.py's mixer, restated
-__device__ __forceinline__ unsigned long long degrade_splitmix64(unsigned long long z) {
-    z += 0x9E3779B97F4A7C15ULL;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
-    return z ^ (z >> 31);
-}
-
-// twelve-term Irwin-Hall variate from the twelve 16-bit fields of three hashed counters: exact in float64
-__device__ __forceinline__ double degrade_gauss(unsigned long long key, unsigned long long e) {
-    int sum = 0;
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        const unsigned long long z = degrade_splitmix64(key + 3ULL * e + (unsigned long long)j);
-        sum += (int)(z & 0xffff) + (int)((z >> 16) & 0xffff) + (int)((z >> 32) & 0xffff) + (int)(z >> 48);
-    }
-    return (double)(2 * sum - 786420) / 131072.0;
-}
-
-__device__ __forceinline__ int degrade_clamp(int j, int n) { return j < 0 ? 0 : (j >= n ? n - 1 : j); }
-
-// plain operators under this file's `fp contract(off)` (see resize.hip on why not __dmul_rn / __dadd_rn)
-__device__ __forceinline__ double degrade_mac(double acc, double w, unsigned v) {
-    const double prod = w * (double)v;
-    return acc + prod;
-}
-
-__device__ __forceinline__ double degrade_noise(double acc, double sigma, double g) {
-    const double prod = sigma * g;
-    return acc + prod;
-}
-
-__device__ __forceinline__ unsigned char degrade_round(double acc) {
-    acc = fmin(fmax(acc, 0.0), 255.0);
-    return (unsigned char)floor(acc + 0.5);
-}
 
 template <int S>
 __global__ __launch_bounds__(DEGRADE_THREADS) void degrade_kernel(const unsigned char* __restrict__ src, unsigned char* __restrict__ dst,
@@ -69,7 +33,7 @@ __global__ __launch_bounds__(DEGRADE_THREADS) void degrade_kernel(const unsigned
         const int H = (int)d[2], W = (int)d[3], y0 = (int)d[4], x0 = (int)d[5], h = (int)d[6], w = (int)d[7];
         const double* kern = bank + d[8] * (long long)(K * K);
         const double sigma = __longlong_as_double(d[9]);
-        const unsigned long long key = degrade_splitmix64((unsigned long long)d[10]);
+        const unsigned long long key = exact_splitmix64((unsigned long long)d[10]);
         const long long xtiles = (w + DEGRADE_TILE - 1) / DEGRADE_TILE;
         const long long tiles = ((h + DEGRADE_TILE - 1) / DEGRADE_TILE) * xtiles;
         for (long long t = blockIdx.x; t < tiles; t += gridDim.x) {
@@ -80,9 +44,9 @@ __global__ __launch_bounds__(DEGRADE_THREADS) void degrade_kernel(const unsigned
             __syncthreads();                                // the previous tile's readers are done
             for (int p = threadIdx.x; p < K * K; p += DEGRADE_THREADS) sw[p] = kern[p];
             for (int p = threadIdx.x; p < sy * sx; p += DEGRADE_THREADS) {
-                const int r = degrade_clamp(row0 + p / sx, H), c = degrade_clamp(col0 + p % sx, W);
+                const int r = exact_replicate(row0 + p / sx, H), c = exact_replicate(col0 + p % sx, W);
                 const unsigned char* px = src + so + ((long long)r * W + c) * 3;
-                spx[p] = (unsigned)px[0] | ((unsigned)px[1] << 8) | ((unsigned)px[2] << 16);
+                spx[p] = exact_load_px(px);
             }
             __syncthreads();
             const int ly = threadIdx.x / DEGRADE_TILE, lx = threadIdx.x % DEGRADE_TILE;
@@ -93,22 +57,22 @@ __global__ __launch_bounds__(DEGRADE_THREADS) void degrade_kernel(const unsigned
                     for (int j = 0; j < K; ++j) {
                         const double wt = sw[i * K + j];
                         const unsigned v = base[i * sx + j];
-                        a0 = degrade_mac(a0, wt, v & 0xff);
-                        a1 = degrade_mac(a1, wt, (v >> 8) & 0xff);
-                        a2 = degrade_mac(a2, wt, v >> 16);
+                        a0 = exact_mac_u(a0, wt, v & 0xff);
+                        a1 = exact_mac_u(a1, wt, (v >> 8) & 0xff);
+                        a2 = exact_mac_u(a2, wt, v >> 16);
                     }
                 }
                 const long long pix = (long long)(ty + ly) * w + (tx + lx);
                 if (sigma != 0.0) {
                     const unsigned long long e = 3ULL * (unsigned long long)pix;
-                    a0 = degrade_noise(a0, sigma, degrade_gauss(key, e));
-                    a1 = degrade_noise(a1, sigma, degrade_gauss(key, e + 1));
-                    a2 = degrade_noise(a2, sigma, degrade_gauss(key, e + 2));
+                    a0 = exact_noise(a0, sigma, exact_gauss(key, e));
+                    a1 = exact_noise(a1, sigma, exact_gauss(key, e + 1));
+                    a2 = exact_noise(a2, sigma, exact_gauss(key, e + 2));
                 }
                 unsigned char* o = dst + dof + pix * 3;
-                o[0] = degrade_round(a0);
-                o[1] = degrade_round(a1);
-                o[2] = degrade_round(a2);
+                o[0] = (unsigned char)exact_round8(a0);
+                o[1] = (unsigned char)exact_round8(a1);
+                o[2] = (unsigned char)exact_round8(a2);
             }
         }
     }
@@ -128,16 +92,11 @@ int pesr_degrade_u8_launch(const unsigned char* src, unsigned char* dst, const l
         if (d[8] < 0 || d[8] >= n_kernels) return PESR_EINVAL;
         double sigma;
         __builtin_memcpy(&sigma, &d[9], 8);
-        if (!(sigma >= 0.0) || sigma > 1.7976931348623157e308) return PESR_EINVAL;             // negative, NaN, infinite
+        if (!exact_sigma_ok(sigma)) return PESR_EINVAL;
         const long long tiles = ((h + DEGRADE_TILE - 1) / DEGRADE_TILE) * ((w + DEGRADE_TILE - 1) / DEGRADE_TILE);
         if (tiles > max_tiles) max_tiles = tiles;
     }
-    // about 32 K workgroups in all: each walks its entry's tiles with a stride, and gridDim.y walks the entries
-    const int gy = n < 65535 ? n : 65535;
-    long long gx = 32768 / gy;
-    if (gx < 1) gx = 1;
-    if (gx > max_tiles) gx = max_tiles;
-    const dim3 grid((unsigned)gx, (unsigned)gy);
+    const dim3 grid = exact_pool_grid(n, max_tiles);
     if (s == 2) hipLaunchKernelGGL(degrade_kernel<2>, grid, dim3(DEGRADE_THREADS), 0, stream, src, dst, desc_dev, n, K, bank_dev);
     else if (s == 3) hipLaunchKernelGGL(degrade_kernel<3>, grid, dim3(DEGRADE_THREADS), 0, stream, src, dst, desc_dev, n, K, bank_dev);
     else hipLaunchKernelGGL(degrade_kernel<4>, grid, dim3(DEGRADE_THREADS), 0, stream, src, dst, desc_dev, n, K, bank_dev);

@@ -13,22 +13,12 @@
 #pragma clang fp contract(off)
 #include "common.h"
 #include "launchers.h"
+#include "exact_u8.h"
 
 constexpr int JPEG_THREADS = 256;
 constexpr int JPEG_MCU = 16;                               // pixels per workgroup and axis
 constexpr int JPEG_DESC = 8;                               // int64 words per entry (include/pesr_hip.h)
 constexpr long long JPEG_MAX_SIDE = 1LL << 26;             // 3 * stride stays inside an int
-
-__device__ __forceinline__ double jpeg_round8(double v) {
-    v = fmin(fmax(v, 0.0), 255.0);
-    return floor(v + 0.5);
-}
-
-// plain operators under this file's `fp contract(off)` (see resize.hip on why not __dmul_rn / __dadd_rn)
-__device__ __forceinline__ double jpeg_mac(double acc, double t, double v) {
-    const double prod = t * v;
-    return acc + prod;
-}
 
 __host__ __device__ __forceinline__ long long jpeg_entry_bytes(long long h, long long w, bool c420) {
     return c420 ? h * w + 2 * ((h + 1) / 2) * ((w + 1) / 2) : 3 * h * w;
@@ -67,22 +57,22 @@ __global__ __launch_bounds__(JPEG_THREADS) void jpeg_code_kernel(const unsigned 
                 const unsigned char* px = src + so + ((long long)y * sstride + x) * 3;
                 const double R = (double)px[0], G = (double)px[1], B = (double)px[2];
                 double Y = 0.299 * R;
-                Y = jpeg_mac(Y, 0.587, G);
-                Y = jpeg_mac(Y, 0.114, B);
+                Y = exact_mac(Y, 0.587, G);
+                Y = exact_mac(Y, 0.114, B);
                 double Cb = 128.0 - 0.168736 * R;
                 Cb = Cb - 0.331264 * G;
-                Cb = jpeg_mac(Cb, 0.5, B);
-                double Cr = jpeg_mac(128.0, 0.5, R);
+                Cb = exact_mac(Cb, 0.5, B);
+                double Cr = exact_mac(128.0, 0.5, R);
                 Cr = Cr - 0.418688 * G;
                 Cr = Cr - 0.081312 * B;
                 const int at = ((ly >> 3) * 2 + (lx >> 3)) * 64 + (ly & 7) * 8 + (lx & 7);
-                bufa[at] = jpeg_round8(Y) - 128.0;
+                bufa[at] = exact_round8(Y) - 128.0;
                 if (C420) {
-                    sc[0][tid] = (unsigned char)jpeg_round8(Cb);
-                    sc[1][tid] = (unsigned char)jpeg_round8(Cr);
+                    sc[0][tid] = (unsigned char)exact_round8(Cb);
+                    sc[1][tid] = (unsigned char)exact_round8(Cr);
                 } else {
-                    bufa[4 * 64 + at] = jpeg_round8(Cb) - 128.0;
-                    bufa[8 * 64 + at] = jpeg_round8(Cr) - 128.0;
+                    bufa[4 * 64 + at] = exact_round8(Cb) - 128.0;
+                    bufa[8 * 64 + at] = exact_round8(Cr) - 128.0;
                 }
             }
             if (C420) {
@@ -110,7 +100,7 @@ __global__ __launch_bounds__(JPEG_THREADS) void jpeg_code_kernel(const unsigned 
                 const double* p = bufa + blk * 64 + y * 8;
                 double acc = 0.0;
 #pragma unroll
-                for (int x = 0; x < 8; ++x) acc = jpeg_mac(acc, st[u * 8 + x], p[x]);
+                for (int x = 0; x < 8; ++x) acc = exact_mac(acc, st[u * 8 + x], p[x]);
                 bufb[idx] = acc;
             }
             __syncthreads();
@@ -121,7 +111,7 @@ __global__ __launch_bounds__(JPEG_THREADS) void jpeg_code_kernel(const unsigned 
                 const double* g = bufb + blk * 64 + u;
                 double acc = 0.0;
 #pragma unroll
-                for (int y = 0; y < 8; ++y) acc = jpeg_mac(acc, st[v * 8 + y], g[y * 8]);
+                for (int y = 0; y < 8; ++y) acc = exact_mac(acc, st[v * 8 + y], g[y * 8]);
                 const double Q = sq[(blk >= 4 ? 64 : 0) + v * 8 + u];
                 const double kq = floor(fabs(acc) / Q + 0.5) * Q;
                 bufa[idx] = acc < 0.0 ? -kq : kq;
@@ -134,7 +124,7 @@ __global__ __launch_bounds__(JPEG_THREADS) void jpeg_code_kernel(const unsigned 
                 const double* f = bufa + blk * 64 + u;
                 double acc = 0.0;
 #pragma unroll
-                for (int v = 0; v < 8; ++v) acc = jpeg_mac(acc, st[v * 8 + y], f[v * 8]);
+                for (int v = 0; v < 8; ++v) acc = exact_mac(acc, st[v * 8 + y], f[v * 8]);
                 bufb[idx] = acc;
             }
             __syncthreads();
@@ -145,8 +135,8 @@ __global__ __launch_bounds__(JPEG_THREADS) void jpeg_code_kernel(const unsigned 
                 const double* hm = bufb + blk * 64 + y * 8;
                 double acc = 0.0;
 #pragma unroll
-                for (int u = 0; u < 8; ++u) acc = jpeg_mac(acc, st[u * 8 + x], hm[u]);
-                const unsigned char out = (unsigned char)jpeg_round8(acc + 128.0);
+                for (int u = 0; u < 8; ++u) acc = exact_mac(acc, st[u * 8 + x], hm[u]);
+                const unsigned char out = (unsigned char)exact_round8(acc + 128.0);
                 if (C420 && blk >= 4) {
                     const int gy = my / 2 + y, gx = mx / 2 + x;
                     if (gy < ch && gx < cw) (blk == 4 ? pcb : pcr)[(long long)gy * cw + gx] = out;
@@ -188,14 +178,14 @@ __global__ __launch_bounds__(JPEG_THREADS) void jpeg_rgb_kernel(const unsigned c
                 icr = pcr[(long long)y * w + x];
             }
             const double cb = (double)(icb - 128), cr = (double)(icr - 128);
-            const double R = jpeg_mac(Y, 1.402, cr);
+            const double R = exact_mac(Y, 1.402, cr);
             double G = Y - 0.344136 * cb;
             G = G - 0.714136 * cr;
-            const double B = jpeg_mac(Y, 1.772, cb);
+            const double B = exact_mac(Y, 1.772, cb);
             unsigned char* o = dst + dof + ((long long)y * dstride + x) * 3;
-            o[0] = (unsigned char)jpeg_round8(R);
-            o[1] = (unsigned char)jpeg_round8(G);
-            o[2] = (unsigned char)jpeg_round8(B);
+            o[0] = (unsigned char)exact_round8(R);
+            o[1] = (unsigned char)exact_round8(G);
+            o[2] = (unsigned char)exact_round8(B);
         }
     }
 }
@@ -228,12 +218,7 @@ int pesr_jpeg_u8_launch(const unsigned char* src, unsigned char* dst, const long
     long long max_mcus = 1;
     const long long need = jpeg_checked_bytes(desc_host, n, chroma, &max_mcus);
     if (need < 1 || (unsigned long long)need > (unsigned long long)ws_bytes) return PESR_EINVAL;
-    // about 32 K workgroups in all: each walks its entry's MCUs with a stride, and gridDim.y walks the entries
-    const int gy = n < 65535 ? n : 65535;
-    long long gx = 32768 / gy;
-    if (gx < 1) gx = 1;
-    if (gx > max_mcus) gx = max_mcus;
-    const dim3 grid((unsigned)gx, (unsigned)gy);
+    const dim3 grid = exact_pool_grid(n, max_mcus);
     unsigned char* wsp = (unsigned char*)ws;
     if (chroma == 420) {
         hipLaunchKernelGGL(jpeg_code_kernel<true>, grid, dim3(JPEG_THREADS), 0, stream, src, wsp, desc_dev, n, dct_dev, quant_dev);

@@ -8,7 +8,7 @@
 // count x > 0, sum |x|}, then the sum of sigma.  The AGGD fits, the features and the score are host work (pesr_amd/niqe.py).
 //
 // float64 throughout, every filter pass  acc = 0; for k ascending: acc = acc + g[k] * v  with the product and the sum rounded
-// separately: `fp contract(off)` and plain * + - as in ssim.hip and resize.hip, so that the restatement reproduces every bit of both
+// separately: `fp contract(off)` and plain * + - as in exact_u8.h, so that the restatement reproduces every bit of both
 // MSCN maps (the division and the square root are the IEEE ones).  Four kernels, none fused (nobody has measured a fusion yet):
 //   niqe_luma_kernel   one lane per cropped pixel, RGB floats -> the luma as a double image;
 //   niqe_down2_kernel  one lane per scale-2 pixel: the 8 x 8 window straight from the luma image (it sits in L2), the height pass
@@ -24,6 +24,7 @@
 #pragma clang fp contract(off)
 #include "common.h"
 #include "launchers.h"
+#include "exact_u8.h"
 
 constexpr int NIQE_TAPS = 7;
 constexpr int NIQE_HALO = NIQE_TAPS - 1;
@@ -41,18 +42,6 @@ __device__ __forceinline__ constexpr double niqe_g(int k) {
 __device__ __forceinline__ constexpr double niqe_w2(int t) {
     const int d = t < 4 ? 3 - t : t - 4;
     return d == 0 ? 111.0 / 256 : d == 1 ? 29.0 / 256 : d == 2 ? -9.0 / 256 : -3.0 / 256;
-}
-
-__device__ __forceinline__ double niqe_mac(double acc, double g, double v) {
-    const double prod = g * v;
-    return acc + prod;
-}
-
-__device__ __forceinline__ int niqe_reflect(int j, int n) {         // resize.hip's border rule
-    if ((unsigned)j < (unsigned)n) return j;
-    int m = j % (2 * n);
-    if (m < 0) m += 2 * n;
-    return m < n ? m : 2 * n - 1 - m;
 }
 
 // mode 0: floor(((r*0.2989.. + g*0.5870..) + b*0.1140..) + 0.5), MATLAB's rgb2gray; mode 1: ssim.hip's Y.  Integers in 0..255.
@@ -89,18 +78,18 @@ __global__ __launch_bounds__(NIQE_THREADS) void niqe_down2_kernel(const double* 
     const double* src = lum + n * Hc * (long)Wc;
     long row[8];
 #pragma unroll
-    for (int k = 0; k < 8; ++k) row[k] = (long)niqe_reflect(2 * oy - 3 + k, Hc) * Wc;
+    for (int k = 0; k < 8; ++k) row[k] = (long)exact_reflect(2 * oy - 3 + k, Hc) * Wc;
     double acc = 0.0;
 #pragma unroll
     for (int t = 0; t < 8; ++t) {
-        const int c = niqe_reflect(2 * ox - 3 + t, Wc);
+        const int c = exact_reflect(2 * ox - 3 + t, Wc);
         double v[8];
 #pragma unroll
         for (int k = 0; k < 8; ++k) v[k] = src[row[k] + c];
         double h = 0.0;
 #pragma unroll
-        for (int k = 0; k < 8; ++k) h = niqe_mac(h, niqe_w2(k), v[k]);
-        acc = niqe_mac(acc, niqe_w2(t), h);
+        for (int k = 0; k < 8; ++k) h = exact_mac(h, niqe_w2(k), v[k]);
+        acc = exact_mac(acc, niqe_w2(t), h);
     }
     out[n * P + i] = acc;
 }
@@ -126,8 +115,8 @@ __global__ __launch_bounds__(NIQE_THREADS) void niqe_mscn_kernel(const double* _
         for (int k = 0; k < NIQE_TAPS; ++k) {
             const double v = in[(r + k) * YW + c];
             const double vv = v * v;
-            am = niqe_mac(am, niqe_g(k), v);
-            aq = niqe_mac(aq, niqe_g(k), vv);
+            am = exact_mac(am, niqe_g(k), v);
+            aq = exact_mac(aq, niqe_g(k), vv);
         }
         hm[item] = am;
         hq[item] = aq;
@@ -138,8 +127,8 @@ __global__ __launch_bounds__(NIQE_THREADS) void niqe_mscn_kernel(const double* _
         double mu = 0.0, q = 0.0;
 #pragma unroll
         for (int k = 0; k < NIQE_TAPS; ++k) {
-            mu = niqe_mac(mu, niqe_g(k), hm[r * YW + c + k]);
-            q = niqe_mac(q, niqe_g(k), hq[r * YW + c + k]);
+            mu = exact_mac(mu, niqe_g(k), hm[r * YW + c + k]);
+            q = exact_mac(q, niqe_g(k), hq[r * YW + c + k]);
         }
         const int oy = oy0 + r, ox = ox0 + c;
         if (oy < Hs && ox < Ws) {

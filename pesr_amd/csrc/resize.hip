@@ -5,7 +5,7 @@
 //   down: out[o] = round(sum_t w[t] * in[reflect(s*o + T0 + t)]),  t = 0 .. NT-1          (NT = 8 / 11 / 16, T0 = -3 / -4 / -6)
 //   up:   out[s*q + p] = round(sum_i w[p][i] * in[reflect(q + d_p + i)]),  i = 0 .. 3     (d_p = -2 if 2p + 1 < s, else -1)
 // float64, acc = acc + w * v in ascending tap order with the product and the sum rounded separately (no fused multiply-add: the
-// host restatement must reproduce every bit), clamp to [0, 255], floor(acc + 0.5).  The weights come from the host by value.
+// host restatement must reproduce every bit), clamp to [0, 255], round half up (exact_u8.h).  The weights come from the host by value.
 // Height pass: all taps of an output byte sit at the same byte column of other rows, so a lane owns 4 consecutive bytes of an output
 // row and walks the taps down the rows with dword loads (coalesced; rows of 3W bytes start at any alignment - gfx950 global memory
 // takes unaligned dwords).  Width pass: neighbouring outputs read overlapping windows 3 bytes apart: a workgroup stages the row
@@ -13,6 +13,7 @@
 #pragma clang fp contract(off)
 #include "common.h"
 #include "launchers.h"
+#include "exact_u8.h"
 
 struct ResizeWeights { double w[16]; };
 
@@ -20,46 +21,6 @@ template <int S> struct DownTaps {
     static constexpr int N = S == 2 ? 8 : (S == 3 ? 11 : 16);
     static constexpr int T0 = S == 2 ? -3 : (S == 3 ? -4 : -6);
 };
-
-// ... 1 0 | 0 1 ... n-1 | n-1 n-2 ... (period 2n)
-__device__ __forceinline__ int resize_reflect(int j, int n) {
-    if ((unsigned)j < (unsigned)n) return j;
-    int m = j % (2 * n);
-    if (m < 0) m += 2 * n;
-    return m < n ? m : 2 * n - 1 - m;
-}
-
-// Plain operators under this file's `fp contract(off)`: the multiply and the add carry no contraction flag, so the backend cannot
-// fuse them.  (__dmul_rn / __dadd_rn are defined in the HIP headers, ahead of the pragma and under hipcc's default fast contraction:
-// inlined here, they DO come out as v_fma_f64.)
-__device__ __forceinline__ double resize_mac(double acc, double w, unsigned v) {
-    const double prod = w * (double)v;
-    return acc + prod;
-}
-
-__device__ __forceinline__ unsigned resize_round(double acc) {
-    acc = fmin(fmax(acc, 0.0), 255.0);
-    return (unsigned)floor(acc + 0.5);
-}
-
-// 4 bytes (nb of them inside the row) from any alignment
-__device__ __forceinline__ unsigned resize_load4(const unsigned char* __restrict__ p, int nb) {
-    unsigned v = 0;
-    if (nb == 4) {
-        __builtin_memcpy(&v, p, 4);
-    } else {
-        for (int b = 0; b < nb; ++b) v |= (unsigned)p[b] << (8 * b);
-    }
-    return v;
-}
-
-__device__ __forceinline__ void resize_store4(unsigned char* __restrict__ p, unsigned v, int nb) {
-    if (nb == 4) {
-        __builtin_memcpy(p, &v, 4);
-    } else {
-        for (int b = 0; b < nb; ++b) p[b] = (unsigned char)(v >> (8 * b));
-    }
-}
 
 constexpr int RESIZE_THREADS = 256;
 constexpr int RESIZE_H_TILE = RESIZE_THREADS * 4;      // bytes of one output row per workgroup
@@ -99,18 +60,18 @@ __global__ __launch_bounds__(RESIZE_THREADS) void resize_h_kernel(const unsigned
             const unsigned char* base = src + so + col;
             unsigned v[NT];
 #pragma unroll
-            for (int i = 0; i < NT; ++i) v[i] = resize_load4(base + (long long)resize_reflect(j0 + i, H) * R, nb);
+            for (int i = 0; i < NT; ++i) v[i] = exact_load4(base + (long long)exact_reflect(j0 + i, H) * R, nb);
             double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
 #pragma unroll
             for (int i = 0; i < NT; ++i) {
                 const double w = UP ? sw[wbase + i] : W.w[i];
-                a0 = resize_mac(a0, w, v[i] & 0xff);
-                a1 = resize_mac(a1, w, (v[i] >> 8) & 0xff);
-                a2 = resize_mac(a2, w, (v[i] >> 16) & 0xff);
-                a3 = resize_mac(a3, w, v[i] >> 24);
+                a0 = exact_mac_u(a0, w, v[i] & 0xff);
+                a1 = exact_mac_u(a1, w, (v[i] >> 8) & 0xff);
+                a2 = exact_mac_u(a2, w, (v[i] >> 16) & 0xff);
+                a3 = exact_mac_u(a3, w, v[i] >> 24);
             }
-            const unsigned o = resize_round(a0) | (resize_round(a1) << 8) | (resize_round(a2) << 16) | (resize_round(a3) << 24);
-            resize_store4(dst + dof + (long long)yo * R + col, o, nb);
+            const unsigned o = exact_round8x4(a0, a1, a2, a3);
+            exact_store4(dst + dof + (long long)yo * R + col, o, nb);
         }
     }
 }
@@ -152,7 +113,7 @@ __global__ __launch_bounds__(RESIZE_THREADS) void resize_w_kernel(const unsigned
                 } else {
                     for (int b = 0; b < 4 && k + b < nbytes; ++b) {
                         const int kk = k + b;
-                        sm[kk] = rowp[3LL * resize_reflect(in_lo + kk / 3, Wi) + kk % 3];
+                        sm[kk] = rowp[3LL * exact_reflect(in_lo + kk / 3, Wi) + kk % 3];
                     }
                 }
             }
@@ -176,11 +137,11 @@ __global__ __launch_bounds__(RESIZE_THREADS) void resize_w_kernel(const unsigned
                         }
                         double acc = 0.0;
 #pragma unroll
-                        for (int i = 0; i < NT; ++i) acc = resize_mac(acc, UP ? sw[wbase + i] : W.w[i], sm[idx + 3 * i]);
-                        o |= resize_round(acc) << (8 * b);
+                        for (int i = 0; i < NT; ++i) acc = exact_mac_u(acc, UP ? sw[wbase + i] : W.w[i], sm[idx + 3 * i]);
+                        o |= (unsigned)exact_round8(acc) << (8 * b);
                     }
                 }
-                resize_store4(dst + dof + (long long)y * (3LL * Wo) + 3LL * xo_lo + ob0, o, nb);
+                exact_store4(dst + dof + (long long)y * (3LL * Wo) + 3LL * xo_lo + ob0, o, nb);
             }
         }
     }
@@ -214,12 +175,7 @@ int pesr_imresize_u8_pass_launch(const unsigned char* src, unsigned char* dst, c
         }
         if (tiles > max_tiles) max_tiles = tiles;
     }
-    // about 32 K workgroups in all: each walks its image's tiles with a stride, and gridDim.y walks the images
-    const int gy = n_images < 65535 ? n_images : 65535;
-    long long gx = 32768 / gy;
-    if (gx < 1) gx = 1;
-    if (gx > max_tiles) gx = max_tiles;
-    const dim3 grid((unsigned)gx, (unsigned)gy);
+    const dim3 grid = exact_pool_grid(n_images, max_tiles);
     ResizeWeights W;
     for (int i = 0; i < 16; ++i) W.w[i] = weights_host[i];
     if (up) {

@@ -1,6 +1,6 @@
 // Resize of uint8 HWC images from any size to any size (each axis within 8:1 either way) with a bicubic, bilinear or box filter, as
 // pinned in docs/modes.md section 4m: section 4f's arithmetic (float64, acc = acc + w * v in ascending tap order with the product and
-// the sum rounded separately, symmetric reflection at the border, clamp, floor(acc + 0.5), height pass then width pass with a uint8
+// the sum rounded separately, symmetric reflection at the border, clamp, round half up, height pass then width pass with a uint8
 // intermediate) with taps and weights that come from a table the HOST makes - the device evaluates no polynomial and no division.
 // One launch per pass serves n entries through a descriptor array of RT_DESC int64 words per entry:
 //   {source byte offset, source row stride in pixels, destination byte offset, destination row stride in pixels, h_in, w_in, h_out,
@@ -21,6 +21,7 @@
 #pragma clang fp contract(off)
 #include "common.h"
 #include "launchers.h"
+#include "exact_u8.h"
 
 constexpr int RT_THREADS = 256;
 constexpr int RT_DESC = 12;                            // int64 words per entry (include/pesr_hip.h)
@@ -30,77 +31,11 @@ constexpr int RT_H_TILE = RT_THREADS * 4;              // bytes of one output ro
 constexpr int RT_W_PIX = RT_THREADS;                   // output pixels of one row per workgroup (width pass)
 constexpr int RT_W_SPAN = RT_W_PIX * RT_MAX_RATIO + RT_MAX_TAPS;   // source pixels a tile can need at the 8:1 limit (8 KiB + 128 B of LDS)
 
-// oracle/detrand.py's mixer, restated (as in degrade.hip)
-__device__ __forceinline__ unsigned long long rt_splitmix64(unsigned long long z) {
-    z += 0x9E3779B97F4A7C15ULL;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
-    return z ^ (z >> 31);
-}
-
-// section 4j's twelve-term Irwin-Hall variate: exact in float64
-__device__ __forceinline__ double rt_gauss(unsigned long long key, unsigned long long e) {
-    int sum = 0;
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        const unsigned long long z = rt_splitmix64(key + 3ULL * e + (unsigned long long)j);
-        sum += (int)(z & 0xffff) + (int)((z >> 16) & 0xffff) + (int)((z >> 32) & 0xffff) + (int)(z >> 48);
-    }
-    return (double)(2 * sum - 786420) / 131072.0;
-}
-
-// ... 1 0 | 0 1 ... n-1 | n-1 n-2 ... (period 2n), for any j
-__device__ __forceinline__ int rt_reflect(long long j, int n) {
-    if ((unsigned long long)j < (unsigned long long)n) return (int)j;
-    long long m = j % (2LL * n);
-    if (m < 0) m += 2LL * n;
-    return (int)(m < n ? m : 2LL * n - 1 - m);
-}
-
 // a first tap as the table holds it, kept where first + k cannot overflow whatever the table says
 __device__ __forceinline__ long long rt_first(const long long* __restrict__ tab, int o) {
     const long long lim = 1LL << 40;
     const long long f = tab[o];
     return f < -lim ? -lim : (f > lim ? lim : f);
-}
-
-// plain operators under this file's `fp contract(off)` (see resize.hip on why not __dmul_rn / __dadd_rn)
-__device__ __forceinline__ double rt_mac(double acc, double w, unsigned v) {
-    const double prod = w * (double)v;
-    return acc + prod;
-}
-
-__device__ __forceinline__ double rt_noise(double acc, double sigma, double g) {
-    const double prod = sigma * g;
-    return acc + prod;
-}
-
-__device__ __forceinline__ unsigned rt_round(double acc) {
-    acc = fmin(fmax(acc, 0.0), 255.0);
-    return (unsigned)floor(acc + 0.5);
-}
-
-// 4 bytes (nb of them inside the row) from any alignment
-__device__ __forceinline__ unsigned rt_load4(const unsigned char* __restrict__ p, int nb) {
-    unsigned v = 0;
-    if (nb == 4) {
-        __builtin_memcpy(&v, p, 4);
-    } else {
-        for (int b = 0; b < nb; ++b) v |= (unsigned)p[b] << (8 * b);
-    }
-    return v;
-}
-
-__device__ __forceinline__ void rt_store4(unsigned char* __restrict__ p, unsigned v, int nb) {
-    if (nb == 4) {
-        __builtin_memcpy(p, &v, 4);
-    } else {
-        for (int b = 0; b < nb; ++b) p[b] = (unsigned char)(v >> (8 * b));
-    }
-}
-
-__device__ __forceinline__ unsigned rt_load_px(const unsigned char* __restrict__ p) {
-    return (unsigned)p[0] | ((unsigned)p[1] << 8) | ((unsigned)p[2] << 16);
 }
 
 __global__ __launch_bounds__(RT_THREADS) void resize_to_h_kernel(const unsigned char* __restrict__ src, unsigned char* __restrict__ dst,
@@ -125,14 +60,14 @@ __global__ __launch_bounds__(RT_THREADS) void resize_to_h_kernel(const unsigned 
             double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
             for (int k = 0; k < T; ++k) {
                 const double w = wt[(long long)k * Ho + yo];
-                const unsigned v = rt_load4(base + rt_reflect(j0 + k, H) * sstride, nb);
-                a0 = rt_mac(a0, w, v & 0xff);
-                a1 = rt_mac(a1, w, (v >> 8) & 0xff);
-                a2 = rt_mac(a2, w, (v >> 16) & 0xff);
-                a3 = rt_mac(a3, w, v >> 24);
+                const unsigned v = exact_load4(base + exact_reflect(j0 + k, H) * sstride, nb);
+                a0 = exact_mac_u(a0, w, v & 0xff);
+                a1 = exact_mac_u(a1, w, (v >> 8) & 0xff);
+                a2 = exact_mac_u(a2, w, (v >> 16) & 0xff);
+                a3 = exact_mac_u(a3, w, v >> 24);
             }
-            const unsigned o = rt_round(a0) | (rt_round(a1) << 8) | (rt_round(a2) << 16) | (rt_round(a3) << 24);
-            rt_store4(dst + dof + yo * dstride + col, o, nb);
+            const unsigned o = exact_round8x4(a0, a1, a2, a3);
+            exact_store4(dst + dof + yo * dstride + col, o, nb);
         }
     }
 }
@@ -149,7 +84,7 @@ __global__ __launch_bounds__(RT_THREADS) void resize_to_w_kernel(const unsigned 
         const double* wt = (const double*)tab + Wo;
         double sigma;
         __builtin_memcpy(&sigma, &d[10], 8);
-        const unsigned long long key = rt_splitmix64((unsigned long long)d[11]);
+        const unsigned long long key = exact_splitmix64((unsigned long long)d[11]);
         const long long ctiles = (Wo + RT_W_PIX - 1) / RT_W_PIX;
         const long long tiles = H * ctiles;
         for (long long t = blockIdx.x; t < tiles; t += gridDim.x) {
@@ -161,7 +96,7 @@ __global__ __launch_bounds__(RT_THREADS) void resize_to_w_kernel(const unsigned 
             span = span < 0 ? 0 : (span > RT_W_SPAN ? RT_W_SPAN : span);
             const unsigned char* rowp = src + so + y * sstride;
             __syncthreads();                                            // the previous tile's readers are done
-            for (int p = threadIdx.x; p < (int)span; p += RT_THREADS) spx[p] = rt_load_px(rowp + 3LL * rt_reflect(in_lo + p, Wi));
+            for (int p = threadIdx.x; p < (int)span; p += RT_THREADS) spx[p] = exact_load_px(rowp + 3LL * exact_reflect(in_lo + p, Wi));
             __syncthreads();
             const int xo = xo_lo + threadIdx.x;
             if (xo <= xo_hi) {
@@ -174,29 +109,29 @@ __global__ __launch_bounds__(RT_THREADS) void resize_to_w_kernel(const unsigned 
                     for (int k = 0; k < T; ++k) {
                         const double wk = w[(long long)k * Wo];
                         const unsigned v = px[k];
-                        a0 = rt_mac(a0, wk, v & 0xff);
-                        a1 = rt_mac(a1, wk, (v >> 8) & 0xff);
-                        a2 = rt_mac(a2, wk, v >> 16);
+                        a0 = exact_mac_u(a0, wk, v & 0xff);
+                        a1 = exact_mac_u(a1, wk, (v >> 8) & 0xff);
+                        a2 = exact_mac_u(a2, wk, v >> 16);
                     }
                 } else {
                     for (int k = 0; k < T; ++k) {
                         const double wk = w[(long long)k * Wo];
-                        const unsigned v = rt_load_px(rowp + 3LL * rt_reflect(j0 + k, Wi));
-                        a0 = rt_mac(a0, wk, v & 0xff);
-                        a1 = rt_mac(a1, wk, (v >> 8) & 0xff);
-                        a2 = rt_mac(a2, wk, v >> 16);
+                        const unsigned v = exact_load_px(rowp + 3LL * exact_reflect(j0 + k, Wi));
+                        a0 = exact_mac_u(a0, wk, v & 0xff);
+                        a1 = exact_mac_u(a1, wk, (v >> 8) & 0xff);
+                        a2 = exact_mac_u(a2, wk, v >> 16);
                     }
                 }
                 if (sigma != 0.0) {
                     const unsigned long long e = 3ULL * ((unsigned long long)y * (unsigned long long)Wo + (unsigned long long)xo);
-                    a0 = rt_noise(a0, sigma, rt_gauss(key, e));
-                    a1 = rt_noise(a1, sigma, rt_gauss(key, e + 1));
-                    a2 = rt_noise(a2, sigma, rt_gauss(key, e + 2));
+                    a0 = exact_noise(a0, sigma, exact_gauss(key, e));
+                    a1 = exact_noise(a1, sigma, exact_gauss(key, e + 1));
+                    a2 = exact_noise(a2, sigma, exact_gauss(key, e + 2));
                 }
                 unsigned char* o = dst + dof + y * dstride + 3LL * xo;
-                o[0] = (unsigned char)rt_round(a0);
-                o[1] = (unsigned char)rt_round(a1);
-                o[2] = (unsigned char)rt_round(a2);
+                o[0] = (unsigned char)(unsigned)exact_round8(a0);        // (through unsigned, as exact_round8x4 converts)
+                o[1] = (unsigned char)(unsigned)exact_round8(a1);
+                o[2] = (unsigned char)(unsigned)exact_round8(a2);
             }
         }
     }
@@ -222,17 +157,12 @@ int pesr_resize_to_u8_pass_launch(const unsigned char* src, unsigned char* dst, 
         if (toff < 0 || toff > table_words || (T + 1) * n_out > table_words - toff) return PESR_EINVAL;
         double sigma;
         __builtin_memcpy(&sigma, &d[10], 8);
-        if (!(sigma >= 0.0) || sigma > 1.7976931348623157e308) return PESR_EINVAL;             // negative, NaN, infinite
+        if (!exact_sigma_ok(sigma)) return PESR_EINVAL;
         if (axis == 0 && sigma != 0.0) return PESR_EINVAL;                                     // the noise belongs to the width pass
         const long long tiles = axis == 0 ? ho * ((3 * wi + RT_H_TILE - 1) / RT_H_TILE) : hi * ((wo + RT_W_PIX - 1) / RT_W_PIX);
         if (tiles > max_tiles) max_tiles = tiles;
     }
-    // about 32 K workgroups in all: each walks its entry's tiles with a stride, and gridDim.y walks the entries
-    const int gy = n < 65535 ? n : 65535;
-    long long gx = 32768 / gy;
-    if (gx < 1) gx = 1;
-    if (gx > max_tiles) gx = max_tiles;
-    const dim3 grid((unsigned)gx, (unsigned)gy);
+    const dim3 grid = exact_pool_grid(n, max_tiles);
     const long long* tables = (const long long*)tables_dev;
     if (axis == 0)
         hipLaunchKernelGGL(resize_to_h_kernel, grid, dim3(RT_THREADS), 0, stream, src, dst, desc_dev, n, tables);

@@ -4,7 +4,7 @@
 // Five maps (x, y, x*x, y*y, x*y) are filtered with the 11 x 11 Gaussian window of sigma 1.5, separably - height pass, then width
 // pass, "valid" region - each pass  acc = 0; for k ascending: acc = acc + g[k] * v  in float64 with the product and the sum rounded
 // separately.  No fused multiply-add anywhere in the filter and the map arithmetic: the float64 host restatement
-// (tests/ssim_oracle.py) reproduces every bit of the map.  Hence `fp contract(off)` and plain * and + as in resize.hip (the
+// (tests/ssim_oracle.py) reproduces every bit of the map.  Hence `fp contract(off)` and exact_u8.h's plain * and + (the
 // __dmul_rn / __dadd_rn of the HIP headers are fused once inlined).  The only v_fma_f64 / v_div_fmas_f64 left in this file's code are
 // those of the IEEE double division's own expansion (v_div_scale, v_rcp, the Newton steps, v_div_fmas, v_div_fixup), which is
 // correctly rounded.
@@ -21,6 +21,7 @@
 #pragma clang fp contract(off)
 #include "common.h"
 #include "launchers.h"
+#include "exact_u8.h"
 
 // Tile and per-lane blocks.  Overridable for experiment builds only (scripts/build_variant.sh, PESR_HIP_LIB).
 #ifndef PESR_SSIM_TH
@@ -55,11 +56,6 @@ __device__ __forceinline__ double ssim_luma(const float (&p)[3]) {
     const double b = rint(fmin(fmax((double)p[2], 0.0), 255.0));
     const double y = ((r * (65.738 / 256) + g * (129.057 / 256)) + b * (25.064 / 256)) + 16.0;
     return rint(fmin(fmax(y, 0.0), 255.0));
-}
-
-__device__ __forceinline__ double ssim_mac(double acc, double g, double v) {
-    const double prod = g * v;
-    return acc + prod;
 }
 
 __device__ __forceinline__ double ssim_value(double mx, double my, double xx, double yy, double xy) {
@@ -133,11 +129,11 @@ __global__ __launch_bounds__(SSIM_THREADS) void ssim_y_kernel(const float* __res
             for (int r = 0; r < RB; ++r) {
                 const int k = i - r;                               // ascending in i for every output row r
                 if (k >= 0 && k < SSIM_TAPS) {
-                    acc[0][r] = ssim_mac(acc[0][r], ssim_g(k), x);
-                    acc[1][r] = ssim_mac(acc[1][r], ssim_g(k), y);
-                    acc[2][r] = ssim_mac(acc[2][r], ssim_g(k), xx);
-                    acc[3][r] = ssim_mac(acc[3][r], ssim_g(k), yy);
-                    acc[4][r] = ssim_mac(acc[4][r], ssim_g(k), xy);
+                    acc[0][r] = exact_mac(acc[0][r], ssim_g(k), x);
+                    acc[1][r] = exact_mac(acc[1][r], ssim_g(k), y);
+                    acc[2][r] = exact_mac(acc[2][r], ssim_g(k), xx);
+                    acc[3][r] = exact_mac(acc[3][r], ssim_g(k), yy);
+                    acc[4][r] = exact_mac(acc[4][r], ssim_g(k), xy);
                 }
             }
         }
@@ -167,7 +163,7 @@ __global__ __launch_bounds__(SSIM_THREADS) void ssim_y_kernel(const float* __res
                 const int k = j - q;
                 if (k >= 0 && k < SSIM_TAPS) {
 #pragma unroll
-                    for (int m = 0; m < 5; ++m) acc[m][q] = ssim_mac(acc[m][q], ssim_g(k), v[m]);
+                    for (int m = 0; m < 5; ++m) acc[m][q] = exact_mac(acc[m][q], ssim_g(k), v[m]);
                 }
             }
         }

@@ -5,20 +5,18 @@ csrc/degrade.hip.  The blur kernels are made here, on the host, in float64; the 
 """
 from __future__ import annotations
 
-import ctypes
 import math
-import struct
 from typing import NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, _pool
+from .resize import METHODS, imresize_to_pool_u8
 
 SCALES = (2, 3, 4)
 MAX_K = 24
 DESC_WORDS = 11            # int64 words per descriptor row (include/pesr_hip.h)
-_MASK = (1 << 64) - 1
 
 
 def legal_kernel_size(s: int, K: int) -> bool:
@@ -60,24 +58,13 @@ def delta_kernel(s: int) -> np.ndarray:
     return np.full((K, K), 1.0 / (K * K), dtype=np.float64)
 
 
-def _f64_bits(x: float) -> int:
-    return struct.unpack("<q", struct.pack("<d", float(x)))[0]
-
-
-def _i64(q: int) -> int:
-    q &= _MASK
-    return q - (1 << 64) if q >> 63 else q
-
-
 def degrade_pool_u8(pool: torch.Tensor, offsets: Sequence[int], shapes: Sequence[Tuple[int, int]], s: int, kernels, kernel_index: Sequence[int],
                     noise_sigma: Sequence[float], noise_stream: Sequence[int], windows: Optional[Sequence[Tuple[int, int, int, int]]] = None):
     """Degrade windows of the images of a flat device-resident uint8 pool (image of entry i: HWC bytes at offsets[i], shapes[i] =
     (H, W), both multiples of s) in ONE launch.  kernels: float64 [n_kernels][K][K]; entry i uses kernels[kernel_index[i]], noise
     level noise_sigma[i] and noise stream noise_stream[i]; windows[i] = (y0, x0, h, w) in the image's LR grid, None = every whole
     image.  Several entries may name the same image.  -> (out_pool, out_offsets, out_shapes), the results back to back."""
-    if not (torch.is_tensor(pool) and pool.is_cuda):
-        raise _lib.PesrHipError("degrade_pool_u8 needs a device tensor: pesr_amd has no CPU fallback")
-    assert pool.dtype == torch.uint8 and pool.dim() == 1 and pool.is_contiguous()
+    _pool.check_pool(pool, "degrade_pool_u8")
     n = len(offsets)
     assert n > 0 and n == len(shapes) == len(kernel_index) == len(noise_sigma) == len(noise_stream)
     bank = np.ascontiguousarray(np.asarray(kernels, dtype=np.float64))
@@ -97,25 +84,19 @@ def degrade_pool_u8(pool: torch.Tensor, offsets: Sequence[int], shapes: Sequence
         assert 0 <= offsets[i] and offsets[i] + 3 * H * W <= pool.numel(), "image outside the pool"
         if H < 1 or W < 1 or H % s or W % s:
             raise _lib.PesrHipError(f"degrade: a {H} x {W} image cannot be reduced by {s}: mod-crop it first (modcrop)")
-        desc[i] = (int(offsets[i]), out_off, H, W, y0, x0, h, w, int(kernel_index[i]), _f64_bits(noise_sigma[i]), _i64(int(noise_stream[i])))
+        desc[i] = (int(offsets[i]), out_off, H, W, y0, x0, h, w, int(kernel_index[i]), _pool.f64_bits(noise_sigma[i]), _pool.i64(int(noise_stream[i])))
         out_off += 3 * max(h, 0) * max(w, 0)
     dev = pool.device
     out = torch.empty(max(out_off, 1), dtype=torch.uint8, device=dev)
     bank_dev = torch.from_numpy(bank).to(dev)
-    desc_dev = torch.from_numpy(desc).to(dev)              # the library checks the host copy; the kernel reads this one
-    stream = torch.cuda.current_stream(dev).cuda_stream
-    _lib.check(_lib.lib().pesr_degrade_u8(pool.data_ptr(), out.data_ptr(), desc.ctypes.data_as(ctypes.c_void_p), desc_dev.data_ptr(), n, int(s),
-                                          K, bank_dev.data_ptr(), int(bank.shape[0]), stream), "pesr_degrade_u8")
+    _pool.launch("pesr_degrade_u8", pool, out, desc, int(s), K, bank_dev.data_ptr(), int(bank.shape[0]))
     return out[:out_off], [int(v) for v in desc[:, 1]], [(int(wd[2]), int(wd[3])) for wd in windows]
 
 
 def degrade_u8(img: torch.Tensor, s: int, kernel, noise_sigma: float = 0.0, noise_stream: int = 0) -> torch.Tensor:
     """uint8 HWC device tensor (sides multiples of s) -> its uint8 HWC LR image, sides divided by s."""
-    if not (torch.is_tensor(img) and img.is_cuda):
-        raise _lib.PesrHipError("degrade_u8 needs a device tensor: pesr_amd has no CPU fallback")
-    assert img.dtype == torch.uint8 and img.dim() == 3 and img.shape[2] == 3, "uint8 [H][W][3] expected"
-    h, w = int(img.shape[0]), int(img.shape[1])
-    out, _, [(ho, wo)] = degrade_pool_u8(img.contiguous().view(-1), [0], [(h, w)], s, np.asarray(kernel, dtype=np.float64)[None], [0],
+    flat, h, w = _pool.image_as_pool(img, "degrade_u8")
+    out, _, [(ho, wo)] = degrade_pool_u8(flat, [0], [(h, w)], s, np.asarray(kernel, dtype=np.float64)[None], [0],
                                          [noise_sigma], [noise_stream])
     return out.view(ho, wo, 3)
 
@@ -200,7 +181,6 @@ def resize_jitter_pool_u8(pool: torch.Tensor, offsets: Sequence[int], shapes: Se
     """The resize-jitter round trip of docs/modes.md section 4m for n windows of a device-resident uint8 pool: entry i goes from
     h x w to Q(h) x Q(w) with filter METHODS[m1[i]] and back to h x w with METHODS[m2[i]], the noise in the second resize's width
     pass: two pooled resizes, four launches.  -> (out_pool, out_offsets, out_shapes), the results back to back."""
-    from .resize import METHODS, imresize_to_pool_u8
     shapes = [(int(h), int(w)) for h, w in shapes]
     mids = [(jitter_size(h, ri), jitter_size(w, ri)) for (h, w), ri in zip(shapes, r)]
     mid, mid_off, _ = imresize_to_pool_u8(pool, offsets, shapes, mids, [METHODS[i] for i in m1], strides=strides)
@@ -209,18 +189,14 @@ def resize_jitter_pool_u8(pool: torch.Tensor, offsets: Sequence[int], shapes: Se
 
 def resize_jitter_u8(img: torch.Tensor, r: float, m1: int = 0, m2: int = 0, noise_sigma: float = 0.0, noise_stream: int = 0) -> torch.Tensor:
     """uint8 HWC device tensor -> the same size, after the resize-jitter round trip through Q(h) x Q(w)."""
-    if not (torch.is_tensor(img) and img.is_cuda):
-        raise _lib.PesrHipError("resize_jitter_u8 needs a device tensor: pesr_amd has no CPU fallback")
-    assert img.dtype == torch.uint8 and img.dim() == 3 and img.shape[2] == 3, "uint8 [H][W][3] expected"
-    h, w = int(img.shape[0]), int(img.shape[1])
-    out, _, _ = resize_jitter_pool_u8(img.contiguous().view(-1), [0], [(h, w)], [r], [m1], [m2], [noise_sigma], [noise_stream])
+    flat, h, w = _pool.image_as_pool(img, "resize_jitter_u8")
+    out, _, _ = resize_jitter_pool_u8(flat, [0], [(h, w)], [r], [m1], [m2], [noise_sigma], [noise_stream])
     return out.view(h, w, 3)
 
 
 def parse_resize_jitter(text: str, who: str):
     """test.py's 'R[,M1[,M2]]' -> (r, m1, m2), the filters as indices into pesr_amd.resize.METHODS (default bicubic); SystemExit
     naming the flag for a bad number, a ratio outside 0.125 .. 8 or an unknown filter name."""
-    from .resize import METHODS
     parts = str(text).split(",")
     try:
         r = float(parts[0])

@@ -11,7 +11,7 @@ from typing import Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, _pool
 
 DESC_WORDS = 8             # int64 words per descriptor row (include/pesr_hip.h)
 
@@ -70,9 +70,7 @@ def jpeg_pool_u8(pool: torch.Tensor, offsets: Sequence[int], shapes: Sequence[Tu
     windows must not overlap.  out = None: -> (out_pool, out_offsets), the results back to back, rows w pixels apart.  out = a
     tensor of the pool's size (the pool itself: in place): every result is written where its window lies in the pool, the bytes
     outside the windows are not touched, -> (out, offsets)."""
-    if not (torch.is_tensor(pool) and pool.is_cuda):
-        raise _lib.PesrHipError("jpeg_pool_u8 needs a device tensor: pesr_amd has no CPU fallback")
-    assert pool.dtype == torch.uint8 and pool.dim() == 1 and pool.is_contiguous()
+    _pool.check_pool(pool, "jpeg_pool_u8")
     n = len(offsets)
     assert n > 0 and n == len(shapes) == len(strides) == len(qualities)
     dev = pool.device
@@ -93,27 +91,19 @@ def jpeg_pool_u8(pool: torch.Tensor, offsets: Sequence[int], shapes: Sequence[Tu
         ws_off += entry_bytes(h, w, chroma420)
     if out is None:
         out = torch.empty(out_off, dtype=torch.uint8, device=dev)
-    L = _lib.lib()
     chroma = 420 if chroma420 else 444
-    host = desc.ctypes.data_as(ctypes.c_void_p)
-    need = int(L.pesr_jpeg_workspace_bytes(host, n, chroma))
+    need = int(_lib.lib().pesr_jpeg_workspace_bytes(desc.ctypes.data_as(ctypes.c_void_p), n, chroma))
     assert need == ws_off, (need, ws_off)
     ws = torch.empty(need, dtype=torch.uint8, device=dev)
     T, quant = _device_tables(dev)
-    desc_dev = torch.from_numpy(desc).to(dev)              # the library checks the host copy; the kernels read this one
-    stream = torch.cuda.current_stream(dev).cuda_stream
-    _lib.check(L.pesr_jpeg_u8(pool.data_ptr(), out.data_ptr(), host, desc_dev.data_ptr(), n, chroma, T.data_ptr(), quant.data_ptr(),
-                              ws.data_ptr(), need, stream), "pesr_jpeg_u8")
+    _pool.launch("pesr_jpeg_u8", pool, out, desc, chroma, T.data_ptr(), quant.data_ptr(), ws.data_ptr(), need)
     return out, [int(v) for v in desc[:, 2]]
 
 
 def jpeg_u8(img: torch.Tensor, q: int, chroma420: bool = True) -> torch.Tensor:
     """uint8 HWC device tensor -> the uint8 HWC image a JPEG encoder at quality q and a decoder make of it."""
-    if not (torch.is_tensor(img) and img.is_cuda):
-        raise _lib.PesrHipError("jpeg_u8 needs a device tensor: pesr_amd has no CPU fallback")
-    assert img.dtype == torch.uint8 and img.dim() == 3 and img.shape[2] == 3, "uint8 [H][W][3] expected"
-    h, w = int(img.shape[0]), int(img.shape[1])
-    out, _ = jpeg_pool_u8(img.contiguous().view(-1), [0], [(h, w)], [w], [q], chroma420)
+    flat, h, w = _pool.image_as_pool(img, "jpeg_u8")
+    out, _ = jpeg_pool_u8(flat, [0], [(h, w)], [w], [q], chroma420)
     return out.view(h, w, 3)
 
 

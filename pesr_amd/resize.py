@@ -12,8 +12,7 @@ from typing import List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from . import _lib
-from .degrade import _f64_bits, _i64           # (degrade.py imports this module inside its functions only)
+from . import _lib, _pool
 
 SCALES = (2, 3, 4)
 METHODS = ("bicubic", "bilinear", "box")           # the filters of the any-size resize (docs/modes.md section 4m)
@@ -79,9 +78,7 @@ def _out_len(n: int, s: int, up: bool) -> int:
 def imresize_pool_u8(pool: torch.Tensor, offsets: Sequence[int], shapes: Sequence[Tuple[int, int]], s: int, up: bool = False):
     """Resize every image of a flat device-resident uint8 pool (image i: HWC bytes at offsets[i], shapes[i] = (H, W)) in two
     launches.  -> (out_pool, out_offsets, out_shapes), the results back to back."""
-    if not (torch.is_tensor(pool) and pool.is_cuda):
-        raise _lib.PesrHipError("imresize_pool_u8 needs a device tensor: pesr_amd has no CPU fallback")
-    assert pool.dtype == torch.uint8 and pool.dim() == 1 and pool.is_contiguous()
+    _pool.check_pool(pool, "imresize_pool_u8")
     n = len(offsets)
     assert n == len(shapes) and n > 0
     if s not in SCALES:
@@ -99,27 +96,20 @@ def imresize_pool_u8(pool: torch.Tensor, offsets: Sequence[int], shapes: Sequenc
     wts = np.zeros(16, dtype=np.float64)
     w = resize_weights(s, up).reshape(-1)
     wts[:w.size] = w
-    L = _lib.lib()
-    stream = torch.cuda.current_stream(dev).cuda_stream
     mid = torch.empty(max(int(mid_off[-1]), 1), dtype=torch.uint8, device=dev)
     out = torch.empty(max(int(out_off[-1]), 1), dtype=torch.uint8, device=dev)
     wp = wts.ctypes.data_as(ctypes.c_void_p)
     passes = ((pool, mid, offsets, mid_off, shapes, 0), (mid, out, mid_off, out_off, mid_shapes, 1))
     for src, dst, so, do, shp, axis in passes:
         desc = np.array([(int(so[i]), int(do[i]), shp[i][0], shp[i][1]) for i in range(n)], dtype=np.int64)
-        desc_dev = torch.from_numpy(desc).to(dev)          # the library checks the host copy; the kernel reads this one
-        _lib.check(L.pesr_imresize_u8_pass(src.data_ptr(), dst.data_ptr(), desc.ctypes.data_as(ctypes.c_void_p), desc_dev.data_ptr(), n, axis,
-                                           int(s), int(bool(up)), wp, stream), "pesr_imresize_u8_pass")
+        _pool.launch("pesr_imresize_u8_pass", src, dst, desc, axis, int(s), int(bool(up)), wp)
     return out[:int(out_off[-1])], [int(v) for v in out_off[:-1]], out_shapes
 
 
 def imresize_u8(img: torch.Tensor, s: int, up: bool = False) -> torch.Tensor:
     """uint8 HWC device tensor -> uint8 HWC device tensor, sides divided (up=False; they must be multiples of s) or multiplied by s."""
-    if not (torch.is_tensor(img) and img.is_cuda):
-        raise _lib.PesrHipError("imresize_u8 needs a device tensor: pesr_amd has no CPU fallback")
-    assert img.dtype == torch.uint8 and img.dim() == 3 and img.shape[2] == 3, "uint8 [H][W][3] expected"
-    h, w = int(img.shape[0]), int(img.shape[1])
-    out, _, [(ho, wo)] = imresize_pool_u8(img.contiguous().view(-1), [0], [(h, w)], s, up)
+    flat, h, w = _pool.image_as_pool(img, "imresize_u8")
+    out, _, [(ho, wo)] = imresize_pool_u8(flat, [0], [(h, w)], s, up)
     return out.view(ho, wo, 3)
 
 
@@ -201,7 +191,7 @@ def resize_to_plan(offsets, shapes, out_shapes, methods, strides, noise_sigma, n
         at, T = tables[(h, ho, m)][:2]
         d0[i] = (int(offsets[i]), int(strides[i]), int(mid_off[i]), w, h, w, ho, w, at, T, 0, 0)
         at, T = tables[(w, wo, m)][:2]
-        d1[i] = (int(mid_off[i]), w, int(out_off[i]), wo, ho, w, ho, wo, at, T, _f64_bits(noise_sigma[i]), _i64(int(noise_stream[i])))
+        d1[i] = (int(mid_off[i]), w, int(out_off[i]), wo, ho, w, ho, wo, at, T, _pool.f64_bits(noise_sigma[i]), _pool.i64(int(noise_stream[i])))
     return buf, (d0, d1), int(mid_off[-1]), out_off, out_shapes
 
 
@@ -212,9 +202,7 @@ def imresize_to_pool_u8(pool: torch.Tensor, offsets: Sequence[int], shapes: Sequ
     strides[i] pixels apart, None = w) to out_shapes[i] with filter methods[i] (one name serves every entry) in two launches: height,
     then width.  noise_sigma[i] / noise_stream[i]: section 4j's noise, added before the last rounding.  The reflection is at the
     window's own border.  -> (out_pool, out_offsets, out_shapes), the results back to back."""
-    if not (torch.is_tensor(pool) and pool.is_cuda):
-        raise _lib.PesrHipError("imresize_to_pool_u8 needs a device tensor: pesr_amd has no CPU fallback")
-    assert pool.dtype == torch.uint8 and pool.dim() == 1 and pool.is_contiguous()
+    _pool.check_pool(pool, "imresize_to_pool_u8")
     n = len(offsets)
     methods = [methods] * n if isinstance(methods, str) else list(methods)
     strides = [w for _, w in shapes] if strides is None else list(strides)
@@ -228,21 +216,14 @@ def imresize_to_pool_u8(pool: torch.Tensor, offsets: Sequence[int], shapes: Sequ
     buf_dev = torch.from_numpy(buf).to(dev)
     mid = torch.empty(max(mid_bytes, 1), dtype=torch.uint8, device=dev)
     out = torch.empty(max(int(out_off[-1]), 1), dtype=torch.uint8, device=dev)
-    L = _lib.lib()
-    stream = torch.cuda.current_stream(dev).cuda_stream
     for axis, desc in enumerate(descs):
         src, dst = (pool, mid) if axis == 0 else (mid, out)
-        desc_dev = torch.from_numpy(desc).to(dev)              # the library checks the host copy; the kernel reads this one
-        _lib.check(L.pesr_resize_to_u8_pass(src.data_ptr(), dst.data_ptr(), desc.ctypes.data_as(ctypes.c_void_p), desc_dev.data_ptr(), n, axis,
-                                            buf_dev.data_ptr(), int(buf.size), stream), "pesr_resize_to_u8_pass")
+        _pool.launch("pesr_resize_to_u8_pass", src, dst, desc, axis, buf_dev.data_ptr(), int(buf.size))
     return out[:int(out_off[-1])], [int(v) for v in out_off[:-1]], out_shapes
 
 
 def imresize_to_u8(img: torch.Tensor, size: Tuple[int, int], method: str = "bicubic") -> torch.Tensor:
     """uint8 HWC device tensor -> uint8 HWC device tensor of size = (h_out, w_out)."""
-    if not (torch.is_tensor(img) and img.is_cuda):
-        raise _lib.PesrHipError("imresize_to_u8 needs a device tensor: pesr_amd has no CPU fallback")
-    assert img.dtype == torch.uint8 and img.dim() == 3 and img.shape[2] == 3, "uint8 [H][W][3] expected"
-    h, w = int(img.shape[0]), int(img.shape[1])
-    out, _, [(ho, wo)] = imresize_to_pool_u8(img.contiguous().view(-1), [0], [(h, w)], [(int(size[0]), int(size[1]))], method)
+    flat, h, w = _pool.image_as_pool(img, "imresize_to_u8")
+    out, _, [(ho, wo)] = imresize_to_pool_u8(flat, [0], [(h, w)], [(int(size[0]), int(size[1]))], method)
     return out.view(ho, wo, 3)

@@ -66,7 +66,8 @@ def report(what, ts, **extra):
 def launch_only(pool, offsets, shapes, s, bank, kidx, sigmas, qs, windows):
     """-> (callable that issues the one launch through the C ABI on prepared buffers, output tensor)."""
     from pesr_amd import _lib
-    from pesr_amd.degrade import DESC_WORDS, _f64_bits, _i64
+    from pesr_amd._pool import f64_bits as _f64_bits, i64 as _i64
+    from pesr_amd.degrade import DESC_WORDS
     n, dev = len(offsets), pool.device
     desc = np.empty((n, DESC_WORDS), dtype=np.int64)
     off = 0

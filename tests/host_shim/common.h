@@ -1,6 +1,7 @@
-// Stands in for pesr_amd/csrc/common.h when csrc/jpeg.hip is compiled as plain C++ for the host (tests/test_jpeg_host_cpu.py): the
-// lanes of a workgroup run as std::threads with a std::barrier for __syncthreads, `__shared__` arrays are statics, workgroups run one
-// after the other.  The kernels' own code - indexing, order of operations, barriers - is what runs; no GPU is involved.
+// Stands in for pesr_amd/csrc/common.h when a byte-image kernel file (csrc/jpeg.hip, resize_to.hip, resize.hip, degrade.hip) is
+// compiled as plain C++ for the host (tests/host_build.py, used by the tests/test_*_host_cpu.py modules): the lanes of a workgroup
+// run as std::threads with a std::barrier for __syncthreads, `__shared__` arrays are statics, workgroups run one after the other.
+// The kernels' own code - indexing, order of operations, barriers - is what runs; no GPU is involved.
 #pragma once
 #include <cmath>
 #include <cstddef>
@@ -31,6 +32,7 @@ inline dim3 blockIdx, gridDim;
 inline std::barrier<>* emu_barrier;
 inline void __syncthreads() { emu_barrier->arrive_and_wait(); }
 static inline int pesr_launch_status() { return 0; }
+inline double __longlong_as_double(long long v) { double d; memcpy(&d, &v, 8); return d; }
 inline void emu_launch(dim3 grid, dim3 block, std::function<void()> fn) {
     gridDim = grid;
     for (unsigned by = 0; by < grid.y; ++by) for (unsigned bx = 0; bx < grid.x; ++bx) {

@@ -1,8 +1,7 @@
-// Runs pesr_resize_to_u8_pass_launch of csrc/resize_to.hip, compiled for the host with tests/jpeg_host's shim headers, on one call
-// read from a file (tests/test_resize_to_host_cpu.py).
+// Runs pesr_resize_to_u8_pass_launch of csrc/resize_to.hip, compiled for the host, on one call read from a file
+// (tests/test_resize_to_host_cpu.py).
 #include "common.h"
-int pesr_resize_to_u8_pass_launch(const unsigned char* src, unsigned char* dst, const long long* desc_host, const long long* desc_dev,
-                                  int n, int axis, const void* tables_dev, long table_words, hipStream_t stream);
+#include "launchers.h"
 // in.bin: int64 n, axis, pool_bytes, table_words, dst_bytes; desc n*12 int64; the table words; pool bytes.  out.bin: dst bytes, which
 // start out as 9s
 int main(int argc, char** argv) {

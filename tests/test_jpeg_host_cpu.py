@@ -1,40 +1,24 @@
-"""CPU: pesr_amd/csrc/jpeg.hip compiled as plain C++ into a stand-alone program (tests/jpeg_host: the lanes of a workgroup as
+"""CPU: pesr_amd/csrc/jpeg.hip compiled as plain C++ into a stand-alone program (tests/host_build.py: the lanes of a workgroup as
 threads, __syncthreads as a barrier) and run on the host - both launches, the descriptor checks and the grid walk as they are - against
 the float64 restatement tests/jpeg_oracle.py, bit for bit.  Nothing is loaded into Python; no GPU is involved."""
-import os
-import shutil
-import subprocess
-
 import numpy as np
 import pytest
 
+import host_build
 import jpeg_oracle as JO
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HOST = os.path.join(ROOT, "tests", "jpeg_host")
 
 
 @pytest.fixture(scope="module")
 def program(tmp_path_factory):
-    d = tmp_path_factory.mktemp("jpeg_host")
-    cxx = shutil.which("clang++") or shutil.which("g++")
-    assert cxx, "a host C++20 compiler (clang++ or g++) is needed"
-    shutil.copy(os.path.join(ROOT, "pesr_amd", "csrc", "jpeg.hip"), d / "jpeg_kernels.cpp")       # (its "common.h" is then tests/jpeg_host's)
-    exe = str(d / "jpeg_host")
-    subprocess.run([cxx, "-std=c++20", "-O1", "-ffp-contract=off", "-Wno-unknown-pragmas", "-I", HOST, os.path.join(HOST, "main.cpp"),
-                    str(d / "jpeg_kernels.cpp"), "-o", exe, "-pthread"], check=True, capture_output=True, text=True, timeout=300)
-    return exe, d
+    return host_build.build("jpeg", tmp_path_factory.mktemp("jpeg_host"))
 
 
 def _run(program, pool, rows, c420, inplace):
     from pesr_amd.jpeg import dct_table, quant_tables
-    exe, d = program
     quant = np.stack([np.stack(quant_tables(q)).reshape(2, 64) for q in range(1, 101)]).astype(np.float64)
-    with open(d / "in.bin", "wb") as f:
-        f.write(np.array([len(rows), 420 if c420 else 444, pool.size, int(inplace)], dtype=np.int64).tobytes())
-        f.write(np.array(rows, dtype=np.int64).tobytes() + dct_table().tobytes() + quant.tobytes() + pool.tobytes())
-    r = subprocess.run([exe, str(d / "in.bin"), str(d / "out.bin")], capture_output=True, text=True, timeout=120)
-    return r.returncode, np.fromfile(d / "out.bin", dtype=np.uint8)
+    head = np.array([len(rows), 420 if c420 else 444, pool.size, int(inplace)], dtype=np.int64)
+    return host_build.run(program, [head.tobytes(), np.array(rows, dtype=np.int64).tobytes(), dct_table().tobytes(), quant.tobytes(),
+                                    pool.tobytes()])
 
 
 @pytest.mark.parametrize("c420", [True, False])

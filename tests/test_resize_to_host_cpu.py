@@ -1,36 +1,22 @@
-"""CPU: pesr_amd/csrc/resize_to.hip compiled as plain C++ into a stand-alone program (tests/resize_to_host/main.cpp with
-tests/jpeg_host's shim headers: the lanes of a workgroup as threads, __syncthreads as a barrier) and run on the host - both passes,
+"""CPU: pesr_amd/csrc/resize_to.hip compiled as plain C++ into a stand-alone program (tests/host_build.py:
+the lanes of a workgroup as threads, __syncthreads as a barrier) and run on the host - both passes,
 the descriptor checks and the grid walk as they are - against the float64 restatement tests/resize_to_oracle.py, bit for bit.
 Nothing is loaded into Python; no GPU is involved."""
-import os
-import shutil
-import struct
-import subprocess
-
 import numpy as np
 import pytest
 
+import host_build
 import resize_to_oracle as RT
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SHIM = os.path.join(ROOT, "tests", "jpeg_host")
-HOST = os.path.join(ROOT, "tests", "resize_to_host")
 
 
 @pytest.fixture(scope="module")
 def program(tmp_path_factory):
-    d = tmp_path_factory.mktemp("resize_to_host")
-    cxx = shutil.which("clang++") or shutil.which("g++")
-    assert cxx, "a host C++20 compiler (clang++ or g++) is needed"
-    shutil.copy(os.path.join(ROOT, "pesr_amd", "csrc", "resize_to.hip"), d / "resize_to_kernels.cpp")   # (its "common.h" is then the shim's)
-    exe = str(d / "resize_to_host")
-    subprocess.run([cxx, "-std=c++20", "-O1", "-ffp-contract=off", "-Wno-unknown-pragmas", "-I", SHIM, os.path.join(HOST, "main.cpp"),
-                    str(d / "resize_to_kernels.cpp"), "-o", exe, "-pthread"], check=True, capture_output=True, text=True, timeout=300)
-    return exe, d
+    return host_build.build("resize_to", tmp_path_factory.mktemp("resize_to_host"))
 
 
 def _bits(x):
-    return struct.unpack("<q", struct.pack("<d", float(x)))[0]
+    from pesr_amd._pool import f64_bits
+    return f64_bits(x)
 
 
 class Tables:
@@ -52,13 +38,8 @@ class Tables:
 
 
 def _run(program, axis, pool, rows, table, dst_bytes, n=None):
-    exe, d = program
-    n = len(rows) if n is None else n
-    with open(d / "in.bin", "wb") as f:
-        f.write(np.array([n, axis, pool.size, table.size, dst_bytes], dtype=np.int64).tobytes())
-        f.write(np.array(rows, dtype=np.int64).tobytes() + table.tobytes() + pool.tobytes())
-    r = subprocess.run([exe, str(d / "in.bin"), str(d / "out.bin")], capture_output=True, text=True, timeout=120)
-    return r.returncode, np.fromfile(d / "out.bin", dtype=np.uint8)
+    head = np.array([len(rows) if n is None else n, axis, pool.size, table.size, dst_bytes], dtype=np.int64)
+    return host_build.run(program, [head.tobytes(), np.array(rows, dtype=np.int64).tobytes(), table.tobytes(), pool.tobytes()])
 
 
 def _mid(img, ho, m):
