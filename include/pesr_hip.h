@@ -88,6 +88,18 @@ int pesr_conv3x3_dgrad(const float* dy, const float* w_packed_dgrad, const float
 size_t pesr_conv3x3_wgrad_workspace_bytes(int N, int H, int W, int Cin, int Cout, int stride, int algo);
 int pesr_conv3x3_wgrad(const float* x, const float* dy, float* dw, float* db, int N, int H, int W, int Cin, int Cout,
                        int stride, float alpha, int ps_in, int algo, int accumulate, void* workspace, size_t ws_bytes, void* stream);
+/* (ABI 19) Host only: the kernel pesr_conv3x3_wgrad runs for these arguments when its workspace has pesr_conv3x3_wgrad_workspace_bytes
+ * - the rule the call itself dispatches by - as a PESR_WGRAD_KERNEL_* value, or PESR_EINVAL for arguments the call refuses.
+ * pesr_conv3x3_wgrad_wino4_side: images the F(4,3) plan lays side by side in one 48-pixel strip (1; 2 .. 6 for widths below 48), 0 where
+ * that plan does not cover the shape (whatever ps_in, algo and accumulate then decide). */
+#define PESR_WGRAD_KERNEL_DIRECT 0         /* conv3x3_wgrad_kernel */
+#define PESR_WGRAD_KERNEL_WINO23 1         /* conv3x3_wgrad_wino_kernel: F(2,3) along x */
+#define PESR_WGRAD_KERNEL_WINO4_16X16 2    /* conv3x3_wgrad_wino4_kernel: F(4,3) along x, 16x16x4 MFMA, 8 waves */
+#define PESR_WGRAD_KERNEL_WINO4_12W_1D 3   /* conv3x3_wgrad_wino4x_kernel: F(4,3) along x, 32x32x2 MFMA, 12 waves */
+#define PESR_WGRAD_KERNEL_WINO4_12W 4      /* the same kernel, F(2,3) along y nested on top */
+#define PESR_WGRAD_KERNEL_WINO4_PRODUCER 5 /* conv3x3_wgrad_wino4p_kernel: the nested transform, 12 MFMA waves + 4 staging waves (what AUTO runs) */
+int pesr_conv3x3_wgrad_kernel(int N, int H, int W, int Cin, int Cout, int stride, int ps_in, int algo, int accumulate);
+int pesr_conv3x3_wgrad_wino4_side(int N, int H, int W, int Cin, int Cout);
 
 /* Stride-1 3x3 conv (pad 1) with a 1-D Winograd F(2,3) transform along x: 2/3 of the multiplies of pesr_conv3x3_fwd, same
  * tensors and fused epilogue (y = act(alpha * (conv + bias) [masked] + skip)), for even W, Cin % 16 == 0, Cout % 128 == 0

@@ -31,6 +31,8 @@ SIGNATURES = {
 }
 
 SIGNATURES.update({
+    "pesr_conv3x3_wgrad_kernel": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
+    "pesr_conv3x3_wgrad_wino4_side": (c_int, [c_int, c_int, c_int, c_int, c_int]),
     "pesr_conv3x3_wgrad_rgb_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
     "pesr_conv3x3_wgrad_rgb": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_float, c_int, _P, c_size_t, _P]),
     "pesr_conv3x3_wino_supported": (c_int, [c_int, c_int, c_int, c_int, c_int]),

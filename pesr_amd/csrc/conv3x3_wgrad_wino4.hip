@@ -24,6 +24,13 @@
 // has the direct kernel's [split][9][Cout][Cin] layout and its fixed-order reduce kernel (alpha, PixelShuffle channel
 // un-permutation, OIHW store, bias) is shared.  The bias gradient is accumulated on the VALU from the dM_1 fragments
 // (dy0+dy1+dy2+dy3).
+//
+// Three generations of the kernel live here, all selectable (PESR_WGRAD_* of include/pesr_hip.h): the 16x16x4 form (round 2), the 12-wave
+// 32x32x2 form (rounds 3 / 4) and the 16-wave form with producer waves (round 5: the product).  What they share - workgroup decode,
+// segment walk, input transforms, k-step arithmetic, epilogue, G4^T - is written once, as the wg4_* device functions below.  Which of
+// them a call runs on is decided in ONE place, pesr_conv3x3_wgrad_kernel_impl (conv3x3_wgrad.hip), from wg4_plan below through
+// pesr_conv3x3_wgrad_wino4_ws_bytes / _side_impl; the same function answers the host-only query pesr_conv3x3_wgrad_kernel, and
+// Python (ops.wgrad_kernel_for, ops._wg4_plan_ok) asks it instead of re-typing the plan.
 #include <mutex>
 #include "common.h"
 #include "launchers.h"
@@ -49,6 +56,183 @@ constexpr int G4_NT = 512, G4_TXT = 12, G4_K4 = G4_TXT / 4;
 constexpr int G4_VPLANE = G4_K4 * 128, G4_VROW = 6 * G4_VPLANE;       // floats: V row slot [6 xi][3 blocks][4 x-tiles x 32 ci]
 constexpr int G4_DPLANE = G4_K4 * 256, G4_DROW = 6 * G4_DPLANE;       // floats: dM row     [6 xi][3 blocks][4 x-tiles x 64 co]
 constexpr int G4_RING = 6;
+// the two 32x32x2 kernels (below): LDS planes are plain [x-tile][channel] arrays
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+constexpr int X4_VPLANE = G4_TXT * 32, X4_VROW = 6 * X4_VPLANE;       // floats: V row slot [6 xi][12 x-tiles][32 ci]
+constexpr int X4_DPLANE = G4_TXT * 64, X4_DROW = 6 * X4_DPLANE;       // floats: dM row     [6 xi][12 x-tiles][64 co]
+constexpr int X4_RING = 8;                                            // V row slots: four in use, four for the segment behind (a strip start needs all four)
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// What the kernels of this file share, written ONCE: the 12-wave kernel and the producer kernel must agree in every bit (same transform,
+// same order of additions), so they run the same functions.
+// ---------------------------------------------------------------------------------------------------------------------------
+// A segment of the walk: image (or image group), strip, top output row; cont = it continues the previous segment's strip (its
+// rows row-1, row are already in the ring), valid = it exists in this workgroup's slice.
+struct Wg4Seg { int img, xs, row; bool cont, valid; };
+struct Wg4Block { int cit, cot, sp, ci0, co0, seg_begin, seg_end; Wg4Seg first; };
+
+__device__ __forceinline__ Wg4Seg wg4_seg_at(const Wg4Args& a, int seg) {     // segment number -> where a walk that starts there begins
+    Wg4Seg s;
+    const int strip = seg / a.segs_y;
+    s.row = 2 * (seg - strip * a.segs_y);
+    s.img = strip / a.segs_x;
+    s.xs = strip - s.img * a.segs_x;
+    s.cont = false; s.valid = true;
+    return s;
+}
+__device__ __forceinline__ Wg4Seg wg4_seg_after(const Wg4Args& a, const Wg4Seg& c, int index, int seg_end) {   // the segment behind c; index = its number in the walk
+    Wg4Seg n;
+    n.valid = index < seg_end;
+    if (c.row + 2 < a.H) { n.img = c.img; n.xs = c.xs; n.row = c.row + 2; n.cont = true; }
+    else { n.cont = false; n.row = 0; n.xs = c.xs + 1; n.img = c.img; if (n.xs == a.segs_x) { n.xs = 0; n.img = c.img + 1; } }
+    return n;
+}
+// blockIdx -> (split slice, co tile, ci tile), the slice's segments and the first of them.  Workgroups b and b + 8 share an XCD: hand
+// every XCD a contiguous range of logical ids (channel tiles fastest), so the workgroups that stream the same pixels share an L2.
+__device__ __forceinline__ Wg4Block wg4_decode(const Wg4Args& a) {
+    Wg4Block b;
+    int bid = blockIdx.x;
+    if ((gridDim.x & 7) == 0) bid = (bid & 7) * (gridDim.x >> 3) + (bid >> 3);
+    b.cit = bid % a.ci_tiles;  bid /= a.ci_tiles;
+    b.cot = bid % a.co_tiles;
+    b.sp = bid / a.co_tiles;
+    b.ci0 = b.cit * 32; b.co0 = b.cot * 64;
+    b.seg_begin = b.sp * a.segs_per_split;
+    b.seg_end = b.seg_begin + a.segs_per_split;
+    if (b.seg_end > a.total_segs) b.seg_end = a.total_segs;
+    b.first = wg4_seg_at(a, b.seg_begin);
+    return b;
+}
+
+// Input transforms, one LDS plane at a time (n = 0 .. 5, a constant at every call): plane n of V = B^T d from an item's six input columns
+// st[0..5], plane n of dM = A dy from its four gradient columns st[0..3].  tA / tB carry the terms planes 1 and 3 share with 2 and 4, so
+// plane 1 comes before 2 and 3 before 4.  (Signed constants: written as d4 - 5.0f * d2 hipcc negates d2 with a v_xor per register in
+// front of each v_pk_fma.)
+__device__ __forceinline__ f32x4 wg4_v_plane(const int n, const u32x4* st, f32x4& tA, f32x4& tB) {
+    const f32x4 c_m5 = {-5.0f, -5.0f, -5.0f, -5.0f}, c_m4 = {-4.0f, -4.0f, -4.0f, -4.0f}, c_p4 = {4.0f, 4.0f, 4.0f, 4.0f};
+    const f32x4 d0 = __builtin_bit_cast(f32x4, st[0]), d1 = __builtin_bit_cast(f32x4, st[1]), d2 = __builtin_bit_cast(f32x4, st[2]),
+                d3 = __builtin_bit_cast(f32x4, st[3]), d4 = __builtin_bit_cast(f32x4, st[4]), d5 = __builtin_bit_cast(f32x4, st[5]);
+    if (n == 0) return __builtin_elementwise_fma(c_p4, d0, __builtin_elementwise_fma(c_m5, d2, d4));
+    if (n == 1) { tA = __builtin_elementwise_fma(c_m4, d2, d4); tB = __builtin_elementwise_fma(c_m4, d1, d3); return tA + tB; }
+    if (n == 2) return tA - tB;
+    if (n == 3) { tA = d4 - d2; tB = 2.0f * (d3 - d1); return tA + tB; }
+    if (n == 4) return tA - tB;
+    return __builtin_elementwise_fma(c_p4, d1, __builtin_elementwise_fma(c_m5, d3, d5));
+}
+__device__ __forceinline__ f32x4 wg4_dm_plane(const int n, const u32x4* st, f32x4& tA, f32x4& tB) {
+    const f32x4 g0 = __builtin_bit_cast(f32x4, st[0]), g1 = __builtin_bit_cast(f32x4, st[1]), g2 = __builtin_bit_cast(f32x4, st[2]),
+                g3 = __builtin_bit_cast(f32x4, st[3]);
+    if (n == 0) return g0;
+    if (n == 1) { tA = g0 + g2; tB = g1 + g3; return tA + tB; }
+    if (n == 2) return tA - tB;
+    if (n == 3) { tA = g0 + 4.0f * g2; tB = 2.0f * (g1 + 4.0f * g3); return tA + tB; }
+    if (n == 4) return tA - tB;
+    return g3;
+}
+
+// G4^T, the output transform along x, in two halves (T = float or f32x4): what U0, U1, U2 and what U3, U4, U5 give to the three kx taps.
+// A tap is lo + hi:   dw[kx = 0] = U0/4 - (U1+U2)/6 + (U3+U4)/24,   dw[1] = -(U1-U2)/6 + (U3-U4)/12,   dw[2] = -(U1+U2)/6 + (U3+U4)/6 + U5.
+template <class T>
+__device__ __forceinline__ void wg4_gt4_lo(const T u0, const T u1, const T u2, T& w0, T& w1, T& w2) {
+    const T s12 = u1 + u2, d12 = u1 - u2;
+    w0 = 0.25f * u0 - (1.0f / 6.0f) * s12;
+    w1 = (-1.0f / 6.0f) * d12;
+    w2 = (-1.0f / 6.0f) * s12;
+}
+template <class T>
+__device__ __forceinline__ void wg4_gt4_hi(const T u3, const T u4, const T u5, T& w0, T& w1, T& w2) {
+    const T s34 = u3 + u4, d34 = u3 - u4;
+    w0 = (1.0f / 24.0f) * s34;
+    w1 = (1.0f / 12.0f) * d34;
+    w2 = (1.0f / 6.0f) * s34 + u5;
+}
+
+// ---- the two 32x32x2 kernels: fragment read, k-step, epilogue -----------------------------------------------------------------
+// The fragments of k-step q: three ds_read2st64_b32 - the two dM rows, V rows 0 / 1, V rows 2 / 3.
+__device__ __forceinline__ void wg4_read(float (&fa)[2], float (&fb)[4], const float* db, const float* (&vb)[2], const int q) {
+    fa[0] = db[q * 128]; fa[1] = db[X4_DROW + q * 128];
+    fb[0] = vb[0][q * 64]; fb[1] = vb[0][X4_VROW + q * 64];
+    fb[2] = vb[1][q * 64]; fb[3] = vb[1][X4_VROW + q * 64];
+}
+// The y-nesting's operands of a k-step: the four products P0 .. P3 of F(2,3) along y, P_j += a[j] * b[j], from the two dM fragments (rows
+// 0, 1) and the four V fragments (rows -1 .. 2) of the wave's xi plane.
+struct Wg4Nest { float a[4], b[4]; };
+__device__ __forceinline__ Wg4Nest wg4_nest_terms(const float (&fa)[2], const float (&fb)[4]) {
+    return {{fa[0], fa[0] + fa[1], fa[0] - fa[1], fa[1]}, {fb[0] - fb[2], fb[1] + fb[2], fb[2] - fb[1], fb[3] - fb[1]}};
+}
+// bsum += dM_1 = dy0+dy1+dy2+dy3 of both rows, on the xi = 1 waves.  The empty asm keeps this a scalar BRANCH: if-converted (v_add +
+// v_cndmask on all twelve waves) it cost every wave two VALU instructions per k-step.
+__device__ __forceinline__ void wg4_bias_add(float& bsum, const int xi, const float rows01) {
+    if (xi == 1) { asm volatile("" : "+v"(bsum)); bsum += rows01; }
+}
+// One whole k-step without staging: the producer kernel's consumers, and the 1-D form of the 12-wave kernel behind its hooks.  (The
+// y-nested form of the 12-wave kernel runs the same terms and MFMAs with a staging hook and two scheduling fences in front of each MFMA:
+// its skeleton stays in that kernel.)
+template <bool NEST>
+__device__ __forceinline__ void wg4_kstep(f32x16 (&acc)[NEST ? 4 : 3], float& bsum, const int xi, const float (&fa)[2], const float (&fb)[4]) {
+    if constexpr (NEST) {
+        const Wg4Nest t = wg4_nest_terms(fa, fb);
+        wg4_bias_add(bsum, xi, t.a[1]);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(t.a[j], t.b[j], acc[j], 0, 0, 0);
+    } else {
+#pragma unroll
+        for (int ky = 0; ky < 3; ++ky) {
+            acc[ky] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[0], fb[ky], acc[ky], 0, 0, 0);
+            acc[ky] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[1], fb[ky + 1], acc[ky], 0, 0, 0);
+        }
+        wg4_bias_add(bsum, xi, fa[0] + fa[1]);
+    }
+}
+
+// Behind the last segment's barrier: bias column sums, G2^T, G4^T and the slab store, by all NT threads of the workgroup (consumer: this wave
+// holds accumulators - every wave of the 12-wave kernel, waves 0..11 of the producer kernel).
+template <bool NEST, int NT>
+__device__ __forceinline__ void wg4_epilogue(const Wg4Args& a, const Wg4Block& b, float* const lds, f32x16 (&acc)[NEST ? 4 : 3], const float bsum,
+                                             const bool consumer, const int tid, const int cot2, const int xi) {
+    const int lane = tid & 63, c32 = lane & 31, ks = lane >> 5;
+    if (a.bias_part && b.cit == 0) {     // the xi = 1 waves hold column sums of dy: lane pairs (c, c + 32) meet in LDS, fixed order
+        float* red = lds;
+        if (consumer && xi == 1) red[cot2 * 64 + lane] = bsum;
+        __syncthreads();
+        if (tid < 64 && b.co0 + tid < a.Cout) {
+            const int h = tid >> 5, c = tid & 31;
+            a.bias_part[(size_t)b.sp * a.Cout + b.co0 + tid] = red[h * 64 + c] + red[h * 64 + 32 + c];
+        }
+        __syncthreads();
+    }
+    // ---- G^T: park the accumulators as ob[cot2][xi][ky][row 32][col 32], then every thread finishes 8 (or 6) (co, ci) positions ------
+    float* const ob = lds;
+    if (consumer) {
+        if constexpr (NEST) {      // G2^T first, in registers: the four y-planes of this wave's (co half, xi) become its three ky taps
+#pragma unroll
+            for (int j = 0; j < 16; ++j) {
+                const float hs = 0.5f * (acc[1][j] + acc[2][j]), hd = 0.5f * (acc[1][j] - acc[2][j]);
+                acc[0][j] = acc[0][j] + hs; acc[1][j] = hd; acc[2][j] = hs + acc[3][j];
+            }
+        }
+        float* o = ob + ((cot2 * 6 + xi) * 3) * 1024 + c32;
+#pragma unroll
+        for (int ky = 0; ky < 3; ++ky)
+#pragma unroll
+            for (int j = 0; j < 16; ++j) {
+                const int rw = (j >> 2) * 8 + ks * 4 + (j & 3);          // D layout of the 32x32 tile: row = co, col = lane & 31 = ci
+                o[ky * 1024 + rw * 32] = acc[ky][j];
+            }
+    }
+    __syncthreads();
+    float* const out = a.slab + (size_t)b.sp * 9 * a.Cout * a.Cin;
+    const unsigned tap = (unsigned)a.Cout * a.Cin;
+    for (int e = tid; e < 2 * 3 * 1024; e += NT) {
+        const int col = e & 31, rw = (e >> 5) & 31, ky = (e >> 10) % 3, h = e / 3072;
+        const float* u = ob + (h * 6 * 3 + ky) * 1024 + rw * 32 + col;       // + xi * 3 * 1024
+        float l0, l1, l2, h0, h1, h2;
+        wg4_gt4_lo(u[0], u[3072], u[2 * 3072], l0, l1, l2);
+        wg4_gt4_hi(u[3 * 3072], u[4 * 3072], u[5 * 3072], h0, h1, h2);
+        const unsigned go = ((unsigned)(ky * 3) * a.Cout + b.co0 + h * 32 + rw) * a.Cin + b.ci0 + col;
+        out[go] = l0 + h0; out[go + tap] = l1 + h1; out[go + 2 * tap] = l2 + h2;
+    }
+}
 
 
 __global__ __launch_bounds__(G4_NT) void conv3x3_wgrad_wino4_kernel(const Wg4Args a) {
@@ -60,18 +244,8 @@ __global__ __launch_bounds__(G4_NT) void conv3x3_wgrad_wino4_kernel(const Wg4Arg
     const int r = lane & 15, g = lane >> 4;
     const int xh = wave >> 2, co_half = (wave >> 1) & 1, ci_tile = wave & 1;
 
-    // blockIdx -> (split slice, co tile, ci tile).  Workgroups b and b + 8 share an XCD: hand every XCD a contiguous range of
-    // logical ids (channel tiles fastest), so the workgroups that stream the same pixels share an L2.
-    int bid = blockIdx.x;
-    if ((gridDim.x & 7) == 0) bid = (bid & 7) * (gridDim.x >> 3) + (bid >> 3);
-    const int cit = bid % a.ci_tiles;  bid /= a.ci_tiles;
-    const int cot = bid % a.co_tiles;
-    const int sp = bid / a.co_tiles;
-    const int ci0 = cit * 32, co0 = cot * 64;
-
-    const int seg_begin = sp * a.segs_per_split;
-    int seg_end = seg_begin + a.segs_per_split;
-    if (seg_end > a.total_segs) seg_end = a.total_segs;
+    const Wg4Block blk = wg4_decode(a);
+    const int cit = blk.cit, sp = blk.sp, ci0 = blk.ci0, co0 = blk.co0, seg_begin = blk.seg_begin, seg_end = blk.seg_end;
 
     f32x4 acc[9][2];
 #pragma unroll
@@ -145,16 +319,10 @@ __global__ __launch_bounds__(G4_NT) void conv3x3_wgrad_wino4_kernel(const Wg4Arg
     };
     auto store_v = [&](int slot) {
         if (wave < 3) {
-            const f32x4 d0 = __builtin_bit_cast(f32x4, vx[0]), d1 = __builtin_bit_cast(f32x4, vx[1]), d2 = __builtin_bit_cast(f32x4, vx[2]),
-                        d3 = __builtin_bit_cast(f32x4, vx[3]), d4 = __builtin_bit_cast(f32x4, vx[4]), d5 = __builtin_bit_cast(f32x4, vx[5]);
             float* p = vring + slot * G4_VROW + v_pos;
-            const f32x4 t1 = d4 - 4.0f * d2, t2 = d3 - 4.0f * d1, t3 = d4 - d2, t4 = d3 - d1;
-            *(f32x4*)(p) = 4.0f * d0 + (d4 - 5.0f * d2);
-            *(f32x4*)(p + G4_VPLANE) = t1 + t2;
-            *(f32x4*)(p + 2 * G4_VPLANE) = t1 - t2;
-            *(f32x4*)(p + 3 * G4_VPLANE) = t3 + 2.0f * t4;
-            *(f32x4*)(p + 4 * G4_VPLANE) = t3 - 2.0f * t4;
-            *(f32x4*)(p + 5 * G4_VPLANE) = 4.0f * d1 + (d5 - 5.0f * d3);
+            f32x4 tA, tB;
+#pragma unroll
+            for (int n = 0; n < 6; ++n) *(f32x4*)(p + n * G4_VPLANE) = wg4_v_plane(n, vx, tA, tB);
         }
     };
     auto load_d = [&](int img, int oy) {                   // output-gradient row oy (>= H: zeros)
@@ -171,23 +339,11 @@ __global__ __launch_bounds__(G4_NT) void conv3x3_wgrad_wino4_kernel(const Wg4Arg
     };
     auto store_d = [&](int buf) {
         if (wave >= 2) {
-            const f32x4 g0 = __builtin_bit_cast(f32x4, dd[0]), g1 = __builtin_bit_cast(f32x4, dd[1]), g2 = __builtin_bit_cast(f32x4, dd[2]),
-                        g3 = __builtin_bit_cast(f32x4, dd[3]);
             float* p = dmbuf + (buf * 2 + d_rr) * G4_DROW + d_pos;
-            const f32x4 e02 = g0 + g2, e13 = g1 + g3, f02 = g0 + 4.0f * g2, f13 = g1 + 4.0f * g3;
-            *(f32x4*)(p) = g0;
-            *(f32x4*)(p + G4_DPLANE) = e02 + e13;
-            *(f32x4*)(p + 2 * G4_DPLANE) = e02 - e13;
-            *(f32x4*)(p + 3 * G4_DPLANE) = f02 + 2.0f * f13;
-            *(f32x4*)(p + 4 * G4_DPLANE) = f02 - 2.0f * f13;
-            *(f32x4*)(p + 5 * G4_DPLANE) = g3;
+            f32x4 tA, tB;
+#pragma unroll
+            for (int n = 0; n < 6; ++n) *(f32x4*)(p + n * G4_DPLANE) = wg4_dm_plane(n, dd, tA, tB);
         }
-    };
-    auto seg_coords = [&](int seg, int& img, int& xs, int& row) {
-        const int strip = seg / a.segs_y;
-        row = 2 * (seg - strip * a.segs_y);
-        img = strip / a.segs_x;
-        xs = strip - img * a.segs_x;
     };
     auto stage_strip_start = [&](int img, int row, int buf) {   // halo rows row-1 .. row+2 -> slots 0 .. 3; dM(row, row+1) -> buf
         load_v(img, row - 1); store_v(v_rr);
@@ -201,8 +357,7 @@ __global__ __launch_bounds__(G4_NT) void conv3x3_wgrad_wino4_kernel(const Wg4Arg
     const int a_lane1 = ((co_half * 2 + 1) * 4 + ((g + co_half * 2 + 1) & 3)) * 16 + r + xh * 3 * G4_DPLANE;   // m-tile 2 co_half + 1
 
     if (seg_begin >= seg_end) return;                       // (never: the planner hands every workgroup at least one segment)
-    int img, xs, row;
-    seg_coords(seg_begin, img, xs, row);
+    int img = blk.first.img, xs = blk.first.xs, row = blk.first.row;
     set_strip(xs);
     stage_strip_start(img, row, 0);
     // Staging runs a full segment ahead of its ds_writes: the loads for segment s+1's new rows are issued at the store point
@@ -279,7 +434,8 @@ __global__ __launch_bounds__(G4_NT) void conv3x3_wgrad_wino4_kernel(const Wg4Arg
             row += 2;
         } else if (more) {                                  // new strip / image: its four halo rows are staged from scratch
             __syncthreads();
-            seg_coords(seg + 1, img, xs, row);
+            const Wg4Seg nx = wg4_seg_at(a, seg + 1);
+            img = nx.img; xs = nx.xs; row = nx.row;
             set_strip(xs);
             stage_strip_start(img, row, par ^ 1);
             if (seg + 2 < seg_end && row + 2 < a.H) { load_v(img, row + 3); load_d(img, row + 2 + d_rr); }
@@ -314,17 +470,8 @@ __global__ __launch_bounds__(G4_NT) void conv3x3_wgrad_wino4_kernel(const Wg4Arg
                 for (int i = 0; i < 2; ++i) {
                     const f32x4 u0 = acc[ky * 3 + 0][i], u1 = acc[ky * 3 + 1][i], u2 = acc[ky * 3 + 2][i];
                     f32x4 w0, w1, w2;
-                    if (ph == 0) {       // U0, U1, U2
-                        const f32x4 s12 = u1 + u2, d12 = u1 - u2;
-                        w0 = 0.25f * u0 - (1.0f / 6.0f) * s12;
-                        w1 = (-1.0f / 6.0f) * d12;
-                        w2 = (-1.0f / 6.0f) * s12;
-                    } else {             // U3, U4, U5
-                        const f32x4 s34 = u0 + u1, d34 = u0 - u1;
-                        w0 = (1.0f / 24.0f) * s34;
-                        w1 = (1.0f / 12.0f) * d34;
-                        w2 = (1.0f / 6.0f) * s34 + u2;
-                    }
+                    if (ph == 0) wg4_gt4_lo(u0, u1, u2, w0, w1, w2);       // U0, U1, U2
+                    else wg4_gt4_hi(u0, u1, u2, w0, w1, w2);               // U3, U4, U5
 #pragma unroll
                     for (int jj = 0; jj < 4; ++jj) {
                         const int col = (co_half * 2 + i) * 16 + g * 4 + jj, cil = ci_tile * 16 + r;
@@ -352,11 +499,7 @@ __global__ __launch_bounds__(G4_NT) void conv3x3_wgrad_wino4_kernel(const Wg4Arg
 // G^T needs all six xi of a tap: the waves park their accumulators in LDS (147 KB, the staging buffers are free by then) and all
 // 768 threads finish the nine taps of the block in the same order of additions as the kernel above.
 // ---------------------------------------------------------------------------------------------------------------------------
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 constexpr int X4_NT = 768;
-constexpr int X4_VPLANE = G4_TXT * 32, X4_VROW = 6 * X4_VPLANE;       // floats: V row slot [6 xi][12 x-tiles][32 ci]
-constexpr int X4_DPLANE = G4_TXT * 64, X4_DROW = 6 * X4_DPLANE;       // floats: dM row     [6 xi][12 x-tiles][64 co]
-constexpr int X4_RING = 8;                                            // V row slots: four in use, four for the segment behind (a strip start needs all four)
 
 // ---------------------------------------------------------------------------------------------------------------------------
 // Round 4, NEST = true (the default): the transform NESTED in y - F(2,3) along y on top of F(4,3) along x - at no cost in staging.
@@ -380,16 +523,8 @@ __global__ __launch_bounds__(X4_NT) void conv3x3_wgrad_wino4x_kernel(const Wg4Ar
     const int c32 = lane & 31, ks = lane >> 5;            // fragment lane: channel, k-slot (x-tile 2q + ks of k-step q)
     const int cot2 = wave / 6, xi = wave - cot2 * 6;
 
-    int bid = blockIdx.x;
-    if ((gridDim.x & 7) == 0) bid = (bid & 7) * (gridDim.x >> 3) + (bid >> 3);
-    const int cit = bid % a.ci_tiles;  bid /= a.ci_tiles;
-    const int cot = bid % a.co_tiles;
-    const int sp = bid / a.co_tiles;
-    const int ci0 = cit * 32, co0 = cot * 64;
-
-    const int seg_begin = sp * a.segs_per_split;
-    int seg_end = seg_begin + a.segs_per_split;
-    if (seg_end > a.total_segs) seg_end = a.total_segs;
+    const Wg4Block blk = wg4_decode(a);
+    const int ci0 = blk.ci0, co0 = blk.co0, seg_begin = blk.seg_begin, seg_end = blk.seg_end;
 
     constexpr int NACC = NEST ? 4 : 3;
     f32x16 acc[NACC];
@@ -475,16 +610,7 @@ __global__ __launch_bounds__(X4_NT) void conv3x3_wgrad_wino4x_kernel(const Wg4Ar
         const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
         return (const float*)(((unsigned long long)hi << 32) | lo);
     };
-    // A segment of the walk: image (or image group), strip, top output row; cont = it continues the previous segment's strip (its
-    // rows row-1, row are already in the ring), valid = it exists in this workgroup's slice.
-    struct Seg { int img, xs, row; bool cont, valid; };
-    auto seg_after = [&](const Seg& c, int index) {           // the segment behind c; index = its number in the walk
-        Seg n;
-        n.valid = index < seg_end;
-        if (c.row + 2 < a.H) { n.img = c.img; n.xs = c.xs; n.row = c.row + 2; n.cont = true; }
-        else { n.cont = false; n.row = 0; n.xs = c.xs + 1; n.img = c.img; if (n.xs == a.segs_x) { n.xs = 0; n.img = c.img + 1; } }
-        return n;
-    };
+    using Seg = Wg4Seg;
     // The staging loads of segment g, unconditional (a segment that does not exist is fetched through zero-size descriptors: nothing
     // moves): a continuing segment adds input rows row+1, row+2 (waves 0..2), a segment that starts a strip needs row-1 .. row+2
     // (waves 0..2: row-1, row; waves 8..10: row+1, row+2); the dM waves its two gradient rows.  Loads go through a buffer
@@ -540,50 +666,30 @@ __global__ __launch_bounds__(X4_NT) void conv3x3_wgrad_wino4x_kernel(const Wg4Ar
     // ~850 cycles of transform + stores and 400 - 1100 cycles of queued-up buffer loads all at the same point of the segment, and the
     // matrix pipes of their SIMDs starved meanwhile (in-kernel stamps, profiles/r05_wgrad_notes.txt).
     f32x4 tA, tB;                                             // transform terms that live from one step to the next
-    // (signed constants: written as d4 - 5.0f * d2 hipcc negates d2 with a v_xor per register in front of each v_pk_fma)
-    const f32x4 c_m5 = {-5.0f, -5.0f, -5.0f, -5.0f}, c_m4 = {-4.0f, -4.0f, -4.0f, -4.0f}, c_p4 = {4.0f, 4.0f, 4.0f, 4.0f};
     float* sp_ = nullptr;                                     // the item's LDS address for the segment being stored
+    // (one arm per plane, though the arms differ in a constant only: written as sp_ + n * X4_VPLANE hipcc merges the V and the dM arm of
+    // every step into one ds_write behind a select, and the 12-wave kernel's instruction order changes)
     auto stage_step = [&](const int n, int v_slot0, int d_buf, bool four) {
         if (v_role) {
             if (!v_hi || four) {
-                const f32x4 d0 = __builtin_bit_cast(f32x4, st[0]), d1 = __builtin_bit_cast(f32x4, st[1]), d2 = __builtin_bit_cast(f32x4, st[2]),
-                            d3 = __builtin_bit_cast(f32x4, st[3]), d4 = __builtin_bit_cast(f32x4, st[4]), d5 = __builtin_bit_cast(f32x4, st[5]);
                 if (n == 0) {
                     sp_ = vring + ((v_slot0 + (v_hi ? 2 : 0) + s_rr) & (X4_RING - 1)) * X4_VROW + s_pos;
-                    *(f32x4*)(sp_) = __builtin_elementwise_fma(c_p4, d0, __builtin_elementwise_fma(c_m5, d2, d4));
-                } else if (n == 1) {
-                    tA = __builtin_elementwise_fma(c_m4, d2, d4); tB = __builtin_elementwise_fma(c_m4, d1, d3);
-                    *(f32x4*)(sp_ + X4_VPLANE) = tA + tB;
-                } else if (n == 2) {
-                    *(f32x4*)(sp_ + 2 * X4_VPLANE) = tA - tB;
-                } else if (n == 3) {
-                    tA = d4 - d2; tB = 2.0f * (d3 - d1);
-                    *(f32x4*)(sp_ + 3 * X4_VPLANE) = tA + tB;
-                } else if (n == 4) {
-                    *(f32x4*)(sp_ + 4 * X4_VPLANE) = tA - tB;
-                } else {
-                    *(f32x4*)(sp_ + 5 * X4_VPLANE) = __builtin_elementwise_fma(c_p4, d1, __builtin_elementwise_fma(c_m5, d3, d5));
-                }
+                    *(f32x4*)(sp_) = wg4_v_plane(0, st, tA, tB);
+                } else if (n == 1) { *(f32x4*)(sp_ + X4_VPLANE) = wg4_v_plane(1, st, tA, tB);
+                } else if (n == 2) { *(f32x4*)(sp_ + 2 * X4_VPLANE) = wg4_v_plane(2, st, tA, tB);
+                } else if (n == 3) { *(f32x4*)(sp_ + 3 * X4_VPLANE) = wg4_v_plane(3, st, tA, tB);
+                } else if (n == 4) { *(f32x4*)(sp_ + 4 * X4_VPLANE) = wg4_v_plane(4, st, tA, tB);
+                } else { *(f32x4*)(sp_ + 5 * X4_VPLANE) = wg4_v_plane(5, st, tA, tB); }
             }
         } else {
-            const f32x4 g0 = __builtin_bit_cast(f32x4, st[0]), g1 = __builtin_bit_cast(f32x4, st[1]), g2 = __builtin_bit_cast(f32x4, st[2]),
-                        g3 = __builtin_bit_cast(f32x4, st[3]);
             if (n == 0) {
                 sp_ = dmbuf + (d_buf * 2 + s_rr) * X4_DROW + s_pos;
-                *(f32x4*)(sp_) = g0;
-            } else if (n == 1) {
-                tA = g0 + g2; tB = g1 + g3;
-                *(f32x4*)(sp_ + X4_DPLANE) = tA + tB;
-            } else if (n == 2) {
-                *(f32x4*)(sp_ + 2 * X4_DPLANE) = tA - tB;
-            } else if (n == 3) {
-                tA = g0 + 4.0f * g2; tB = 2.0f * (g1 + 4.0f * g3);
-                *(f32x4*)(sp_ + 3 * X4_DPLANE) = tA + tB;
-            } else if (n == 4) {
-                *(f32x4*)(sp_ + 4 * X4_DPLANE) = tA - tB;
-            } else {
-                *(f32x4*)(sp_ + 5 * X4_DPLANE) = g3;
-            }
+                *(f32x4*)(sp_) = wg4_dm_plane(0, st, tA, tB);
+            } else if (n == 1) { *(f32x4*)(sp_ + X4_DPLANE) = wg4_dm_plane(1, st, tA, tB);
+            } else if (n == 2) { *(f32x4*)(sp_ + 2 * X4_DPLANE) = wg4_dm_plane(2, st, tA, tB);
+            } else if (n == 3) { *(f32x4*)(sp_ + 3 * X4_DPLANE) = wg4_dm_plane(3, st, tA, tB);
+            } else if (n == 4) { *(f32x4*)(sp_ + 4 * X4_DPLANE) = wg4_dm_plane(4, st, tA, tB);
+            } else { *(f32x4*)(sp_ + 5 * X4_DPLANE) = wg4_dm_plane(5, st, tA, tB); }
         }
     };
     auto store_stage = [&](int v_slot0, int d_buf, bool four) {      // all six at once (the workgroup's first segment)
@@ -596,15 +702,8 @@ __global__ __launch_bounds__(X4_NT) void conv3x3_wgrad_wino4x_kernel(const Wg4Ar
     const int a_lane = xi * X4_DPLANE + ks * 64 + cot2 * 32 + c32;
 
     if (seg_begin >= seg_end) return;
-    Seg cur;
-    {
-        const int strip = seg_begin / a.segs_y;
-        cur.row = 2 * (seg_begin - strip * a.segs_y);
-        cur.img = strip / a.segs_x;
-        cur.xs = strip - cur.img * a.segs_x;
-        cur.cont = false; cur.valid = true;
-    }
-    Seg n2 = seg_after(cur, seg_begin + 1);
+    const Seg cur = blk.first;
+    Seg n2 = wg4_seg_after(a, cur, seg_begin + 1, seg_end);
     bool n1_valid = n2.valid, n1_cont = n2.cont;              // the segment behind the one being computed (n2: the one after that)
     // The walk is ONE software pipeline over all segments of the slice, strip changes included (round 5): at its store point a
     // segment stores what the segment behind it needs (two new rows, or the four halo rows of a new strip: the ring has EIGHT
@@ -615,7 +714,7 @@ __global__ __launch_bounds__(X4_NT) void conv3x3_wgrad_wino4x_kernel(const Wg4Ar
     store_stage(0, 0, true);
     if (n2.valid && !n2.cont) set_strip(n2.xs, n2.img);
     X4_LOAD_ALL(n2)
-    n2 = seg_after(n2, seg_begin + 2);
+    n2 = wg4_seg_after(a, n2, seg_begin + 2, seg_end);
     __syncthreads();
     int base = 0, par = 0;                                  // ring slot of the segment's top halo row (row - 1); its dM buffer
     constexpr int KQ = G4_TXT / 2;                          // k-steps per row
@@ -626,38 +725,28 @@ __global__ __launch_bounds__(X4_NT) void conv3x3_wgrad_wino4x_kernel(const Wg4Ar
 
     float fa0[2], fb0[4], fa1[2], fb1[4];
 #define X4_FENCE() __builtin_amdgcn_sched_barrier(0)
-#define X4_READ(FA, FB, DB, VB, Q)      /* three ds_read2st64_b32: the dM rows, V rows 0 / 1, V rows 2 / 3 */ \
-        {                                                                                        \
-            FA[0] = DB[(Q) * 128]; FA[1] = DB[X4_DROW + (Q) * 128];                              \
-            FB[0] = VB[0][(Q) * 64]; FB[1] = VB[0][X4_VROW + (Q) * 64];                          \
-            FB[2] = VB[1][(Q) * 64]; FB[3] = VB[1][X4_VROW + (Q) * 64];                          \
-        }
-    // One k-step: the y-nesting's VALU work first, then its MFMAs with one hook in front of each (HB < 0: none).  hook(n), n = 0 .. 11
-    // over three consecutive k-steps: staging steps 0 .. 5 (one LDS plane each), then the six loads of the segment after next.
+    // One k-step (the arithmetic is wg4_kstep's): the y-nesting's VALU work first, then its MFMAs with one hook in front of each (HB < 0:
+    // none).  hook(n), n = 0 .. 11 over three consecutive k-steps: staging steps 0 .. 5 (one LDS plane each), then the six loads of the
+    // segment after next.
 #define X4_KSTEP(FA, FB, HB)                                                                     \
-        if (NEST) {                                                                              \
-            const float ds_ = FA[0] + FA[1], dd_ = FA[0] - FA[1];                                \
-            const float x0_ = FB[0] - FB[2], x1_ = FB[1] + FB[2], x2_ = FB[2] - FB[1], x3_ = FB[3] - FB[1]; \
-            if (xi == 1) { asm volatile("" : "+v"(bsum)); bsum += ds_; }   /* dM_1 = dy0+dy1+dy2+dy3, both rows; the empty asm keeps this a scalar BRANCH: if-converted (v_add + v_cndmask on all twelve waves) it cost every wave two VALU instructions per k-step */ \
+        if constexpr (NEST) {                                                                    \
+            const Wg4Nest t_ = wg4_nest_terms(FA, FB);                                           \
+            wg4_bias_add(bsum, xi, t_.a[1]);                                                     \
             X4_FENCE(); if ((HB) >= 0) hook((HB) + 0); X4_FENCE();                               \
-            acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(FA[0], x0_, acc[0], 0, 0, 0);          \
+            acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(t_.a[0], t_.b[0], acc[0], 0, 0, 0);    \
             X4_FENCE(); if ((HB) >= 0) hook((HB) + 1); X4_FENCE();                               \
-            acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(ds_, x1_, acc[1], 0, 0, 0);            \
+            acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(t_.a[1], t_.b[1], acc[1], 0, 0, 0);    \
             X4_FENCE(); if ((HB) >= 0) hook((HB) + 2); X4_FENCE();                               \
-            acc[2] = __builtin_amdgcn_mfma_f32_32x32x2f32(dd_, x2_, acc[2], 0, 0, 0);            \
+            acc[2] = __builtin_amdgcn_mfma_f32_32x32x2f32(t_.a[2], t_.b[2], acc[2], 0, 0, 0);    \
             X4_FENCE(); if ((HB) >= 0) hook((HB) + 3); X4_FENCE();                               \
-            acc[3] = __builtin_amdgcn_mfma_f32_32x32x2f32(FA[1], x3_, acc[3], 0, 0, 0);          \
+            acc[3] = __builtin_amdgcn_mfma_f32_32x32x2f32(t_.a[3], t_.b[3], acc[3], 0, 0, 0);    \
         } else {                                                                                 \
             if ((HB) >= 0) { hook((HB) + 0); hook((HB) + 1); hook((HB) + 2); hook((HB) + 3); }   \
-            _Pragma("unroll") for (int ky = 0; ky < 3; ++ky) {                                   \
-                acc[ky] = __builtin_amdgcn_mfma_f32_32x32x2f32(FA[0], FB[ky], acc[ky], 0, 0, 0); \
-                acc[ky] = __builtin_amdgcn_mfma_f32_32x32x2f32(FA[1], FB[ky + 1], acc[ky], 0, 0, 0); \
-            }                                                                                    \
-            if (xi == 1) { asm volatile("" : "+v"(bsum)); bsum += FA[0] + FA[1]; }   /* dM_1 = dy0+dy1+dy2+dy3 */ \
+            wg4_kstep<false>(acc, bsum, xi, FA, FB);                                             \
         }
     const float* db = dmbuf + a_lane;
     const float* vb[2] = {vring + b_lane, vring + 2 * X4_VROW + b_lane};     // rows (base, base + 1) and (base + 2, base + 3): the base is even, a pair never wraps
-    X4_READ(fa0, fb0, db, vb, 0)
+    wg4_read(fa0, fb0, db, vb, 0);
     int seg = seg_begin;
 #pragma unroll 1
     for (;;) {
@@ -679,23 +768,23 @@ __global__ __launch_bounds__(X4_NT) void conv3x3_wgrad_wino4x_kernel(const Wg4Ar
                 for (int t = 0; t < 6; ++t) load_step(t);
             }
         };
-        X4_READ(fa1, fb1, db, vb, 1)
+        wg4_read(fa1, fb1, db, vb, 1);
         X4_FENCE();
         X4_KSTEP(fa0, fb0, -1)
         X4_FENCE();
-        X4_READ(fa0, fb0, db, vb, 2)
+        wg4_read(fa0, fb0, db, vb, 2);
         X4_FENCE();
         X4_KSTEP(fa1, fb1, -1)
         X4_FENCE();
-        X4_READ(fa1, fb1, db, vb, 3)
+        wg4_read(fa1, fb1, db, vb, 3);
         X4_FENCE();
         X4_KSTEP(fa0, fb0, 0)
         X4_FENCE();
-        X4_READ(fa0, fb0, db, vb, 4)
+        wg4_read(fa0, fb0, db, vb, 4);
         X4_FENCE();
         X4_KSTEP(fa1, fb1, 4)
         X4_FENCE();
-        X4_READ(fa1, fb1, db, vb, 5)
+        wg4_read(fa1, fb1, db, vb, 5);
         X4_FENCE();
         X4_KSTEP(fa0, fb0, -1)
         X4_FENCE();
@@ -708,93 +797,30 @@ __global__ __launch_bounds__(X4_NT) void conv3x3_wgrad_wino4x_kernel(const Wg4Ar
         db = dmbuf + ((par ^ 1) * 2) * X4_DROW + a_lane;       // (this segment's last fragments are in registers: the pointers move on)
         vb[0] = vring + nbase * X4_VROW + b_lane;
         vb[1] = vring + ((nbase + 2) & (X4_RING - 1)) * X4_VROW + b_lane;
-        X4_READ(fa0, fb0, db, vb, 0)
+        wg4_read(fa0, fb0, db, vb, 0);
         X4_FENCE();
         X4_KSTEP(fa1, fb1, -1)
         X4_FENCE();
         base = nbase; par ^= 1;
         if (!n1_valid) break;
         n1_valid = n2.valid; n1_cont = n2.cont; ++seg;
-        n2 = seg_after(n2, seg + 2);
+        n2 = wg4_seg_after(a, n2, seg + 2, seg_end);
     }
-#undef X4_READ
 #undef X4_KSTEP
 #undef X4_FENCE
     __syncthreads();
 
-    if (a.bias_part && cit == 0) {     // the xi = 1 waves hold column sums of dy: lane pairs (c, c + 32) meet in LDS, fixed order
-        float* red = lds;
-        if (xi == 1) red[cot2 * 64 + lane] = bsum;
-        __syncthreads();
-        if (tid < 64 && co0 + tid < a.Cout) {
-            const int h = tid >> 5, c = tid & 31;
-            a.bias_part[(size_t)sp * a.Cout + co0 + tid] = red[h * 64 + c] + red[h * 64 + 32 + c];
-        }
-        __syncthreads();
-    }
-    // ---- G^T: park the accumulators as ob[cot2][xi][ky][row 32][col 32], then every thread finishes 8 (co, ci) positions ------
-    float* const ob = lds;
-    if (NEST) {      // G2^T first, in registers: the four y-planes of this wave's (co half, xi) become its three ky taps
-#pragma unroll
-        for (int j = 0; j < 16; ++j) {
-            const float hs = 0.5f * (acc[1][j] + acc[2][j]), hd = 0.5f * (acc[1][j] - acc[2][j]);
-            acc[0][j] = acc[0][j] + hs; acc[1][j] = hd; acc[2][j] = hs + acc[3][j];
-        }
-    }
-    {
-        float* o = ob + ((cot2 * 6 + xi) * 3) * 1024 + c32;
-#pragma unroll
-        for (int ky = 0; ky < 3; ++ky)
-#pragma unroll
-            for (int j = 0; j < 16; ++j) {
-                const int rw = (j >> 2) * 8 + ks * 4 + (j & 3);          // D layout of the 32x32 tile: row = co, col = lane & 31 = ci
-                o[ky * 1024 + rw * 32] = acc[ky][j];
-            }
-    }
-    __syncthreads();
-    float* const out = a.slab + (size_t)sp * 9 * a.Cout * a.Cin;
-    const unsigned tap = (unsigned)a.Cout * a.Cin;
-    for (int e = tid; e < 2 * 3 * 1024; e += X4_NT) {
-        const int col = e & 31, rw = (e >> 5) & 31, ky = (e >> 10) % 3, h = e / 3072;
-        const float* u = ob + (h * 6 * 3 + ky) * 1024 + rw * 32 + col;       // + xi * 3 * 1024
-        const float u0 = u[0], u1 = u[3072], u2 = u[2 * 3072], u3 = u[3 * 3072], u4 = u[4 * 3072], u5 = u[5 * 3072];
-        const float s12 = u1 + u2, d12 = u1 - u2, s34 = u3 + u4, d34 = u3 - u4;
-        const float w0 = (0.25f * u0 - (1.0f / 6.0f) * s12) + (1.0f / 24.0f) * s34;
-        const float w1 = ((-1.0f / 6.0f) * d12) + (1.0f / 12.0f) * d34;
-        const float w2 = ((-1.0f / 6.0f) * s12) + ((1.0f / 6.0f) * s34 + u5);
-        const unsigned go = ((unsigned)(ky * 3) * a.Cout + co0 + h * 32 + rw) * a.Cin + ci0 + col;
-        out[go] = w0; out[go + tap] = w1; out[go + 2 * tap] = w2;
-    }
+    wg4_epilogue<NEST, X4_NT>(a, blk, lds, acc, bsum, true, tid, cot2, xi);
 }
 
-// ---------------------------------------------------------------------------------------------------------------------------
-// Round 5: the same kernel with the staging on waves of its OWN (conv3x3_wgrad_wino4p_kernel, 16 waves: 12 consumers + 4 producers,
-// one producer per SIMD).  fp32 MFMAs and VALU instructions share the SIMD's datapath, so the staging's ~400 VALU instructions per
-// segment cost matrix time wherever they run - but in the 12-wave form they sat in the MFMA waves' own instruction streams: nine of the
-// twelve waves left the MFMA loop for ~1000 - 1500 cycles at the same point of every segment, the other three ran ahead into the barrier
-// and waited (in-kernel stamps, profiles/r05_wgrad_notes.txt).  Here a consumer wave's stream is fragment reads, six adds and four
-// MFMAs per k-step and nothing else; a producer wave loads, transforms and stores what the NEXT segment needs and waits at the
-// segment's barrier; its VALU work is spread evenly over the four SIMDs (V wave-item p + dM wave-item p on producers 0..2, the three
-// row-1 dM wave-items on producer 3: 98 / 98 / 98 / 111 VALU-equivalents per segment).  Same LDS image, ring, segment walk, split-K
-// slab and epilogue as above; 128 VGPRs per wave (four waves per SIMD).
-// ---------------------------------------------------------------------------------------------------------------------------
 constexpr int P4_NT = 1024;
-
-struct P4Seg { int img, xs, row; bool cont, valid; };
-__device__ __forceinline__ P4Seg p4_seg_after(const Wg4Args& a, const P4Seg& c, int index, int seg_end) {   // the segment behind c; index = its number in the walk
-    P4Seg n;
-    n.valid = index < seg_end;
-    if (c.row + 2 < a.H) { n.img = c.img; n.xs = c.xs; n.row = c.row + 2; n.cont = true; }
-    else { n.cont = false; n.row = 0; n.xs = c.xs + 1; n.img = c.img; if (n.xs == a.segs_x) { n.xs = 0; n.img = c.img + 1; } }
-    return n;
-}
 
 // The producer waves' whole life (P3: the wave that stages the three row-1 dM wave-items; otherwise V wave-item pw + dM wave-item pw).
 template <bool P3>
 __device__ __forceinline__ void p4_producer(const Wg4Args& a, float* const vring, float* const dmbuf, const int pw, const int lane,
-                                            const int ci0, const int co0, const int seg_begin, const int seg_end, const P4Seg cur) {
-    using Seg = P4Seg;
-    auto seg_after = [&](const Seg& c, int index) { return p4_seg_after(a, c, index, seg_end); };
+                                            const int ci0, const int co0, const int seg_begin, const int seg_end, const Wg4Seg cur) {
+    using Seg = Wg4Seg;
+    auto seg_after = [&](const Seg& c, int index) { return wg4_seg_after(a, c, index, seg_end); };
     // Wave-items (64 items each): V wave-item k = items 64k .. 64k+63 of the 192 (row rr = item / 96, x-tile (item % 96) >> 3,
     // ci group item & 7: six input columns of four channels), dM wave-item k of the 384 (row k / 3, x-tile (item % 192) >> 4,
     // co group item & 15: four gradient columns).  Producers 0..2: slot V = V wave-item p (r[0..5]), slot H = the same item of the
@@ -903,29 +929,18 @@ __device__ __forceinline__ void p4_producer(const Wg4Args& a, float* const vring
             }
         }
     };
-    const f32x4 c_m5 = {-5.0f, -5.0f, -5.0f, -5.0f}, c_m4 = {-4.0f, -4.0f, -4.0f, -4.0f}, c_p4 = {4.0f, 4.0f, 4.0f, 4.0f};
-    auto store_v = [&](const int rb, float* p) {           // six planes of one V item
-        const f32x4 d0 = __builtin_bit_cast(f32x4, r[rb]), d1 = __builtin_bit_cast(f32x4, r[rb + 1]), d2 = __builtin_bit_cast(f32x4, r[rb + 2]),
-                    d3 = __builtin_bit_cast(f32x4, r[rb + 3]), d4 = __builtin_bit_cast(f32x4, r[rb + 4]), d5 = __builtin_bit_cast(f32x4, r[rb + 5]);
-        *(f32x4*)(p) = __builtin_elementwise_fma(c_p4, d0, __builtin_elementwise_fma(c_m5, d2, d4));
-        *(f32x4*)(p + 5 * X4_VPLANE) = __builtin_elementwise_fma(c_p4, d1, __builtin_elementwise_fma(c_m5, d3, d5));
-        const f32x4 t1 = __builtin_elementwise_fma(c_m4, d2, d4), t2 = __builtin_elementwise_fma(c_m4, d1, d3);
-        *(f32x4*)(p + X4_VPLANE) = t1 + t2;
-        *(f32x4*)(p + 2 * X4_VPLANE) = t1 - t2;
-        const f32x4 t3 = d4 - d2, t4 = 2.0f * (d3 - d1);
-        *(f32x4*)(p + 3 * X4_VPLANE) = t3 + t4;
-        *(f32x4*)(p + 4 * X4_VPLANE) = t3 - t4;
+    auto store_v = [&](const int rb, float* p) {           // six planes of one V item: 0 and 5 first, then the two pairs
+        f32x4 tA, tB;
+#pragma unroll
+        for (int i = 0; i < 6; ++i) {
+            const int n = i == 0 ? 0 : (i == 1 ? 5 : i - 1);
+            *(f32x4*)(p + n * X4_VPLANE) = wg4_v_plane(n, r + rb, tA, tB);
+        }
     };
     auto store_d = [&](const int rb, float* p) {           // six planes of one dM item
-        const f32x4 g0 = __builtin_bit_cast(f32x4, r[rb]), g1 = __builtin_bit_cast(f32x4, r[rb + 1]), g2 = __builtin_bit_cast(f32x4, r[rb + 2]),
-                    g3 = __builtin_bit_cast(f32x4, r[rb + 3]);
-        const f32x4 e02 = g0 + g2, e13 = g1 + g3, f02 = g0 + 4.0f * g2, f13 = 2.0f * (g1 + 4.0f * g3);
-        *(f32x4*)(p) = g0;
-        *(f32x4*)(p + X4_DPLANE) = e02 + e13;
-        *(f32x4*)(p + 2 * X4_DPLANE) = e02 - e13;
-        *(f32x4*)(p + 3 * X4_DPLANE) = f02 + f13;
-        *(f32x4*)(p + 4 * X4_DPLANE) = f02 - f13;
-        *(f32x4*)(p + 5 * X4_DPLANE) = g3;
+        f32x4 tA, tB;
+#pragma unroll
+        for (int n = 0; n < 6; ++n) *(f32x4*)(p + n * X4_DPLANE) = wg4_dm_plane(n, r + rb, tA, tB);
     };
     // what was loaded for segment g goes to ring slots v_slot0 .. (+3 at a strip start) and dM buffer d_buf
     auto store_seg = [&](const Seg& g, int v_slot0, int d_buf) {
@@ -973,28 +988,10 @@ __global__ __launch_bounds__(P4_NT) void conv3x3_wgrad_wino4p_kernel(const Wg4Ar
     const int c32 = lane & 31, ks = lane >> 5;            // consumer fragment lane: channel, k-slot (x-tile 2q + ks of k-step q)
     const int cot2 = producer ? 0 : wave / 6, xi = producer ? 0 : wave - cot2 * 6;
 
-    int bid = blockIdx.x;
-    if ((gridDim.x & 7) == 0) bid = (bid & 7) * (gridDim.x >> 3) + (bid >> 3);
-    const int cit = bid % a.ci_tiles;  bid /= a.ci_tiles;
-    const int cot = bid % a.co_tiles;
-    const int sp = bid / a.co_tiles;
-    const int ci0 = cit * 32, co0 = cot * 64;
-
-    const int seg_begin = sp * a.segs_per_split;
-    int seg_end = seg_begin + a.segs_per_split;
-    if (seg_end > a.total_segs) seg_end = a.total_segs;
+    const Wg4Block blk = wg4_decode(a);
+    const int ci0 = blk.ci0, co0 = blk.co0, seg_begin = blk.seg_begin, seg_end = blk.seg_end;
     if (seg_begin >= seg_end) return;
-
-    using Seg = P4Seg;
-    auto seg_after = [&](const Seg& c, int index) { return p4_seg_after(a, c, index, seg_end); };
-    Seg cur;
-    {
-        const int strip = seg_begin / a.segs_y;
-        cur.row = 2 * (seg_begin - strip * a.segs_y);
-        cur.img = strip / a.segs_x;
-        cur.xs = strip - cur.img * a.segs_x;
-        cur.cont = false; cur.valid = true;
-    }
+    const Wg4Seg cur = blk.first;
 
     constexpr int NACC = NEST ? 4 : 3;
     f32x16 acc[NACC];
@@ -1015,106 +1012,41 @@ __global__ __launch_bounds__(P4_NT) void conv3x3_wgrad_wino4p_kernel(const Wg4Ar
         // ================================================= consumers =================================================
         const int b_lane = xi * X4_VPLANE + ks * 32 + c32;
         const int a_lane = xi * X4_DPLANE + ks * 64 + cot2 * 32 + c32;
-        Seg n1 = seg_after(cur, seg_begin + 1);
+        Wg4Seg n1 = wg4_seg_after(a, cur, seg_begin + 1, seg_end);
         __syncthreads();                                       // the first segment is staged
         int base = 0, par = 0;
         constexpr int KQ = G4_TXT / 2;
         float fa0[2], fb0[4], fa1[2], fb1[4];
-#define P4_READ(FA, FB, DB, VB, Q)                                                               \
-        {                                                                                        \
-            FA[0] = DB[(Q) * 128]; FA[1] = DB[X4_DROW + (Q) * 128];                              \
-            FB[0] = VB[0][(Q) * 64]; FB[1] = VB[0][X4_VROW + (Q) * 64];                          \
-            FB[2] = VB[1][(Q) * 64]; FB[3] = VB[1][X4_VROW + (Q) * 64];                          \
-        }
-#define P4_KSTEP(FA, FB)                                                                         \
-        if (NEST) {                                                                              \
-            const float ds_ = FA[0] + FA[1], dd_ = FA[0] - FA[1];                                \
-            const float x0_ = FB[0] - FB[2], x1_ = FB[1] + FB[2], x2_ = FB[2] - FB[1], x3_ = FB[3] - FB[1]; \
-            if (xi == 1) { asm volatile("" : "+v"(bsum)); bsum += ds_; }                         \
-            acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(FA[0], x0_, acc[0], 0, 0, 0);          \
-            acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(ds_, x1_, acc[1], 0, 0, 0);            \
-            acc[2] = __builtin_amdgcn_mfma_f32_32x32x2f32(dd_, x2_, acc[2], 0, 0, 0);            \
-            acc[3] = __builtin_amdgcn_mfma_f32_32x32x2f32(FA[1], x3_, acc[3], 0, 0, 0);          \
-        } else {                                                                                 \
-            _Pragma("unroll") for (int ky = 0; ky < 3; ++ky) {                                   \
-                acc[ky] = __builtin_amdgcn_mfma_f32_32x32x2f32(FA[0], FB[ky], acc[ky], 0, 0, 0); \
-                acc[ky] = __builtin_amdgcn_mfma_f32_32x32x2f32(FA[1], FB[ky + 1], acc[ky], 0, 0, 0); \
-            }                                                                                    \
-            if (xi == 1) { asm volatile("" : "+v"(bsum)); bsum += FA[0] + FA[1]; }               \
-        }
         const float* db = dmbuf + a_lane;
         const float* vb[2] = {vring + b_lane, vring + 2 * X4_VROW + b_lane};
-        P4_READ(fa0, fb0, db, vb, 0)
+        wg4_read(fa0, fb0, db, vb, 0);
 #pragma unroll 1
         for (int seg = seg_begin; seg < seg_end; ++seg) {
             const int nbase = (base + (n1.cont ? 2 : 4)) & (X4_RING - 1);
 #pragma unroll
             for (int q = 0; q < KQ - 2; q += 2) {
-                P4_READ(fa1, fb1, db, vb, q + 1)
-                P4_KSTEP(fa0, fb0)
-                P4_READ(fa0, fb0, db, vb, q + 2)
-                P4_KSTEP(fa1, fb1)
+                wg4_read(fa1, fb1, db, vb, q + 1);
+                wg4_kstep<NEST>(acc, bsum, xi, fa0, fb0);
+                wg4_read(fa0, fb0, db, vb, q + 2);
+                wg4_kstep<NEST>(acc, bsum, xi, fa1, fb1);
             }
-            P4_READ(fa1, fb1, db, vb, KQ - 1)
-            P4_KSTEP(fa0, fb0)
+            wg4_read(fa1, fb1, db, vb, KQ - 1);
+            wg4_kstep<NEST>(acc, bsum, xi, fa0, fb0);
             // the segment's one barrier, in front of its last k-step: this segment's last fragments are in registers, the next
             // segment's rows are stored - its first fragments are read here, under that k-step's MFMAs
             __syncthreads();
             db = dmbuf + ((par ^ 1) * 2) * X4_DROW + a_lane;
             vb[0] = vring + nbase * X4_VROW + b_lane;
             vb[1] = vring + ((nbase + 2) & (X4_RING - 1)) * X4_VROW + b_lane;
-            P4_READ(fa0, fb0, db, vb, 0)
-            P4_KSTEP(fa1, fb1)
+            wg4_read(fa0, fb0, db, vb, 0);
+            wg4_kstep<NEST>(acc, bsum, xi, fa1, fb1);
             base = nbase; par ^= 1;
-            n1 = seg_after(n1, seg + 2);
+            n1 = wg4_seg_after(a, n1, seg + 2, seg_end);
         }
-#undef P4_READ
-#undef P4_KSTEP
     }
     __syncthreads();
 
-    if (a.bias_part && cit == 0) {     // the xi = 1 waves hold column sums of dy: lane pairs (c, c + 32) meet in LDS, fixed order
-        float* red = lds;
-        if (!producer && xi == 1) red[cot2 * 64 + lane] = bsum;
-        __syncthreads();
-        if (tid < 64 && co0 + tid < a.Cout) {
-            const int h = tid >> 5, c = tid & 31;
-            a.bias_part[(size_t)sp * a.Cout + co0 + tid] = red[h * 64 + c] + red[h * 64 + 32 + c];
-        }
-        __syncthreads();
-    }
-    float* const ob = lds;
-    if (!producer) {
-        if (NEST) {
-#pragma unroll
-            for (int j = 0; j < 16; ++j) {
-                const float hs = 0.5f * (acc[1][j] + acc[2][j]), hd = 0.5f * (acc[1][j] - acc[2][j]);
-                acc[0][j] = acc[0][j] + hs; acc[1][j] = hd; acc[2][j] = hs + acc[3][j];
-            }
-        }
-        float* o = ob + ((cot2 * 6 + xi) * 3) * 1024 + c32;
-#pragma unroll
-        for (int ky = 0; ky < 3; ++ky)
-#pragma unroll
-            for (int j = 0; j < 16; ++j) {
-                const int rw = (j >> 2) * 8 + ks * 4 + (j & 3);
-                o[ky * 1024 + rw * 32] = acc[ky][j];
-            }
-    }
-    __syncthreads();
-    float* const out = a.slab + (size_t)sp * 9 * a.Cout * a.Cin;
-    const unsigned tap = (unsigned)a.Cout * a.Cin;
-    for (int e = tid; e < 2 * 3 * 1024; e += P4_NT) {
-        const int col = e & 31, rw = (e >> 5) & 31, ky = (e >> 10) % 3, h = e / 3072;
-        const float* u = ob + (h * 6 * 3 + ky) * 1024 + rw * 32 + col;
-        const float u0 = u[0], u1 = u[3072], u2 = u[2 * 3072], u3 = u[3 * 3072], u4 = u[4 * 3072], u5 = u[5 * 3072];
-        const float s12 = u1 + u2, d12 = u1 - u2, s34 = u3 + u4, d34 = u3 - u4;
-        const float w0 = (0.25f * u0 - (1.0f / 6.0f) * s12) + (1.0f / 24.0f) * s34;
-        const float w1 = ((-1.0f / 6.0f) * d12) + (1.0f / 12.0f) * d34;
-        const float w2 = ((-1.0f / 6.0f) * s12) + ((1.0f / 6.0f) * s34 + u5);
-        const unsigned go = ((unsigned)(ky * 3) * a.Cout + co0 + h * 32 + rw) * a.Cin + ci0 + col;
-        out[go] = w0; out[go + tap] = w1; out[go + 2 * tap] = w2;
-    }
+    wg4_epilogue<NEST, P4_NT>(a, blk, lds, acc, bsum, !producer, tid, cot2, xi);
 }
 
 namespace {
@@ -1162,14 +1094,19 @@ size_t pesr_conv3x3_wgrad_wino4_ws_bytes(int N, int H, int W, int Cin, int Cout)
     return wg4_plan(N, H, W, Cin, Cout, &p) ? p.total_bytes : 0;
 }
 
-// returns PESR_EINVAL when the shape is not covered (the caller then tries the F(2,3) form / the direct kernel)
-// variant 0: the 16x16x4 kernel (8 waves); 1: the 32x32x2 kernel (12 waves), 1-D transform; 2: the same kernel with the transform nested in y;
-// 3: the y-nested transform with the staging on four producer waves (16 waves; the product)
+int pesr_conv3x3_wgrad_wino4_side_impl(int N, int H, int W, int Cin, int Cout) {
+    Wg4Plan p;
+    return wg4_plan(N, H, W, Cin, Cout, &p) ? p.side : 0;
+}
+
+// returns PESR_EINVAL when the shape is not covered (pesr_conv3x3_wgrad_kernel_impl of conv3x3_wgrad.hip sends such calls to the F(2,3)
+// form / the direct kernel).  variant: PESR_WGK_WINO4_16X16 (8 waves), _12W_1D (12 waves, 1-D transform), _12W (the same kernel with the
+// transform nested in y) or _PRODUCER (the y-nested transform with the staging on four producer waves: 16 waves; the product)
 int pesr_conv3x3_wgrad_wino4_launch(const float* x, const float* dy, float* dw, float* db, int N, int H, int W, int Cin, int Cout,
                                     float alpha, int ps_in, int accumulate, int variant, void* ws, size_t ws_bytes, hipStream_t stream) {
     Wg4Plan p;
-    if (!wg4_plan(N, H, W, Cin, Cout, &p)) return PESR_EINVAL;
-    if (p.side > 1 && (variant == 0 || ps_in)) return PESR_EINVAL;     // side-by-side strips: the 32x32x2 kernel, plain gradients
+    if (variant < PESR_WGK_WINO4_16X16 || variant > PESR_WGK_WINO4_PRODUCER || !wg4_plan(N, H, W, Cin, Cout, &p)) return PESR_EINVAL;
+    if (p.side > 1 && (variant == PESR_WGK_WINO4_16X16 || ps_in)) return PESR_EINVAL;     // side-by-side strips: the 32x32x2 kernel, plain gradients
     if (!ws || ws_bytes < p.total_bytes) return PESR_EWORKSPACE;
     if (ps_in && Cout % 256) return PESR_EINVAL;
     Wg4Args a{};
@@ -1181,22 +1118,19 @@ int pesr_conv3x3_wgrad_wino4_launch(const float* x, const float* dy, float* dw, 
     constexpr size_t lds = (size_t)(G4_RING * G4_VROW + 4 * G4_DROW) * sizeof(float);
     static_assert(lds >= (size_t)9 * 64 * 32 * sizeof(float), "epilogue staging fits");
     static_assert(lds <= 160 * 1024, "wgrad-wino4 LDS budget");
+    constexpr size_t ldsx = (size_t)2 * 6 * 3 * 1024 * sizeof(float);      // the variant's G^T staging (144 KiB) = its eight-slot ring + dM buffers
+    static_assert(ldsx >= (size_t)(X4_RING * X4_VROW + 4 * X4_DROW) * sizeof(float) && ldsx <= 160 * 1024, "wgrad-wino4x LDS budget");
     static PesrDeviceOnce attr_once;
     attr_once([&] {
         (void)hipFuncSetAttribute((const void*)conv3x3_wgrad_wino4_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    });
-    constexpr size_t ldsx = (size_t)2 * 6 * 3 * 1024 * sizeof(float);      // the variant's G^T staging (144 KiB) = its eight-slot ring + dM buffers
-    static_assert(ldsx >= (size_t)(X4_RING * X4_VROW + 4 * X4_DROW) * sizeof(float) && ldsx <= 160 * 1024, "wgrad-wino4x LDS budget");
-    static PesrDeviceOnce attr_once_x;
-    attr_once_x([&] {
         (void)hipFuncSetAttribute((const void*)conv3x3_wgrad_wino4x_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         (void)hipFuncSetAttribute((const void*)conv3x3_wgrad_wino4x_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         (void)hipFuncSetAttribute((const void*)conv3x3_wgrad_wino4p_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     });
     const int grid = p.split * p.co_tiles * p.ci_tiles;
-    if (variant == 3) hipLaunchKernelGGL(conv3x3_wgrad_wino4p_kernel<true>, dim3(grid), dim3(P4_NT), ldsx, stream, a);
-    else if (variant == 2) hipLaunchKernelGGL(conv3x3_wgrad_wino4x_kernel<true>, dim3(grid), dim3(X4_NT), ldsx, stream, a);
-    else if (variant == 1) hipLaunchKernelGGL(conv3x3_wgrad_wino4x_kernel<false>, dim3(grid), dim3(X4_NT), ldsx, stream, a);
+    if (variant == PESR_WGK_WINO4_PRODUCER) hipLaunchKernelGGL(conv3x3_wgrad_wino4p_kernel<true>, dim3(grid), dim3(P4_NT), ldsx, stream, a);
+    else if (variant == PESR_WGK_WINO4_12W) hipLaunchKernelGGL(conv3x3_wgrad_wino4x_kernel<true>, dim3(grid), dim3(X4_NT), ldsx, stream, a);
+    else if (variant == PESR_WGK_WINO4_12W_1D) hipLaunchKernelGGL(conv3x3_wgrad_wino4x_kernel<false>, dim3(grid), dim3(X4_NT), ldsx, stream, a);
     else hipLaunchKernelGGL(conv3x3_wgrad_wino4_kernel, dim3(grid), dim3(G4_NT), lds, stream, a);
     int rc = pesr_launch_status();
     if (rc) return rc;

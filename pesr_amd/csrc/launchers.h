@@ -29,6 +29,19 @@ int pesr_conv3x3_s2_dgrad_launch(const float* dy, const float* wp, const float* 
                                  int Cout_fwd, int Cin_fwd, float alpha, hipStream_t stream, PesrBnFuseArgs* fuse = nullptr);
 
 size_t pesr_conv3x3_wgrad_ws_bytes(int N, int H, int W, int Cin, int Cout, int stride, int algo);
+// The kernel a weight gradient runs on (include/pesr_hip.h PESR_WGRAD_KERNEL_*): the answer of pesr_conv3x3_wgrad_kernel_impl, the rule
+// pesr_conv3x3_wgrad_launch dispatches by, and (the four F(4,3) values) the `variant` of pesr_conv3x3_wgrad_wino4_launch.
+enum PesrWgradKernel {
+    PESR_WGK_DIRECT = 0,          // conv3x3_wgrad_kernel
+    PESR_WGK_WINO23 = 1,          // conv3x3_wgrad_wino_kernel
+    PESR_WGK_WINO4_16X16 = 2,     // conv3x3_wgrad_wino4_kernel: 16x16x4 MFMA, 8 waves, 1-D transform
+    PESR_WGK_WINO4_12W_1D = 3,    // conv3x3_wgrad_wino4x_kernel<false>: 32x32x2 MFMA, 12 waves, 1-D transform
+    PESR_WGK_WINO4_12W = 4,       // conv3x3_wgrad_wino4x_kernel<true>: the same kernel with the transform nested in y
+    PESR_WGK_WINO4_PRODUCER = 5   // conv3x3_wgrad_wino4p_kernel<true>: the y-nested transform, staging on four producer waves (the product)
+};
+// Host only.  A PesrWgradKernel, or the error the launch returns (PESR_EINVAL, PESR_EWORKSPACE).  ws_bytes: the caller's workspace (a Winograd form that
+// needs more than it is passed over, as the launch always did); a query passes SIZE_MAX.
+int pesr_conv3x3_wgrad_kernel_impl(int N, int H, int W, int Cin, int Cout, int stride, int ps_in, int algo, int accumulate, size_t ws_bytes);
 int pesr_conv3x3_wgrad_launch(const float* x, const float* dy, float* dw, float* db, int N, int H, int W, int Cin, int Cout,
                               int stride, float alpha, int ps_in, int algo, int accumulate, void* ws, size_t ws_bytes, hipStream_t stream);
 int pesr_bias_grad_launch(const float* dy, float* db, long pixels, int Cout, int OW, float alpha, int ps_in, float* part,
@@ -105,8 +118,11 @@ int pesr_reduce_rows_launch(const float* part, double* dsum, int nb, int ncols, 
 // fixed-order split-K reduce of the direct wgrad kernel: slab [split][9][Cout][Cin] -> dw OIHW (+ bias partials -> db)
 int pesr_wgrad_reduce_launch(const float* slab, float* dw, int split, int Cout, int Cin, float alpha, int ps, const float* bias_part,
                              int bias_rows, float* db, int accumulate, hipStream_t stream);
-// transposed Winograd F(4,3) weight gradient (conv3x3_wgrad_wino4.hip); PESR_EINVAL for shapes it does not cover
+// transposed Winograd F(4,3) weight gradient (conv3x3_wgrad_wino4.hip); PESR_EINVAL for shapes it does not cover.  _side: images per
+// 12-x-tile strip of its plan (1; 2 .. 6 for rows shorter than a strip), 0 where the plan does not cover the shape.  variant: a
+// PESR_WGK_WINO4_* value.
 size_t pesr_conv3x3_wgrad_wino4_ws_bytes(int N, int H, int W, int Cin, int Cout);
+int pesr_conv3x3_wgrad_wino4_side_impl(int N, int H, int W, int Cin, int Cout);
 int pesr_conv3x3_wgrad_wino4_launch(const float* x, const float* dy, float* dw, float* db, int N, int H, int W, int Cin, int Cout,
                                     float alpha, int ps_in, int accumulate, int variant, void* ws, size_t ws_bytes, hipStream_t stream);
 // transposed Winograd weight gradient (conv3x3_wgrad_wino.hip); the launch returns PESR_EINVAL for shapes it does not cover

@@ -146,45 +146,46 @@ USE_WGRAD_WINO = os.environ.get("PESR_WGRAD_WINO", "1") != "0"
 USE_WGRAD_WINO4 = os.environ.get("PESR_WGRAD_WINO4", "1") != "0"   # =0: F(2,3) weight gradient instead of F(4,3)
 
 
+WGRAD_AUTO, WGRAD_DIRECT, WGRAD_WINO23, WGRAD_WINO4_16X16, WGRAD_WINO4_1D, WGRAD_WINO4_12W = 0, 1, 2, 3, 4, 5      # include/pesr_hip.h PESR_WGRAD_*
+# PESR_WGRAD_WINO4_16X16=1: round 2's 16x16x4-MFMA form of the F(4,3) weight gradient instead of the 32x32x2 form (A/B switch)
+USE_WGRAD_WINO4_16X16 = os.environ.get("PESR_WGRAD_WINO4_16X16", "0") == "1"
+# PESR_WGRAD_WINO4_1D=1: round 3's 1-D F(4,3) transform on the 32x32x2 kernel instead of the y-nested one (A/B switch)
+USE_WGRAD_WINO4_1D = os.environ.get("PESR_WGRAD_WINO4_1D", "0") == "1"
+# include/pesr_hip.h PESR_WGRAD_KERNEL_* (the answer of pesr_conv3x3_wgrad_kernel) -> (kernel name, fraction of the algorithmic flops it
+# issues on the matrix pipe, the key FLOPS.add files them under)
+_WGRAD_KERNELS = (("conv3x3_wgrad_kernel", 1.0, "direct"),
+                  ("conv3x3_wgrad_wino_kernel", 2.0 / 3.0, "F(2,3)"),
+                  ("conv3x3_wgrad_wino4_kernel", 0.5, "F(4,3)"),
+                  ("conv3x3_wgrad_wino4x_kernel", 0.5, "F(4,3)"),
+                  ("conv3x3_wgrad_wino4x_kernel", 1.0 / 3.0, "F(2,3)y x F(4,3)x"),
+                  ("conv3x3_wgrad_wino4p_kernel", 1.0 / 3.0, "F(2,3)y x F(4,3)x"))
+
+
+def _wgrad_algo():
+    """The `algo` argument the PESR_WGRAD_* / PESR_WINO4 switches ask for."""
+    if not USE_WGRAD_WINO:
+        return WGRAD_DIRECT
+    if not (USE_WINO4 and USE_WGRAD_WINO4):
+        return WGRAD_WINO23
+    return WGRAD_WINO4_16X16 if USE_WGRAD_WINO4_16X16 else (WGRAD_WINO4_1D if USE_WGRAD_WINO4_1D else WGRAD_AUTO)
+
+
+def _wgrad_kernel(N, H, W, Cin, Cout, stride, ps_in, algo, accumulate):
+    """The library's own answer: the _WGRAD_KERNELS row of the kernel pesr_conv3x3_wgrad runs for these arguments (the direct kernel's
+    row for a shape the call refuses)."""
+    return _WGRAD_KERNELS[max(0, _memo("pesr_conv3x3_wgrad_kernel", N, H, W, Cin, Cout, stride, int(ps_in), algo, int(accumulate)))]
+
+
 def _wg4_plan_ok(N, H, W, Cin, Cout):
-    """wg4_plan of csrc/conv3x3_wgrad_wino4.hip: (covered, images per strip)."""
-    if W % 4 or Cin % 64 or Cout % 64 or N < 1 or H < 1:
-        return False, 1
-    xtw, segs_y, side = W // 4, (H + 1) // 2, 1
-    if W < 48:
-        if xtw < 2 or 12 % xtw:
-            return False, 1
-        side = 12 // xtw
-        groups = (N + side - 1) // side
-        if groups * 12 * 8 > N * xtw * 9 or side * H * W * max(Cin, Cout) * 4 >= 1 << 31:
-            return False, side
-        total = groups * segs_y
-    else:
-        segs_x = (xtw + 11) // 12
-        if segs_x * 12 * 8 > xtw * 9:
-            return False, 1
-        total = N * segs_x * segs_y
-    tiles = (Cout // 64) * (Cin // 32)
-    split = max(1, min((256 + tiles - 1) // tiles, total))
-    sps = (total + split - 1) // split
-    if sps > segs_y:
-        sps = (sps + segs_y - 1) // segs_y * segs_y
-    split = (total + sps - 1) // sps
-    return tiles * split >= 8, side
+    """wg4_plan of csrc/conv3x3_wgrad_wino4.hip, asked of the library: (covered, images per strip)."""
+    side = _memo("pesr_conv3x3_wgrad_wino4_side", N, H, W, Cin, Cout)
+    return side > 0, max(side, 1)
 
 
 def wgrad_kernel_for(N, H, W, Cin, Cout):
-    """(kernel name, fraction of the algorithmic flops it issues on the matrix pipe) of the stride-1 weight gradient."""
-    if USE_WGRAD_WINO and Cin % 64 == 0 and Cout % 64 == 0:
-        if USE_WINO4 and USE_WGRAD_WINO4:
-            ok, side = _wg4_plan_ok(N, H, W, Cin, Cout)
-            if ok and side == 1 and USE_WGRAD_WINO4_16X16:
-                return "conv3x3_wgrad_wino4_kernel", 0.5
-            if ok and not USE_WGRAD_WINO4_16X16:     # (rows shorter than a strip - images side by side - exist on the 32x32x2 kernel only)
-                return ("conv3x3_wgrad_wino4x_kernel", 0.5) if USE_WGRAD_WINO4_1D else ("conv3x3_wgrad_wino4p_kernel", 1.0 / 3.0)
-        if W >= 48 and W % 2 == 0 and ((W // 2 + 23) // 24) * 24 * 8 <= (W // 2) * 9:
-            return "conv3x3_wgrad_wino_kernel", 2.0 / 3.0
-    return "conv3x3_wgrad_kernel", 1.0
+    """(kernel name, fraction of the algorithmic flops it issues on the matrix pipe) of the stride-1 weight gradient, as
+    conv3x3_wgrad dispatches it under the current switches (plain gradient, not accumulating)."""
+    return _wgrad_kernel(N, H, W, Cin, Cout, 1, False, _wgrad_algo(), False)[:2]
 
 
 def wino_eligible(N: int, H: int, W: int, Cin: int, Cout: int, stride: int = 1) -> bool:
@@ -565,13 +566,6 @@ def _out(t, shape, device):
     return torch.empty(shape, dtype=torch.float32, device=device)
 
 
-WGRAD_AUTO, WGRAD_DIRECT, WGRAD_WINO23, WGRAD_WINO4_16X16, WGRAD_WINO4_1D, WGRAD_WINO4_12W = 0, 1, 2, 3, 4, 5      # include/pesr_hip.h PESR_WGRAD_*
-# PESR_WGRAD_WINO4_16X16=1: round 2's 16x16x4-MFMA form of the F(4,3) weight gradient instead of the 32x32x2 form (A/B switch)
-USE_WGRAD_WINO4_16X16 = os.environ.get("PESR_WGRAD_WINO4_16X16", "0") == "1"
-# PESR_WGRAD_WINO4_1D=1: round 3's 1-D F(4,3) transform on the 32x32x2 kernel instead of the y-nested one (A/B switch)
-USE_WGRAD_WINO4_1D = os.environ.get("PESR_WGRAD_WINO4_1D", "0") == "1"
-
-
 def wgrad_bf16_eligible(N: int, H: int, W: int, Cin: int, Cout: int, stride: int = 1, ps_in: bool = False) -> bool:
     """PRECISION is "bf16" and the bf16 weight-gradient kernel covers the shape (and has at least ~one round of workgroups)."""
     if PRECISION != "bf16" or stride != 1 or W % 48 or Cin % 64 or Cout % 128 or (ps_in and Cout % 512):
@@ -619,8 +613,7 @@ def conv3x3_wgrad(x: torch.Tensor, dy: torch.Tensor, stride: int = 1, alpha: flo
         return conv3x3_wgrad_bf16(x, dy, alpha, want_bias, ps_in, dw_out, db_out, accumulate)
     L = _lib.lib()
     if algo is None:
-        algo = ((WGRAD_WINO4_16X16 if USE_WGRAD_WINO4_16X16 else (WGRAD_WINO4_1D if USE_WGRAD_WINO4_1D else WGRAD_AUTO))
-                if (USE_WINO4 and USE_WGRAD_WINO4) else 2) if USE_WGRAD_WINO else 1
+        algo = _wgrad_algo()
     nbytes = L.pesr_conv3x3_wgrad_workspace_bytes(N, H, W, Cin, cout, stride, algo)
     if nbytes == 0:
         raise _lib.PesrHipError(f"pesr_conv3x3_wgrad: unsupported shape Cin={Cin} Cout={cout} stride={stride}")
@@ -628,10 +621,7 @@ def conv3x3_wgrad(x: torch.Tensor, dy: torch.Tensor, stride: int = 1, alpha: flo
     dw = _out(dw_out, (cout, Cin, 3, 3), x.device)
     db = _out(db_out, (cout,), x.device) if want_bias else None
     if FLOPS.on:
-        name, frac = wgrad_kernel_for(N, H, W, Cin, cout) if (stride == 1 and algo != WGRAD_DIRECT) else ("conv3x3_wgrad_kernel", 1.0)
-        if algo == WGRAD_WINO23 and frac == 0.5:
-            frac = 2.0 / 3.0
-        label = next((f.label for f in (_WINO4, _WINO, _DIRECT) if f.frac == frac), "F(2,3)y x F(4,3)x")
+        _, frac, label = _wgrad_kernel(N, H, W, Cin, cout, stride, ps_in, algo, accumulate)
         FLOPS.add(18.0 * N * ((H - 1) // stride + 1) * ((W - 1) // stride + 1) * Cin * cout, frac, label)
     br = KERNEL_EVENTS.begin("wgrad", N, H, W, Cin, cout, stride)
     rc = L.pesr_conv3x3_wgrad(_p(x), _p(dy), _p(dw), _p(db), N, H, W, Cin, cout, stride, alpha, int(ps_in), algo, int(accumulate),
