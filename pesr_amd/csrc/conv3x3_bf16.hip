@@ -1,6 +1,6 @@
 // 3x3 convolution (stride 1; stride 2 forward) on the bf16 MFMA (v_mfma_f32_16x16x32_bf16), gfx950: the OPTIONAL reduced-precision mode.
 //
-// Same contract and fused epilogue as conv3x3_wino4.hip (reference nn.Conv2d(k=3, padding=1), model/basic.py:4-7, forward and -
+// The contract and fused epilogue of conv_epilogue.h (reference nn.Conv2d(k=3, padding=1), model/basic.py:4-7, forward and -
 // with mode-1 packed weights - input gradient): y = act(alpha * (conv + bias) [masked] + skip), fused PixelShuffle store / fused
 // pixel-unshuffle load.  Activations stay fp32 in HBM; BOTH operands of every product are rounded to bf16 (round to nearest
 // even) on their way into the matrix pipe and the products are accumulated in fp32.  That is a different arithmetic from the
@@ -22,9 +22,8 @@
 #include <mutex>
 #include "common.h"
 #include "launchers.h"
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+#include "conv_epilogue.h"
+#include "conv3x3_bf16_common.h"
 
 struct Bf16Args {
     const float* x;            // [N][H][W][Cin]
@@ -46,8 +45,6 @@ struct Bf16Args {
 
 constexpr int B16_STAGE_T = 6; // the staged halo is converted and stored after this tap (4 / 6 / 8 measured the same)
 constexpr int B16_FXD = 3;     // register sets of the pixel-fragment ring (2 measured the same)
-constexpr int B16_MG = 9;      // m-tiles of 16 pixels per workgroup
-constexpr int B16_PX = 96;     // LDS bytes per halo pixel: 64 of data + 32 of padding
 
 // WTC: the halo width TW + 2 as a compile-time constant (the tile shapes of the networks' layers), or 0 = a.WT at run time.  With it
 // a tap's LDS offset is an immediate of the ds_read, and the fragment reads need no address arithmetic inside the loop: with two
@@ -89,27 +86,15 @@ __device__ __forceinline__ void conv3x3_bf16_body(const Bf16Args& a) {
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int r = lane & 15, g = lane >> 4;
 
-    // blockIdx -> (pixel tile, n-tile).  Workgroups b and b + 8 share an XCD: give every XCD a contiguous range of logical tiles,
-    // n-tile fastest, so the workgroups that read the same pixels share an L2.
-    int b = blockIdx.x;
-    if ((gridDim.x & 7) == 0) b = (b & 7) * (gridDim.x >> 3) + (b >> 3);
-    int bid = b;
-    const int nt = bid % a.n_tiles;  bid /= a.n_tiles;
-    const int tx = bid % a.tiles_x;  bid /= a.tiles_x;
-    const int ty = bid % a.tiles_y;
-    const int img = bid / a.tiles_y;
-    const int gy0 = ty * a.TR, gx0 = tx * a.TW;
-    const int n0 = nt * BN;
+    const Bf16Wg wg = b16_decode_wg(a);                                 // blockIdx -> (pixel tile, n-tile), n-tiles of a pixel tile on one XCD
+    const int img = wg.img;
+    const int gy0 = wg.ty * a.TR, gx0 = wg.tx * a.TW;
+    const int n0 = wg.nt * BN;
     const int C32 = a.Cin >> 5;
 
     // ---- pixel-operand fragment offsets: lane (r, g) reads k-group g of pixel 16 i + r, shifted by the tap's column kx ---------
     int a_off[B16_MG];
-#pragma unroll
-    for (int i = 0; i < B16_MG; ++i) {
-        const int m = i * 16 + r;
-        const int trow = m / a.TW, tcol = m - trow * a.TW;
-        a_off[i] = (S * trow * WT + tcol) * B16_PX + g * 16;
-    }
+    b16_frag_offsets<S>(a_off, a.TW, WT, r, g);
 
     // ---- weight operand: this lane's 16 bytes of slab (tap, chunk), n-tile j.  A buffer load: the slab's offset is a SCALAR offset
     // and j a 1-KiB immediate, so a weight fetch costs the vector unit nothing but its issue slot (the packed weights are < 4 GB).
@@ -123,37 +108,13 @@ __device__ __forceinline__ void conv3x3_bf16_body(const Bf16Args& a) {
     };
 
     // ---- staging items: (halo pixel, 4-channel group q of 8) ---------------------------------------------------------------------
-    const float* const x_img = a.x + (size_t)img * a.H * a.W * a.Cin;
-    const int n_items = a.HT * WT * 8;
-    const int Cq = a.Cin >> 2;
     unsigned st_off[NU];
     int st_dst[NU];
-#pragma unroll
-    for (int u = 0; u < NU; ++u) {
-        const int it = tid + u * NT;
-        const int q = it & 7, px = it >> 3;
-        const int hrow = px / WT, slot = px - hrow * WT;
-        const int hcol = S == 2 ? (slot < WE ? 2 * slot : 2 * (slot - WE) + 1) : slot;      // LDS slot `slot` of the row holds halo column hcol
-        const int iy = S * gy0 - (CLS < 0 ? 1 : 0) + hrow, ix = S * gx0 - (CLS < 0 ? 1 : 0) + hcol;
-        const bool ok = it < n_items && iy >= 0 && iy < a.H && ix >= 0 && ix < a.W;
-        const int pix = a.ps_in ? ((2 * iy) * (2 * a.W) + 2 * ix) * Cq : (iy * a.W + ix) * a.Cin;
-        // out-of-image pixels are fetched beyond the buffer descriptor's range: the load returns zeros (images are < 2 GB)
-        st_off[u] = ok ? (unsigned)((pix + q * 4) * 4) : 0x80000000u;
-        st_dst[u] = (it < n_items ? px : a.HT * WT) * B16_PX + q * 8;     // items past the halo land in a dump pixel behind it
-    }
-    const __amdgpu_buffer_rsrc_t x_rsrc =
-        __builtin_amdgcn_make_buffer_rsrc((void*)x_img, 0, (unsigned)((size_t)a.H * a.W * a.Cin * 4), 0x00020000);
-    auto chunk_off = [&](int cc) -> int {                  // channel part of an input address (bytes)
-        int coff = cc * 32;
-        if (a.ps_in) {   // chunk = channels [32cc, 32cc+32) of sub-pixel `sub`: one pixel of the shuffled tensor
-            const int sub = coff / Cq, cc0 = coff - sub * Cq;
-            coff = ((sub >> 1) * (2 * a.W) + (sub & 1)) * Cq + cc0;
-        }
-        return coff * 4;
-    };
+    b16_stage_items<S, CLS, NU, NT>(a, WT, tid, gy0, gx0, st_off, st_dst);
+    const __amdgpu_buffer_rsrc_t x_rsrc = b16_x_rsrc(a, img);
     u32x4 sx[NU];
     auto stage_load = [&](int cc) {
-        const int so = __builtin_amdgcn_readfirstlane(chunk_off(cc));
+        const int so = __builtin_amdgcn_readfirstlane(b16_chunk_off(a, cc));
 #pragma unroll
         for (int u = 0; u < NU; ++u) sx[u] = __builtin_amdgcn_raw_buffer_load_b128(x_rsrc, st_off[u], so, 0);
     };
@@ -256,13 +217,8 @@ __device__ __forceinline__ void conv3x3_bf16_body(const Bf16Args& a) {
                 const int trow = m / a.TW, tcol = m - trow * a.TW;
                 const int oy = CLS < 0 ? gy0 + trow : 2 * (gy0 + trow) + PY, ox = CLS < 0 ? gx0 + tcol : 2 * (gx0 + tcol) + PX;
                 ok[e] = oy < a.OH && ox < a.OW;
-                if (a.ps) {   // packed channel co = (2*si+sj)*C + c  ->  out[n][2*oy+si][2*ox+sj][c]
-                    const int C = a.Cout >> 2;
-                    const int sub = co / C, cc = co - sub * C;
-                    idx[e] = (((size_t)img * (2 * a.OH) + 2 * oy + (sub >> 1)) * (2 * a.OW) + 2 * ox + (sub & 1)) * C + cc;
-                } else {
-                    idx[e] = (img_out + (size_t)oy * a.OW + ox) * a.Cout + co;
-                }
+                if (a.ps) idx[e] = pesr_ps_out_index(img, oy, ox, co, a.OH, a.OW, a.Cout);
+                else idx[e] = (img_out + (size_t)oy * a.OW + ox) * a.Cout + co;
                 if (!ok[e]) idx[e] = 0;
                 if (a.mask) mkv[e] = *(const f32x4*)(a.mask + idx[e]);
                 if (a.skip) skv[e] = *(const f32x4*)(a.skip + idx[e]);
@@ -270,21 +226,8 @@ __device__ __forceinline__ void conv3x3_bf16_body(const Bf16Args& a) {
 #pragma unroll
             for (int e = 0; e < 3; ++e) {
                 if (!ok[e]) continue;
-                f32x4 o = acc[j][ib + e];
-                if (a.bias) o += bias4;
-                o *= a.alpha;
-                if (a.mask) {
-                    const f32x4 mk = mkv[e];
-                    o.x = mk.x > 0.f ? o.x : 0.f; o.y = mk.y > 0.f ? o.y : 0.f; o.z = mk.z > 0.f ? o.z : 0.f; o.w = mk.w > 0.f ? o.w : 0.f;
-                }
-                if (a.skip) o += skv[e];
-                if (a.act == PESR_ACT_RELU) {
-                    o.x = o.x > 0.f ? o.x : 0.f; o.y = o.y > 0.f ? o.y : 0.f; o.z = o.z > 0.f ? o.z : 0.f; o.w = o.w > 0.f ? o.w : 0.f;
-                } else if (a.act == PESR_ACT_LRELU) {
-                    o.x = o.x > 0.f ? o.x : o.x * a.slope; o.y = o.y > 0.f ? o.y : o.y * a.slope;
-                    o.z = o.z > 0.f ? o.z : o.z * a.slope; o.w = o.w > 0.f ? o.w : o.w * a.slope;
-                }
-                *(f32x4*)(a.y + idx[e]) = o;
+                *(f32x4*)(a.y + idx[e]) = pesr_epi4(acc[j][ib + e], a.bias != nullptr, bias4, a.alpha, a.mask != nullptr, mkv[e],
+                                                    a.skip != nullptr, skv[e], a.act, a.slope);
             }
         }
     }
@@ -307,25 +250,11 @@ __global__ __launch_bounds__(NW * 64) void conv3x3_bf16_s2_dgrad_kernel(const Bf
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
-// weight packing: OIHW fp32 -> [9][R/32][Nn][32] bf16 (round to nearest even)
-//   mode 0 (forward): out[t][c][n][k] = w[o = unperm(n)][i = 32c + k][t]
-//   mode 1 (dgrad)  : out[t][c][n][k] = w[o = unperm(32c + k)][i = n][8 - t]   (the input gradient is the conv with the flipped kernel)
-// ps = 1: the conv feeds nn.PixelShuffle(2); its output channels are ordered sub-pixel-major like pack.hip does.
+// weight packing: OIHW fp32 -> [9][R/32][Nn][32] bf16 (round to nearest even), in the order of pesr_bf16_pack_src (conv3x3_bf16_common.h)
 __global__ void pack_bf16_kernel(const float* __restrict__ w, __bf16* __restrict__ out, int O, int I, int mode, int ps) {
-    const int R = mode == 0 ? I : O, Nn = mode == 0 ? O : I;
-    const long total = 9L * R * Nn;
-    for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
-        const int k = (int)(e & 31);
-        long rest = e >> 5;
-        const int n = (int)(rest % Nn); rest /= Nn;
-        const int c = (int)(rest % (R >> 5));
-        const int t = (int)(rest / (R >> 5));
-        const int red = c * 32 + k;
-        int o = mode == 0 ? n : red;
-        const int i = mode == 0 ? red : n;
-        if (ps) { const int C = O >> 2; const int sub = o / C, cc = o - sub * C; o = 4 * cc + sub; }
-        out[e] = (__bf16)w[((long)o * I + i) * 9 + (mode == 0 ? t : 8 - t)];
-    }
+    const long total = 9L * O * I;
+    for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x)
+        out[e] = (__bf16)w[pesr_bf16_pack_src(e, O, I, mode, ps)];
 }
 
 int pesr_pack_conv3x3_bf16_launch(const float* w, void* out, int O, int I, int mode, int ps, hipStream_t stream) {
@@ -337,93 +266,55 @@ int pesr_pack_conv3x3_bf16_launch(const float* w, void* out, int O, int I, int m
 }
 
 namespace {
-struct B16Plan { int TR, TW, HT, WT, tiles_x, tiles_y, n_tiles, ntw, bn; long tiles; size_t lds; int score; };
-
 // Tile shape TR x TW == 144 pixels with the least out-of-image area whose halo fits the four staging items per thread.
-static bool b16_plan(int N, int H, int W, int Cin, int Cout, B16Plan* p, int min_wgs = 128) {
+static bool b16_plan(int N, int H, int W, int Cin, int Cout, Bf16Plan* p, int min_wgs = 128) {
     if (N < 1 || H < 1 || W < 1 || Cin % 32 || Cin < 32 || Cout % 64) return false;
     if ((size_t)H * W * Cin * 4 >= ((size_t)1 << 31)) return false;   // one image per buffer descriptor, offsets below 2^31
-    long best = -1;
-    for (int TW = 1; TW <= 144; ++TW) {
-        if (144 % TW) continue;
-        const int TR = 144 / TW, HT = TR + 2, WT = TW + 2;
-        if (HT * WT * 8 > 2048) continue;                    // NU * NT staging items
-        const long cover = (long)pesr_cdiv(H, TR) * TR * pesr_cdiv(W, TW) * TW;
-        // least waste first; then m-tiles that stay inside one row (conflict-free fragment reads); then the smallest halo
-        const long score = cover * 8192 + (TW % 16 ? 4096 : 0) + (long)HT * WT;
-        if (best < 0 || score < best) { best = score; p->TR = TR; p->TW = TW; }
-    }
-    if (best < 0) return false;
-    p->HT = p->TR + 2; p->WT = p->TW + 2;
-    p->tiles_y = pesr_cdiv(H, p->TR); p->tiles_x = pesr_cdiv(W, p->TW);
+    if (!b16_pick_tile(H, W, B16_HALO_S1, 2048, p)) return false;
     // 256 output channels per workgroup unless that leaves fewer than 128 workgroups (the 12^2 / 24^2 layers): then 128 each
     p->ntw = (Cout % 256 == 0 && (long)N * p->tiles_y * p->tiles_x * (Cout / 256) >= 128) ? 2 : 1;
     p->bn = Cout % 128 == 0 ? 128 * p->ntw : 64;              // 64: the four-wave workgroups
     p->n_tiles = Cout / p->bn;
     p->tiles = (long)N * p->tiles_y * p->tiles_x * p->n_tiles;
     p->lds = (size_t)2 * (p->HT * p->WT + 1) * B16_PX;
-    const double cover_eff = (double)H * W / ((double)p->tiles_y * p->TR * p->tiles_x * p->TW);
-    p->score = p->tiles >= min_wgs ? (int)(1000.0 * cover_eff) : 0;
+    p->score = p->tiles >= min_wgs ? b16_cover_permille(H, W, p) : 0;
     return true;
 }
 // Stride 2 (forward only): TR x TW == 144 OUTPUT pixels whose (2 TR + 1) x (2 TW + 1) halo fits the ten staging items per thread;
 // 128 output channels per eight-wave workgroup (64: four waves).  These layers are small (the Discriminator's 24^2 / 12^2 outputs
 // give 128 / 64 workgroups) and the fp32 alternative is the small-tile direct kernel: half of min_wgs is already worth the switch.
-static bool b16_plan_s2(int N, int H, int W, int Cin, int Cout, B16Plan* p, int min_wgs = 128) {
+static bool b16_plan_s2(int N, int H, int W, int Cin, int Cout, Bf16Plan* p, int min_wgs = 128) {
     if (N < 1 || H < 2 || W < 2 || Cin % 32 || Cin < 32 || Cout % 64) return false;
     if ((size_t)H * W * Cin * 4 >= ((size_t)1 << 31)) return false;
     const int OH = (H - 1) / 2 + 1, OW = (W - 1) / 2 + 1;
-    long best = -1;
-    for (int TW = 1; TW <= 144; ++TW) {
-        if (144 % TW) continue;
-        const int TR = 144 / TW, HT = 2 * TR + 1, WT = 2 * TW + 1;
-        if (HT * WT * 8 > 5120) continue;
-        const long cover = (long)pesr_cdiv(OH, TR) * TR * pesr_cdiv(OW, TW) * TW;
-        const long score = cover * 8192 + (TW % 16 ? 4096 : 0) + (long)HT * WT;
-        if (best < 0 || score < best) { best = score; p->TR = TR; p->TW = TW; }
-    }
-    if (best < 0) return false;
-    p->HT = 2 * p->TR + 1; p->WT = 2 * p->TW + 1;
+    if (!b16_pick_tile(OH, OW, B16_HALO_S2, 5120, p)) return false;
     p->ntw = 1;
     p->bn = Cout % 128 == 0 ? 128 : 64;
-    p->tiles_y = pesr_cdiv(OH, p->TR); p->tiles_x = pesr_cdiv(OW, p->TW); p->n_tiles = Cout / p->bn;
+    p->n_tiles = Cout / p->bn;
     p->tiles = (long)N * p->tiles_y * p->tiles_x * p->n_tiles;
     p->lds = (size_t)2 * (p->HT * p->WT + 1) * B16_PX;
-    const double cover_eff = (double)OH * OW / ((double)p->tiles_y * p->TR * p->tiles_x * p->TW);
-    p->score = p->tiles >= (min_wgs + 1) / 2 ? (int)(1000.0 * cover_eff) : 0;
+    p->score = p->tiles >= (min_wgs + 1) / 2 ? b16_cover_permille(OH, OW, p) : 0;
     return true;
 }
 // Stride-2 input gradient (four parity classes over dy [N][DH][DW][Cin]; Cout = the forward conv's input channels): TR x TW == 144
 // dy positions per tile, (TR + 1) x (TW + 1) halo; blockIdx.y = class.
-static bool b16_plan_s2d(int N, int DH, int DW, int Cin, int Cout, B16Plan* p, int min_wgs = 128) {
+static bool b16_plan_s2d(int N, int DH, int DW, int Cin, int Cout, Bf16Plan* p, int min_wgs = 128) {
     if (N < 1 || DH < 1 || DW < 1 || Cin % 32 || Cin < 32 || Cout % 64) return false;
     if ((size_t)DH * DW * Cin * 4 >= ((size_t)1 << 31)) return false;
-    long best = -1;
-    for (int TW = 1; TW <= 144; ++TW) {
-        if (144 % TW) continue;
-        const int TR = 144 / TW, HT = TR + 1, WT = TW + 1;
-        if (HT * WT * 8 > 2048) continue;
-        const long cover = (long)pesr_cdiv(DH, TR) * TR * pesr_cdiv(DW, TW) * TW;
-        const long score = cover * 8192 + (TW % 16 ? 4096 : 0) + (long)HT * WT;
-        if (best < 0 || score < best) { best = score; p->TR = TR; p->TW = TW; }
-    }
-    if (best < 0) return false;
-    p->HT = p->TR + 1; p->WT = p->TW + 1;
-    p->tiles_y = pesr_cdiv(DH, p->TR); p->tiles_x = pesr_cdiv(DW, p->TW);
+    if (!b16_pick_tile(DH, DW, B16_HALO_S2D, 2048, p)) return false;
     p->ntw = (Cout % 256 == 0 && (long)N * p->tiles_y * p->tiles_x * (Cout / 256) * 4 >= 128) ? 2 : 1;
     p->bn = Cout % 128 == 0 ? 128 * p->ntw : 64;
     p->n_tiles = Cout / p->bn;
     p->tiles = (long)N * p->tiles_y * p->tiles_x * p->n_tiles;       // per class
     p->lds = (size_t)2 * (p->HT * p->WT + 1) * B16_PX;
-    const double cover_eff = (double)DH * DW / ((double)p->tiles_y * p->TR * p->tiles_x * p->TW);
-    p->score = 4 * p->tiles >= min_wgs ? (int)(1000.0 * cover_eff) : 0;
+    p->score = 4 * p->tiles >= min_wgs ? b16_cover_permille(DH, DW, p) : 0;
     return true;
 }
 }  // namespace
 
 // per-mille of tile area inside the image (0: unsupported shape, or fewer than min_wgs workgroups: not worth leaving the fp32 kernels)
 int pesr_conv3x3_bf16_score_impl(int N, int H, int W, int Cin, int Cout, int min_wgs) {
-    B16Plan p;
+    Bf16Plan p;
     if (!b16_plan(N, H, W, Cin, Cout, &p, min_wgs)) return 0;
     return p.score;
 }
@@ -431,7 +322,7 @@ int pesr_conv3x3_bf16_score_impl(int N, int H, int W, int Cin, int Cout, int min
 int pesr_conv3x3_bf16_launch(const float* x, const void* wp, const float* bias, const float* skip, const float* mask, float* y,
                              int N, int H, int W, int Cin, int Cout, float alpha, int act, float slope, int ps, int ps_in,
                              hipStream_t stream) {
-    B16Plan p;
+    Bf16Plan p;
     if (!b16_plan(N, H, W, Cin, Cout, &p)) return PESR_EINVAL;
     if (ps && (Cout % (4 * p.bn) || skip || mask)) return PESR_EINVAL;          // an n-tile must stay inside one sub-pixel plane
     if (ps_in && Cin % 128) return PESR_EINVAL;                                 // a 32-channel chunk must stay inside one sub-pixel
@@ -458,14 +349,14 @@ int pesr_conv3x3_bf16_launch(const float* x, const void* wp, const float* bias, 
 
 // Stride-2 forward (input [N][H][W][Cin] -> output [N][(H-1)/2+1][(W-1)/2+1][Cout]); same packed weights as the stride-1 forward.
 int pesr_conv3x3_bf16_s2_score_impl(int N, int H, int W, int Cin, int Cout, int min_wgs) {
-    B16Plan p;
+    Bf16Plan p;
     if (!b16_plan_s2(N, H, W, Cin, Cout, &p, min_wgs)) return 0;
     return p.score;
 }
 
 int pesr_conv3x3_bf16_s2_launch(const float* x, const void* wp, const float* bias, const float* skip, const float* mask, float* y,
                                 int N, int H, int W, int Cin, int Cout, float alpha, int act, float slope, hipStream_t stream) {
-    B16Plan p;
+    Bf16Plan p;
     if (!b16_plan_s2(N, H, W, Cin, Cout, &p)) return PESR_EINVAL;
     Bf16Args a{};
     a.x = x; a.wp = (const char*)wp; a.bias = bias; a.skip = skip; a.mask = mask; a.y = y;
@@ -489,14 +380,14 @@ int pesr_conv3x3_bf16_s2_launch(const float* x, const void* wp, const float* bia
 // Stride-2 input gradient: dy [N][DH][DW][Cout_fwd] (DH = (H-1)/2+1 ...) -> dx [N][H][W][Cin_fwd]; weights: mode-1 packing of the
 // forward weights [Cout_fwd][Cin_fwd][3][3] (the stride-1 input gradient's packing).  dx = alpha * grad [masked] + skip.
 int pesr_conv3x3_bf16_s2_dgrad_score_impl(int N, int H, int W, int Cout_fwd, int Cin_fwd, int min_wgs) {
-    B16Plan p;
+    Bf16Plan p;
     if (H < 1 || W < 1 || !b16_plan_s2d(N, (H - 1) / 2 + 1, (W - 1) / 2 + 1, Cout_fwd, Cin_fwd, &p, min_wgs)) return 0;
     return p.score;
 }
 
 int pesr_conv3x3_bf16_s2_dgrad_launch(const float* dy, const void* wp, const float* mask, const float* skip, float* dx, int N, int H, int W,
                                       int Cout_fwd, int Cin_fwd, float alpha, hipStream_t stream) {
-    B16Plan p;
+    Bf16Plan p;
     if (H < 1 || W < 1) return PESR_EINVAL;
     const int DH = (H - 1) / 2 + 1, DW = (W - 1) / 2 + 1;
     if (!b16_plan_s2d(N, DH, DW, Cout_fwd, Cin_fwd, &p)) return PESR_EINVAL;

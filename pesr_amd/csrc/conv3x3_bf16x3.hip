@@ -1,7 +1,7 @@
 // 3x3 stride-1 convolution on the bf16 MFMA with SPLIT operands (v_mfma_f32_16x16x32_bf16 x 3), gfx950: the OPTIONAL
 // "split-bf16" mode (SURVEY 8 f4 "bf16/split-bf16 MFMA"; never the default, never the headline row).
 //
-// Same contract and fused epilogue as conv3x3_wino4.hip / conv3x3_bf16.hip (reference nn.Conv2d(k=3, padding=1), model/basic.py:4-7,
+// The contract and fused epilogue of conv_epilogue.h, like conv3x3_wino4.hip / conv3x3_bf16.hip (reference nn.Conv2d(k=3, padding=1), model/basic.py:4-7,
 // forward and - with mode-1 packed weights - input gradient).  Every fp32 operand v is written as hi + lo with hi = bf16(v) and
 // lo = bf16(v - hi) (v - hi is exact in fp32), and a product a*b is replaced by THREE bf16 products, each exact in fp32, summed in
 // the fp32 accumulator smallest terms first:
@@ -22,9 +22,8 @@
 //   * 3 MFMAs per (tap, m-tile, n-tile): 16 cycles each, i.e. 3/16 of the direct fp32 MFMA's time and 3/8 of the F(4,3) kernel's.
 #include "common.h"
 #include "launchers.h"
-
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
+#include "conv_epilogue.h"
+#include "conv3x3_bf16_common.h"
 
 struct B3Args {
     const float* x;            // [N][H][W][Cin]
@@ -43,8 +42,8 @@ struct B3Args {
     int ps_in;                 // 1: x is a pixel-shuffled tensor read as its sub-pixel-major view
 };
 
-constexpr int B3_MG = 9;       // m-tiles of 16 pixels per workgroup
-constexpr int B3_PX = 96;      // LDS bytes per halo pixel and plane
+constexpr int B3_MG = B16_MG;  // m-tiles of 16 pixels per workgroup
+constexpr int B3_PX = B16_PX;  // LDS bytes per halo pixel and plane
 constexpr int B3_WD = 3;       // weight ring depth (taps)
 constexpr int B3_STAGE_T = 6;  // the staged halo is converted and stored after this tap
 
@@ -59,24 +58,14 @@ __global__ __launch_bounds__(512) void conv3x3_bf16x3_kernel(const B3Args a) {
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int r = lane & 15, g = lane >> 4;
 
-    int b = blockIdx.x;
-    if ((gridDim.x & 7) == 0) b = (b & 7) * (gridDim.x >> 3) + (b >> 3);     // n-tiles of a pixel tile on one XCD / L2
-    int bid = b;
-    const int nt = bid % a.n_tiles;  bid /= a.n_tiles;
-    const int tx = bid % a.tiles_x;  bid /= a.tiles_x;
-    const int ty = bid % a.tiles_y;
-    const int img = bid / a.tiles_y;
-    const int gy0 = ty * a.TR, gx0 = tx * a.TW;
-    const int n0 = nt * BN;
+    const Bf16Wg wg = b16_decode_wg(a);                                 // n-tiles of a pixel tile on one XCD / L2
+    const int img = wg.img;
+    const int gy0 = wg.ty * a.TR, gx0 = wg.tx * a.TW;
+    const int n0 = wg.nt * BN;
     const int C32 = a.Cin >> 5;
 
     int a_off[B3_MG];          // lane (r, g) reads k-group g of pixel 16 i + r
-#pragma unroll
-    for (int i = 0; i < B3_MG; ++i) {
-        const int m = i * 16 + r;
-        const int trow = m / a.TW, tcol = m - trow * a.TW;
-        a_off[i] = (trow * WT + tcol) * B3_PX + g * 16;
-    }
+    b16_frag_offsets<1>(a_off, a.TW, WT, r, g);
 
     // weights: this lane's 16 bytes of slab (plane, tap, chunk), n-tile j: scalar slab offset + 1-KiB immediate per n-tile
     const int slab_bytes = a.Cout * 64;
@@ -89,35 +78,13 @@ __global__ __launch_bounds__(512) void conv3x3_bf16x3_kernel(const B3Args a) {
     };
 
     // staging items: (halo pixel, 4-channel group q of 8)
-    const float* const x_img = a.x + (size_t)img * a.H * a.W * a.Cin;
-    const int n_items = a.HT * WT * 8;
-    const int Cq = a.Cin >> 2;
     unsigned st_off[NU];
     int st_dst[NU];
-#pragma unroll
-    for (int u = 0; u < NU; ++u) {
-        const int it = tid + u * NT;
-        const int q = it & 7, px = it >> 3;
-        const int hrow = px / WT, hcol = px - hrow * WT;
-        const int iy = gy0 - 1 + hrow, ix = gx0 - 1 + hcol;
-        const bool ok = it < n_items && iy >= 0 && iy < a.H && ix >= 0 && ix < a.W;
-        const int pix = a.ps_in ? ((2 * iy) * (2 * a.W) + 2 * ix) * Cq : (iy * a.W + ix) * a.Cin;
-        st_off[u] = ok ? (unsigned)((pix + q * 4) * 4) : 0x80000000u;      // beyond the descriptor: the load returns zeros
-        st_dst[u] = (it < n_items ? px : a.HT * WT) * B3_PX + q * 8;        // items past the halo land in the dump pixel
-    }
-    const __amdgpu_buffer_rsrc_t x_rsrc =
-        __builtin_amdgcn_make_buffer_rsrc((void*)x_img, 0, (unsigned)((size_t)a.H * a.W * a.Cin * 4), 0x00020000);
-    auto chunk_off = [&](int cc) -> int {
-        int coff = cc * 32;
-        if (a.ps_in) {
-            const int sub = coff / Cq, cc0 = coff - sub * Cq;
-            coff = ((sub >> 1) * (2 * a.W) + (sub & 1)) * Cq + cc0;
-        }
-        return coff * 4;
-    };
+    b16_stage_items<1, -1, NU, NT>(a, WT, tid, gy0, gx0, st_off, st_dst);
+    const __amdgpu_buffer_rsrc_t x_rsrc = b16_x_rsrc(a, img);
     u32x4 sx[NU];
     auto stage_load = [&](int cc) {
-        const int so = __builtin_amdgcn_readfirstlane(chunk_off(cc));
+        const int so = __builtin_amdgcn_readfirstlane(b16_chunk_off(a, cc));
 #pragma unroll
         for (int u = 0; u < NU; ++u) sx[u] = __builtin_amdgcn_raw_buffer_load_b128(x_rsrc, st_off[u], so, 0);
     };
@@ -231,13 +198,8 @@ __global__ __launch_bounds__(512) void conv3x3_bf16x3_kernel(const B3Args a) {
                 const int trow = m / a.TW, tcol = m - trow * a.TW;
                 const int oy = gy0 + trow, ox = gx0 + tcol;
                 ok[e] = oy < a.H && ox < a.W;
-                if (a.ps) {   // packed channel co = (2*si+sj)*C + c  ->  out[n][2*oy+si][2*ox+sj][c]
-                    const int C = a.Cout >> 2;
-                    const int sub = co / C, cc = co - sub * C;
-                    idx[e] = (((size_t)img * (2 * a.H) + 2 * oy + (sub >> 1)) * (2 * a.W) + 2 * ox + (sub & 1)) * C + cc;
-                } else {
-                    idx[e] = (img_out + (size_t)oy * a.W + ox) * a.Cout + co;
-                }
+                if (a.ps) idx[e] = pesr_ps_out_index(img, oy, ox, co, a.H, a.W, a.Cout);
+                else idx[e] = (img_out + (size_t)oy * a.W + ox) * a.Cout + co;
                 if (!ok[e]) idx[e] = 0;
                 if (a.mask) mkv[e] = *(const f32x4*)(a.mask + idx[e]);
                 if (a.skip) skv[e] = *(const f32x4*)(a.skip + idx[e]);
@@ -245,29 +207,16 @@ __global__ __launch_bounds__(512) void conv3x3_bf16x3_kernel(const B3Args a) {
 #pragma unroll
             for (int e = 0; e < 3; ++e) {
                 if (!ok[e]) continue;
-                f32x4 o = acc[j][ib + e];
-                if (a.bias) o += bias4;
-                o *= a.alpha;
-                if (a.mask) {
-                    const f32x4 mk = mkv[e];
-                    o.x = mk.x > 0.f ? o.x : 0.f; o.y = mk.y > 0.f ? o.y : 0.f; o.z = mk.z > 0.f ? o.z : 0.f; o.w = mk.w > 0.f ? o.w : 0.f;
-                }
-                if (a.skip) o += skv[e];
-                if (a.act == PESR_ACT_RELU) {
-                    o.x = o.x > 0.f ? o.x : 0.f; o.y = o.y > 0.f ? o.y : 0.f; o.z = o.z > 0.f ? o.z : 0.f; o.w = o.w > 0.f ? o.w : 0.f;
-                } else if (a.act == PESR_ACT_LRELU) {
-                    o.x = o.x > 0.f ? o.x : o.x * a.slope; o.y = o.y > 0.f ? o.y : o.y * a.slope;
-                    o.z = o.z > 0.f ? o.z : o.z * a.slope; o.w = o.w > 0.f ? o.w : o.w * a.slope;
-                }
-                *(f32x4*)(a.y + idx[e]) = o;
+                *(f32x4*)(a.y + idx[e]) = pesr_epi4(acc[j][ib + e], a.bias != nullptr, bias4, a.alpha, a.mask != nullptr, mkv[e],
+                                                    a.skip != nullptr, skv[e], a.act, a.slope);
             }
         }
     }
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
-// weight packing: OIHW fp32 -> [2 (hi, lo)][9][R/32][Nn][32] bf16; hi = bf16(w), lo = bf16(w - hi)
-//   mode 0 (forward): out[p][t][c][n][k] from w[o = unperm(n)][i = 32c + k][t];  mode 1 (dgrad): w[o = unperm(32c + k)][i = n][8 - t]
+// weight packing: OIHW fp32 -> [2 (hi, lo)][9][R/32][Nn][32] bf16; hi = bf16(w), lo = bf16(w - hi); both planes in the order of
+// pesr_bf16_pack_src (conv3x3_bf16_common.h)
 __device__ __forceinline__ void b3_split(float v, __bf16* hi, __bf16* lo) {
     const __bf16 h = (__bf16)v;
     *hi = h;
@@ -275,20 +224,9 @@ __device__ __forceinline__ void b3_split(float v, __bf16* hi, __bf16* lo) {
 }
 
 __global__ void pack_bf16x3_kernel(const float* __restrict__ w, __bf16* __restrict__ out, int O, int I, int mode, int ps) {
-    const int R = mode == 0 ? I : O, Nn = mode == 0 ? O : I;
-    const long total = 9L * R * Nn;
-    for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
-        const int k = (int)(e & 31);
-        long rest = e >> 5;
-        const int n = (int)(rest % Nn); rest /= Nn;
-        const int c = (int)(rest % (R >> 5));
-        const int t = (int)(rest / (R >> 5));
-        const int red = c * 32 + k;
-        int o = mode == 0 ? n : red;
-        const int i = mode == 0 ? red : n;
-        if (ps) { const int C = O >> 2; const int sub = o / C, cc = o - sub * C; o = 4 * cc + sub; }
-        b3_split(w[((long)o * I + i) * 9 + (mode == 0 ? t : 8 - t)], out + e, out + total + e);
-    }
+    const long total = 9L * O * I;
+    for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x)
+        b3_split(w[pesr_bf16_pack_src(e, O, I, mode, ps)], out + e, out + total + e);
 }
 
 int pesr_pack_conv3x3_bf16x3_launch(const float* w, void* out, int O, int I, int mode, int ps, hipStream_t stream) {
@@ -300,39 +238,25 @@ int pesr_pack_conv3x3_bf16x3_launch(const float* w, void* out, int O, int I, int
 }
 
 namespace {
-struct B3Plan { int TR, TW, HT, WT, tiles_x, tiles_y, n_tiles, ntw, bn; long tiles; size_t lds; int score; };
-
 // Tile shape TR x TW == 144 pixels with the least out-of-image area whose halo fits the four staging items per thread.
-static bool b3_plan(int N, int H, int W, int Cin, int Cout, B3Plan* p, int min_wgs = 128) {
+static bool b3_plan(int N, int H, int W, int Cin, int Cout, Bf16Plan* p, int min_wgs = 128) {
     if (N < 1 || H < 1 || W < 1 || Cin % 32 || Cin < 32 || Cout % 128) return false;
     if ((size_t)H * W * Cin * 4 >= ((size_t)1 << 31)) return false;   // one image per buffer descriptor, offsets below 2^31
-    long best = -1;
-    for (int TW = 1; TW <= 144; ++TW) {
-        if (144 % TW) continue;
-        const int TR = 144 / TW, HT = TR + 2, WT = TW + 2;
-        if (HT * WT * 8 > 2048) continue;
-        const long cover = (long)pesr_cdiv(H, TR) * TR * pesr_cdiv(W, TW) * TW;
-        const long score = cover * 8192 + (TW % 16 ? 4096 : 0) + (long)HT * WT;
-        if (best < 0 || score < best) { best = score; p->TR = TR; p->TW = TW; }
-    }
-    if (best < 0) return false;
-    p->HT = p->TR + 2; p->WT = p->TW + 2;
-    p->tiles_y = pesr_cdiv(H, p->TR); p->tiles_x = pesr_cdiv(W, p->TW);
+    if (!b16_pick_tile(H, W, B16_HALO_S1, 2048, p)) return false;
     // 256 output channels per workgroup unless that leaves fewer than 128 workgroups: then 128 each
     p->ntw = (Cout % 256 == 0 && (long)N * p->tiles_y * p->tiles_x * (Cout / 256) >= 128) ? 2 : 1;
     p->bn = 128 * p->ntw;
     p->n_tiles = Cout / p->bn;
     p->tiles = (long)N * p->tiles_y * p->tiles_x * p->n_tiles;
     p->lds = (size_t)4 * (p->HT * p->WT + 1) * B3_PX;          // two buffers x (hi, lo)
-    const double cover_eff = (double)H * W / ((double)p->tiles_y * p->TR * p->tiles_x * p->TW);
-    p->score = (p->tiles >= min_wgs && p->lds <= 160 * 1024) ? (int)(1000.0 * cover_eff) : 0;
+    p->score = (p->tiles >= min_wgs && p->lds <= 160 * 1024) ? b16_cover_permille(H, W, p) : 0;
     return true;
 }
 }  // namespace
 
 // per-mille of tile area inside the image (0: unsupported shape, or fewer than min_wgs workgroups)
 int pesr_conv3x3_bf16x3_score_impl(int N, int H, int W, int Cin, int Cout, int min_wgs) {
-    B3Plan p;
+    Bf16Plan p;
     if (!b3_plan(N, H, W, Cin, Cout, &p, min_wgs)) return 0;
     return p.score;
 }
@@ -340,7 +264,7 @@ int pesr_conv3x3_bf16x3_score_impl(int N, int H, int W, int Cin, int Cout, int m
 int pesr_conv3x3_bf16x3_launch(const float* x, const void* wp, const float* bias, const float* skip, const float* mask, float* y,
                                int N, int H, int W, int Cin, int Cout, float alpha, int act, float slope, int ps, int ps_in,
                                hipStream_t stream) {
-    B3Plan p;
+    Bf16Plan p;
     if (!b3_plan(N, H, W, Cin, Cout, &p, 1) || p.lds > 160 * 1024) return PESR_EINVAL;
     if (ps && (Cout % (4 * p.bn) || skip || mask)) return PESR_EINVAL;          // an n-tile must stay inside one sub-pixel plane
     if (ps_in && Cin % 128) return PESR_EINVAL;                                 // a 32-channel chunk must stay inside one sub-pixel

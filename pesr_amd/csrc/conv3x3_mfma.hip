@@ -22,6 +22,7 @@
 #include <mutex>
 #include "common.h"
 #include "launchers.h"
+#include "conv_epilogue.h"
 
 __device__ __attribute__((aligned(16))) const float g_zero16[4] = {0.f, 0.f, 0.f, 0.f};   // source of the zero padding for LDS-DMA
 
@@ -156,11 +157,7 @@ __device__ __forceinline__ void conv3x3_mfma_body(const ConvArgs& a, const int b
 
     auto load_halo = [&](int c) {
         int coff = (CB + c) * 16;
-        if (a.ps_in) {  // chunk c covers packed channels (2*si+sj)*C + cc0 .. +15
-            const int C = a.Cin >> 2;
-            const int sub = coff / C, cc0 = coff - sub * C;
-            coff = ((sub >> 1) * (2 * a.W) + (sub & 1)) * C + cc0;
-        }
+        if (a.ps_in) coff = pesr_ps_in_chunk_off(coff, a.Cin >> 2, a.W);  // chunk c covers packed channels (2*si+sj)*C + cc0 .. +15
         if (a.cin_real == 3) {  // RGB input: 3 floats per pixel, chunk 0 only, channels 3..15 are zero
 #pragma unroll
             for (int k = 0; k < HL; ++k) {
@@ -214,11 +211,7 @@ __device__ __forceinline__ void conv3x3_mfma_body(const ConvArgs& a, const int b
     };
     auto dma_halo = [&](int c, char* hb) {
         int coff = (CB + c) * 16;
-        if (a.ps_in) {
-            const int C = a.Cin >> 2;
-            const int sub = coff / C, cc0 = coff - sub * C;
-            coff = ((sub >> 1) * (2 * a.W) + (sub & 1)) * C + cc0;
-        }
+        if (a.ps_in) coff = pesr_ps_in_chunk_off(coff, a.Cin >> 2, a.W);
 #pragma unroll
         for (int k = 0; k < HL; ++k) {
             if (h_src[k] != -2) {
@@ -355,7 +348,7 @@ __device__ __forceinline__ void conv3x3_mfma_body(const ConvArgs& a, const int b
         const bool bn_on = bn_mode != 0;
         const float bn_slope = bn->slope;
         f32x4 st1 = {0.f, 0.f, 0.f, 0.f}, st2 = {0.f, 0.f, 0.f, 0.f};
-        f32x4 bmu = st1, bis = st1, bga = st1, bbe = st1;
+        PesrBnCoef4 bnk = pesr_bn_coef4_zero();
         // output element u = tid + k * NT of the tile -> (in range, element offset of its four channels)
         auto out_index = [&](int u, size_t* idx) -> bool {
             const int m = u / C4, c4 = u - m * C4;
@@ -364,10 +357,8 @@ __device__ __forceinline__ void conv3x3_mfma_body(const ConvArgs& a, const int b
             const int gy = gy0 + py, gx = gx0 + px;
             if (u >= MT * C4 || gy >= a.GH || gx >= a.GW || co >= a.cout_store) return false;
             const int oy = gy * a.out_my + a.out_ay, ox = gx * a.out_mx + a.out_ax;
-            if (a.ps) {   // packed channel co = (2*si+sj)*C + c  ->  out[n][2*oy+si][2*ox+sj][c]
-                const int C = a.Cout >> 2;
-                const int sub = co / C, cc = co - sub * C;
-                *idx = (((size_t)img * (2 * a.OH) + 2 * oy + (sub >> 1)) * (2 * a.OW) + 2 * ox + (sub & 1)) * C + cc;
+            if (a.ps) {
+                *idx = pesr_ps_out_index(img, oy, ox, co, a.OH, a.OW, a.Cout);
             } else {
                 *idx = (img_out + (size_t)oy * a.OW + ox) * a.cout_store + co;
             }
@@ -376,10 +367,7 @@ __device__ __forceinline__ void conv3x3_mfma_body(const ConvArgs& a, const int b
         f32x4 zpre[EIT];
         if (bn_mode == 2) {
             const int cq = n0 + (tid % C4) * 4;
-            if (cq < a.cout_store) {
-                bmu = *(const f32x4*)(bn->mi + cq); bis = *(const f32x4*)(bn->mi + a.cout_store + cq);
-                bga = *(const f32x4*)(bn->gamma + cq); bbe = *(const f32x4*)(bn->beta + cq);
-            }
+            if (cq < a.cout_store) bnk = pesr_bn_coef4_load(bn, a.cout_store, cq);
         }
 #pragma unroll
         for (int i = 0; i < WM; ++i)
@@ -412,12 +400,7 @@ __device__ __forceinline__ void conv3x3_mfma_body(const ConvArgs& a, const int b
                 size_t idx;
                 if (!out_index(u, &idx)) continue;
                 const int m = u / C4, c4 = u - m * C4;
-                f32x4 v = *(const f32x4*)(ob + m * RS + c4 * 16) * a.alpha;
-                const f32x4 xh = (zpre[k] - bmu) * bis;
-                const f32x4 zz = bga * xh + bbe;
-                v.x = zz.x > 0.f ? v.x : v.x * bn_slope; v.y = zz.y > 0.f ? v.y : v.y * bn_slope;
-                v.z = zz.z > 0.f ? v.z : v.z * bn_slope; v.w = zz.w > 0.f ? v.w : v.w * bn_slope;
-                st1 += v; st2 += v * xh;
+                const f32x4 v = pesr_bn_lrelu_grad4(*(const f32x4*)(ob + m * RS + c4 * 16) * a.alpha, zpre[k], bnk, bn_slope, st1, st2);
                 *(f32x4*)(a.y + idx) = v;
             }
         } else {
@@ -431,19 +414,7 @@ __device__ __forceinline__ void conv3x3_mfma_body(const ConvArgs& a, const int b
                     *(f32x4*)(a.slab + slab_off + idx) = v;
                     continue;
                 }
-                if (a.bias) v += *(const f32x4*)(a.bias + co);
-                v *= a.alpha;
-                if (a.mask) {
-                    const f32x4 mk = *(const f32x4*)(a.mask + idx);
-                    v.x = mk.x > 0.f ? v.x : 0.f; v.y = mk.y > 0.f ? v.y : 0.f; v.z = mk.z > 0.f ? v.z : 0.f; v.w = mk.w > 0.f ? v.w : 0.f;
-                }
-                if (a.skip) v += *(const f32x4*)(a.skip + idx);
-                if (a.act == PESR_ACT_RELU) {
-                    v.x = v.x > 0.f ? v.x : 0.f; v.y = v.y > 0.f ? v.y : 0.f; v.z = v.z > 0.f ? v.z : 0.f; v.w = v.w > 0.f ? v.w : 0.f;
-                } else if (a.act == PESR_ACT_LRELU) {
-                    v.x = v.x > 0.f ? v.x : v.x * a.slope; v.y = v.y > 0.f ? v.y : v.y * a.slope;
-                    v.z = v.z > 0.f ? v.z : v.z * a.slope; v.w = v.w > 0.f ? v.w : v.w * a.slope;
-                }
+                v = pesr_epi4_at(v, a.bias, co, a.alpha, a.mask, a.skip, idx, a.act, a.slope);
                 if (bn_on) { st1 += v; st2 += v * v; }
                 *(f32x4*)(a.y + idx) = v;
             }
@@ -487,28 +458,16 @@ __device__ __forceinline__ void conv3x3_mfma_body(const ConvArgs& a, const int b
             for (int j = 0; j < WN; ++j) {
                 const int co = n0 + (wave_n * WN + j) * 16 + r;
                 if (co >= a.cout_store) continue;
-                float v = acc[i][j][jj];
-                v += bias_r[j];
-                v *= a.alpha;
                 size_t idx;
                 if (a.ksplit > 1) {   // raw partial sum; bias / scale / mask / skip / activation happen in the finish kernel
                     idx = (img_out + (size_t)oy * a.OW + ox) * a.cout_store + co;
                     a.slab[(size_t)ks * ((size_t)a.N * a.OH * a.OW * a.cout_store) + idx] = acc[i][j][jj];
                     continue;
                 }
-                if (a.ps) {
-                    // packed channel co = (2*si+sj)*C + c  ->  out[n][2*oy+si][2*ox+sj][c]
-                    const int C = a.Cout >> 2;
-                    const int sub = co / C, cc = co - sub * C;
-                    idx = (((size_t)img * (2 * a.OH) + 2 * oy + (sub >> 1)) * (2 * a.OW) + 2 * ox + (sub & 1)) * C + cc;
-                } else {
-                    idx = (img_out + (size_t)oy * a.OW + ox) * a.cout_store + co;
-                }
-                if (a.mask) v = a.mask[idx] > 0.f ? v : 0.f;
-                if (a.skip) v += a.skip[idx];
-                if (a.act == PESR_ACT_RELU) v = v > 0.f ? v : 0.f;
-                else if (a.act == PESR_ACT_LRELU) v = v > 0.f ? v : v * a.slope;
-                a.y[idx] = v;
+                if (a.ps) idx = pesr_ps_out_index(img, oy, ox, co, a.OH, a.OW, a.Cout);
+                else idx = (img_out + (size_t)oy * a.OW + ox) * a.cout_store + co;
+                // (the bias is in a register already, zero where there is none)
+                a.y[idx] = pesr_epi1_at(acc[i][j][jj] + bias_r[j], nullptr, 0, a.alpha, a.mask, a.skip, idx, a.act, a.slope);
             }
         }
     }
@@ -542,20 +501,14 @@ __global__ __launch_bounds__(WAVES_M* WAVES_N * 64) void conv3x3_s2dgrad4_kernel
     }
 }
 
-// y = act(alpha * (sum_ks slab[ks] + bias) [masked] + skip): fixed-order sum of the split-K partials + the epilogue
+// y = act(alpha * (sum_ks slab[ks] + bias) [masked] + skip): fixed-order sum of the split-K partials + the epilogue of conv_epilogue.h
 __global__ void conv_splitk_finish_kernel(const float* __restrict__ slab, const float* __restrict__ bias, const float* __restrict__ skip,
                                           const float* __restrict__ mask, float* __restrict__ y, long total, int C, int ksplit,
                                           float alpha, int act, float slope) {
     for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
         float v = slab[e];
         for (int k = 1; k < ksplit; ++k) v += slab[(size_t)k * total + e];
-        if (bias) v += bias[e % C];
-        v *= alpha;
-        if (mask) v = mask[e] > 0.f ? v : 0.f;
-        if (skip) v += skip[e];
-        if (act == PESR_ACT_RELU) v = v > 0.f ? v : 0.f;
-        else if (act == PESR_ACT_LRELU) v = v > 0.f ? v : v * slope;
-        y[e] = v;
+        y[e] = pesr_epi1_at(v, bias, bias ? e % C : 0, alpha, mask, skip, e, act, slope);
     }
 }
 // the same on 4 consecutive channels (C % 4 == 0): 16-byte loads, all ksplit partials of an element in flight together
@@ -571,20 +524,7 @@ __global__ void conv_splitk_finish4_kernel(const f32x4* __restrict__ slab, const
 #pragma unroll
         for (int k = 1; k < 8; ++k)
             if (k < ksplit) v += p[k];
-        if (bias) v += *(const f32x4*)(bias + (e * 4) % C);
-        v *= alpha;
-        if (mask) {
-            const f32x4 mk = mask[e];
-            v.x = mk.x > 0.f ? v.x : 0.f; v.y = mk.y > 0.f ? v.y : 0.f; v.z = mk.z > 0.f ? v.z : 0.f; v.w = mk.w > 0.f ? v.w : 0.f;
-        }
-        if (skip) v += skip[e];
-        if (act == PESR_ACT_RELU) {
-            v.x = v.x > 0.f ? v.x : 0.f; v.y = v.y > 0.f ? v.y : 0.f; v.z = v.z > 0.f ? v.z : 0.f; v.w = v.w > 0.f ? v.w : 0.f;
-        } else if (act == PESR_ACT_LRELU) {
-            v.x = v.x > 0.f ? v.x : v.x * slope; v.y = v.y > 0.f ? v.y : v.y * slope;
-            v.z = v.z > 0.f ? v.z : v.z * slope; v.w = v.w > 0.f ? v.w : v.w * slope;
-        }
-        y[e] = v;
+        y[e] = pesr_epi4_at(v, bias, (e * 4) % C, alpha, (const float*)mask, (const float*)skip, e * 4, act, slope);
     }
 }
 
@@ -599,11 +539,9 @@ __global__ __launch_bounds__(256) void conv_splitk_finish4_bn_kernel(const f32x4
                                                                       long total4, int C, int ksplit, float alpha, const BnEpi bn) {
     const int C4 = C >> 2;
     const int c4 = (int)(((long)blockIdx.x * 256 + threadIdx.x) % C4);            // (gridDim.x * 256) % C4 == 0: fixed over the walk
-    f32x4 st1 = {0.f, 0.f, 0.f, 0.f}, st2 = st1, bmu = st1, bis = st1, bga = st1, bbe = st1, b4 = st1;
-    if (MODE == 2) {
-        bmu = *(const f32x4*)(bn.mi + c4 * 4); bis = *(const f32x4*)(bn.mi + C + c4 * 4);
-        bga = *(const f32x4*)(bn.gamma + c4 * 4); bbe = *(const f32x4*)(bn.beta + c4 * 4);
-    }
+    f32x4 st1 = {0.f, 0.f, 0.f, 0.f}, st2 = st1, b4 = st1;
+    PesrBnCoef4 bnk = pesr_bn_coef4_zero();
+    if (MODE == 2) bnk = pesr_bn_coef4_load(&bn, C, c4 * 4);
     if (bias) b4 = *(const f32x4*)(bias + c4 * 4);
     for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < total4; e += (long)gridDim.x * 256) {
         f32x4 p[8];
@@ -616,11 +554,7 @@ __global__ __launch_bounds__(256) void conv_splitk_finish4_bn_kernel(const f32x4
             if (k < ksplit) v += p[k];
         v = (v + b4) * alpha;
         if (MODE == 2) {
-            const f32x4 xh = (((const f32x4*)bn.z)[e] - bmu) * bis;
-            const f32x4 zz = bga * xh + bbe;
-            v.x = zz.x > 0.f ? v.x : v.x * bn.slope; v.y = zz.y > 0.f ? v.y : v.y * bn.slope;
-            v.z = zz.z > 0.f ? v.z : v.z * bn.slope; v.w = zz.w > 0.f ? v.w : v.w * bn.slope;
-            st1 += v; st2 += v * xh;
+            v = pesr_bn_lrelu_grad4(v, ((const f32x4*)bn.z)[e], bnk, bn.slope, st1, st2);
         } else {
             st1 += v; st2 += v * v;
         }

@@ -1,6 +1,6 @@
 // 3x3 stride-1 convolution with a 1-D Winograd F(2,3) transform along x, on the fp32-input MFMA, gfx950.
 //
-// Same contract as conv3x3_mfma.hip (reference nn.Conv2d(k=3, padding=1), model/basic.py:4-7, forward and - with
+// Same contract as conv3x3_mfma.hip, the fused epilogue of conv_epilogue.h (reference nn.Conv2d(k=3, padding=1), model/basic.py:4-7, forward and - with
 // dgrad-transformed weights - input gradient) for even widths and Cout % 128 == 0, with 2/3 of the multiplies:
 // for an output pixel pair (2t, 2t+1) of a row and the input columns d0..d3 = x[2t-1 .. 2t+2],
 //     V  = [d0 - d2, d1 + d2, d2 - d1, d1 - d3]                        (input transform, per row and channel)
@@ -23,6 +23,7 @@
 #include <mutex>
 #include "common.h"
 #include "launchers.h"
+#include "conv_epilogue.h"
 #include "wino_pack.h"
 
 __device__ __attribute__((aligned(16))) const float g_wino_zero16[4] = {0.f, 0.f, 0.f, 0.f};
@@ -112,11 +113,7 @@ __global__ __launch_bounds__(WINO_NT) void conv3x3_wino_kernel(const WinoArgs a)
     }
     auto dma_raw = [&](int c) {
         int coff = (CB + c) * 16;
-        if (a.ps_in) {   // chunk c = channels [16c, 16c+16) of sub-pixel `sub`: one pixel of the shuffled tensor
-            const int C = a.Cin >> 2;
-            const int sub = coff / C, cc0 = coff - sub * C;
-            coff = ((sub >> 1) * (2 * a.W) + (sub & 1)) * C + cc0;
-        }
+        if (a.ps_in) coff = pesr_ps_in_chunk_off(coff, a.Cin >> 2, a.W);   // chunk c = channels [16c, 16c+16) of one sub-pixel
 #pragma unroll
         for (int k = 0; k < WINO_HL; ++k) {
             if (h_src[k] != -2) {
@@ -263,31 +260,13 @@ __global__ __launch_bounds__(WINO_NT) void conv3x3_wino_kernel(const WinoArgs a)
         if (oy >= a.H || ox >= a.W) continue;
         f32x4 v = *(const f32x4*)(ob + p * RS + c4 * 16);
         size_t idx;
-        if (a.ps) {   // packed channel co = (2*si+sj)*C + c  ->  out[n][2*oy+si][2*ox+sj][c]
-            const int C = a.Cout >> 2;
-            const int sub = co / C, cc = co - sub * C;
-            idx = (((size_t)img * (2 * a.H) + 2 * oy + (sub >> 1)) * (2 * a.W) + 2 * ox + (sub & 1)) * C + cc;
-        } else {
-            idx = (img_out + (size_t)oy * a.W + ox) * a.Cout + co;
-        }
+        if (a.ps) idx = pesr_ps_out_index(img, oy, ox, co, a.H, a.W, a.Cout);
+        else idx = (img_out + (size_t)oy * a.W + ox) * a.Cout + co;
         if (a.ksplit > 1) {   // raw partial sums; the finish kernel applies the epilogue
             *(f32x4*)(a.slab + (size_t)ks * ((size_t)a.N * a.H * a.W * a.Cout) + idx) = v;
             continue;
         }
-        if (a.bias) v += *(const f32x4*)(a.bias + co);
-        v *= a.alpha;
-        if (a.mask) {
-            const f32x4 mk = *(const f32x4*)(a.mask + idx);
-            v.x = mk.x > 0.f ? v.x : 0.f; v.y = mk.y > 0.f ? v.y : 0.f; v.z = mk.z > 0.f ? v.z : 0.f; v.w = mk.w > 0.f ? v.w : 0.f;
-        }
-        if (a.skip) v += *(const f32x4*)(a.skip + idx);
-        if (a.act == PESR_ACT_RELU) {
-            v.x = v.x > 0.f ? v.x : 0.f; v.y = v.y > 0.f ? v.y : 0.f; v.z = v.z > 0.f ? v.z : 0.f; v.w = v.w > 0.f ? v.w : 0.f;
-        } else if (a.act == PESR_ACT_LRELU) {
-            v.x = v.x > 0.f ? v.x : v.x * a.slope; v.y = v.y > 0.f ? v.y : v.y * a.slope;
-            v.z = v.z > 0.f ? v.z : v.z * a.slope; v.w = v.w > 0.f ? v.w : v.w * a.slope;
-        }
-        *(f32x4*)(a.y + idx) = v;
+        *(f32x4*)(a.y + idx) = pesr_epi4_at(v, a.bias, co, a.alpha, a.mask, a.skip, idx, a.act, a.slope);
     }
 }
 

@@ -1,6 +1,6 @@
 // 3x3 stride-1 convolution with a 1-D Winograd F(4,3) transform along x, on the fp32-input MFMA, gfx950.
 //
-// Same contract as conv3x3_mfma.hip / conv3x3_wino.hip (reference nn.Conv2d(k=3, padding=1), model/basic.py:4-7, forward
+// Same contract as conv3x3_mfma.hip / conv3x3_wino.hip, the fused epilogue of conv_epilogue.h (reference nn.Conv2d(k=3, padding=1), model/basic.py:4-7, forward
 // and - with dgrad-transformed weights - input gradient) for widths that are multiples of 4 and Cout % 64 == 0, with HALF of
 // the direct conv's multiplies (F(2,3): 2/3).  For an x-tile of four output pixels (4t .. 4t+3) of a row and the six input
 // columns d0..d5 = x[4t-1 .. 4t+4]  (interpolation points 0, +-1, +-2, inf):
@@ -28,6 +28,7 @@
 #include <mutex>
 #include "common.h"
 #include "launchers.h"
+#include "conv_epilogue.h"
 #include "wino4_pack.h"
 
 struct Wino4Args {
@@ -180,10 +181,7 @@ __global__ __launch_bounds__(512) void conv3x3_wino4_kernel(const Wino4Args a, c
         __builtin_amdgcn_make_buffer_rsrc((void*)x_img, 0, (unsigned)((size_t)(a.stack ? a.stack_n : 1) * a.H * a.W * a.Cin * 4), 0x00020000);
     auto chunk_off = [&](int cc) -> int {                  // channel part of an input address (bytes), chunk cc (absolute)
         int coff = cc * 16;
-        if (a.ps_in) {   // chunk = channels [16cc, 16cc+16) of sub-pixel `sub`: one pixel of the shuffled tensor
-            const int sub = coff / Cq, cc0 = coff - sub * Cq;
-            coff = ((sub >> 1) * (2 * a.W) + (sub & 1)) * Cq + cc0;
-        }
+        if (a.ps_in) coff = pesr_ps_in_chunk_off(coff, Cq, a.W);   // chunk = channels [16cc, 16cc+16) of one sub-pixel
         return coff * 4;
     };
     // The two items of a thread go through the SAME six staging registers one after the other: item 0 is loaded
@@ -342,10 +340,8 @@ __global__ __launch_bounds__(512) void conv3x3_wino4_kernel(const Wino4Args a, c
             ok = im < a.stack_n && yy < a.H && ox < a.W;
             oy = im * a.H + yy;
         }
-        if (a.ps) {   // packed channel co = (2*si+sj)*C + c  ->  out[n][2*oy+si][2*ox+sj][c]
-            const int C = a.Cout >> 2;
-            const int sub = co / C, cc = co - sub * C;
-            *idx = (((size_t)img * (2 * a.H) + 2 * oy + (sub >> 1)) * (2 * a.W) + 2 * ox + (sub & 1)) * C + cc;
+        if (a.ps) {
+            *idx = pesr_ps_out_index(img, oy, ox, co, a.H, a.W, a.Cout);
         } else {
             *idx = (img_out + (size_t)oy * a.W + ox) * a.Cout + co;
         }
@@ -372,11 +368,8 @@ __global__ __launch_bounds__(512) void conv3x3_wino4_kernel(const Wino4Args a, c
     const bool bn_on = BNF && bn_mode != 0;
     const float bn_slope = BNF ? bn->slope : 0.f;
     f32x4 st1 = {0.f, 0.f, 0.f, 0.f}, st2 = {0.f, 0.f, 0.f, 0.f};
-    f32x4 bmu = st1, bis = st1, bga = st1, bbe = st1;
-    if (BNF && bn_mode == 2) {
-        bmu = *(const f32x4*)(bn->mi + co); bis = *(const f32x4*)(bn->mi + a.Cout + co);
-        bga = *(const f32x4*)(bn->gamma + co); bbe = *(const f32x4*)(bn->beta + co);
-    }
+    PesrBnCoef4 bnk = pesr_bn_coef4_zero();
+    if (BNF && bn_mode == 2) bnk = pesr_bn_coef4_load(bn, a.Cout, co);
     // batches of three m-tiles x two outputs: a batch's LDS reads and skip / mask loads are issued before its first store.
     // (Round 4 measured the skip / mask loads issued ONE BATCH AHEAD, the first batch's in front of the exchange barrier: 175.9 vs
     // 172.6 us with bias + ReLU, 179.4 vs 177.1 with the skip, 179.0 vs 177.3 with the mask - slower in every form; and a PERSISTENT
@@ -409,26 +402,10 @@ __global__ __launch_bounds__(512) void conv3x3_wino4_kernel(const Wino4Args a, c
                 *(f32x4*)(a.slab + (size_t)ks * ((size_t)(a.stack ? a.stack_n : a.N) * a.H * a.W * a.Cout) + idx[e]) = o;
                 continue;
             }
-            if (a.bias) o += bias4;
-            o *= a.alpha;
-            if (a.mask) {
-                const f32x4 mk = mkv[e];
-                o.x = mk.x > 0.f ? o.x : 0.f; o.y = mk.y > 0.f ? o.y : 0.f; o.z = mk.z > 0.f ? o.z : 0.f; o.w = mk.w > 0.f ? o.w : 0.f;
-            }
-            if (a.skip) o += skv[e];
-            if (a.act == PESR_ACT_RELU) {
-                o.x = o.x > 0.f ? o.x : 0.f; o.y = o.y > 0.f ? o.y : 0.f; o.z = o.z > 0.f ? o.z : 0.f; o.w = o.w > 0.f ? o.w : 0.f;
-            } else if (a.act == PESR_ACT_LRELU) {
-                o.x = o.x > 0.f ? o.x : o.x * a.slope; o.y = o.y > 0.f ? o.y : o.y * a.slope;
-                o.z = o.z > 0.f ? o.z : o.z * a.slope; o.w = o.w > 0.f ? o.w : o.w * a.slope;
-            }
+            o = pesr_epi4(o, a.bias != nullptr, bias4, a.alpha, a.mask != nullptr, mkv[e], a.skip != nullptr, skv[e], a.act, a.slope);
             if (bn_on) {
                 if (bn_mode == 2) {
-                    const f32x4 xh = (zall[BNF ? ib * 2 + e : 0] - bmu) * bis;
-                    const f32x4 zz = bga * xh + bbe;
-                    o.x = zz.x > 0.f ? o.x : o.x * bn_slope; o.y = zz.y > 0.f ? o.y : o.y * bn_slope;
-                    o.z = zz.z > 0.f ? o.z : o.z * bn_slope; o.w = zz.w > 0.f ? o.w : o.w * bn_slope;
-                    st1 += o; st2 += o * xh;
+                    o = pesr_bn_lrelu_grad4(o, zall[BNF ? ib * 2 + e : 0], bnk, bn_slope, st1, st2);
                 } else {
                     st1 += o; st2 += o * o;
                 }
