@@ -217,7 +217,7 @@ class _OnSide:
     stream - makes the main stream wait for the side stream on exit (`fast=False`)."""
 
     def __init__(self, device, *tensors, fast=False, where="g"):
-        self.enabled = SIDE_MODE == "1" or SIDE_MODE == where
+        self.enabled = where is not None and (SIDE_MODE == "1" or SIDE_MODE == where)      # where=None: a node without a side stream
         self.fast, self.device = fast, device
         if self.enabled:
             if not _JOIN_QUEUED[0]:
@@ -323,6 +323,81 @@ def _c(t: torch.Tensor) -> torch.Tensor:
 
 
 # ------------------------------------------------------------------------------------------------
+# The routing of every 3x3 conv node: which kernel runs its forward, its input gradient and its weight gradient.  The nodes
+# below keep the bookkeeping that is their own (saved tensors, masks, needs_input_grad) and call these three.
+# ------------------------------------------------------------------------------------------------
+def _conv_fwd(x, weight, bias, cache, stride=1, **epilogue):
+    """y = epilogue(conv(x, weight) + bias); epilogue: act, slope, alpha, skip, mask of ops.conv3x3_fwd.  The pack is lazy (it is the
+    launch right before the kernel that reads it, and none when an RGB kernel runs on the OIHW weights)."""
+    return ops.conv3x3_fwd(x, lambda: cache.for_fwd(weight, x.shape, stride), cache.bias(bias), weight.shape[0], stride,
+                           ps_out=cache.ps, w_oihw=weight.detach(), **epilogue)
+
+
+def _conv_wgrad(x, gy, weight, bias_ref, stride, ps, want_w, want_b, *, alpha=1.0, where=None, again=None):
+    """(dw, db) of y = conv(x, weight) + bias: the RGB kernel where one side has three channels, else ops.conv3x3_wgrad; a parameter's
+    first gradient of the step is written into its flat-gradient view (grad_out; plain tensors have none).  where: the SIDE_MODE under
+    which this node's weight gradient runs on the side stream (None: never).  again: the (weight, bias) views _second_use returned -
+    the gradient is added to them on the current stream and autograd gets (None, None)."""
+    if not want_w:
+        return None, None
+    if again is not None:
+        (o_w, o_b), where = again, None
+        want_b = o_b is not None
+    else:
+        o_w, o_b = grad_out(weight), grad_out(bias_ref) if want_b else None
+    kw = dict(alpha=alpha, want_bias=want_b, dw_out=o_w, db_out=o_b, accumulate=again is not None)
+    side = ops.wgrad_rgb_side(x.shape[3], weight.shape[0])
+    with _OnSide(gy.device, x, gy, fast=o_w is not None and (o_b is not None or not want_b), where=where):
+        if side is None:
+            dw, db = ops.conv3x3_wgrad(x, gy, stride, ps_in=ps, **kw)
+        else:
+            dw, db = ops.conv3x3_wgrad_rgb(gy, x, 0, **kw) if side == 0 else ops.conv3x3_wgrad_rgb(x, gy, 1, **kw)
+    return (None, None) if again is not None else (dw, db)
+
+
+def _dgrad_pack(weight, cache, x_shape, stride, plain=True):
+    """The packed weights _conv_dgrad will run on, or None where one of the two HBM-bound RGB kernels runs on the OIHW weights: dx of a
+    C -> 3 conv is a 3 -> C conv of dy, dx of a 3 -> C conv a C -> 3 conv of dy (plain: no fused mask / skip / scale, which they lack).
+    Nodes that pack before their weight gradient (packing happens on the main stream) call this first and hand the result on."""
+    cin, cout = x_shape[3], weight.shape[0]
+    if plain and not cache.ps and (ops.rgb_in_eligible(cout, cin, stride) or ops.rgb_in_dgrad_eligible(cin, cout, stride)):
+        return None
+    return cache.for_dgrad(weight, x_shape, stride)
+
+
+_PACK_NOW = object()
+
+
+def _conv_dgrad(gy, weight, cache, x_shape, stride=1, *, mask=None, skip=None, alpha=1.0, prev_link=None, wpd=_PACK_NOW):
+    """dx = alpha * dgrad(gy) [masked by mask > 0] [+ skip].  prev_link: x is the output of a BatchNorm + LeakyReLU block (BnLink): where
+    the kernel can, it folds that block's backward reductions into its epilogue and leaves them in the link.  wpd: the answer of an
+    earlier _dgrad_pack."""
+    x_shape = tuple(x_shape)
+    if wpd is _PACK_NOW:
+        wpd = _dgrad_pack(weight, cache, x_shape, stride, mask is None and skip is None and alpha == 1.0)
+    if wpd is None:
+        return (ops.conv3x3_rgb_in_dgrad if x_shape[3] == 3 else ops.conv3x3_rgb_dgrad)(gy, weight.detach(), x_shape)
+    if prev_link is not None and prev_link.z is not None:
+        res = ops.conv3x3_dgrad_bn_sums(gy, wpd, x_shape, stride, prev_link.z, prev_link.stats, prev_link.gamma, prev_link.beta, prev_link.slope)
+        if res is not None:
+            dx, prev_link.part = res
+            prev_link.g_ptr = dx.data_ptr()
+            return dx
+    return ops.conv3x3_dgrad(gy, wpd, x_shape, stride, alpha=alpha, mask=mask, skip=skip, ps_in=cache.ps)
+
+
+def _second_use(params, allowed, grad_free):
+    """The SECOND use of a layer inside one backward pass (the Discriminator sees hr and sr in one graph, reference train.py:205-214) may
+    add its parameter gradients to the flat-gradient slices the first use wrote, so that autograd gets nothing to add: -> the claimed
+    views of `params`, or None when it may not.  allowed: the conditions of the calling node; grad_free: the parameters that must not
+    have a .grad yet.  See INPLACE_SECOND_USE for when the whole protocol is off."""
+    if not (INPLACE_SECOND_USE and allowed):
+        return None
+    views = [grad_out_again(p) for p in params]        # (None for a parameter that is no leaf, has no slice or has not claimed it)
+    return None if any(v is None for v in views) or any(p.grad is not None for p in grad_free) else views
+
+
+# ------------------------------------------------------------------------------------------------
 # generic 3x3 conv (+bias, +ReLU, fused PixelShuffle)          reference model/basic.py:4-7, 56-60
 # ------------------------------------------------------------------------------------------------
 class Conv3x3Fn(Function):
@@ -337,9 +412,7 @@ class Conv3x3Fn(Function):
     @staticmethod
     def forward(ctx, x, weight, bias, cache: PackedConvWeights, stride, act, relu_in, relu_grad_by_consumer):
         x = _c(x)
-        cout = weight.shape[0]
-        y = ops.conv3x3_fwd(x, lambda: cache.for_fwd(weight, x.shape, stride), cache.bias(bias), cout, stride, act=act, ps_out=cache.ps,
-                            w_oihw=weight.detach())
+        y = _conv_fwd(x, weight, bias, cache, stride, act=act)
         ctx.cache, ctx.stride, ctx.act, ctx.relu_in = cache, stride, act, relu_in
         ctx.mask_here = act == ops.ACT_RELU and not relu_grad_by_consumer
         ctx.has_bias = bias is not None
@@ -353,30 +426,11 @@ class Conv3x3Fn(Function):
         gy = _c(gy)
         if ctx.mask_here:
             gy = ops.relu_mask(gy, y)
-        cin, ps = x.shape[3], ctx.cache.ps
-        dx = dw = db = None
-        # dx of a C -> 3 conv is a 3 -> C conv of dy: the HBM-bound direct kernel, no packed weights
-        rgb_dgrad = weight.shape[0] == 3 and ctx.stride == 1 and not ctx.relu_in and not ps and cin % 4 == 0 and 256 % (cin // 4) == 0
-        # ... and dx of a 3 -> C conv is a C -> 3 conv of dy: the HBM-bound kernel of the C -> 3 forward, on the OIHW weights
-        rgb_in_dgrad = not ctx.relu_in and not ps and ops.rgb_in_dgrad_eligible(cin, weight.shape[0], ctx.stride)
-        wpd = ctx.cache.for_dgrad(weight, x.shape, ctx.stride) if ctx.needs_input_grad[0] and not (rgb_dgrad or rgb_in_dgrad) else None
-        if ctx.needs_input_grad[1]:
-            want_b = ctx.has_bias and ctx.needs_input_grad[2]
-            outs = dict(dw_out=grad_out(weight), db_out=grad_out(ctx.bias_ref) if want_b else None)
-            with _OnSide(gy.device, x, gy, fast=outs["dw_out"] is not None and (outs["db_out"] is not None or not want_b)):
-                if cin == 3:
-                    dw, db = ops.conv3x3_wgrad_rgb(gy, x, 0, want_bias=want_b, **outs)
-                elif weight.shape[0] == 3:
-                    dw, db = ops.conv3x3_wgrad_rgb(x, gy, 1, want_bias=want_b, **outs)
-                else:
-                    dw, db = ops.conv3x3_wgrad(x, gy, ctx.stride, want_bias=want_b, ps_in=ps, **outs)
-        if ctx.needs_input_grad[0]:
-            if rgb_dgrad:
-                dx = ops.conv3x3_rgb_dgrad(gy, weight.detach(), tuple(x.shape))
-            elif rgb_in_dgrad:
-                dx = ops.conv3x3_rgb_in_dgrad(gy, weight.detach(), tuple(x.shape))
-            else:
-                dx = ops.conv3x3_dgrad(gy, wpd, tuple(x.shape), ctx.stride, mask=x if ctx.relu_in else None, ps_in=ps)
+        need_dx = ctx.needs_input_grad[0]
+        wpd = _dgrad_pack(weight, ctx.cache, x.shape, ctx.stride, not ctx.relu_in) if need_dx else None
+        dw, db = _conv_wgrad(x, gy, weight, ctx.bias_ref, ctx.stride, ctx.cache.ps, ctx.needs_input_grad[1],
+                             ctx.has_bias and ctx.needs_input_grad[2], where="g")
+        dx = _conv_dgrad(gy, weight, ctx.cache, x.shape, ctx.stride, mask=x if ctx.relu_in else None, wpd=wpd) if need_dx else None
         return dx, dw, db, None, None, None, None, None
 
 
@@ -387,8 +441,7 @@ class ConvLReluFn(Function):
     @staticmethod
     def forward(ctx, x, weight, bias, cache, stride, slope):
         x = _c(x)
-        y = ops.conv3x3_fwd(x, lambda: cache.for_fwd(weight, x.shape, stride), cache.bias(bias), weight.shape[0], stride,
-                            act=ops.ACT_LRELU, slope=slope, ps_out=cache.ps, w_oihw=weight.detach())
+        y = _conv_fwd(x, weight, bias, cache, stride, act=ops.ACT_LRELU, slope=slope)
         ctx.cache, ctx.stride, ctx.slope, ctx.bias_ref = cache, stride, slope, bias
         ctx.save_for_backward(x, weight, y)
         return y
@@ -397,19 +450,9 @@ class ConvLReluFn(Function):
     def backward(ctx, gy):
         x, weight, y = ctx.saved_tensors
         gz = ops.relu_mask(_c(gy), y, slope=ctx.slope)          # sign(y) == sign(z) for a positive slope
-        dx = dw = db = None
-        if ctx.needs_input_grad[1]:
-            want_b = ctx.bias_ref is not None and ctx.needs_input_grad[2]
-            if x.shape[3] == 3:
-                dw, db = ops.conv3x3_wgrad_rgb(gz, x, 0, want_bias=want_b, dw_out=grad_out(weight), db_out=grad_out(ctx.bias_ref) if want_b else None)
-            else:
-                dw, db = ops.conv3x3_wgrad(x, gz, ctx.stride, want_bias=want_b, ps_in=ctx.cache.ps, dw_out=grad_out(weight),
-                                           db_out=grad_out(ctx.bias_ref) if want_b else None)
-        if ctx.needs_input_grad[0]:
-            if not ctx.cache.ps and ops.rgb_in_dgrad_eligible(x.shape[3], weight.shape[0], ctx.stride):
-                dx = ops.conv3x3_rgb_in_dgrad(gz, weight.detach(), tuple(x.shape))
-            else:
-                dx = ops.conv3x3_dgrad(gz, ctx.cache.for_dgrad(weight, x.shape, ctx.stride), tuple(x.shape), ctx.stride, ps_in=ctx.cache.ps)
+        dw, db = _conv_wgrad(x, gz, weight, ctx.bias_ref, ctx.stride, ctx.cache.ps, ctx.needs_input_grad[1],
+                             ctx.bias_ref is not None and ctx.needs_input_grad[2])
+        dx = _conv_dgrad(gz, weight, ctx.cache, x.shape, ctx.stride) if ctx.needs_input_grad[0] else None
         return dx, dw, db, None, None, None
 
 
@@ -451,7 +494,7 @@ class ConvAddFn(Function):
     @staticmethod
     def forward(ctx, x, skip, weight, bias, cache):
         x, skip = _c(x), _c(skip)
-        y = ops.conv3x3_fwd(x, cache.for_fwd(weight, x.shape), cache.bias(bias), weight.shape[0], 1, skip=skip)
+        y = _conv_fwd(x, weight, bias, cache, skip=skip)
         ctx.cache, ctx.bias_ref = cache, bias
         ctx.save_for_backward(x, weight)
         return y
@@ -460,13 +503,9 @@ class ConvAddFn(Function):
     def backward(ctx, gy):
         x, weight = ctx.saved_tensors
         gy = _c(gy)
-        wpd = ctx.cache.for_dgrad(weight, x.shape) if ctx.needs_input_grad[0] else None
-        dw = db = None
-        if ctx.needs_input_grad[2]:
-            o_w, o_b = grad_out(weight), grad_out(ctx.bias_ref)
-            with _OnSide(gy.device, x, gy, fast=o_w is not None and o_b is not None):
-                dw, db = ops.conv3x3_wgrad(x, gy, 1, want_bias=True, dw_out=o_w, db_out=o_b)
-        dx = ops.conv3x3_dgrad(gy, wpd, tuple(x.shape), 1) if ctx.needs_input_grad[0] else None
+        wpd = _dgrad_pack(weight, ctx.cache, x.shape, 1) if ctx.needs_input_grad[0] else None
+        dw, db = _conv_wgrad(x, gy, weight, ctx.bias_ref, 1, False, ctx.needs_input_grad[2], True, where="g")
+        dx = _conv_dgrad(gy, weight, ctx.cache, x.shape, wpd=wpd) if ctx.needs_input_grad[0] else None
         return dx, gy, dw, db, None
 
 
@@ -482,9 +521,8 @@ class ResBlockFn(Function):
     @staticmethod
     def forward(ctx, x, w1, b1, w2, b2, c1: PackedConvWeights, c2: PackedConvWeights, res_scale):
         x = _c(x)
-        C = w1.shape[0]
-        r = ops.conv3x3_fwd(x, c1.for_fwd(w1, x.shape), b1.detach(), C, 1, act=ops.ACT_RELU)
-        y = ops.conv3x3_fwd(r, c2.for_fwd(w2, x.shape), b2.detach(), C, 1, alpha=res_scale, skip=x)
+        r = _conv_fwd(x, w1, b1, c1, act=ops.ACT_RELU)
+        y = _conv_fwd(r, w2, b2, c2, alpha=res_scale, skip=x)
         ctx.c1, ctx.c2, ctx.res_scale = c1, c2, res_scale
         ctx.b1_ref, ctx.b2_ref = b1, b2
         ctx.save_for_backward(x, r, w1, w2)
@@ -496,18 +534,12 @@ class ResBlockFn(Function):
         gy = _c(gy)
         s = ctx.res_scale
         need_w = ctx.needs_input_grad[1] or ctx.needs_input_grad[3]
-        dw1 = db1 = dw2 = db2 = None
-        wpd2, wpd1 = ctx.c2.for_dgrad(w2, x.shape), ctx.c1.for_dgrad(w1, x.shape)      # (packing happens on the main stream)
-        if need_w:
-            o_w, o_b = grad_out(w2), grad_out(ctx.b2_ref)
-            with _OnSide(gy.device, r, gy, fast=o_w is not None and o_b is not None):
-                dw2, db2 = ops.conv3x3_wgrad(r, gy, 1, alpha=s, dw_out=o_w, db_out=o_b)
-        dr = ops.conv3x3_dgrad(gy, wpd2, tuple(r.shape), 1, alpha=s, mask=r)
-        if need_w:
-            o_w, o_b = grad_out(w1), grad_out(ctx.b1_ref)
-            with _OnSide(gy.device, x, dr, fast=o_w is not None and o_b is not None):
-                dw1, db1 = ops.conv3x3_wgrad(x, dr, 1, dw_out=o_w, db_out=o_b)
-        dx = ops.conv3x3_dgrad(dr, wpd1, tuple(x.shape), 1, skip=gy) if ctx.needs_input_grad[0] else None
+        # (packing happens on the main stream, before the first weight gradient)
+        wpd2, wpd1 = _dgrad_pack(w2, ctx.c2, x.shape, 1, False), _dgrad_pack(w1, ctx.c1, x.shape, 1, False)
+        dw2, db2 = _conv_wgrad(r, gy, w2, ctx.b2_ref, 1, False, need_w, True, alpha=s, where="g")
+        dr = _conv_dgrad(gy, w2, ctx.c2, r.shape, alpha=s, mask=r, wpd=wpd2)
+        dw1, db1 = _conv_wgrad(x, dr, w1, ctx.b1_ref, 1, False, need_w, True, where="g")
+        dx = _conv_dgrad(dr, w1, ctx.c1, x.shape, skip=gy, wpd=wpd1) if ctx.needs_input_grad[0] else None
         return dx, dw1, db1, dw2, db2, None, None, None
 
 
@@ -580,8 +612,7 @@ class ConvBnLReluFn(Function):
                 y, stats = ops.bn_finalize_apply(z, part, gamma.detach(), beta.detach(), running_mean, running_var, num_batches, eps, momentum,
                                                  slope, y_nchw)
             else:
-                z = ops.conv3x3_fwd(x, lambda: cache.for_fwd(weight, x.shape, stride), None if bias is None else bias.detach(), weight.shape[0],
-                                    stride, w_oihw=weight.detach())
+                z = _conv_fwd(x, weight, bias, cache, stride)
                 if training:
                     y, stats = ops.bn_lrelu_fwd(z, gamma.detach(), beta.detach(), running_mean, running_var, num_batches, eps,
                                                 momentum, slope, y_nchw)
@@ -613,50 +644,23 @@ class ConvBnLReluFn(Function):
             def bwd(z_, gy_, gamma_, beta_, stats_, slope_, nchw_, need_, dgamma_out=None, dbeta_out=None, accumulate=False):   # noqa: F811
                 return ops.bn_lrelu_bwd_fused(z_, gy_, part, gamma_, beta_, stats_, need_, dgamma_out=dgamma_out, dbeta_out=dbeta_out,
                                               accumulate=accumulate)
-        # SECOND use of this block inside one backward pass (the Discriminator sees hr and sr in one graph, reference
-        # train.py:205-214): the parameter gradients are ADDED to the flat-gradient slices the first use wrote and autograd gets
-        # nothing to add - its fan-in add_ plus the copy of the sum into the flat buffer were two launches per parameter tensor
-        # (see INPLACE_SECOND_USE for when this is allowed)
-        again = INPLACE_SECOND_USE and ctx.training and need_p and ctx.needs_input_grad[1] and ctx.bias_ref is None and \
-            _SIDE_OFF and all(grad_view_claimed(p) and p.grad is None for p in (gamma, beta, weight))
+        # second use of this block inside one backward pass: the parameter gradients are ADDED to the slices the first use wrote
+        # (autograd's fan-in add_ plus the copy of the sum into the flat buffer were two launches per parameter tensor); in-place
+        # accumulation assumes every weight gradient is written on one stream
+        again = _second_use((gamma, beta, weight), ctx.training and need_p and ctx.needs_input_grad[1] and ctx.bias_ref is None and _SIDE_OFF,
+                            (gamma, beta, weight))
         if again:
-            a_g, a_b, a_w = grad_out_again(gamma), grad_out_again(beta), grad_out_again(weight)
-            again = a_g is not None and a_b is not None and a_w is not None
-        if again:
-            dz, _, _ = bwd(z, gy, gamma.detach(), beta.detach(), stats, ctx.slope, ctx.y_nchw, True, dgamma_out=a_g, dbeta_out=a_b,
+            dz, _, _ = bwd(z, gy, gamma.detach(), beta.detach(), stats, ctx.slope, ctx.y_nchw, True, dgamma_out=again[0], dbeta_out=again[1],
                            accumulate=True)
             dgamma = dbeta = None
         else:
             dz, dgamma, dbeta = bwd(z, gy, gamma.detach(), beta.detach(), stats, ctx.slope, ctx.y_nchw, need_p,
                                     dgamma_out=grad_out(gamma) if need_p else None, dbeta_out=grad_out(beta) if need_p else None)
-        dx = dw = db = None
-        rgb_in_dgrad = ops.rgb_in_dgrad_eligible(x.shape[3], weight.shape[0], ctx.stride)     # Discriminator features.0
-        wpd = ctx.cache.for_dgrad(weight, x.shape, ctx.stride) if ctx.needs_input_grad[0] and not rgb_in_dgrad else None
-        if again:
-            if x.shape[3] == 3:
-                ops.conv3x3_wgrad_rgb(dz, x, 0, want_bias=False, dw_out=a_w, accumulate=True)
-            else:
-                ops.conv3x3_wgrad(x, dz, ctx.stride, want_bias=False, dw_out=a_w, accumulate=True)
-        elif ctx.needs_input_grad[1]:
-            want_b = ctx.bias_ref is not None and ctx.needs_input_grad[2]
-            o_w = grad_out(weight)
-            o_b = grad_out(ctx.bias_ref) if want_b else None
-            with _OnSide(dz.device, x, dz, fast=o_w is not None and (o_b is not None or not want_b), where="d"):
-                if x.shape[3] == 3:
-                    dw, db = ops.conv3x3_wgrad_rgb(dz, x, 0, want_bias=want_b, dw_out=o_w, db_out=o_b)
-                else:
-                    dw, db = ops.conv3x3_wgrad(x, dz, ctx.stride, want_bias=want_b, dw_out=o_w, db_out=o_b)
-        if ctx.needs_input_grad[0]:
-            prev = ctx.prev_link
-            res = None
-            if prev is not None and prev.z is not None and not rgb_in_dgrad:
-                # x is the output of a BatchNorm + LeakyReLU block: fold that block's backward reductions into this kernel's epilogue
-                res = ops.conv3x3_dgrad_bn_sums(dz, wpd, tuple(x.shape), ctx.stride, prev.z, prev.stats, prev.gamma, prev.beta, prev.slope)
-            if res is not None:
-                dx, prev.part = res
-                prev.g_ptr = dx.data_ptr()
-            else:
-                dx = ops.conv3x3_rgb_in_dgrad(dz, weight.detach(), tuple(x.shape)) if rgb_in_dgrad else ops.conv3x3_dgrad(dz, wpd, tuple(x.shape), ctx.stride)
+        need_dx = ctx.needs_input_grad[0]
+        wpd = _dgrad_pack(weight, ctx.cache, x.shape, ctx.stride) if need_dx else None
+        dw, db = _conv_wgrad(x, dz, weight, ctx.bias_ref, ctx.stride, ctx.cache.ps, ctx.needs_input_grad[1],
+                             ctx.bias_ref is not None and ctx.needs_input_grad[2], where="d", again=(again[2], None) if again else None)
+        dx = _conv_dgrad(dz, weight, ctx.cache, x.shape, ctx.stride, prev_link=ctx.prev_link, wpd=wpd) if need_dx else None
         return dx, dw, db, dgamma, dbeta, None, None, None, None, None, None, None, None, None, None, None, None
 
 
@@ -723,7 +727,7 @@ class Conv2Fn(Function):
     @staticmethod
     def forward(ctx, x, weight, cache, stride):
         x = _c(x)
-        z = ops.conv3x3_fwd(x, lambda: cache.for_fwd(weight, x.shape, stride), None, weight.shape[0], stride, w_oihw=weight.detach())
+        z = _conv_fwd(x, weight, None, cache, stride)
         ctx.cache, ctx.stride = cache, stride
         ctx.save_for_backward(x, weight)
         return z
@@ -732,15 +736,8 @@ class Conv2Fn(Function):
     def backward(ctx, gz):
         x, weight = ctx.saved_tensors
         gz = _c(gz)
-        dx = dw = None
-        if ctx.needs_input_grad[0]:
-            dx = ConvDgrad2Fn.apply(gz, weight, tuple(x.shape), ctx.cache, ctx.stride)
-        if ctx.needs_input_grad[1]:
-            xd, gd = x.detach(), gz.detach()
-            if x.shape[3] == 3:
-                dw, _ = ops.conv3x3_wgrad_rgb(gd, xd, 0, want_bias=False)
-            else:
-                dw, _ = ops.conv3x3_wgrad(xd, gd, ctx.stride, want_bias=False)
+        dx = ConvDgrad2Fn.apply(gz, weight, tuple(x.shape), ctx.cache, ctx.stride) if ctx.needs_input_grad[0] else None
+        dw, _ = _conv_wgrad(x.detach(), gz.detach(), weight.detach(), None, ctx.stride, False, ctx.needs_input_grad[1], False)
         return dx, dw, None, None
 
 
@@ -751,7 +748,8 @@ class ConvDgrad2Fn(Function):
     @staticmethod
     def forward(ctx, gz, weight, x_shape, cache, stride):
         gz = _c(gz)
-        dx = ops.conv3x3_dgrad(gz, cache.for_dgrad(weight, x_shape, stride), x_shape, stride)
+        # (always on the packed weights: its backward differentiates that kernel's arithmetic)
+        dx = _conv_dgrad(gz, weight, cache, x_shape, stride, wpd=cache.for_dgrad(weight, x_shape, stride))
         ctx.cache, ctx.stride = cache, stride
         ctx.save_for_backward(gz, weight)
         return dx
@@ -761,15 +759,8 @@ class ConvDgrad2Fn(Function):
     def backward(ctx, g):
         gz, weight = ctx.saved_tensors
         g = _c(g)
-        l_gz = l_w = None
-        if ctx.needs_input_grad[0]:
-            l_gz = ops.conv3x3_fwd(g, lambda: ctx.cache.for_fwd(weight, g.shape, ctx.stride), None, weight.shape[0], ctx.stride,
-                                   w_oihw=weight.detach())
-        if ctx.needs_input_grad[1]:
-            if g.shape[3] == 3:
-                l_w, _ = ops.conv3x3_wgrad_rgb(gz, g, 0, want_bias=False)
-            else:
-                l_w, _ = ops.conv3x3_wgrad(g, gz, ctx.stride, want_bias=False)
+        l_gz = _conv_fwd(g, weight, None, ctx.cache, ctx.stride) if ctx.needs_input_grad[0] else None
+        l_w, _ = _conv_wgrad(g, gz, weight.detach(), None, ctx.stride, False, ctx.needs_input_grad[1], False)
         return l_gz, l_w, None, None, None
 
 
@@ -931,14 +922,12 @@ class LinearFn(Function):
         dw = db = None
         if ctx.needs_input_grad[1]:
             o_w, o_b = grad_out(weight), grad_out(ctx.bias_ref)
-            if INPLACE_SECOND_USE and o_w is None and o_b is None and weight.grad is None:
-                # second use of this layer in the same backward pass (the Discriminator sees hr and sr in one graph,
-                # reference train.py:205-214): accumulate straight into the flat-gradient slices the first use wrote,
-                # and hand autograd nothing to add - for classifier.0 that add was a 302 MB elementwise kernel
-                a_w, a_b = grad_out_again(weight), grad_out_again(ctx.bias_ref)
-                if a_w is not None and a_b is not None:
-                    ops.linear_wgrad(gy, x, want_bias=True, dw_out=a_w, db_out=a_b, accumulate=True)
-                    return dx, None, None, None, None, None
+            # second use of this layer in the same backward pass: accumulate straight into the slices the first use wrote and hand
+            # autograd nothing to add - for classifier.0 that add was a 302 MB elementwise kernel
+            again = _second_use((weight, ctx.bias_ref), o_w is None and o_b is None, (weight,))
+            if again:
+                ops.linear_wgrad(gy, x, want_bias=True, dw_out=again[0], db_out=again[1], accumulate=True)
+                return dx, None, None, None, None, None
             dw, db = ops.linear_wgrad(gy, x, want_bias=True, dw_out=o_w, db_out=o_b)
         return dx, dw, db, None, None, None
 
@@ -1000,8 +989,7 @@ class VggTailFn(Function):
             saved.append(x[:B])                     # (the sr half: a contiguous view)
             if kind == "conv":
                 plan.append((kind, m, prev_relu, tuple(x[:B].shape)))
-                x = ops.conv3x3_fwd(x, m.packed.for_fwd(m.weight, x.shape, 1), m.packed.bias(m.bias), m.out_channels, 1,
-                                    act=ops.ACT_RELU if has_relu else ops.ACT_NONE, w_oihw=m.weight.detach())
+                x = _conv_fwd(x, m.weight, m.bias, m.packed, act=ops.ACT_RELU if has_relu else ops.ACT_NONE)
                 prev_relu = has_relu
             else:
                 plan.append((kind, m, prev_relu, None))
@@ -1018,7 +1006,7 @@ class VggTailFn(Function):
         g = _c(ga)
         for (kind, m, relu_in, shape), xin in zip(reversed(ctx.plan), reversed(ctx.saved_tensors)):
             if kind == "conv":
-                g = ops.conv3x3_dgrad(g, m.packed.for_dgrad(m.weight, shape, 1), shape, 1, mask=xin if relu_in else None)
+                g = _conv_dgrad(g, m.weight, m.packed, shape, mask=xin if relu_in else None)
             else:
                 g = ops.maxpool2x2_bwd(xin, g, relu_in)
         return g, None, None

@@ -423,7 +423,35 @@ def _conv3x3_wino(x, wp, bias, skip, mask, y, N, H, W, Cin, cout, alpha, act, sl
     _lib.check(rc, f"{f.launch}[{what} {N}x{H}x{W}x{Cin}->{cout}]")
 
 
+def _conv_flops(N, OH, OW, Cin, cout, fam) -> None:
+    """Tally a 3x3 conv over N x OH x OW output pixels.  fam: the _Family that runs it, its (frac, label), or a callable returning them -
+    asked only while the tally is on (the weight gradient's answer is a planner call)."""
+    if FLOPS.on:
+        frac, label = (fam.frac, fam.label) if isinstance(fam, _Family) else fam() if callable(fam) else fam
+        FLOPS.add(18.0 * N * OH * OW * Cin * cout, frac, label)
+
+
+def _chk_epilogue(what: str, shape, skip, mask) -> None:
+    """The tensors a fused epilogue adds (skip) or masks by (mask) have the shape of the kernel's output."""
+    for t, n in ((skip, "skip"), (mask, "mask")):
+        if t is not None:
+            _chk(t, f"{what}.{n}")
+            assert t.shape == shape, (t.shape, shape)
+
+
+_RGB_VALU, _RGB_MFMA = (0.0, "rgb (HBM-bound, VALU)"), (1.0, "rgb (HBM-bound, MFMA)")
 USE_RGB_OUT = True   # tests switch it off to compare with the implicit-GEMM kernel
+
+
+def rgb_in_eligible(cin: int, cout: int, stride: int) -> bool:
+    """Shapes of pesr_conv3x3_rgb_fwd (3 -> C, stride 1) and of its BatchNorm form; with cin and cout swapped, of pesr_conv3x3_rgb_dgrad
+    (the input gradient of a C -> 3 conv is a 3 -> C conv of dy)."""
+    return cin == 3 and stride == 1 and cout % 4 == 0 and 256 % (cout // 4) == 0
+
+
+def wgrad_rgb_side(cin: int, cout: int) -> Optional[int]:
+    """The `mode` of conv3x3_wgrad_rgb for a conv with a 3-channel side (0: the input, 1: the output); None: conv3x3_wgrad."""
+    return 0 if cin == 3 else 1 if cout == 3 else None
 
 
 def rgb_out_eligible(cin: int, cout: int, stride: int) -> bool:
@@ -443,22 +471,19 @@ def conv3x3_fwd(x: torch.Tensor, wp: torch.Tensor, bias: Optional[torch.Tensor],
         y = torch.empty((N, 2 * OH, 2 * OW, cout // 4), dtype=torch.float32, device=x.device)
     else:
         y = torch.empty((N, OH, OW, cout), dtype=torch.float32, device=x.device)
-    for t, n in ((skip, "skip"), (mask, "mask")):
-        if t is not None:
-            _chk(t, f"conv3x3_fwd.{n}")
-            assert t.shape == y.shape, (t.shape, y.shape)
-    if Cin == 3 and stride == 1 and skip is None and mask is None and not ps_out and alpha == 1.0 and w_oihw is not None \
-            and cout % 4 == 0 and 256 % (cout // 4) == 0:
+    _chk_epilogue("conv3x3_fwd", y.shape, skip, mask)
+    plain = skip is None and mask is None and not ps_out and alpha == 1.0 and w_oihw is not None
+    if plain and rgb_in_eligible(Cin, cout, stride):
         # RGB input layer: dedicated HBM-bound direct kernel on the un-packed OIHW weights
-        FLOPS.add(18.0 * N * OH * OW * Cin * cout, 0.0, "rgb (HBM-bound, VALU)")
+        _conv_flops(N, OH, OW, Cin, cout, _RGB_VALU)
         br = OP_EVENTS.begin(f"conv_rgb_in 3->{cout}")
         rc = _lib.lib().pesr_conv3x3_rgb_fwd(_p(x), _p(w_oihw), _p(bias), _p(y), N, H, W, cout, act, slope, _stream())
         OP_EVENTS.end(br)
         _lib.check(rc, f"pesr_conv3x3_rgb_fwd[{N}x{H}x{W}x3->{cout}]")
         return y
-    if rgb_out_eligible(Cin, cout, stride) and skip is None and mask is None and not ps_out and alpha == 1.0 and w_oihw is not None:
+    if plain and rgb_out_eligible(Cin, cout, stride):
         # -> RGB output layer: dedicated HBM-bound kernel on the un-packed OIHW weights (no pack, no padded MFMAs)
-        FLOPS.add(18.0 * N * OH * OW * Cin * cout, 1.0, "rgb (HBM-bound, MFMA)")
+        _conv_flops(N, OH, OW, Cin, cout, _RGB_MFMA)
         br = OP_EVENTS.begin(f"conv_rgb_out {Cin}->3")
         rc = _lib.lib().pesr_conv3x3_rgb_out_fwd(_p(x), _p(w_oihw), _p(bias), _p(y), N, H, W, Cin, act, slope, _stream())
         OP_EVENTS.end(br)
@@ -467,7 +492,7 @@ def conv3x3_fwd(x: torch.Tensor, wp: torch.Tensor, bias: Optional[torch.Tensor],
     if callable(wp):
         wp = wp()
     fam = _conv_family(wp)
-    FLOPS.add(18.0 * N * OH * OW * Cin * cout, fam.frac, fam.label)
+    _conv_flops(N, OH, OW, Cin, cout, fam)
     br = KERNEL_EVENTS.begin("fwd", N, H, W, Cin, cout, stride)
     L = _lib.lib()
     if isinstance(wp, Bf16Packed) and stride == 2:
@@ -495,13 +520,10 @@ def conv3x3_dgrad(dy: torch.Tensor, wpd: torch.Tensor, in_shape, stride: int = 1
     N, H, W, Cin = in_shape
     cout = dy.shape[3] * (4 if ps_in else 1)
     dx = torch.empty((N, H, W, Cin), dtype=torch.float32, device=dy.device)
-    for t, n in ((skip, "skip"), (mask, "mask")):
-        if t is not None:
-            _chk(t, f"conv3x3_dgrad.{n}")
-            assert t.shape == dx.shape
+    _chk_epilogue("conv3x3_dgrad", dx.shape, skip, mask)
     L = _lib.lib()
     fam = _conv_family(wpd)
-    FLOPS.add(18.0 * N * ((H - 1) // stride + 1) * ((W - 1) // stride + 1) * Cin * cout, fam.frac, fam.label)
+    _conv_flops(N, (H - 1) // stride + 1, (W - 1) // stride + 1, Cin, cout, fam)
     br = KERNEL_EVENTS.begin("dgrad", N, H, W, Cin, cout, stride)
     if isinstance(wpd, Bf16Packed) and stride == 2:
         assert not ps_in
@@ -538,7 +560,7 @@ def conv3x3_rgb_in_dgrad(dy: torch.Tensor, w_oihw: torch.Tensor, in_shape) -> to
     C = dy.shape[3]
     assert three == 3 and dy.shape == (N, H, W, C) and w_oihw.shape == (C, 3, 3, 3)
     dx = torch.empty((N, H, W, 3), dtype=torch.float32, device=dy.device)
-    FLOPS.add(18.0 * N * H * W * C * 3, 1.0, "rgb (HBM-bound, MFMA)")
+    _conv_flops(N, H, W, C, 3, _RGB_MFMA)
     br = OP_EVENTS.begin(f"conv_rgb_in_dgrad {C}->3")
     rc = _lib.lib().pesr_conv3x3_rgb_in_dgrad(_p(dy), _p(w_oihw), _p(dx), N, H, W, C, _stream())
     OP_EVENTS.end(br)
@@ -552,7 +574,7 @@ def conv3x3_rgb_dgrad(dy: torch.Tensor, w_oihw: torch.Tensor, in_shape) -> torch
     N, H, W, C = in_shape
     assert dy.shape == (N, H, W, 3) and w_oihw.shape == (3, C, 3, 3)
     dx = torch.empty((N, H, W, C), dtype=torch.float32, device=dy.device)
-    FLOPS.add(18.0 * N * H * W * C * 3, 0.0, "rgb (HBM-bound, VALU)")
+    _conv_flops(N, H, W, C, 3, _RGB_VALU)
     rc = _lib.lib().pesr_conv3x3_rgb_dgrad(_p(dy), _p(w_oihw), _p(dx), N, H, W, C, _stream())
     _lib.check(rc, f"pesr_conv3x3_rgb_dgrad[{N}x{H}x{W}x{C}<-3]")
     return dx
@@ -589,8 +611,7 @@ def conv3x3_wgrad_bf16(x: torch.Tensor, dy: torch.Tensor, alpha: float = 1.0, wa
     ws = workspace(nbytes, x.device)
     dw = _out(dw_out, (cout, Cin, 3, 3), x.device)
     db = _out(db_out, (cout,), x.device) if want_bias else None
-    if FLOPS.on:
-        FLOPS.add(18.0 * N * H * W * Cin * cout, 1.0, "bf16")
+    _conv_flops(N, H, W, Cin, cout, _BF16)
     br = KERNEL_EVENTS.begin("wgrad", N, H, W, Cin, cout, 1)
     rc = L.pesr_conv3x3_wgrad_bf16(_p(x), _p(dy), _p(dw), _p(db), N, H, W, Cin, cout, alpha, int(ps_in), int(accumulate), _p(ws),
                                    ws.numel(), _stream())
@@ -620,9 +641,8 @@ def conv3x3_wgrad(x: torch.Tensor, dy: torch.Tensor, stride: int = 1, alpha: flo
     ws = workspace(nbytes, x.device)
     dw = _out(dw_out, (cout, Cin, 3, 3), x.device)
     db = _out(db_out, (cout,), x.device) if want_bias else None
-    if FLOPS.on:
-        _, frac, label = _wgrad_kernel(N, H, W, Cin, cout, stride, ps_in, algo, accumulate)
-        FLOPS.add(18.0 * N * ((H - 1) // stride + 1) * ((W - 1) // stride + 1) * Cin * cout, frac, label)
+    _conv_flops(N, (H - 1) // stride + 1, (W - 1) // stride + 1, Cin, cout,
+                lambda: _wgrad_kernel(N, H, W, Cin, cout, stride, ps_in, algo, accumulate)[1:])
     br = KERNEL_EVENTS.begin("wgrad", N, H, W, Cin, cout, stride)
     rc = L.pesr_conv3x3_wgrad(_p(x), _p(dy), _p(dw), _p(db), N, H, W, Cin, cout, stride, alpha, int(ps_in), algo, int(accumulate),
                               _p(ws), ws.numel(), _stream())
@@ -645,7 +665,7 @@ def conv3x3_wgrad_rgb(a: torch.Tensor, b3: torch.Tensor, mode: int, alpha: float
     ws = workspace(nbytes, a.device)
     dw = _out(dw_out, (C, 3, 3, 3) if mode == 0 else (3, C, 3, 3), a.device)
     db = _out(db_out, (C if mode == 0 else 3,), a.device) if want_bias else None
-    FLOPS.add(18.0 * N * H * W * C * 3, 1.0 if C % 256 == 0 else 0.0, "rgb (HBM-bound, MFMA)" if C % 256 == 0 else "rgb (HBM-bound, VALU)")
+    _conv_flops(N, H, W, C, 3, _RGB_MFMA if C % 256 == 0 else _RGB_VALU)
     assert not accumulate or (dw_out is not None and not want_bias)
     rc = L.pesr_conv3x3_wgrad_rgb(_p(a), _p(b3), _p(dw), _p(db), N, H, W, C, mode, alpha, int(accumulate), _p(ws), ws.numel(), _stream())
     _lib.check(rc, "pesr_conv3x3_wgrad_rgb")
@@ -766,7 +786,7 @@ def bn_lrelu_fwd(x, gamma, beta, running_mean, running_var, num_batches, eps=1e-
 
 def conv_rgb_bn_eligible(cin: int, cout: int, stride: int) -> bool:
     """Shapes of pesr_conv3x3_rgb_bn_lrelu_fwd (3 -> C conv whose kernel also leaves the BatchNorm partial sums)."""
-    return cin == 3 and stride == 1 and cout % 4 == 0 and 256 % (cout // 4) == 0
+    return rgb_in_eligible(cin, cout, stride)
 
 
 def conv_rgb_bn_lrelu_fwd(x, w_oihw, gamma, beta, running_mean, running_var, num_batches, eps=1e-5, momentum=0.1, slope=0.2,
@@ -782,7 +802,7 @@ def conv_rgb_bn_lrelu_fwd(x, w_oihw, gamma, beta, running_mean, running_var, num
     z = torch.empty((N, H, W, C), dtype=torch.float32, device=x.device)
     y = torch.empty((N, C, H, W) if y_nchw else (N, H, W, C), dtype=torch.float32, device=x.device)
     stats = torch.empty((2, C), dtype=torch.float32, device=x.device)
-    FLOPS.add(18.0 * N * H * W * Cin * C, 0.0, "rgb (HBM-bound, VALU)")
+    _conv_flops(N, H, W, Cin, C, _RGB_VALU)
     rc = L.pesr_conv3x3_rgb_bn_lrelu_fwd(_p(x), _p(w_oihw), _p(z), _p(gamma), _p(beta), _p(y), _p(stats), _p(running_mean), _p(running_var),
                                          _p(num_batches), N, H, W, C, eps, momentum, slope, int(y_nchw), _p(ws), ws.numel(), _stream())
     _lib.check(rc, f"pesr_conv3x3_rgb_bn_lrelu_fwd[{N}x{H}x{W}x3->{C}]")
@@ -835,7 +855,7 @@ def conv3x3_fwd_bn_stats(x: torch.Tensor, wp, bias: Optional[torch.Tensor], cout
     nws = L.pesr_conv3x3_workspace_bytes(N, OH, OW, cout)
     ws = workspace(nws, x.device) if nws else None
     fam = _conv_family(wp)
-    FLOPS.add(18.0 * N * OH * OW * Cin * cout, fam.frac, fam.label)
+    _conv_flops(N, OH, OW, Cin, cout, fam)
     br = KERNEL_EVENTS.begin("fwd", N, H, W, Cin, cout, stride)
     if four:
         rc = L.pesr_conv3x3_wino4_bn(_p(x), _p(wp.t), _p(bias), _p(z), N, H, W, Cin, cout, _p(ws), nws, ctypes.byref(f), _stream())
@@ -878,7 +898,7 @@ def conv3x3_dgrad_bn_sums(dy: torch.Tensor, wpd, in_shape, stride, z, stats, gam
     nws = L.pesr_conv3x3_workspace_bytes(N, H, W, Cin) if stride == 1 else 0
     ws = workspace(nws, dy.device) if nws else None
     fam = _conv_family(wpd)
-    FLOPS.add(18.0 * N * ((H - 1) // stride + 1) * ((W - 1) // stride + 1) * Cin * cout, fam.frac, fam.label)
+    _conv_flops(N, (H - 1) // stride + 1, (W - 1) // stride + 1, Cin, cout, fam)
     br = KERNEL_EVENTS.begin("dgrad", N, H, W, Cin, cout, stride)
     if four:
         rc = L.pesr_conv3x3_wino4_bn(_p(dy), _p(wpd.t), None, _p(g), N, H, W, cout, Cin, _p(ws), nws, ctypes.byref(f), _stream())
@@ -1084,19 +1104,22 @@ def adam_ema_step_dev(p, g, m, v, ema, ema_decay, state, beta1, beta2, eps, grad
     _lib.check(rc, "pesr_adam_ema_step_dev")
 
 
+def _image_layout(t, err: str, min_n: int = 0, max_n: Optional[int] = None):
+    """[n, 3, h, w] fp32 device tensor -> (tensor, 0 if NCHW-contiguous / 1 if channels_last).  A tensor in neither layout is copied
+    by torch first; anything else, or n outside min_n .. max_n, raises `err`."""
+    if not torch.is_tensor(t) or not t.is_cuda or t.dtype != torch.float32 or t.dim() != 4 or t.shape[1] != 3 \
+            or t.shape[0] < min_n or (max_n is not None and t.shape[0] > max_n):
+        raise _lib.PesrHipError(err)
+    if t.is_contiguous():
+        return t, 0
+    if t.is_contiguous(memory_format=torch.channels_last):
+        return t, 1
+    return t.contiguous(), 0
+
+
 def psnr_y(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     """Y-channel PSNR of two [1, 3, H, W] image tensors (NCHW-contiguous or channels_last) -> device double [mse, psnr]."""
-    outs = []
-    for t in (a, b):
-        if not t.is_cuda or t.dtype != torch.float32 or t.dim() != 4 or t.shape[0] != 1 or t.shape[1] != 3:
-            raise _lib.PesrHipError("psnr_y: expected [1, 3, H, W] float32 GPU tensors")
-        if t.is_contiguous():
-            outs.append((t, 0))
-        elif t.is_contiguous(memory_format=torch.channels_last):
-            outs.append((t, 1))
-        else:
-            outs.append((t.contiguous(), 0))
-    (ta, la), (tb, lb) = outs
+    (ta, la), (tb, lb) = (_image_layout(t, "psnr_y: expected [1, 3, H, W] float32 GPU tensors", 1, 1) for t in (a, b))
     assert ta.shape == tb.shape
     H, W = ta.shape[2], ta.shape[3]
     out = torch.empty(2, dtype=torch.float64, device=ta.device)
@@ -1116,17 +1139,7 @@ SSIM_WINDOW = (0.00102838008447911, 0.007598758135239185, 0.03600077212843083, 0
 def ssim_y(a: torch.Tensor, b: torch.Tensor, shave: int = 0, return_map: bool = False):
     """Y-channel SSIM of N image pairs [N, 3, H, W] (each NCHW-contiguous or channels_last), a border of `shave` pixels ignored
     -> device double [N], the mean of each pair's map; with return_map also the [N, H-2*shave-10, W-2*shave-10] double map."""
-    outs = []
-    for t in (a, b):
-        if not torch.is_tensor(t) or not t.is_cuda or t.dtype != torch.float32 or t.dim() != 4 or t.shape[0] < 1 or t.shape[1] != 3:
-            raise _lib.PesrHipError("ssim_y: expected [N, 3, H, W] float32 GPU tensors")
-        if t.is_contiguous():
-            outs.append((t, 0))
-        elif t.is_contiguous(memory_format=torch.channels_last):
-            outs.append((t, 1))
-        else:
-            outs.append((t.contiguous(), 0))
-    (ta, la), (tb, lb) = outs
+    (ta, la), (tb, lb) = (_image_layout(t, "ssim_y: expected [N, 3, H, W] float32 GPU tensors", 1) for t in (a, b))
     if ta.shape != tb.shape:
         raise ValueError(f"ssim_y: the two tensors differ in shape: {tuple(ta.shape)} and {tuple(tb.shape)}")
     shave = int(shave)
@@ -1155,15 +1168,8 @@ def _tile_desc(desc, cols: int, device):
 
 
 def _entry_layout(t: torch.Tensor, name: str):
-    """[n, 3, h, w] fp32 device tensor -> (tensor, 0 if NCHW-contiguous / 1 if channels_last).  A tensor in neither layout is copied
-    by torch first (the Generator's outputs and their leading slices are in one of the two: the driver never takes that copy)."""
-    if not torch.is_tensor(t) or not t.is_cuda or t.dtype != torch.float32 or t.dim() != 4 or t.shape[1] != 3:
-        raise _lib.PesrHipError(f"tile_scatter: {name}: expected an [n, 3, h, w] float32 GPU tensor")
-    if t.is_contiguous():
-        return t, 0
-    if t.is_contiguous(memory_format=torch.channels_last):
-        return t, 1
-    return t.contiguous(), 0
+    """_image_layout of a tile_scatter argument (the Generator's outputs and their slices are in one of the two: never the copy)."""
+    return _image_layout(t, f"tile_scatter: {name}: expected an [n, 3, h, w] float32 GPU tensor")
 
 
 def tile_gather(src: torch.Tensor, desc, oh: int, ow: int) -> torch.Tensor:

@@ -517,6 +517,29 @@ def test_basic_block_constructor_branches(bias, bn, act, train):
         close(blk[1].running_mean, ref[1].running_mean, 1e-5, what="running_mean"); close(blk[1].running_var, ref[1].running_var, 1e-5, what="running_var")
 
 
+@pytest.mark.parametrize("cin,cout", [(64, 3), (3, 64)])
+def test_basic_block_leaky_relu_with_a_three_channel_side(cin, cout):
+    """BasicBlock(bn=False, act=LeakyReLU) into and out of three channels: the node behind it (ConvLReluFn) takes its weight and input
+    gradients from the same routing as every other conv node, so the C -> 3 block has a weight gradient (it used to end in
+    "unsupported shape": the general kernel refuses Cout % 4 != 0) - against the same nn.Sequential on the CPU."""
+    import torch.nn as nn
+    from model import BasicBlock
+    torch.manual_seed(3)
+    blk = BasicBlock(cin, cout, 3, bias=True, bn=False, act=nn.LeakyReLU(0.2, True), sn=False)
+    ref = _ref_basic_block(cin, cout, 1, True, False, nn.LeakyReLU(0.2, True))
+    ref.load_state_dict(blk.state_dict())
+    blk = blk.cuda()
+    x = detrand.uniform((2, cin, 12, 16), 11)
+    xr = x.clone().requires_grad_(True); xg = x.cuda().requires_grad_(True)
+    gy = detrand.uniform((2, cout, 12, 16), 12)
+    yr = ref(xr); yr.backward(gy)
+    yg = blk(xg); yg.backward(gy.cuda())
+    close(yg, yr.detach(), 2e-5, what="forward")
+    close(xg.grad, xr.grad, 1e-4, what="grad input")
+    for (k, pg), (_, pr) in zip(blk.named_parameters(), ref.named_parameters()):
+        close(pg.grad, pr.grad, 1e-4, what="grad " + k)
+
+
 @pytest.mark.parametrize("bias,bn,act", [(True, True, "relu"), (False, False, "relu"), (True, False, "lrelu")])
 def test_res_block_constructor_branches(bias, bn, act):
     """ResBlock variants of reference model/basic.py:33-52 beyond the one the Generator uses (bn=True, bias=False, LeakyReLU)."""
