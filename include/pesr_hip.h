@@ -232,6 +232,8 @@ int pesr_relu_mask(const float* g, const float* ref, const float* add, float* ou
                    void* stream);
 
 /* ---- 2x2/2 max-pool (torchvision vgg19 features, reference model/vgg.py:8-10) ------------------ */
+/* forward: floor mode, y is [N][H/2][W/2][C] (an odd side's last row / column is dropped); H, W >= 2, C % 4 == 0.  The backward
+ * takes even sides only. */
 int pesr_maxpool2x2_fwd(const float* x, float* y, int N, int H, int W, int C, void* stream);
 /* relu_in=1 also applies the mask of the ReLU that produced x (gradient only where x > 0) */
 int pesr_maxpool2x2_bwd(const float* x, const float* dy, float* dx, int N, int H, int W, int C, int relu_in, void* stream);
@@ -398,6 +400,18 @@ int pesr_ssim_y(const float* a, const float* b, double* out, int N, int H, int W
  * fewer than 2 blocks, N < 1 or N > 65535, luma not 0 or 1.  64-bit offsets. */
 int pesr_niqe_stats(const float* img, int N, int H, int W, int nhwc, int shave, int B, int luma, double* stats,
                     double* mscn1_or_null, double* mscn2_or_null, void* workspace, size_t ws_bytes, void* stream);
+
+/* ---- LPIPS head of one tapped layer (docs/modes.md section 4n), N pairs of NHWC feature maps ------- */
+/* feat: fp32 [2N][H][W][C], entries 0 .. N-1 the features of image a, N .. 2N-1 those of image b (the trunk runs [a; b] as one
+ * batch); w: C floats, the layer's 1 x 1 "lin" weights.  Per pixel p: na = sqrt(sum_c a_c^2), nb likewise, d(p) = sum_c w_c *
+ * (a_c / (na + 1e-10) - b_c / (nb + 1e-10))^2; out: N device doubles, the mean of d over the H * W pixels of each pair.
+ * map_or_null: when non-null the [N][H][W] double map d is written too; the score is the same bits either way.  Every feature
+ * element is read once; float64 after the load, no fused multiply-add, every sum in an order that depends on (H, W, C) alone, no
+ * atomics: bit-identical to the ordered float64 host restatement and on every call.  The workspace holds one double per 64 pixels
+ * of an image: 8 * N * ceil(H * W / 64) bytes, less -> PESR_EWORKSPACE.  PESR_EINVAL (nothing launched): C not 64, 128, 256 or
+ * 512, N < 1 or N > 65535, a side < 1, feat not on a 16-byte boundary.  64-bit offsets. */
+int pesr_lpips_layer(const float* feat, const float* w, double* out, int N, int H, int W, int C, double* map_or_null,
+                     void* workspace, size_t ws_bytes, void* stream);
 
 /* ---- tiled inference (docs/modes.md section 4h): tiles of one LR image -> a batch, a batch's outputs -> the image ------- */
 /* Gather.  src: the LR image, fp32 [3][H][W] (src_u8 = 0) or uint8 [H][W][3] (src_u8 = 1).  desc: n rows of 3 int32 {y0, x0, m}:

@@ -191,8 +191,10 @@ __global__ void maxpool_bwd_kernel(const f32x4* __restrict__ x, const f32x4* __r
         dx[base] = oa; dx[base + C4] = ob; dx[base + (long)W * C4] = oc; dx[base + (long)W * C4 + C4] = od;
     }
 }
+// The forward is floor-mode as nn.MaxPool2d(2): y is [N][H/2][W/2][C] and the last row / column of an odd side is not read (the LPIPS
+// trunk, docs/modes.md section 4n, pools odd sides).  The backward keeps to even sides: it writes dx window by window.
 int pesr_maxpool2x2_fwd_launch(const float* x, float* y, int N, int H, int W, int C, hipStream_t stream) {
-    if (C % 4 || H % 2 || W % 2) return PESR_EINVAL;
+    if (C % 4 || N < 1 || H < 2 || W < 2) return PESR_EINVAL;
     const long total = (long)N * (H / 2) * (W / 2) * (C / 4);
     const int grid = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
     hipLaunchKernelGGL(maxpool_fwd_kernel, dim3(grid), dim3(256), 0, stream, (const f32x4*)x, (f32x4*)y, N, H, W, C / 4);

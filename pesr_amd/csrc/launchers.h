@@ -222,6 +222,10 @@ int pesr_ssim_y_launch(const float* a, const float* b, double* out, int N, int H
 int pesr_niqe_stats_launch(const float* img, int N, int H, int W, int nhwc, int shave, int B, int luma, double* stats, double* mscn1,
                            double* mscn2, void* ws, size_t ws_bytes, hipStream_t stream);
 
+// LPIPS head of one tapped layer: unit-normalise two feature maps, weighted squared difference, mean per image pair (lpips.hip)
+int pesr_lpips_layer_launch(const float* feat, const float* w, double* out, int N, int H, int W, int C, double* map, void* ws,
+                            size_t ws_bytes, hipStream_t stream);
+
 // tiled inference: tiles of one image -> a batch, and a batch's outputs -> the owned pixels of the image (tile.hip)
 int pesr_tile_gather_launch(const void* src, int src_u8, int H, int W, float* dst, const int* desc_host, const int* desc_dev, int n,
                             int oh, int ow, hipStream_t stream);

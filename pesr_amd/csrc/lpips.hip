@@ -1,0 +1,176 @@
+// The LPIPS head of one tapped layer (docs/modes.md section 4n): for every pixel p of an NHWC feature tensor [2N][H][W][C] whose first N
+// entries are the features of image a and whose last N those of image b,
+//     na = sqrt(sum_c a_c^2),  nb likewise,  d(p) = sum_c w_c * (a_c / (na + 1e-10) - b_c / (nb + 1e-10))^2,
+// and per image pair the mean of d(p) over the H * W pixels.  Zhang et al.'s "lin" layer on the squared difference of the
+// unit-normalised features, the two-pass form: the one-pass expansion into sum a^2, sum b^2, sum w a^2, sum w b^2, sum w a b cancels
+// when a ~ b, the regime a good result is in.
+//
+// Every feature element is read once.  One wave per pixel: lane l holds K = C / 64 channels of a and of b in registers, loaded as the
+// widest vector C allows (C = 64: one float, channel l; 128: two, 2l + e; 256: four, 4l + e; 512: two vectors of four, 256 j + 4l + e),
+// so a wave's load of a pixel is one contiguous run.  All arithmetic after the load is float64 with plain operators and no fused
+// multiply-add (`fp contract(off)`, as ssim.hip), and every sum has one fixed order, which tests/lpips_oracle.py restates operation
+// by operation:
+//   lane partial   s = 0; for k = 0 .. K-1 ascending: s = s + x_k * x_k             (a and b: two independent chains)
+//   across lanes   lpips_wave_sum: v = v + v[lane ^ off], off = 1, 2, 4, 8, 16, 32    (every lane ends with the same bits)
+//   per channel    t = a_k / (na + 1e-10) - b_k / (nb + 1e-10);  acc = acc + w_k * (t * t), k ascending, then across lanes
+//   workgroup      256 lanes = 4 waves own 64 consecutive pixels of one image, wave v pixels 16 v .. 16 v + 15 in ascending order:
+//                  s = s + d(p); then ((s0 + s1) + s2) + s3 -> one partial per workgroup in the workspace
+//   image          lpips_final_kernel: lane t adds partials t, t + 256, ... ascending, wave_sum_d (off = 32 .. 1), ((r0 + r1) + r2) + r3,
+//                  / (H * W).
+// No atomics; the order is a function of (H, W, C) alone, so the score has the same bits on every call, with or without the map.
+// The IEEE double division and square root are correctly rounded (their expansions are the only fused operations in this file's code).
+#pragma clang fp contract(off)
+#include "common.h"
+#include "launchers.h"
+
+constexpr int LPIPS_THREADS = 256;
+constexpr int LPIPS_WAVE_PIX = 16;                                  // consecutive pixels per wave
+constexpr int LPIPS_WG_PIX = LPIPS_WAVE_PIX * (LPIPS_THREADS / 64);  // 64 per workgroup
+constexpr double LPIPS_EPS = 1e-10;
+
+// v = v + v[lane ^ off], off = 1, 2, 4, 8, 16, 32, all 64 lanes active: three such sums per pixel.
+#ifdef PESR_LPIPS_SHFL_ONLY
+// The plain form, for the A/B measurement of docs/modes.md section 4n only (an experiment build through PESR_HIP_LIB): every step a
+// __shfl_xor, two ds_bpermute per step of a double.  The same bits as the form below.
+__device__ __forceinline__ double lpips_wave_sum(double v) {
+#pragma unroll
+    for (int off = 1; off < 64; off <<= 1) v = v + __shfl_xor(v, off, 64);
+    return v;
+}
+#else
+// The four steps inside a row of 16 lanes are DPP moves, which cost no LDS traffic (measured against the plain form in section 4n).
+template <int CTRL> __device__ __forceinline__ double lpips_dpp(double v) {
+    int lo = __double2loint(v), hi = __double2hiint(v);
+    lo = __builtin_amdgcn_update_dpp(0, lo, CTRL, 0xf, 0xf, false);
+    hi = __builtin_amdgcn_update_dpp(0, hi, CTRL, 0xf, 0xf, false);
+    return __hiloint2double(hi, lo);
+}
+
+// After the first two steps the four lanes of a quad hold the same bits, so the lane that row_half_mirror reads (7 - i of its eight)
+// holds what lane ^ 4 holds; likewise row_mirror and lane ^ 8.
+__device__ __forceinline__ double lpips_wave_sum(double v) {
+    v = v + lpips_dpp<0xB1>(v);                                      // quad_perm [1, 0, 3, 2]
+    v = v + lpips_dpp<0x4E>(v);                                      // quad_perm [2, 3, 0, 1]
+    v = v + lpips_dpp<0x141>(v);                                     // row_half_mirror
+    v = v + lpips_dpp<0x140>(v);                                     // row_mirror
+    v = v + __shfl_xor(v, 16, 64);
+    v = v + __shfl_xor(v, 32, 64);
+    return v;
+}
+#endif
+
+template <int V> __device__ __forceinline__ void lpips_load(const float* __restrict__ p, float* o) {
+    if constexpr (V == 1) {
+        o[0] = __builtin_nontemporal_load(p);
+    } else if constexpr (V == 2) {
+        const f32x2 t = __builtin_nontemporal_load((const f32x2*)p);
+        o[0] = t.x, o[1] = t.y;
+    } else {
+        const f32x4 t = __builtin_nontemporal_load((const f32x4*)p);
+        o[0] = t.x, o[1] = t.y, o[2] = t.z, o[3] = t.w;
+    }
+}
+
+// grid (ceil(HW / 64), N)
+template <int C>
+__global__ __launch_bounds__(LPIPS_THREADS) void lpips_layer_kernel(const float* __restrict__ feat, const float* __restrict__ w,
+                                                                     double* __restrict__ part, double* __restrict__ map, long HW, int N) {
+    constexpr int K = C / 64, V = K < 4 ? K : 4, J = K / V;
+    constexpr int UNROLL = K < 8 ? 4 : 2;                           // pixels whose loads are in flight together in a wave
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int n = blockIdx.y;
+    const float* fa = feat + (long)n * HW * C;
+    const float* fb = feat + ((long)N + n) * HW * C;
+    double wd[K];
+#pragma unroll
+    for (int j = 0; j < J; ++j)
+#pragma unroll
+        for (int e = 0; e < V; ++e) wd[j * V + e] = (double)w[j * 64 * V + lane * V + e];
+
+    const long p0 = (long)blockIdx.x * LPIPS_WG_PIX + wv * LPIPS_WAVE_PIX;
+    double s = 0.0;
+    for (int i0 = 0; i0 < LPIPS_WAVE_PIX; i0 += UNROLL) {
+        float xa[UNROLL][K], xb[UNROLL][K];
+#pragma unroll
+        for (int u = 0; u < UNROLL; ++u) {
+            const long p = p0 + i0 + u;                             // the same for a whole wave: no divergence
+            if (p < HW) {
+#pragma unroll
+                for (int j = 0; j < J; ++j) {
+                    lpips_load<V>(fa + p * C + j * 64 * V + lane * V, &xa[u][j * V]);
+                    lpips_load<V>(fb + p * C + j * 64 * V + lane * V, &xb[u][j * V]);
+                }
+            } else {
+#pragma unroll
+                for (int k = 0; k < K; ++k) xa[u][k] = xb[u][k] = 0.0f;
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < UNROLL; ++u) {
+            const long p = p0 + i0 + u;
+            if (p < HW) {
+                double sa = 0.0, sb = 0.0;
+#pragma unroll
+                for (int k = 0; k < K; ++k) {
+                    const double a = (double)xa[u][k], b = (double)xb[u][k];
+                    const double aa = a * a, bb = b * b;
+                    sa = sa + aa;
+                    sb = sb + bb;
+                }
+                const double da = sqrt(lpips_wave_sum(sa)) + LPIPS_EPS;
+                const double db = sqrt(lpips_wave_sum(sb)) + LPIPS_EPS;
+                double acc = 0.0;
+#pragma unroll
+                for (int k = 0; k < K; ++k) {
+                    const double ah = (double)xa[u][k] / da, bh = (double)xb[u][k] / db;
+                    const double t = ah - bh;
+                    const double tt = t * t;
+                    const double wt = wd[k] * tt;
+                    acc = acc + wt;
+                }
+                const double d = lpips_wave_sum(acc);
+                s = s + d;
+                if (map && lane == 0) map[(long)n * HW + p] = d;
+            }
+        }
+    }
+    __shared__ double red[LPIPS_THREADS / 64];
+    if (lane == 0) red[wv] = s;
+    __syncthreads();
+    if (tid == 0) part[(long)n * gridDim.x + blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
+}
+
+// one workgroup per image pair: lane t adds partials t, t + 256, ... in ascending order, then the fixed tree of wave_sum_d
+__global__ __launch_bounds__(LPIPS_THREADS) void lpips_final_kernel(const double* __restrict__ part, double* __restrict__ out, long groups,
+                                                                     double count) {
+    const double* p = part + blockIdx.x * groups;
+    double s = 0.0;
+    for (long k = threadIdx.x; k < groups; k += LPIPS_THREADS) s = s + p[k];
+    __shared__ double red[LPIPS_THREADS / 64];
+    const double ws = wave_sum_d(s);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = ws;
+    __syncthreads();
+    if (threadIdx.x == 0) out[blockIdx.x] = (((red[0] + red[1]) + red[2]) + red[3]) / count;
+}
+
+int pesr_lpips_layer_launch(const float* feat, const float* w, double* out, int N, int H, int W, int C, double* map, void* ws,
+                            size_t ws_bytes, hipStream_t stream) {
+    if (!feat || !w || !out || N < 1 || N > 65535 || H < 1 || W < 1) return PESR_EINVAL;
+    if (C != 64 && C != 128 && C != 256 && C != 512) return PESR_EINVAL;
+    if (((uintptr_t)feat & 15) || ((uintptr_t)w & 3) || ((uintptr_t)out & 7) || ((uintptr_t)map & 7) || ((uintptr_t)ws & 7))
+        return PESR_EINVAL;                                         // the vector loads need the tensor's base on 16 bytes
+    const long HW = (long)H * W;
+    const long groups = (HW + LPIPS_WG_PIX - 1) / LPIPS_WG_PIX;
+    if (groups > 2147483647L) return PESR_EINVAL;
+    if (!ws || ws_bytes < (size_t)N * (size_t)groups * sizeof(double)) return PESR_EWORKSPACE;
+    const dim3 grid((unsigned)groups, (unsigned)N), block(LPIPS_THREADS);
+    double* part = (double*)ws;
+    switch (C) {
+    case 64: hipLaunchKernelGGL(lpips_layer_kernel<64>, grid, block, 0, stream, feat, w, part, map, HW, N); break;
+    case 128: hipLaunchKernelGGL(lpips_layer_kernel<128>, grid, block, 0, stream, feat, w, part, map, HW, N); break;
+    case 256: hipLaunchKernelGGL(lpips_layer_kernel<256>, grid, block, 0, stream, feat, w, part, map, HW, N); break;
+    default: hipLaunchKernelGGL(lpips_layer_kernel<512>, grid, block, 0, stream, feat, w, part, map, HW, N); break;
+    }
+    hipLaunchKernelGGL(lpips_final_kernel, dim3(N), block, 0, stream, (const double*)part, out, groups, (double)HW);
+    return pesr_launch_status();
+}

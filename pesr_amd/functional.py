@@ -963,6 +963,10 @@ class MaxPoolFn(Function):
     @staticmethod
     def forward(ctx, x, relu_in):
         x = _c(x)
+        if ctx.needs_input_grad[0] and (x.shape[1] % 2 or x.shape[2] % 2):
+            # the forward kernel floors an odd side (the LPIPS trunk, under no_grad, relies on it); the backward does not exist for one
+            raise ops._lib.PesrHipError(f"MaxPoolFn: a {x.shape[1]} x {x.shape[2]} input needs a gradient, and the max-pool backward takes "
+                                        "even sides only")
         ctx.relu_in = relu_in
         ctx.save_for_backward(x)
         return ops.maxpool2x2_fwd(x)

@@ -1156,6 +1156,29 @@ def ssim_y(a: torch.Tensor, b: torch.Tensor, shave: int = 0, return_map: bool = 
     return (out, smap) if return_map else out
 
 
+LPIPS_CHANNELS = (64, 128, 256, 512)
+
+
+def lpips_layer(feat: torch.Tensor, w: torch.Tensor, return_map: bool = False):
+    """The LPIPS head of one tapped layer (docs/modes.md section 4n).  feat: NHWC [2N, H, W, C], entries 0 .. N-1 the features of
+    image a and N .. 2N-1 those of image b; w: [C], the layer's "lin" weights -> device double [N], the mean over the pixels of
+    sum_c w_c (a_c / (|a| + 1e-10) - b_c / (|b| + 1e-10))^2; with return_map also the [N, H, W] double map.  Like every NHWC op
+    here it takes contiguous tensors only (_chk): a view raises."""
+    _chk(feat, "lpips_layer.feat")
+    _chk(w, "lpips_layer.w")
+    if feat.dim() != 4 or feat.shape[0] < 2 or feat.shape[0] % 2:
+        raise _lib.PesrHipError(f"lpips_layer: expected a [2N, H, W, C] tensor (a's features, then b's), got {tuple(feat.shape)}")
+    N, H, W, C = feat.shape[0] // 2, feat.shape[1], feat.shape[2], feat.shape[3]
+    if w.dim() != 1 or w.shape[0] != C:
+        raise _lib.PesrHipError(f"lpips_layer: expected {C} weights, got {tuple(w.shape)}")
+    out = torch.empty(N, dtype=torch.float64, device=feat.device)
+    dmap = torch.empty((N, H, W), dtype=torch.float64, device=feat.device) if return_map else None
+    ws = workspace(8 * N * ((H * W + 63) // 64), feat.device)
+    rc = _lib.lib().pesr_lpips_layer(_p(feat), _p(w), _p(out), N, H, W, C, _p(dmap), _p(ws), ws.numel(), _stream())
+    _lib.check(rc, "pesr_lpips_layer")
+    return (out, dmap) if return_map else out
+
+
 # ------------------------------------------------------------------------------------------------
 # tiled inference (docs/modes.md section 4h; the plan and the driver are pesr_amd/tile.py)
 # ------------------------------------------------------------------------------------------------

@@ -3,7 +3,8 @@
 self-ensemble, image-space blend `alpha*out + (1-alpha)*out_psnr`, PNG output.  Same flags as the reference
 (test.py:13-33) plus --precision, --scale and --from_hr (a test set that ships HR images only: LR made on the device, PSNR-Y of the
 result and of the bicubic baseline printed; --ssim adds SSIM-Y, --shave drops a border before both), --niqe (the no-reference NIQE
-of every saved image against a pristine model, with or without --from_hr; docs/modes.md section 4k) and --tile (every image as
+of every saved image against a pristine model, with or without --from_hr; docs/modes.md section 4k), --lpips (with --from_hr true:
+the full-reference LPIPS of every saved image and of the bicubic baseline against HR; section 4n) and --tile (every image as
 batches of fixed-size tiles, docs/modes.md section 4h); device-agnostic plumbing; the
 Generator itself runs on the MI355X kernels.
 """
@@ -14,7 +15,7 @@ import os
 import numpy as np
 import torch
 
-from utils import compute_NIQE, compute_PSNR, compute_SSIM, default_device, imgs_to_tensors, tensors_to_imgs
+from utils import compute_LPIPS, compute_NIQE, compute_PSNR, compute_SSIM, default_device, imgs_to_tensors, tensors_to_imgs
 
 
 # (flag, type, default, help) - the reference's flags and defaults (reference test.py:15-33)
@@ -57,6 +58,11 @@ def build_parser():
                         help="a NIQE pristine model (.npz from `python -m pesr_amd.niqe fit`, or the standard .mat): also print the NIQE "
                              "of every saved image (measured on the GPU, --shave applied), and of the bicubic baseline with --from_hr "
                              "true; needs no HR images")
+    # an addition (not a reference flag): the full-reference perceptual score, docs/modes.md section 4n
+    parser.add_argument("--lpips", type=str, default="",
+                        help="with --from_hr true: an LPIPS weight file (from `python -m pesr_amd.lpips pack`): also print the LPIPS (v0.1, "
+                             "VGG variant, measured on the GPU, --shave applied) of every saved image and of the bicubic baseline "
+                             "against the HR image")
     # additions (not reference flags): tiled inference, docs/modes.md section 4h
     parser.add_argument("--tile", type=int, default=0,
                         help="run every image as batches of overlapping tiles of one fixed shape on the GPU: the side of the square of "
@@ -240,18 +246,28 @@ def main(argv=None):
     if args.niqe:
         from pesr_amd import niqe as _niqe
         niqe_model = _niqe.load_model_flag("test.py", "--niqe", args.niqe)
+    lpips_model = None
+    if args.lpips:
+        if not args.from_hr:
+            raise SystemExit("test.py: --lpips compares the result with the HR image: it needs --from_hr true")
+        from pesr_amd import lpips as _lpips
+        lpips_model = _lpips.load_model_flag("test.py", "--lpips", args.lpips)
     from pesr_amd import tile as _tile
     tile_halo = _tile.check_flags("test.py", ("--tile", "--tile_halo", "--tile_batch"), args.tile, args.tile_halo, args.tile_batch,
                                   args.num_blocks, args.scale)
     device = default_device()
     lr_paths = sorted(glob.glob(os.path.join("data/origin/test/", args.dataset, "HR" if args.from_hr else "LR", "*.png")))
-    if niqe_model is not None:                # (the size comes from the PNG header: still no GPU)
+    if niqe_model is not None or lpips_model is not None:       # (the size comes from the PNG header: still no GPU)
         from PIL import Image
         for path in lr_paths:
             with Image.open(path) as im:
                 w, h = im.size
             h, w = (h - h % args.scale, w - w % args.scale) if args.from_hr else (h * args.scale, w * args.scale)
-            _niqe.check_fits_flag("test.py", "--niqe / --shave", niqe_model, h, w, shave, os.path.basename(path))
+            if niqe_model is not None:
+                _niqe.check_fits_flag("test.py", "--niqe / --shave", niqe_model, h, w, shave, os.path.basename(path))
+            if lpips_model is not None and min(h, w) - 2 * shave < _lpips.MIN_SIDE:
+                raise SystemExit(f"test.py: --lpips / --shave: {os.path.basename(path)}: {max(h - 2 * shave, 0)} x {max(w - 2 * shave, 0)} "
+                                 f"after the crop and the shave; LPIPS needs at least {_lpips.MIN_SIDE} x {_lpips.MIN_SIDE}")
     opt = {"num_channels": args.num_channels, "depth": args.num_blocks, "res_scale": args.res_scale}
     model = load_generator(opt, args.perceptual_model, args.scale).to(device)
     print("Number of parameters:", sum(p.nelement() for p in model.parameters()))
@@ -260,7 +276,7 @@ def main(argv=None):
         model_psnr = load_generator(opt, args.psnr_model, args.scale).to(device)
     save_path = os.path.join(args.save_path, args.dataset)
     os.makedirs(save_path, exist_ok=True)
-    psnrs, ssims, niqes = [], [], []
+    psnrs, ssims, niqes, lpipss = [], [], [], []
     if args.tile:
         print(_tile.describe(args.tile, tile_halo, _tile.receptive_halo(args.num_blocks, args.scale)))
     with torch.no_grad():
@@ -295,6 +311,9 @@ def main(argv=None):
                 if niqe_model is not None:
                     niqes.append((_niqe_of(sr, niqe_model, shave, lr_path), _niqe_of(bic, niqe_model, shave, lr_path)))
                     line += ", NIQE %.10f, bicubic %.10f" % niqes[-1]
+                if lpips_model is not None:
+                    lpipss.append((compute_LPIPS(sr, hr, lpips_model, shave), compute_LPIPS(bic, hr, lpips_model, shave)))
+                    line += ", LPIPS %.10f, bicubic %.10f" % lpipss[-1]
                 print(line)
             elif niqe_model is not None:
                 # an LR-only set: the NIQE of what was saved needs nothing else
@@ -308,6 +327,8 @@ def main(argv=None):
             line += ", SSIM-Y %.10f, bicubic %.10f" % (float(np.mean([q[0] for q in ssims])), float(np.mean([q[1] for q in ssims])))
         if niqes:
             line += ", NIQE %.10f, bicubic %.10f" % (float(np.mean([q[0] for q in niqes])), float(np.mean([q[1] for q in niqes])))
+        if lpipss:
+            line += ", LPIPS %.10f, bicubic %.10f" % (float(np.mean([q[0] for q in lpipss])), float(np.mean([q[1] for q in lpipss])))
         print(line)
     elif niqes:
         print("Mean NIQE %.10f" % float(np.mean([q[0] for q in niqes])))

@@ -119,6 +119,10 @@ def build_parser():
                    help="a NIQE pristine model (.npz from `python -m pesr_amd.niqe fit`, or the standard .mat): validation also averages "
                         "the NIQE of the results (measured on the GPU, docs/modes.md section 4k) and prints it in a line of its own; "
                         "the best model is still chosen by PSNR")
+    p.add_argument("--valid_lpips", type=str, default="",
+                   help="an LPIPS weight file (from `python -m pesr_amd.lpips pack`): validation also averages the LPIPS (v0.1, VGG variant, "
+                        "measured on the GPU, docs/modes.md section 4n) of the results against the HR images and prints it in a line of "
+                        "its own; the best model is still chosen by PSNR")
     p.add_argument("--valid_tile", type=int, default=0,
                    help="validate every image as batches of overlapping tiles (docs/modes.md section 4h): the side of the square of LR "
                         "pixels a tile owns; 0 (default) = off, one Generator call on the whole image")
@@ -368,10 +372,25 @@ def niqe_model_of(args):
     return model
 
 
+def lpips_model_of(args):
+    """--valid_lpips -> its model (None without the flag); SystemExit naming the flags.  No GPU is touched."""
+    if not args.valid_lpips:
+        return None
+    from pesr_amd import lpips as _lpips
+    model = _lpips.load_model_flag("train.py", "--valid_lpips", args.valid_lpips)
+    if args.synthetic:
+        side = args.patch_size * args.scale - 2 * args.valid_shave
+        if side < _lpips.MIN_SIDE:
+            raise SystemExit(f"train.py: --valid_lpips / --valid_shave / --patch_size: the synthetic validation images are {max(side, 0)} x "
+                             f"{max(side, 0)} after the shave; LPIPS needs at least {_lpips.MIN_SIDE} x {_lpips.MIN_SIDE}")
+    return model
+
+
 def main(argv=None):
     args = build_parser().parse_args(argv)
     degradation_spec(args)      # (refuses a classical run without its companion flags before anything else starts)
     niqe_model = niqe_model_of(args)
+    lpips_model = lpips_model_of(args)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -399,7 +418,7 @@ def main(argv=None):
     _ops.set_precision(args.precision)
     from pesr_amd.optim import FlatAdam
     from pesr_amd.step import Trainer
-    from utils import compute_NIQE, compute_PSNR, compute_SSIM
+    from utils import compute_LPIPS, compute_NIQE, compute_PSNR, compute_SSIM
     from pesr_amd.tile import describe, receptive_halo, tiled_forward
     valid_halo = receptive_halo(args.num_blocks, args.scale) if args.valid_tile_halo == -1 else args.valid_tile_halo
     if args.valid_tile and rank == 0:
@@ -575,7 +594,7 @@ def main(argv=None):
 
         # validation on rank 0 (full images, batch 1, no_grad), reference train.py:281-295
         if rank == 0:
-            psnr, ssim, niqe = [], [], []
+            psnr, ssim, niqe, lpips_v = [], [], [], []
             if G_eval is not G:
                 optim_G.refresh_ema()       # the steps of this epoch rewrote the averaged weights through raw pointers
             with torch.no_grad():
@@ -593,6 +612,11 @@ def main(argv=None):
                             niqe.append(compute_NIQE(sr, niqe_model, args.valid_shave))
                         except ValueError as e:
                             raise SystemExit(f"train.py: --valid_niqe / --valid_shave: a validation image: {e}")
+                    if lpips_model is not None:
+                        try:        # (of the uint8 values the result would be saved as)
+                            lpips_v.append(compute_LPIPS(sr.clamp(0, 255).round(), hr_img, lpips_model, args.valid_shave))
+                        except ValueError as e:
+                            raise SystemExit(f"train.py: --valid_lpips / --valid_shave: a validation image: {e}")
             val_psnr = float(np.mean(psnr)) if psnr else 0.0
             print("Finish valid [%d/%d]. PSNR: %.4fdB%s" % (epoch, args.num_epochs, val_psnr, ema_tag))
             if tb is not None:
@@ -607,6 +631,11 @@ def main(argv=None):
                 print("Finish valid [%d/%d]. NIQE: %.6f" % (epoch, args.num_epochs, val_niqe))
                 if tb is not None:
                     tb.add_scalar("Validate NIQE", val_niqe, epoch)
+            if lpips_model is not None:
+                val_lpips = float(np.mean(lpips_v)) if lpips_v else 0.0
+                print("Finish valid [%d/%d]. LPIPS: %.6f" % (epoch, args.num_epochs, val_lpips))
+                if tb is not None:
+                    tb.add_scalar("Validate LPIPS", val_lpips, epoch)
             if not gan and val_psnr > best_psnr:
                 best_psnr = val_psnr
                 torch.save(G_eval.state_dict(), os.path.join(check_point, "best_model.pt"))

@@ -1,5 +1,6 @@
 """Image <-> tensor helpers, the Y-channel PSNR of the reference (reference utils.py:10-41), the Y-channel SSIM beside it
-(docs/modes.md section 4g) and the no-reference NIQE (section 4k), device-agnostic.
+(docs/modes.md section 4g) and the no-reference NIQE (section 4k), device-agnostic, and the full-reference LPIPS (section 4n), which
+runs on the GPU only.
 
 Tensors carry raw 0..255 values (no /255 anywhere).  Metrics run in numpy on the host exactly as the
 reference does; nothing here is on the hot path.
@@ -127,6 +128,17 @@ def compute_NIQE(out, model, shave=0):
     if not isinstance(model, _niqe.NiqeModel):
         model = _niqe.NiqeModel.load(model)
     return float(np.mean(_niqe.niqe(out, model, int(shave))))
+
+
+def compute_LPIPS(out, lbl, model, shave=0):
+    """LPIPS (v0.1, VGG variant; docs/modes.md section 4n) of N image pairs [N,3,H,W] in 0..255 against a pesr_amd.lpips.LpipsModel
+    or the path of one, a border of `shave` pixels dropped first -> the mean over the N pairs.  The trunk and the head run on the
+    device and there is no CPU path: anything that is not a float32 GPU tensor raises ValueError, as do images that differ in shape
+    or are smaller than 16 x 16 after the shave."""
+    from pesr_amd import lpips as _lpips
+    if not isinstance(model, _lpips.LpipsModel):
+        model = _lpips.LpipsModel.load(model)
+    return float(_lpips.lpips(out, lbl, model, int(shave)).mean())
 
 
 def update_tensorboard(epoch, tb, img_idx, inp, out, lbl):
