@@ -413,6 +413,23 @@ int pesr_niqe_stats(const float* img, int N, int H, int W, int nhwc, int shave, 
 int pesr_lpips_layer(const float* feat, const float* w, double* out, int N, int H, int W, int C, double* map_or_null,
                      void* workspace, size_t ws_bytes, void* stream);
 
+/* The same head with the two feature tensors as separate base pointers fa, fb: fp32 [N][H][W][C] each (the training path,
+ * docs/modes.md section 4o, runs the trunk on sr and on hr apart).  One kernel with pesr_lpips_layer, which is this call with
+ * fb = feat + N * H * W * C: the same bits.  Arguments, workspace and errors as there; fa and fb each on a 16-byte boundary. */
+int pesr_lpips_layer2(const float* fa, const float* fb, const float* w, double* out, int N, int H, int W, int C, double* map_or_null,
+                      void* workspace, size_t ws_bytes, void* stream);
+
+/* The head's gradient with respect to fa (docs/modes.md section 4o).  g: N device doubles, dL/dscore of each pair; ga: fp32
+ * [N][H][W][C].  With ah = a / (na + 1e-10), bh likewise, t = ah - bh and q = sum_c w_c t_c ah_c per pixel:
+ *     ga_j = (2 g[n] / (H W)) * (w_j t_j - (a_j / na) q) / (na + 1e-10),  rounded once to fp32;  ga_j = 0 where na == 0
+ * (a definition: the formula's own value there is 2 w_j t_j / 1e-10).  Float64 after the load, no fused multiply-add, na and nb with
+ * the forward's bits, one fixed order of operations per pixel (the header of csrc/lpips.hip): bit-identical to the ordered float64
+ * host restatement and on every call.  Every feature element is read once, every gradient element written once; no workspace, no
+ * atomics.  fb gets no gradient.  PESR_EINVAL (nothing launched): C not 64, 128, 256 or 512, N < 1 or N > 65535, a side < 1, fa, fb
+ * or ga not on a 16-byte boundary, g not on 8.  64-bit offsets. */
+int pesr_lpips_layer_bwd(const float* fa, const float* fb, const float* w, const double* g, float* ga, int N, int H, int W, int C,
+                         void* stream);
+
 /* ---- tiled inference (docs/modes.md section 4h): tiles of one LR image -> a batch, a batch's outputs -> the image ------- */
 /* Gather.  src: the LR image, fp32 [3][H][W] (src_u8 = 0) or uint8 [H][W][3] (src_u8 = 1).  desc: n rows of 3 int32 {y0, x0, m}:
  * tile origin and ensemble member m in 0..7 = entry m of test.py:x8_forward's inputs (bit 0 reverses the W axis, then bit 1 the H

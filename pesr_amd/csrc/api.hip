@@ -390,6 +390,16 @@ PESR_API int pesr_lpips_layer(const float* feat, const float* w, double* out, in
     return pesr_lpips_layer_launch(feat, w, out, N, H, W, C, map_or_null, workspace, ws_bytes, (hipStream_t)stream);
 }
 
+PESR_API int pesr_lpips_layer2(const float* fa, const float* fb, const float* w, double* out, int N, int H, int W, int C,
+                               double* map_or_null, void* workspace, size_t ws_bytes, void* stream) {
+    return pesr_lpips_layer2_launch(fa, fb, w, out, N, H, W, C, map_or_null, workspace, ws_bytes, (hipStream_t)stream);
+}
+
+PESR_API int pesr_lpips_layer_bwd(const float* fa, const float* fb, const float* w, const double* g, float* ga, int N, int H, int W,
+                                  int C, void* stream) {
+    return pesr_lpips_layer_bwd_launch(fa, fb, w, g, ga, N, H, W, C, (hipStream_t)stream);
+}
+
 PESR_API int pesr_tile_gather(const void* src, int src_u8, int H, int W, float* dst, const int* desc_host, const int* desc_dev, int n,
                              int oh, int ow, void* stream) {
     return pesr_tile_gather_launch(src, src_u8, H, W, dst, desc_host, desc_dev, n, oh, ow, (hipStream_t)stream);

@@ -225,6 +225,11 @@ int pesr_niqe_stats_launch(const float* img, int N, int H, int W, int nhwc, int 
 // LPIPS head of one tapped layer: unit-normalise two feature maps, weighted squared difference, mean per image pair (lpips.hip)
 int pesr_lpips_layer_launch(const float* feat, const float* w, double* out, int N, int H, int W, int C, double* map, void* ws,
                             size_t ws_bytes, hipStream_t stream);
+// ... with fa and fb as two base pointers, and its gradient with respect to fa (docs/modes.md section 4o)
+int pesr_lpips_layer2_launch(const float* fa, const float* fb, const float* w, double* out, int N, int H, int W, int C, double* map,
+                             void* ws, size_t ws_bytes, hipStream_t stream);
+int pesr_lpips_layer_bwd_launch(const float* fa, const float* fb, const float* w, const double* g, float* ga, int N, int H, int W, int C,
+                                hipStream_t stream);
 
 // tiled inference: tiles of one image -> a batch, and a batch's outputs -> the owned pixels of the image (tile.hip)
 int pesr_tile_gather_launch(const void* src, int src_u8, int H, int W, float* dst, const int* desc_host, const int* desc_dev, int n,

@@ -19,6 +19,23 @@
 //                  / (H * W).
 // No atomics; the order is a function of (H, W, C) alone, so the score has the same bits on every call, with or without the map.
 // The IEEE double division and square root are correctly rounded (their expansions are the only fused operations in this file's code).
+//
+// lpips_layer2 is the same forward with the two feature tensors as separate base pointers (the training path has no [a; b] batch);
+// pesr_lpips_layer is a call of it with fb = feat + N * H * W * C: one kernel, the same bits.
+//
+// The head's gradient (docs/modes.md section 4o): with g[n] = dL/dscore of pair n (float64), ga = dL/dfa, fp32, for fa only.  The same
+// wave per pixel, the same lane-to-channel layout, loads and stores of the same width, every feature element read once and every
+// gradient element written once; no LDS, no atomics, no cross-pixel sum.  Per pixel, in this order, which tests/lpips_grad_oracle.py
+// restates operation by operation:
+//   per image      scale = (2 * g[n]) / (double)(H * W)
+//   norms          na = sqrt(lpips_wave_sum(sa)), nb likewise, sa and sb the forward's lane chains;  da = na + 1e-10, db = nb + 1e-10
+//                  (the forward's bits)
+//   per channel    ah = a_k / da;  bh = b_k / db;  t = ah - bh;  wt_k = w_k * t;  acc = acc + wt_k * ah, k ascending;
+//                  q = lpips_wave_sum(acc)
+//   per pixel      r = q / na;  c = scale / da                       (two divisions per pixel, none per element beyond ah and bh)
+//   per channel    ga_k = (float)(c * (wt_k - a_k * r)): one rounding to fp32;  ga_k = 0 for every k where na == 0
+// na == 0 is a definition, not the formula's value: every channel of such a pixel left its ReLU at zero, so the conv behind the tap
+// masks the gradient anyway; the formula would give 2 w t / 1e-10 there and autograd NaN, and neither may reach the trunk.
 #pragma clang fp contract(off)
 #include "common.h"
 #include "launchers.h"
@@ -73,14 +90,15 @@ template <int V> __device__ __forceinline__ void lpips_load(const float* __restr
 
 // grid (ceil(HW / 64), N)
 template <int C>
-__global__ __launch_bounds__(LPIPS_THREADS) void lpips_layer_kernel(const float* __restrict__ feat, const float* __restrict__ w,
-                                                                     double* __restrict__ part, double* __restrict__ map, long HW, int N) {
+__global__ __launch_bounds__(LPIPS_THREADS) void lpips_layer_kernel(const float* __restrict__ fa0, const float* __restrict__ fb0,
+                                                                     const float* __restrict__ w, double* __restrict__ part,
+                                                                     double* __restrict__ map, long HW) {
     constexpr int K = C / 64, V = K < 4 ? K : 4, J = K / V;
     constexpr int UNROLL = K < 8 ? 4 : 2;                           // pixels whose loads are in flight together in a wave
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int n = blockIdx.y;
-    const float* fa = feat + (long)n * HW * C;
-    const float* fb = feat + ((long)N + n) * HW * C;
+    const float* fa = fa0 + (long)n * HW * C;
+    const float* fb = fb0 + (long)n * HW * C;
     double wd[K];
 #pragma unroll
     for (int j = 0; j < J; ++j)
@@ -153,12 +171,110 @@ __global__ __launch_bounds__(LPIPS_THREADS) void lpips_final_kernel(const double
     if (threadIdx.x == 0) out[blockIdx.x] = (((red[0] + red[1]) + red[2]) + red[3]) / count;
 }
 
-int pesr_lpips_layer_launch(const float* feat, const float* w, double* out, int N, int H, int W, int C, double* map, void* ws,
-                            size_t ws_bytes, hipStream_t stream) {
-    if (!feat || !w || !out || N < 1 || N > 65535 || H < 1 || W < 1) return PESR_EINVAL;
-    if (C != 64 && C != 128 && C != 256 && C != 512) return PESR_EINVAL;
-    if (((uintptr_t)feat & 15) || ((uintptr_t)w & 3) || ((uintptr_t)out & 7) || ((uintptr_t)map & 7) || ((uintptr_t)ws & 7))
-        return PESR_EINVAL;                                         // the vector loads need the tensor's base on 16 bytes
+// grid (ceil(HW / 64), N): the forward's loads and norms, then the gradient of fa (the order is in this file's header)
+template <int V> __device__ __forceinline__ void lpips_store(float* __restrict__ p, const float* o) {
+    if constexpr (V == 1) {
+        __builtin_nontemporal_store(o[0], p);
+    } else if constexpr (V == 2) {
+        f32x2 t;
+        t.x = o[0], t.y = o[1];
+        __builtin_nontemporal_store(t, (f32x2*)p);
+    } else {
+        f32x4 t;
+        t.x = o[0], t.y = o[1], t.z = o[2], t.w = o[3];
+        __builtin_nontemporal_store(t, (f32x4*)p);
+    }
+}
+
+template <int C>
+__global__ __launch_bounds__(LPIPS_THREADS) void lpips_layer_bwd_kernel(const float* __restrict__ fa0, const float* __restrict__ fb0,
+                                                                         const float* __restrict__ w, const double* __restrict__ g,
+                                                                         float* __restrict__ ga0, long HW) {
+    constexpr int K = C / 64, V = K < 4 ? K : 4, J = K / V;
+    constexpr int UNROLL = K < 8 ? 4 : 2;
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int n = blockIdx.y;
+    const float* fa = fa0 + (long)n * HW * C;
+    const float* fb = fb0 + (long)n * HW * C;
+    float* ga = ga0 + (long)n * HW * C;
+    double wd[K];
+#pragma unroll
+    for (int j = 0; j < J; ++j)
+#pragma unroll
+        for (int e = 0; e < V; ++e) wd[j * V + e] = (double)w[j * 64 * V + lane * V + e];
+    const double two_g = 2.0 * g[n];
+    const double scale = two_g / (double)HW;
+
+    const long p0 = (long)blockIdx.x * LPIPS_WG_PIX + wv * LPIPS_WAVE_PIX;
+    for (int i0 = 0; i0 < LPIPS_WAVE_PIX; i0 += UNROLL) {
+        float xa[UNROLL][K], xb[UNROLL][K];
+#pragma unroll
+        for (int u = 0; u < UNROLL; ++u) {
+            const long p = p0 + i0 + u;                             // the same for a whole wave: no divergence
+            if (p < HW) {
+#pragma unroll
+                for (int j = 0; j < J; ++j) {
+                    lpips_load<V>(fa + p * C + j * 64 * V + lane * V, &xa[u][j * V]);
+                    lpips_load<V>(fb + p * C + j * 64 * V + lane * V, &xb[u][j * V]);
+                }
+            } else {
+#pragma unroll
+                for (int k = 0; k < K; ++k) xa[u][k] = xb[u][k] = 0.0f;
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < UNROLL; ++u) {
+            const long p = p0 + i0 + u;
+            if (p < HW) {                                           // nothing is written for a pixel past the image
+                double sa = 0.0, sb = 0.0;
+#pragma unroll
+                for (int k = 0; k < K; ++k) {
+                    const double a = (double)xa[u][k], b = (double)xb[u][k];
+                    const double aa = a * a, bb = b * b;
+                    sa = sa + aa;
+                    sb = sb + bb;
+                }
+                const double na = sqrt(lpips_wave_sum(sa));
+                const double nb = sqrt(lpips_wave_sum(sb));
+                const double da = na + LPIPS_EPS, db = nb + LPIPS_EPS;
+                double wt[K];
+                double acc = 0.0;
+#pragma unroll
+                for (int k = 0; k < K; ++k) {
+                    const double ah = (double)xa[u][k] / da, bh = (double)xb[u][k] / db;
+                    const double t = ah - bh;
+                    wt[k] = wd[k] * t;
+                    const double qa = wt[k] * ah;
+                    acc = acc + qa;
+                }
+                const double q = lpips_wave_sum(acc);
+                const double r = q / na;                            // (non-finite where na == 0: not used there)
+                const double c = scale / da;
+                float o[K];
+#pragma unroll
+                for (int k = 0; k < K; ++k) {
+                    const double m = (double)xa[u][k] * r;
+                    const double v = wt[k] - m;
+                    const double cv = c * v;
+                    o[k] = na == 0.0 ? 0.0f : (float)cv;
+                }
+#pragma unroll
+                for (int j = 0; j < J; ++j) lpips_store<V>(ga + p * C + j * 64 * V + lane * V, &o[j * V]);
+            }
+        }
+    }
+}
+
+static bool lpips_shape_ok(int N, int H, int W, int C) {
+    return N >= 1 && N <= 65535 && H >= 1 && W >= 1 && (C == 64 || C == 128 || C == 256 || C == 512);
+}
+
+int pesr_lpips_layer2_launch(const float* fa, const float* fb, const float* w, double* out, int N, int H, int W, int C, double* map,
+                             void* ws, size_t ws_bytes, hipStream_t stream) {
+    if (!fa || !fb || !w || !out || !lpips_shape_ok(N, H, W, C)) return PESR_EINVAL;
+    if (((uintptr_t)fa & 15) || ((uintptr_t)fb & 15) || ((uintptr_t)w & 3) || ((uintptr_t)out & 7) || ((uintptr_t)map & 7) ||
+        ((uintptr_t)ws & 7))
+        return PESR_EINVAL;                                         // the vector loads need each tensor's base on 16 bytes
     const long HW = (long)H * W;
     const long groups = (HW + LPIPS_WG_PIX - 1) / LPIPS_WG_PIX;
     if (groups > 2147483647L) return PESR_EINVAL;
@@ -166,11 +282,36 @@ int pesr_lpips_layer_launch(const float* feat, const float* w, double* out, int 
     const dim3 grid((unsigned)groups, (unsigned)N), block(LPIPS_THREADS);
     double* part = (double*)ws;
     switch (C) {
-    case 64: hipLaunchKernelGGL(lpips_layer_kernel<64>, grid, block, 0, stream, feat, w, part, map, HW, N); break;
-    case 128: hipLaunchKernelGGL(lpips_layer_kernel<128>, grid, block, 0, stream, feat, w, part, map, HW, N); break;
-    case 256: hipLaunchKernelGGL(lpips_layer_kernel<256>, grid, block, 0, stream, feat, w, part, map, HW, N); break;
-    default: hipLaunchKernelGGL(lpips_layer_kernel<512>, grid, block, 0, stream, feat, w, part, map, HW, N); break;
+    case 64: hipLaunchKernelGGL(lpips_layer_kernel<64>, grid, block, 0, stream, fa, fb, w, part, map, HW); break;
+    case 128: hipLaunchKernelGGL(lpips_layer_kernel<128>, grid, block, 0, stream, fa, fb, w, part, map, HW); break;
+    case 256: hipLaunchKernelGGL(lpips_layer_kernel<256>, grid, block, 0, stream, fa, fb, w, part, map, HW); break;
+    default: hipLaunchKernelGGL(lpips_layer_kernel<512>, grid, block, 0, stream, fa, fb, w, part, map, HW); break;
     }
     hipLaunchKernelGGL(lpips_final_kernel, dim3(N), block, 0, stream, (const double*)part, out, groups, (double)HW);
+    return pesr_launch_status();
+}
+
+// [a; b] in one tensor: b's features start N * H * W * C floats behind a's, a multiple of 256 bytes
+int pesr_lpips_layer_launch(const float* feat, const float* w, double* out, int N, int H, int W, int C, double* map, void* ws,
+                            size_t ws_bytes, hipStream_t stream) {
+    if (!feat || !lpips_shape_ok(N, H, W, C)) return PESR_EINVAL;
+    return pesr_lpips_layer2_launch(feat, feat + (size_t)N * H * W * C, w, out, N, H, W, C, map, ws, ws_bytes, stream);
+}
+
+int pesr_lpips_layer_bwd_launch(const float* fa, const float* fb, const float* w, const double* g, float* ga, int N, int H, int W, int C,
+                                hipStream_t stream) {
+    if (!fa || !fb || !w || !g || !ga || !lpips_shape_ok(N, H, W, C)) return PESR_EINVAL;
+    if (((uintptr_t)fa & 15) || ((uintptr_t)fb & 15) || ((uintptr_t)ga & 15) || ((uintptr_t)w & 3) || ((uintptr_t)g & 7))
+        return PESR_EINVAL;                                         // the vector loads and stores need each tensor's base on 16 bytes
+    const long HW = (long)H * W;
+    const long groups = (HW + LPIPS_WG_PIX - 1) / LPIPS_WG_PIX;
+    if (groups > 2147483647L) return PESR_EINVAL;
+    const dim3 grid((unsigned)groups, (unsigned)N), block(LPIPS_THREADS);
+    switch (C) {
+    case 64: hipLaunchKernelGGL(lpips_layer_bwd_kernel<64>, grid, block, 0, stream, fa, fb, w, g, ga, HW); break;
+    case 128: hipLaunchKernelGGL(lpips_layer_bwd_kernel<128>, grid, block, 0, stream, fa, fb, w, g, ga, HW); break;
+    case 256: hipLaunchKernelGGL(lpips_layer_bwd_kernel<256>, grid, block, 0, stream, fa, fb, w, g, ga, HW); break;
+    default: hipLaunchKernelGGL(lpips_layer_bwd_kernel<512>, grid, block, 0, stream, fa, fb, w, g, ga, HW); break;
+    }
     return pesr_launch_status();
 }

@@ -407,12 +407,17 @@ class Conv3x3Fn(Function):
               (mask by x > 0, fused in the dgrad epilogue).
     relu_grad_by_consumer: with act=relu, the consumer of y applies the ReLU mask (it set relu_in);
               otherwise this function masks grad_output itself.
+    precision: None - forward and backward dispatch by ops.PRECISION as it is when each runs (every network's own nodes); a mode - both
+              run under that mode whatever is set then (the LPIPS trunk inside a bf16 step: its backward runs later, inside
+              total_G_loss.backward(), docs/modes.md section 4o).
     """
 
     @staticmethod
-    def forward(ctx, x, weight, bias, cache: PackedConvWeights, stride, act, relu_in, relu_grad_by_consumer):
+    def forward(ctx, x, weight, bias, cache: PackedConvWeights, stride, act, relu_in, relu_grad_by_consumer, precision=None):
         x = _c(x)
-        y = _conv_fwd(x, weight, bias, cache, stride, act=act)
+        with ops.use_precision(precision):
+            y = _conv_fwd(x, weight, bias, cache, stride, act=act)
+        ctx.precision = precision
         ctx.cache, ctx.stride, ctx.act, ctx.relu_in = cache, stride, act, relu_in
         ctx.mask_here = act == ops.ACT_RELU and not relu_grad_by_consumer
         ctx.has_bias = bias is not None
@@ -427,11 +432,12 @@ class Conv3x3Fn(Function):
         if ctx.mask_here:
             gy = ops.relu_mask(gy, y)
         need_dx = ctx.needs_input_grad[0]
-        wpd = _dgrad_pack(weight, ctx.cache, x.shape, ctx.stride, not ctx.relu_in) if need_dx else None
-        dw, db = _conv_wgrad(x, gy, weight, ctx.bias_ref, ctx.stride, ctx.cache.ps, ctx.needs_input_grad[1],
-                             ctx.has_bias and ctx.needs_input_grad[2], where="g")
-        dx = _conv_dgrad(gy, weight, ctx.cache, x.shape, ctx.stride, mask=x if ctx.relu_in else None, wpd=wpd) if need_dx else None
-        return dx, dw, db, None, None, None, None, None
+        with ops.use_precision(ctx.precision):
+            wpd = _dgrad_pack(weight, ctx.cache, x.shape, ctx.stride, not ctx.relu_in) if need_dx else None
+            dw, db = _conv_wgrad(x, gy, weight, ctx.bias_ref, ctx.stride, ctx.cache.ps, ctx.needs_input_grad[1],
+                                 ctx.has_bias and ctx.needs_input_grad[2], where="g")
+            dx = _conv_dgrad(gy, weight, ctx.cache, x.shape, ctx.stride, mask=x if ctx.relu_in else None, wpd=wpd) if need_dx else None
+        return dx, dw, db, None, None, None, None, None, None
 
 
 class ConvLReluFn(Function):
@@ -481,8 +487,8 @@ class ConvKxKFn(Function):
         return dx, dw, db, None
 
 
-def conv3x3(x, weight, bias, cache, stride=1, act=ops.ACT_NONE, relu_in=False, relu_grad_by_consumer=False):
-    return Conv3x3Fn.apply(x, weight, bias, cache, stride, act, relu_in, relu_grad_by_consumer)
+def conv3x3(x, weight, bias, cache, stride=1, act=ops.ACT_NONE, relu_in=False, relu_grad_by_consumer=False, precision=None):
+    return Conv3x3Fn.apply(x, weight, bias, cache, stride, act, relu_in, relu_grad_by_consumer, precision)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -975,6 +981,32 @@ class MaxPoolFn(Function):
     def backward(ctx, gy):
         (x,) = ctx.saved_tensors
         return ops.maxpool2x2_bwd(x, _c(gy), ctx.relu_in), None
+
+
+# ------------------------------------------------------------------------------------------------
+# the LPIPS head of one tapped layer as a loss                 docs/modes.md section 4o
+# ------------------------------------------------------------------------------------------------
+class LpipsLayerFn(Function):
+    """(fa, fb, w) -> float64 [N], ops.lpips_layer_pair; only fa gets a gradient (fb is the no_grad hr pass, the weights are frozen):
+    ops.lpips_layer_bwd on the saved features.  The gradient is NOT masked by fa > 0: fa is a tap, the output of a ReLU that the next
+    conv or pool consumes too, and the tap's conv masks the sum of the two gradients (Conv3x3Fn with relu_grad_by_consumer = False)."""
+
+    @staticmethod
+    def forward(ctx, fa, fb, w):
+        fa, fb, w = _c(fa), _c(fb), _c(w.detach())
+        ctx.save_for_backward(fa, fb, w)
+        return ops.lpips_layer_pair(fa, fb, w)
+
+    @staticmethod
+    def backward(ctx, g):
+        fa, fb, w = ctx.saved_tensors
+        if not ctx.needs_input_grad[0]:
+            return None, None, None
+        return ops.lpips_layer_bwd(fa, fb, w, _c(g)), None, None
+
+
+def lpips_layer(fa, fb, w):
+    return LpipsLayerFn.apply(fa, fb, w)
 
 
 class VggTailFn(Function):

@@ -12,6 +12,10 @@ The project ships no weights.  `LpipsModel.load(path)` reads the one file that
 
 writes from a torchvision vgg16 state_dict and the LPIPS v0.1 linear-layer file (INTEGRATION.md says where a user gets the two);
 `LpipsModel.random(seed)` is for tests and smoke runs.
+
+`lpips_loss(sr, hr, model)` is the same score as a training loss (docs/modes.md section 4o), differentiable with respect to sr: two
+trunk passes (sr under autograd, hr under no_grad), the head's gradient kernel (`ops.lpips_layer_bwd`) at each tap, the trunk's input
+gradients on the fp32 conv kernels whatever `ops.PRECISION` is when the backward runs.
 """
 from __future__ import annotations
 
@@ -21,6 +25,7 @@ import warnings
 import torch
 import torch.nn as nn
 
+from . import functional as PF
 from . import ops
 from .model.basic import Conv, MeanShift, nhwc
 from .model.vgg import _MaxPool
@@ -154,6 +159,28 @@ class LpipsModel(nn.Module):
         return taps
 
 
+    def features_grad(self, x):
+        """features() of one image batch as a differentiable graph, for lpips_loss: every conv node carries the fp32 mode (forward and
+        backward, functional.Conv3x3Fn's `precision`), so the input gradients that run later, inside some loss.backward(), do not
+        depend on the mode set then, and no other network's node is touched.  Each tap is consumed twice, by the head and by the next
+        conv or pool: autograd adds the two gradients and the tap's own conv masks the sum by its ReLU (relu_grad_by_consumer = False,
+        and its consumers do not mask); every other ReLU is masked by the one conv that consumes it, as in model/vgg.py."""
+        h = self.scaling(x)
+        taps, i, masked_by_consumer = [], 0, False
+        for v in CFG:
+            if v == "M":
+                h = self.pool(h, relu_in=masked_by_consumer)
+                masked_by_consumer = False
+                continue
+            tap = i in TAPS
+            h = self.convs[i](h, act=ops.ACT_RELU, relu_in=masked_by_consumer, relu_grad_by_consumer=not tap, precision="fp32")
+            masked_by_consumer = not tap
+            if tap:
+                taps.append(nhwc(h))
+            i += 1
+        return taps
+
+
 def load_model_flag(prog, flag, path):
     """Entry points: the model named by `flag`, or SystemExit naming the program and the flag.  No GPU is touched."""
     try:
@@ -191,6 +218,51 @@ def lpips(a, b, model, shave=0, return_maps=False):
                 maps.append(m)
             total = r if total is None else total + r               # float64, layers in ascending order
     return (total, maps) if return_maps else total
+
+
+LOSS_SIDE = 16                                                      # four 2 x 2 pools, each with an even-sided input
+
+
+def check_loss_side(h, w):
+    """None if lpips_loss takes an h x w image (after the shave), else the reason."""
+    if h < LOSS_SIDE or w < LOSS_SIDE or h % LOSS_SIDE or w % LOSS_SIDE:
+        return (f"both sides must be multiples of {LOSS_SIDE} (at least {LOSS_SIDE}): the trunk has four 2 x 2 max-pools and the max-pool "
+                "backward takes even sides only")
+    return None
+
+
+def lpips_loss(sr, hr, model, shave=0):
+    """LPIPS of N image pairs as a loss: float32 GPU tensors [N, 3, H, W] in 0..255 -> device float64 [N], differentiable with respect
+    to sr.  sr is taken as it is (no clamp, no rounding); hr is detached.  The value is lpips(sr, hr)'s definition; the trunk runs
+    twice, on sr under autograd and on hr under no_grad (a [sr; hr] batch under autograd would run every input gradient on twice the
+    images).  ValueError unless both shaved sides are multiples of 16: the max-pool backward takes even sides only."""
+    for t, name in ((sr, "sr"), (hr, "hr")):
+        if not torch.is_tensor(t) or t.dtype != torch.float32 or t.dim() != 4 or t.shape[1] != 3 or t.shape[0] < 1:
+            raise ValueError(f"lpips_loss: {name}: expected a [N, 3, H, W] float32 GPU tensor (there is no CPU path)")
+    if tuple(sr.shape) != tuple(hr.shape):
+        raise ValueError(f"lpips_loss: the two images differ in shape: {tuple(sr.shape)} and {tuple(hr.shape)}")
+    shave = int(shave)
+    H, W = sr.shape[2], sr.shape[3]
+    if shave < 0:
+        raise ValueError(f"lpips_loss: shave must be >= 0, got {shave}")
+    why = check_loss_side(H - 2 * shave, W - 2 * shave)
+    if why:                                                         # (the shape rule first: it needs no device to be checked)
+        raise ValueError(f"lpips_loss: a {H} x {W} image with shave {shave} leaves {max(H - 2 * shave, 0)} x {max(W - 2 * shave, 0)}; {why}")
+    if not sr.is_cuda or not hr.is_cuda:
+        raise ValueError("lpips_loss: expected [N, 3, H, W] float32 GPU tensors (there is no CPU path)")
+    if model.lins[0].device != sr.device:
+        model.to(sr.device)
+    a, b = sr, hr.detach()
+    if shave:
+        a, b = a[:, :, shave:H - shave, shave:W - shave], b[:, :, shave:H - shave, shave:W - shave]
+    taps_a = model.features_grad(a)
+    with torch.no_grad():
+        taps_b = model.features_grad(b)
+    total = None
+    for fa, fb, w in zip(taps_a, taps_b, model.lins):
+        r = PF.lpips_layer(fa, fb, w)
+        total = r if total is None else total + r                   # float64, layers in ascending order
+    return total
 
 
 # ---- pack: the two published files -> the one file load() reads -----------------------------------------------------------------

@@ -64,12 +64,13 @@ class Conv(nn.Module):
             return self.weight
         return PF.spectral_normalize(self.weight_orig, self.weight_u, self.weight_v, self.training, self._sn_eps)
 
-    def forward(self, x, act=ops.ACT_NONE, relu_in=False, relu_grad_by_consumer=False):
+    def forward(self, x, act=ops.ACT_NONE, relu_in=False, relu_grad_by_consumer=False, precision=None):
+        """precision: None, or the mode this call's forward AND backward run under whatever ops.PRECISION is then (3 x 3 only)."""
         if self.kernel_size != 3:
-            assert act == ops.ACT_NONE and not relu_in, "fused activations exist for the 3x3 kernels only"
+            assert act == ops.ACT_NONE and not relu_in and precision is None, "fused activations exist for the 3x3 kernels only"
             return nchw(PF.ConvKxKFn.apply(nhwc(x), self.effective_weight(), self.bias, self.stride))
         return nchw(PF.conv3x3(nhwc(x), self.effective_weight(), self.bias, self.packed, self.stride, act, relu_in,
-                               relu_grad_by_consumer))
+                               relu_grad_by_consumer, precision))
 
     def extra_repr(self):
         return (f"{self.in_channels}, {self.out_channels}, kernel_size={self.kernel_size}, stride={self.stride}, "

@@ -232,6 +232,26 @@ def set_precision(p: str) -> None:
     PRECISION = p
 
 
+class use_precision:
+    """with use_precision(p): PRECISION is p inside and what it was outside; p = None changes nothing.  For a node whose kernels must not
+    depend on the mode that happens to be set when it runs (the LPIPS trunk's input gradients, docs/modes.md section 4o)."""
+
+    def __init__(self, p: Optional[str]):
+        if p is not None and p not in PRECISIONS:
+            raise ValueError(f"precision must be one of {PRECISIONS}, got {p!r}")
+        self.p, self.prev = p, None
+
+    def __enter__(self):
+        global PRECISION
+        self.prev = PRECISION
+        if self.p is not None:
+            PRECISION = self.p
+
+    def __exit__(self, *a):
+        global PRECISION
+        PRECISION = self.prev
+
+
 def bf16_eligible(N: int, H: int, W: int, Cin: int, Cout: int, stride: int = 1, ps_out: bool = False, ps_in: bool = False) -> bool:
     """PRECISION is "bf16" and the bf16 kernel covers the shape with at least 78 % of its tile area inside the image.
     Cin / Cout are those of the problem the kernel runs."""
@@ -1177,6 +1197,42 @@ def lpips_layer(feat: torch.Tensor, w: torch.Tensor, return_map: bool = False):
     rc = _lib.lib().pesr_lpips_layer(_p(feat), _p(w), _p(out), N, H, W, C, _p(dmap), _p(ws), ws.numel(), _stream())
     _lib.check(rc, "pesr_lpips_layer")
     return (out, dmap) if return_map else out
+
+
+def _chk_lpips_pair(what: str, fa: torch.Tensor, fb: torch.Tensor, w: torch.Tensor):
+    _chk(fa, f"{what}.fa")
+    _chk(fb, f"{what}.fb")
+    _chk(w, f"{what}.w")
+    if fa.dim() != 4 or fa.shape[0] < 1 or tuple(fb.shape) != tuple(fa.shape):
+        raise _lib.PesrHipError(f"{what}: expected two [N, H, W, C] tensors of one shape, got {tuple(fa.shape)} and {tuple(fb.shape)}")
+    if w.dim() != 1 or w.shape[0] != fa.shape[3]:
+        raise _lib.PesrHipError(f"{what}: expected {fa.shape[3]} weights, got {tuple(w.shape)}")
+    return tuple(fa.shape)
+
+
+def lpips_layer_pair(fa: torch.Tensor, fb: torch.Tensor, w: torch.Tensor, return_map: bool = False):
+    """lpips_layer with the two feature tensors apart: fa, fb NHWC [N, H, W, C] each (docs/modes.md section 4o) -> what
+    lpips_layer(cat([fa, fb]), w, return_map) gives, bit for bit (one kernel), without the cat."""
+    N, H, W, C = _chk_lpips_pair("lpips_layer_pair", fa, fb, w)
+    out = torch.empty(N, dtype=torch.float64, device=fa.device)
+    dmap = torch.empty((N, H, W), dtype=torch.float64, device=fa.device) if return_map else None
+    ws = workspace(8 * N * ((H * W + 63) // 64), fa.device)
+    rc = _lib.lib().pesr_lpips_layer2(_p(fa), _p(fb), _p(w), _p(out), N, H, W, C, _p(dmap), _p(ws), ws.numel(), _stream())
+    _lib.check(rc, "pesr_lpips_layer2")
+    return (out, dmap) if return_map else out
+
+
+def lpips_layer_bwd(fa: torch.Tensor, fb: torch.Tensor, w: torch.Tensor, g: torch.Tensor) -> torch.Tensor:
+    """The gradient of lpips_layer_pair(fa, fb, w) with respect to fa (docs/modes.md section 4o).  g: device double [N], dL/dscore of
+    each pair -> fp32 [N, H, W, C]: (2 g[n] / (H W)) (w_j t_j - (a_j / na) q) / (na + 1e-10) with q = sum_c w_c t_c ah_c, and 0 at every
+    pixel whose fa vector is all zero (na == 0: a definition, the formula's value there is 2 w_j t_j / 1e-10).  fb gets none."""
+    N, H, W, C = _chk_lpips_pair("lpips_layer_bwd", fa, fb, w)
+    if not g.is_cuda or g.dtype != torch.float64 or tuple(g.shape) != (N,) or not g.is_contiguous():
+        raise _lib.PesrHipError(f"lpips_layer_bwd.g: expected a contiguous float64 GPU tensor [{N}], got {g.dtype} {tuple(g.shape)}")
+    ga = torch.empty((N, H, W, C), dtype=torch.float32, device=fa.device)
+    rc = _lib.lib().pesr_lpips_layer_bwd(_p(fa), _p(fb), _p(w), _p(g), _p(ga), N, H, W, C, _stream())
+    _lib.check(rc, "pesr_lpips_layer_bwd")
+    return ga
 
 
 # ------------------------------------------------------------------------------------------------

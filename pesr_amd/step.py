@@ -73,8 +73,15 @@ def _img(x: torch.Tensor) -> torch.Tensor:
 
 class Trainer:
     def __init__(self, G, D=None, vgg=None, optim_G=None, optim_D=None, *, gan_type="RSGAN", focal_loss=True, fl_gamma=1.0,
-                 alpha_vgg=50.0, alpha_gan=1.0, alpha_tv=1e-6, alpha_l1=0.0, world_size=1, gradient_penalty=False):
+                 alpha_vgg=50.0, alpha_gan=1.0, alpha_tv=1e-6, alpha_l1=0.0, world_size=1, gradient_penalty=False,
+                 lpips_model=None, alpha_lpips=0.0):
         self.G, self.D, self.vgg = G, D, vgg
+        # LPIPS as a term of the generator's loss (docs/modes.md section 4o): on only with a model AND a positive weight; off, gan_step
+        # launches exactly what it launches without the two arguments
+        self.lpips_model, self.alpha_lpips = lpips_model, float(alpha_lpips)
+        if self.alpha_lpips < 0:
+            raise ValueError(f"alpha_lpips must be >= 0, got {alpha_lpips}")
+        self.use_lpips = lpips_model is not None and self.alpha_lpips > 0
         self.optim_G, self.optim_D = optim_G, optim_D
         self.gan_type, self.use_focal = gan_type, focal_loss
         self.pair_classifier = os.environ.get("PESR_PAIR_CLASSIFIER", "1") != "0"   # D's classifier once per phase on [hr; sr] (gan_step)
@@ -173,6 +180,10 @@ class Trainer:
         vgg_sr, vgg_hr = self.vgg(sr, hr_cl)
         vgg_loss = PF.mse_loss(nhwc(vgg_sr), nhwc(vgg_hr)) * self.alpha_vgg
         tv_local = PF.tv_loss(sr_nhwc) * self.alpha_tv
+        lpips_loss = None
+        if self.use_lpips:       # a batch mean like l1 and vgg: no world_size factor (float64 [B] -> fp32 scalar)
+            from .lpips import lpips_loss as _lpips_loss
+            lpips_loss = _lpips_loss(sr, hr_cl, self.lpips_model).mean().float() * self.alpha_lpips
         self.optim_D.step()
 
         # generator phase
@@ -198,12 +209,16 @@ class Trainer:
                 G_loss = loss_fn(pred_fake if self.gan_type == "SGAN" else pred_fake - pred_real, target_real)
             G_loss = G_loss * self.alpha_gan
         total_G_loss = l1_loss + vgg_loss + G_loss + tv_local * float(self.world_size)
+        if lpips_loss is not None:
+            total_G_loss = total_G_loss + lpips_loss
         total_G_loss.backward()
         self.optim_G.step()
         logs = {"l1": l1_loss.detach(), "vgg": vgg_loss.detach(), "g": G_loss.detach(), "tv": tv_local.detach(),
                 "d": total_D_loss.detach()}
         if gp is not None:
             logs["gp"] = gp.detach()
+        if lpips_loss is not None:
+            logs["lpips"] = lpips_loss.detach()
         return logs
 
     # ---- the GAN step as ONE hipGraph ------------------------------------------------------------------------------------

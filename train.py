@@ -123,6 +123,12 @@ def build_parser():
                    help="an LPIPS weight file (from `python -m pesr_amd.lpips pack`): validation also averages the LPIPS (v0.1, VGG variant, "
                         "measured on the GPU, docs/modes.md section 4n) of the results against the HR images and prints it in a line of "
                         "its own; the best model is still chosen by PSNR")
+    p.add_argument("--lpips_loss", type=str, default="",
+                   help="an LPIPS weight file (from `python -m pesr_amd.lpips pack`) for --alpha_lpips: LPIPS (v0.1, VGG variant) of the "
+                        "super-resolved batch against HR as a term of the generator's loss in --phase train (docs/modes.md section 4o)")
+    p.add_argument("--alpha_lpips", type=float, default=0.0,
+                   help="weight of the LPIPS term of the generator's loss; 0 (default) = off, and the step is then what it is without "
+                        "the flag; > 0 needs --lpips_loss, --phase train and (--patch_size * --scale) % 16 == 0")
     p.add_argument("--valid_tile", type=int, default=0,
                    help="validate every image as batches of overlapping tiles (docs/modes.md section 4h): the side of the square of LR "
                         "pixels a tile owns; 0 (default) = off, one Generator call on the whole image")
@@ -386,11 +392,40 @@ def lpips_model_of(args):
     return model
 
 
+def lpips_loss_model_of(args, valid_model=None):
+    """--lpips_loss / --alpha_lpips -> the model of the loss term (None when the term is off); SystemExit naming the flags.  valid_model:
+    the model --valid_lpips loaded; when both flags name one file the object is shared.  No GPU is touched."""
+    if args.alpha_lpips < 0:
+        raise SystemExit(f"train.py: --alpha_lpips {args.alpha_lpips} must be >= 0 (0 = off)")
+    from pesr_amd import lpips as _lpips
+    model = None
+    if args.lpips_loss:
+        if valid_model is not None and os.path.realpath(args.lpips_loss) == os.path.realpath(args.valid_lpips):
+            model = valid_model
+        else:
+            model = _lpips.load_model_flag("train.py", "--lpips_loss", args.lpips_loss)
+    if args.alpha_lpips == 0:
+        return None
+    if model is None:
+        raise SystemExit(f"train.py: --alpha_lpips {args.alpha_lpips} needs --lpips_loss WEIGHTS (an LPIPS weight file; the project ships "
+                         "none)")
+    if args.phase != "train":
+        raise SystemExit(f"train.py: --alpha_lpips {args.alpha_lpips} / --lpips_loss: the LPIPS term belongs to the generator's loss of "
+                         f"--phase train, not --phase {args.phase}")
+    side = args.patch_size * args.scale
+    why = _lpips.check_loss_side(side, side)
+    if why:
+        raise SystemExit(f"train.py: --alpha_lpips / --lpips_loss: (--patch_size * --scale) = {args.patch_size} * {args.scale} = {side}: "
+                         f"{why}")
+    return model
+
+
 def main(argv=None):
     args = build_parser().parse_args(argv)
     degradation_spec(args)      # (refuses a classical run without its companion flags before anything else starts)
     niqe_model = niqe_model_of(args)
     lpips_model = lpips_model_of(args)
+    lpips_loss_model = lpips_loss_model_of(args, lpips_model)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -459,7 +494,7 @@ def main(argv=None):
     scheduler_D = lr_scheduler.StepLR(optim_D, step_size=args.lr_step, gamma=0.5) if gan else None
     trainer = Trainer(G, D, vgg, optim_G, optim_D, gan_type=args.gan_type, focal_loss=args.focal_loss, fl_gamma=args.fl_gamma,
                       alpha_vgg=args.alpha_vgg, alpha_gan=args.alpha_gan, alpha_tv=args.alpha_tv, alpha_l1=args.alpha_l1,
-                      world_size=world, gradient_penalty=args.GP)
+                      world_size=world, gradient_penalty=args.GP, lpips_model=lpips_loss_model, alpha_lpips=args.alpha_lpips)
 
     check_point = os.path.join(args.check_point, args.phase)
     # what checkpoint.rng_snapshot / rng_restore get besides the process-wide streams: the GPU input pipeline's crop stream, or the
@@ -488,6 +523,8 @@ def main(argv=None):
     G_eval = optim_G.ema_module(G) if args.ema_decay > 0 else G
     ema_tag = " (EMA)" if args.ema_decay > 0 else ""
     keys = ("l1", "vgg", "g", "tv", "d") if gan else ("l1",)
+    if trainer.use_lpips:
+        keys += ("lpips",)
     graphed, graph_shapes, eager_at_shape = None, None, 0
     use_graph = device.type == "cuda" and (world == 1 if args.hip_graph == "auto" else str2bool(args.hip_graph))
     # data-parallel schedule: fixed by flag, or measured once (inside the first epoch that is long enough for it)
@@ -588,7 +625,7 @@ def main(argv=None):
             print("Epoch [%d/%d] lr %g  " % (epoch, args.num_epochs, cur_lr) + "  ".join("%s %.4f" % kv for kv in zip(keys, avg)))
             if tb is not None:
                 tb.add_scalar("Learning rate", cur_lr, epoch)
-                names = {"l1": "L1 Loss", "vgg": "VGG Loss", "g": "G Loss", "tv": "TV Loss", "d": "D Loss"}
+                names = {"l1": "L1 Loss", "vgg": "VGG Loss", "g": "G Loss", "tv": "TV Loss", "d": "D Loss", "lpips": "LPIPS Loss"}
                 for k, v in zip(keys, avg):
                     tb.add_scalar(names[k] if gan else "Pretrain Loss", v, epoch)
 
