@@ -430,6 +430,23 @@ int pesr_lpips_layer2(const float* fa, const float* fb, const float* w, double* 
 int pesr_lpips_layer_bwd(const float* fa, const float* fb, const float* w, const double* g, float* ga, int N, int H, int W, int C,
                          void* stream);
 
+/* ---- backward of the upsampler's tail: conv C -> 4C, PixelShuffle(2), conv C -> 3 (reference model/basic.py:56-60), as the backward
+ * of one virtual 3 x 3 conv V from C to 64 channels (48 used) at the resolution of the tail's input h [N][H][W][C]
+ * (docs/experiments/upsample_tail.md has the algebra).  w2 OIHW [4C][C][3][3], b2 [4C], w4 OIHW [3][C][3][3], all fp32; C % 16 == 0,
+ * 16 <= C <= 4096, else PESR_EINVAL with nothing launched.  No workspace, no atomics, no host synchronisation; the compose and chain
+ * sums run in double in one fixed order and are rounded once: the same bits on every call. */
+/* g: dL/d(output) NHWC [N][2H][2W][3] -> gw NHWC [N][H][W][64] (on a 16-byte boundary), channel z = (k*4+p)*4+q (k < 3; p, q < 4) =
+ * g[n][2y-1+p][2x-1+q][k], zero outside the image; channels 48..63 zero.  Values are copied exactly.  64-bit offsets. */
+int pesr_upsample_tail_gather(const float* g, float* gw, int N, int H, int W, void* stream);
+/* weff OIHW [64][C][3][3] = V's weight: weff[z] = sum over m = 4c+2i+j of w4[k][c][i+2-p][j+2-q] * w2[m] where both taps lie in 0..2;
+ * rows 48..63 zero. */
+int pesr_upsample_tail_compose(const float* w2, const float* w4, float* weff, int C, void* stream);
+/* S [64][C][3][3], T [64]: V's weight and bias gradient from (h, gw) (pesr_conv3x3_wgrad) -> dw2 [4C][C][3][3], db2 [4C],
+ * dw4 [3][C][3][3], db4 [3]; each may be NULL (not wanted; b2 NULL: no bias).  accumulate = 1 adds to them. */
+int pesr_upsample_tail_chain(const float* w2, const float* b2_or_null, const float* w4, const float* S, const float* T,
+                             float* dw2_or_null, float* db2_or_null, float* dw4_or_null, float* db4_or_null, int C, int accumulate,
+                             void* stream);
+
 /* ---- tiled inference (docs/modes.md section 4h): tiles of one LR image -> a batch, a batch's outputs -> the image ------- */
 /* Gather.  src: the LR image, fp32 [3][H][W] (src_u8 = 0) or uint8 [H][W][3] (src_u8 = 1).  desc: n rows of 3 int32 {y0, x0, m}:
  * tile origin and ensemble member m in 0..7 = entry m of test.py:x8_forward's inputs (bit 0 reverses the W axis, then bit 1 the H

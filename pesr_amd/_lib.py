@@ -100,6 +100,9 @@ SIGNATURES.update({
     "pesr_lpips_layer": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, _P, _P, c_size_t, _P]),
     "pesr_lpips_layer2": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, _P, _P, c_size_t, _P]),
     "pesr_lpips_layer_bwd": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P]),
+    "pesr_upsample_tail_gather": (c_int, [_P, _P, c_int, c_int, c_int, _P]),
+    "pesr_upsample_tail_compose": (c_int, [_P, _P, _P, c_int, _P]),
+    "pesr_upsample_tail_chain": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, _P]),
     "pesr_tile_gather": (c_int, [_P, c_int, c_int, c_int, _P, _P, _P, c_int, c_int, c_int, _P]),
     "pesr_tile_scatter": (c_int, [_P, _P, c_int, _P, c_int, c_float, c_float, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int,
                                   _P, _P, _P]),

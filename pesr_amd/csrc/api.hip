@@ -400,6 +400,19 @@ PESR_API int pesr_lpips_layer_bwd(const float* fa, const float* fb, const float*
     return pesr_lpips_layer_bwd_launch(fa, fb, w, g, ga, N, H, W, C, (hipStream_t)stream);
 }
 
+PESR_API int pesr_upsample_tail_gather(const float* g, float* gw, int N, int H, int W, void* stream) {
+    return pesr_upsample_tail_gather_launch(g, gw, N, H, W, (hipStream_t)stream);
+}
+PESR_API int pesr_upsample_tail_compose(const float* w2, const float* w4, float* weff, int C, void* stream) {
+    return pesr_upsample_tail_compose_launch(w2, w4, weff, C, (hipStream_t)stream);
+}
+PESR_API int pesr_upsample_tail_chain(const float* w2, const float* b2_or_null, const float* w4, const float* S, const float* T,
+                                      float* dw2_or_null, float* db2_or_null, float* dw4_or_null, float* db4_or_null, int C,
+                                      int accumulate, void* stream) {
+    return pesr_upsample_tail_chain_launch(w2, b2_or_null, w4, S, T, dw2_or_null, db2_or_null, dw4_or_null, db4_or_null, C, accumulate,
+                                           (hipStream_t)stream);
+}
+
 PESR_API int pesr_tile_gather(const void* src, int src_u8, int H, int W, float* dst, const int* desc_host, const int* desc_dev, int n,
                              int oh, int ow, void* stream) {
     return pesr_tile_gather_launch(src, src_u8, H, W, dst, desc_host, desc_dev, n, oh, ow, (hipStream_t)stream);

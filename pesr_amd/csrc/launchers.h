@@ -231,6 +231,12 @@ int pesr_lpips_layer2_launch(const float* fa, const float* fb, const float* w, d
 int pesr_lpips_layer_bwd_launch(const float* fa, const float* fb, const float* w, const double* g, float* ga, int N, int H, int W, int C,
                                 hipStream_t stream);
 
+// backward of the upsampler's tail (conv C -> 4C, PixelShuffle(2), conv C -> 3) as one virtual C -> 64 conv (upsample_tail.hip)
+int pesr_upsample_tail_gather_launch(const float* g, float* gw, int N, int H, int W, hipStream_t stream);
+int pesr_upsample_tail_compose_launch(const float* w2, const float* w4, float* weff, int C, hipStream_t stream);
+int pesr_upsample_tail_chain_launch(const float* w2, const float* b2, const float* w4, const float* S, const float* T, float* dw2,
+                                    float* db2, float* dw4, float* db4, int C, int accumulate, hipStream_t stream);
+
 // tiled inference: tiles of one image -> a batch, and a batch's outputs -> the owned pixels of the image (tile.hip)
 int pesr_tile_gather_launch(const void* src, int src_u8, int H, int W, float* dst, const int* desc_host, const int* desc_dev, int n,
                             int oh, int ow, hipStream_t stream);

@@ -492,6 +492,58 @@ def conv3x3(x, weight, bias, cache, stride=1, act=ops.ACT_NONE, relu_in=False, r
 
 
 # ------------------------------------------------------------------------------------------------
+# the upsampler's tail: conv C -> 4C, PixelShuffle(2), conv C -> 3            reference model/basic.py:56-60
+# ------------------------------------------------------------------------------------------------
+class UpsampleTailFn(Function):
+    """y = conv(pixel_shuffle(conv(h, W2) + b2), W4) + b4 as ONE node.  The forward is the two launches the two Conv3x3Fn nodes make
+    (same packs, same order: the same bits), but the [N, 2H, 2W, C] tensor between them is not kept.  The gradient that arrives has 3
+    channels, and nothing non-linear sits in the pair: per pixel of h the 4C-channel gradient the two big backward launches of the
+    un-fused nodes consume is a linear image of a 4 x 4 window x 3 colours of it.  So the backward runs as the backward of a virtual
+    3x3 conv V: C -> 64 (48 used) at h's resolution (csrc/upsample_tail.hip): gather the windows, compose V's weight, V's input and
+    weight gradient on the routed conv kernels, and chain V's weight gradient back to the four parameters.  G's gradients come out in
+    another, equally valid fp32 summation order."""
+
+    @staticmethod
+    def forward(ctx, h, w2, b2, w4, b4, c2: PackedConvWeights, c4: PackedConvWeights):
+        h = _c(h)
+        mid = _conv_fwd(h, w2, b2, c2)
+        y = _conv_fwd(mid, w4, b4, c4)
+        ctx.refs = (w2, b2, w4, b4)
+        ctx.save_for_backward(h, w2, b2, w4)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        h, w2, b2, w4 = ctx.saved_tensors
+        p_w2, p_b2, p_w4, p_b4 = ctx.refs
+        need_dh, want = ctx.needs_input_grad[0], tuple(ctx.needs_input_grad[1:5])
+        gw = ops.upsample_tail_gather(_c(gy))
+        dh, grads = None, (None, None, None, None)
+        with ops.use_precision("fp32"):       # (the mode the forward's eligibility was decided under)
+            if need_dh:
+                # V's weight is made anew in every backward: its packing lives in a cache of this call's own (a cache keyed by the
+                # tensor's address would take the next step's weight, composed into a recycled buffer, for this one)
+                weff, cache = ops.upsample_tail_compose(w2.detach(), w4.detach()), PackedConvWeights()
+                wpd = _dgrad_pack(weff, cache, h.shape, 1)
+            if any(want):
+                S, T = ops.conv3x3_wgrad(h, gw, 1, want_bias=True)
+                outs = tuple(grad_out(p) if wnt else None for p, wnt in zip((p_w2, p_b2, p_w4, p_b4), want))
+                grads = ops.upsample_tail_chain(w2.detach(), b2.detach(), w4.detach(), S, T, want, outs)
+            if need_dh:
+                dh = _conv_dgrad(gw, weff, cache, h.shape, wpd=wpd)
+        return (dh, *grads, None, None)
+
+
+def upsample_tail(h, conv2, conv4):
+    """conv4(pixel_shuffle(conv2(h))) for the two last Conv modules of an Upsampler (conv2 packed with the PixelShuffle fused into its
+    store): the collapsed-backward node where it applies, else the two nodes of their own."""
+    if conv2.bias is not None and conv4.bias is not None and ops.upsample_tail_eligible(h, h.shape[3]):
+        return UpsampleTailFn.apply(h, conv2.weight, conv2.bias, conv4.weight, conv4.bias, conv2.packed, conv4.packed)
+    mid = conv3x3(h, conv2.weight, conv2.bias, conv2.packed)
+    return conv3x3(mid, conv4.weight, conv4.bias, conv4.packed)
+
+
+# ------------------------------------------------------------------------------------------------
 # conv + residual add (body tail: `res += x`, reference model/pesr.py:32-33)
 # ------------------------------------------------------------------------------------------------
 class ConvAddFn(Function):

@@ -292,13 +292,13 @@ class Upsampler(nn.Sequential):
             return self._forward_x2_x3(x)
         h = nhwc(x)
         h = PF.conv3x3(h, self[0].weight, self[0].bias, self[0].packed)   # -> [N, 2H, 2W, C]
-        h = PF.conv3x3(h, self[2].weight, self[2].bias, self[2].packed)   # -> [N, 4H, 4W, C]
-        h = PF.conv3x3(h, self[4].weight, self[4].bias, self[4].packed)   # -> [N, 4H, 4W, 3]
+        h = PF.upsample_tail(h, self[2], self[4])                         # -> [N, 4H, 4W, C] -> [N, 4H, 4W, 3]; one node (fp32)
         return nchw(h)
 
     def _forward_x2_x3(self, x):
-        h = PF.conv3x3(nhwc(x), self[0].weight, self[0].bias, self[0].packed)  # x2: -> [N, 2H, 2W, C] (fused); x3: -> [N, H, W, 9C]
-        if self.scale == 3:
-            h = _PixelShuffleRFn.apply(h, 3)                                 # -> [N, 3H, 3W, C]
-        h = PF.conv3x3(h, self[2].weight, self[2].bias, self[2].packed)     # -> [N, sH, sW, 3]
+        if self.scale == 2:
+            return nchw(PF.upsample_tail(nhwc(x), self[0], self[2]))        # -> [N, 2H, 2W, C] (fused) -> [N, 2H, 2W, 3]; one node (fp32)
+        h = PF.conv3x3(nhwc(x), self[0].weight, self[0].bias, self[0].packed)  # -> [N, H, W, 9C]
+        h = _PixelShuffleRFn.apply(h, 3)                                    # -> [N, 3H, 3W, C]
+        h = PF.conv3x3(h, self[2].weight, self[2].bias, self[2].packed)     # -> [N, 3H, 3W, 3]
         return nchw(h)

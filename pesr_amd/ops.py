@@ -693,6 +693,68 @@ def conv3x3_wgrad_rgb(a: torch.Tensor, b3: torch.Tensor, mode: int, alpha: float
 
 
 # ------------------------------------------------------------------------------------------------
+# backward of the upsampler's tail (conv C -> 4C, PixelShuffle(2), conv C -> 3) as one virtual C -> 64 conv: csrc/upsample_tail.hip
+# ------------------------------------------------------------------------------------------------
+# PESR_UPSAMPLE_TAIL=0: the two convs keep their own autograd nodes everywhere; =1: the collapsed backward wherever it applies; unset
+# ("auto"): where it applies AND gains (TAIL_MIN_WORK).  Tests set the attribute.
+UPSAMPLE_TAIL = os.environ.get("PESR_UPSAMPLE_TAIL", "auto")
+TAIL_CHANNELS = 64      # channels of the virtual conv's output: 3 colours x a 4 x 4 window = 48, padded to what the Winograd kernels take
+# What the collapsed backward saves grows with pixels x C^2 (15/16 of the pair's backward flops); composing the virtual weight and chaining
+# its gradient back cost the same whatever the image, and it makes eight launches where the two nodes make six.  Measured forward +
+# backward of the pair (docs/experiments/upsample_tail.md, "Where it gains"): never slower, but below N H W C^2 = 2^24 both paths are
+# launch-bound and the difference (<= 10 us of ~190) is the spread of one path's own repeated runs; at 2^24 it is 8 %, at the training shape 56 %.  "auto"
+# takes the path from there up; toy networks and single small patches keep the two nodes and the launch sequence they always had.
+TAIL_MIN_WORK = 1 << 24
+
+
+def upsample_tail_eligible(x: torch.Tensor, c: int) -> bool:
+    """The collapsed backward applies - fp32 mode (the bf16 rows keep their own kernels), a GPU tensor [N, H, W, C], C % 16 == 0 - and,
+    unless PESR_UPSAMPLE_TAIL=1 asks for it wherever it applies, the problem is large enough for it to gain anything."""
+    if UPSAMPLE_TAIL == "0" or PRECISION != "fp32" or not x.is_cuda or c < 16 or c % 16:
+        return False
+    return UPSAMPLE_TAIL == "1" or x.shape[0] * x.shape[1] * x.shape[2] * c * c >= TAIL_MIN_WORK
+
+
+def upsample_tail_gather(g: torch.Tensor) -> torch.Tensor:
+    """g = dL/d(output) [N, 2H, 2W, 3] -> the window image [N, H, W, 64]: channel (k*4+p)*4+q = g[n, 2y-1+p, 2x-1+q, k], zero outside
+    the image and in channels 48..63."""
+    _chk(g, "upsample_tail_gather.g")
+    N, H2, W2, three = g.shape
+    assert three == 3 and H2 % 2 == 0 and W2 % 2 == 0, tuple(g.shape)
+    gw = torch.empty((N, H2 // 2, W2 // 2, TAIL_CHANNELS), dtype=torch.float32, device=g.device)
+    _lib.check(_lib.lib().pesr_upsample_tail_gather(_p(g), _p(gw), N, H2 // 2, W2 // 2, _stream()), f"pesr_upsample_tail_gather[{N}x{H2}x{W2}]")
+    return gw
+
+
+def upsample_tail_compose(w2: torch.Tensor, w4: torch.Tensor) -> torch.Tensor:
+    """(W2 [4C, C, 3, 3], W4 [3, C, 3, 3]) -> the virtual conv's weight [64, C, 3, 3] (OIHW; rows 48..63 zero)."""
+    _chk(w2, "upsample_tail_compose.w2"); _chk(w4, "upsample_tail_compose.w4")
+    C = w2.shape[1]
+    assert tuple(w2.shape) == (4 * C, C, 3, 3) and tuple(w4.shape) == (3, C, 3, 3), (tuple(w2.shape), tuple(w4.shape))
+    weff = torch.empty((TAIL_CHANNELS, C, 3, 3), dtype=torch.float32, device=w2.device)
+    _lib.check(_lib.lib().pesr_upsample_tail_compose(_p(w2), _p(w4), _p(weff), C, _stream()), f"pesr_upsample_tail_compose[C={C}]")
+    return weff
+
+
+def upsample_tail_chain(w2: torch.Tensor, b2: Optional[torch.Tensor], w4: torch.Tensor, S: torch.Tensor, T: torch.Tensor,
+                        want=(True, True, True, True), outs=(None, None, None, None), accumulate: bool = False):
+    """The virtual conv's weight gradient S [64, C, 3, 3] and bias gradient T [64] -> (dW2, db2, dW4, db4), None where `want` is
+    False.  outs: the tensors to write (flat-gradient views), None: fresh ones.  accumulate: add to `outs` (which then must be given)."""
+    for t, n in ((w2, "w2"), (w4, "w4"), (S, "S"), (T, "T")) + (((b2, "b2"),) if b2 is not None else ()):
+        _chk(t, f"upsample_tail_chain.{n}")
+    C = w2.shape[1]
+    assert tuple(w2.shape) == (4 * C, C, 3, 3) and tuple(w4.shape) == (3, C, 3, 3) and tuple(S.shape) == (TAIL_CHANNELS, C, 3, 3)
+    assert tuple(T.shape) == (TAIL_CHANNELS,) and (b2 is None or tuple(b2.shape) == (4 * C,))
+    assert not accumulate or all(o is not None for o, wnt in zip(outs, want) if wnt)
+    shapes = ((4 * C, C, 3, 3), (4 * C,), (3, C, 3, 3), (3,))
+    res = [_out(o, shp, w2.device) if wnt else None for o, shp, wnt in zip(outs, shapes, want)]
+    if any(want):
+        rc = _lib.lib().pesr_upsample_tail_chain(_p(w2), _p(b2), _p(w4), _p(S), _p(T), *(_p(r) for r in res), C, int(accumulate), _stream())
+        _lib.check(rc, f"pesr_upsample_tail_chain[C={C}]")
+    return tuple(res)
+
+
+# ------------------------------------------------------------------------------------------------
 # MeanShift / PixelShuffle / masks / pooling
 # ------------------------------------------------------------------------------------------------
 def meanshift_fwd(x: torch.Tensor, w: torch.Tensor, b: torch.Tensor, x_nchw: bool = False, y_nchw: bool = False):
