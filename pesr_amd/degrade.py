@@ -2,6 +2,8 @@
 a K x K float64 blur kernel centred on the s x s block of every LR pixel (where the bicubic LR pixel of section 4f sits), replicate
 clamp at the image border, a twelve-term Irwin-Hall noise made from integers, clamp to [0, 255], round half up.  Kernel:
 csrc/degrade.hip.  The blur kernels are made here, on the host, in float64; the device never evaluates exp.
+The steps that may follow it - the resize jitter of section 4m, the JPEG round trip of section 4l - are chained here too, in
+degrade_chain_pool_u8 (n windows of a pool: the training sampler) and lr_image_u8 (one whole image: test.py, train.py's validation).
 """
 from __future__ import annotations
 
@@ -12,7 +14,7 @@ import numpy as np
 import torch
 
 from . import _lib, _pool
-from .resize import METHODS, imresize_to_pool_u8
+from .resize import METHODS, imresize_to_pool_u8, imresize_u8
 
 SCALES = (2, 3, 4)
 MAX_K = 24
@@ -192,6 +194,38 @@ def resize_jitter_u8(img: torch.Tensor, r: float, m1: int = 0, m2: int = 0, nois
     flat, h, w = _pool.image_as_pool(img, "resize_jitter_u8")
     out, _, _ = resize_jitter_pool_u8(flat, [0], [(h, w)], [r], [m1], [m2], [noise_sigma], [noise_stream])
     return out.view(h, w, 3)
+
+
+def degrade_chain_pool_u8(pool: torch.Tensor, offsets: Sequence[int], shapes: Sequence[Tuple[int, int]], s: int, kernels, kernel_index: Sequence[int],
+                          noise_sigma: Sequence[float], noise_stream: Sequence[int], windows=None, jitter=None, jpeg=None, jpeg_420: bool = True):
+    """The whole degradation of n windows, in its one order: degrade_pool_u8 (blur, subsample, noise); with jitter = (r, m1, m2), a
+    list per entry each, resize_jitter_pool_u8, and the noise moves out of the degrade launch into the jitter's second resize; with
+    jpeg = a quality per entry, jpeg_pool_u8 last, in place on the chain's own scratch pool (4:2:0 chroma unless jpeg_420 is
+    false).  The other arguments are degrade_pool_u8's.  -> (out_pool, out_offsets, out_shapes), the results back to back."""
+    out, offs, out_shapes = degrade_pool_u8(pool, offsets, shapes, s, kernels, kernel_index, [0.0] * len(offsets) if jitter else noise_sigma,
+                                            noise_stream, windows)
+    if jitter:
+        out, offs, out_shapes = resize_jitter_pool_u8(out, offs, out_shapes, jitter[0], jitter[1], jitter[2], noise_sigma, noise_stream)
+    if jpeg:
+        from .jpeg import jpeg_pool_u8
+        jpeg_pool_u8(out, offs, out_shapes, [w for _, w in out_shapes], jpeg, jpeg_420, out=out)
+    return out, offs, out_shapes
+
+
+def lr_image_u8(hr: torch.Tensor, s: int, kernel=None, noise_sigma: float = 0.0, noise_stream: int = 0, jitter=None, jpeg_q: int = 0,
+                jpeg_420: bool = True) -> torch.Tensor:
+    """uint8 HWC device tensor (sides multiples of s) -> its uint8 HWC LR image.  kernel None: the bicubic resize of section 4f, then
+    the JPEG round trip when jpeg_q; a blur kernel: the chain above for this one image, jitter = (r, m1, m2)."""
+    if kernel is None:
+        lr = imresize_u8(hr, s, up=False)
+        if jpeg_q:
+            from .jpeg import jpeg_u8
+            lr = jpeg_u8(lr, jpeg_q, jpeg_420)
+        return lr
+    flat, h, w = _pool.image_as_pool(hr, "lr_image_u8")
+    out, _, [(ho, wo)] = degrade_chain_pool_u8(flat, [0], [(h, w)], s, np.asarray(kernel, dtype=np.float64)[None], [0], [noise_sigma], [noise_stream],
+                                               jitter=[[v] for v in jitter] if jitter else None, jpeg=[jpeg_q] if jpeg_q else None, jpeg_420=jpeg_420)
+    return out.view(ho, wo, 3)
 
 
 def parse_resize_jitter(text: str, who: str):

@@ -85,26 +85,19 @@ class GpuPatchSampler:
         return [self._pick(i, patch, rng, augment) for i in images]
 
     def _degraded_patches(self, picks, patch):
-        """The step's LR patches, unaugmented, as a scratch uint8 pool of B patches of patch x patch pixels: one kernel per pick.
-        A spec with a resize jitter then sends every patch through its pick's intermediate size and back (section 4m: two pooled
-        resizes, reflection at the patch's own border), and the noise moves from the degrade launch into the second resize.
-        A spec with a JPEG range then compresses every patch in place at its pick's quality (docs/modes.md section 4l), the block
-        grid starting at the patch's own origin."""
-        from .degrade import degrade_pool_u8, gaussian_kernel, resize_jitter_pool_u8
+        """The step's LR patches, unaugmented, as a scratch uint8 pool of B patches of patch x patch pixels (patch b at byte
+        3 * patch * patch * b): every pick's window of the HR pool through degrade.degrade_chain_pool_u8 with the pick's own kernel,
+        noise, resize jitter (section 4m: reflection at the patch's own border) and JPEG quality (section 4l: the block grid starts
+        at the patch's own origin)."""
+        from .degrade import degrade_chain_pool_u8, gaussian_kernel
         spec, B = self.degradation, len(picks)
         drawn = [spec.named(p[4:]) for p in picks]
         bank = np.stack([gaussian_kernel(self.kernel_size, d["sigma1"], d["sigma2"], d["theta"]) for d in drawn])
-        sigma_n, q = [d["sigma_n"] for d in drawn], [d["q"] for d in drawn]
-        out, offs, shapes = degrade_pool_u8(self.hr_pool, [self.hr_off[p[0]] for p in picks], [self.hr_shapes[p[0]] for p in picks], self.scale,
-                                            bank, range(B), [0.0] * B if spec.jitter_hi else sigma_n, q,
-                                            windows=[(p[1], p[2], patch, patch) for p in picks])
-        if spec.jitter_hi:
-            out, _, _ = resize_jitter_pool_u8(out, offs, shapes, [d["jitter_r"] for d in drawn], [d["jitter_m1"] for d in drawn],
-                                              [d["jitter_m2"] for d in drawn], sigma_n, q)
-        if spec.jpeg_hi:
-            from .jpeg import jpeg_pool_u8
-            jpeg_pool_u8(out, [3 * patch * patch * b for b in range(B)], [(patch, patch)] * B, [patch] * B,
-                         [d["jpeg_quality"] for d in drawn], spec.jpeg_420, out=out)
+        column = lambda name: [d[name] for d in drawn]  # noqa: E731
+        out, _, _ = degrade_chain_pool_u8(self.hr_pool, [self.hr_off[p[0]] for p in picks], [self.hr_shapes[p[0]] for p in picks], self.scale,
+                                          bank, range(B), column("sigma_n"), column("q"), windows=[(p[1], p[2], patch, patch) for p in picks],
+                                          jitter=[column(k) for k in ("jitter_r", "jitter_m1", "jitter_m2")] if spec.jitter_hi else None,
+                                          jpeg=column("jpeg_quality") if spec.jpeg_hi else None, jpeg_420=spec.jpeg_420)
         return out
 
     def assemble(self, picks: List[tuple], patch: int, nhwc: bool = False):

@@ -15,7 +15,7 @@ import os
 import numpy as np
 import torch
 
-from utils import compute_LPIPS, compute_NIQE, compute_PSNR, compute_SSIM, default_device, imgs_to_tensors, tensors_to_imgs
+from utils import default_device, imgs_to_tensors, tensors_to_imgs
 
 
 # (flag, type, default, help) - the reference's flags and defaults (reference test.py:15-33)
@@ -204,26 +204,19 @@ def lr_from_hr(hr_img, scale, device, kernel=None, noise_sigma=0.0, noise_stream
     trip of section 4l, and the bicubic baseline is the upscale of the compressed image.  With jitter = (r, m1, m2) the classical
     LR image goes through the resize round trip of section 4m before that, its noise added in the second resize; the baseline is
     then the upscale of the jittered (or jittered and compressed) image."""
+    from pesr_amd.degrade import lr_image_u8
     from pesr_amd.resize import imresize_u8, modcrop
     hr = torch.from_numpy(np.array(modcrop(hr_img, scale))).to(device)
-    if kernel is not None:
-        from pesr_amd.degrade import degrade_u8, resize_jitter_u8
-        lr = degrade_u8(hr, scale, kernel, 0.0 if jitter else noise_sigma, noise_stream)
-        if jitter:
-            lr = resize_jitter_u8(lr, jitter[0], jitter[1], jitter[2], noise_sigma, noise_stream)
-    else:
-        lr = imresize_u8(hr, scale, up=False)
-    if jpeg_q:
-        from pesr_amd.jpeg import jpeg_u8
-        lr = jpeg_u8(lr, jpeg_q, jpeg_420)
+    lr = lr_image_u8(hr, scale, kernel, noise_sigma, noise_stream, jitter, jpeg_q, jpeg_420)
     bic = imresize_u8(lr, scale, up=True)
     return tuple(t.permute(2, 0, 1)[None].float().contiguous() for t in (lr, hr, bic))
 
 
-def _niqe_of(img, model, shave, path):
+def _score(scorer, path, img, hr=None):
+    from pesr_amd.quality import ScoreError
     try:
-        return compute_NIQE(img, model, shave)
-    except ValueError as e:
+        return scorer.score(img, hr)
+    except ScoreError as e:
         raise ValueError(f"{os.path.basename(path)}: {e}") from None
 
 
@@ -242,32 +235,21 @@ def main(argv=None):
     kernel = classical_kernel(args)
     jpeg_q = jpeg_quality(args)
     jitter = resize_jitter(args)
-    niqe_model = None
-    if args.niqe:
-        from pesr_amd import niqe as _niqe
-        niqe_model = _niqe.load_model_flag("test.py", "--niqe", args.niqe)
-    lpips_model = None
-    if args.lpips:
-        if not args.from_hr:
-            raise SystemExit("test.py: --lpips compares the result with the HR image: it needs --from_hr true")
-        from pesr_amd import lpips as _lpips
-        lpips_model = _lpips.load_model_flag("test.py", "--lpips", args.lpips)
+    from pesr_amd.quality import Scorer
+    scorer = Scorer("test.py", args.ssim, shave, args.niqe, args.lpips, have_hr=args.from_hr)
+    scored = bool(scorer.columns(args.from_hr))     # (an LR-only set has a score only with --niqe)
     from pesr_amd import tile as _tile
     tile_halo = _tile.check_flags("test.py", ("--tile", "--tile_halo", "--tile_batch"), args.tile, args.tile_halo, args.tile_batch,
                                   args.num_blocks, args.scale)
     device = default_device()
     lr_paths = sorted(glob.glob(os.path.join("data/origin/test/", args.dataset, "HR" if args.from_hr else "LR", "*.png")))
-    if niqe_model is not None or lpips_model is not None:       # (the size comes from the PNG header: still no GPU)
+    if scorer.niqe_model is not None or scorer.lpips_model is not None:       # (the size comes from the PNG header: still no GPU)
         from PIL import Image
         for path in lr_paths:
             with Image.open(path) as im:
                 w, h = im.size
             h, w = (h - h % args.scale, w - w % args.scale) if args.from_hr else (h * args.scale, w * args.scale)
-            if niqe_model is not None:
-                _niqe.check_fits_flag("test.py", "--niqe / --shave", niqe_model, h, w, shave, os.path.basename(path))
-            if lpips_model is not None and min(h, w) - 2 * shave < _lpips.MIN_SIDE:
-                raise SystemExit(f"test.py: --lpips / --shave: {os.path.basename(path)}: {max(h - 2 * shave, 0)} x {max(w - 2 * shave, 0)} "
-                                 f"after the crop and the shave; LPIPS needs at least {_lpips.MIN_SIDE} x {_lpips.MIN_SIDE}")
+            scorer.check_size(h, w, os.path.basename(path))
     opt = {"num_channels": args.num_channels, "depth": args.num_blocks, "res_scale": args.res_scale}
     model = load_generator(opt, args.perceptual_model, args.scale).to(device)
     print("Number of parameters:", sum(p.nelement() for p in model.parameters()))
@@ -276,7 +258,7 @@ def main(argv=None):
         model_psnr = load_generator(opt, args.psnr_model, args.scale).to(device)
     save_path = os.path.join(args.save_path, args.dataset)
     os.makedirs(save_path, exist_ok=True)
-    psnrs, ssims, niqes, lpipss = [], [], [], []
+    rows = []           # per image: the scores of what was saved and, with --from_hr, of the bicubic baseline
     if args.tile:
         print(_tile.describe(args.tile, tile_halo, _tile.receptive_halo(args.num_blocks, args.scale)))
     with torch.no_grad():
@@ -300,38 +282,15 @@ def main(argv=None):
                     out = args.alpha * out + (1 - args.alpha) * x8_forward(inp, model_psnr)
                 [img] = tensors_to_imgs([out])
             _write_png(os.path.join(save_path, os.path.basename(lr_path)), img)
-            if args.from_hr:
-                # the PSNR of what was SAVED: the uint8 image back on the device (compute_PSNR rounds the same way itself)
+            if scored:
+                # the scores of what was SAVED: the uint8 image back on the device (compute_PSNR rounds the same way itself); an LR-only
+                # set has no HR image and no baseline, and its NIQE needs neither
                 [sr] = imgs_to_tensors([img], device)
-                psnrs.append((compute_PSNR(sr, hr, shave), compute_PSNR(bic, hr, shave)))
-                line = "%s: PSNR-Y %.10f dB, bicubic %.10f dB" % ((os.path.basename(lr_path),) + psnrs[-1])
-                if args.ssim:
-                    ssims.append((compute_SSIM(sr, hr, shave), compute_SSIM(bic, hr, shave)))
-                    line += ", SSIM-Y %.10f, bicubic %.10f" % ssims[-1]
-                if niqe_model is not None:
-                    niqes.append((_niqe_of(sr, niqe_model, shave, lr_path), _niqe_of(bic, niqe_model, shave, lr_path)))
-                    line += ", NIQE %.10f, bicubic %.10f" % niqes[-1]
-                if lpips_model is not None:
-                    lpipss.append((compute_LPIPS(sr, hr, lpips_model, shave), compute_LPIPS(bic, hr, lpips_model, shave)))
-                    line += ", LPIPS %.10f, bicubic %.10f" % lpipss[-1]
-                print(line)
-            elif niqe_model is not None:
-                # an LR-only set: the NIQE of what was saved needs nothing else
-                [sr] = imgs_to_tensors([img], device)
-                niqes.append((_niqe_of(sr, niqe_model, shave, lr_path),))
-                print("%s: NIQE %.10f" % (os.path.basename(lr_path), niqes[-1][0]))
+                rows.append([_score(scorer, lr_path, t, hr) for t in (sr, bic)] if args.from_hr else [_score(scorer, lr_path, sr)])
+                print("%s: %s" % (os.path.basename(lr_path), scorer.test_line(*rows[-1])))
             print("Tested %d img(s)" % (i + 1))
-    if args.from_hr and psnrs:
-        line = "Mean PSNR-Y %.10f dB, bicubic %.10f dB" % (float(np.mean([p[0] for p in psnrs])), float(np.mean([p[1] for p in psnrs])))
-        if ssims:
-            line += ", SSIM-Y %.10f, bicubic %.10f" % (float(np.mean([q[0] for q in ssims])), float(np.mean([q[1] for q in ssims])))
-        if niqes:
-            line += ", NIQE %.10f, bicubic %.10f" % (float(np.mean([q[0] for q in niqes])), float(np.mean([q[1] for q in niqes])))
-        if lpipss:
-            line += ", LPIPS %.10f, bicubic %.10f" % (float(np.mean([q[0] for q in lpipss])), float(np.mean([q[1] for q in lpipss])))
-        print(line)
-    elif niqes:
-        print("Mean NIQE %.10f" % float(np.mean([q[0] for q in niqes])))
+    if rows:
+        print("Mean " + scorer.test_line(*(scorer.mean(r) for r in zip(*rows))))
     print("Finish")
 
 

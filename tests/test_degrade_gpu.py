@@ -382,3 +382,30 @@ def test_test_entrypoint_classical(tmp_path):
             assert torch.equal(lr_t[0].permute(1, 2, 0).to(torch.uint8).cpu(), torch.from_numpy(lr))
             assert torch.equal(bic_t[0].permute(1, 2, 0).to(torch.uint8).cpu(), torch.from_numpy(bic))
             assert torch.equal(hr_t[0].permute(1, 2, 0).to(torch.uint8).cpu(), torch.from_numpy(np.ascontiguousarray(hr)))
+
+
+@pytest.mark.parametrize("s", [2, 3, 4])
+def test_lr_image_is_the_composition_of_its_steps(s):
+    """degrade.lr_image_u8 (one-entry degrade_chain_pool_u8, the JPEG step in place on the chain's pool) against degrade_u8, then
+    resize_jitter_u8, then jpeg_u8, with the noise placed by hand: in the degrade launch without a jitter, in the jitter's second
+    resize with one.  All eight subsets of {noise, jitter, JPEG}; the 48 x 36 HR image gives LR sides 24 x 18, 16 x 12 and 12 x 9:
+    partial 8 x 8 and 16 x 16 JPEG blocks at 4:2:0.  Without a kernel: the bicubic resize, then the JPEG step when asked."""
+    from pesr_amd.degrade import degrade_u8, gaussian_kernel, kernel_size, lr_image_u8, resize_jitter_u8
+    from pesr_amd.jpeg import jpeg_u8
+    from pesr_amd.resize import imresize_u8
+    hr = torch.from_numpy(_rand(48, 36, 300 + s)).to(DEV)
+    k = gaussian_kernel(kernel_size(s, 2.0), 2.0, 1.1, 0.6)
+    for case in range(8):
+        sigma_n, jitter, q = (6.0 if case & 1 else 0.0), ((0.37, 2, 1) if case & 2 else None), (40 if case & 4 else 0)   # (box, bilinear)
+        want = degrade_u8(hr, s, k, 0.0 if jitter else sigma_n, 77)
+        if jitter:
+            want = resize_jitter_u8(want, jitter[0], jitter[1], jitter[2], sigma_n, 77)
+        if q:
+            want = jpeg_u8(want, q, True)
+        got = lr_image_u8(hr, s, k, sigma_n, 77, jitter, q, True)
+        assert got.dtype == torch.uint8 and tuple(got.shape) == (48 // s, 36 // s, 3)
+        assert torch.equal(got, want), (s, case)
+    bic = imresize_u8(hr, s, up=False)
+    assert torch.equal(lr_image_u8(hr, s), bic)
+    for chroma420 in (True, False):
+        assert torch.equal(lr_image_u8(hr, s, jpeg_q=40, jpeg_420=chroma420), jpeg_u8(bic, 40, chroma420))

@@ -148,8 +148,8 @@ def build_parser():
 
 def device_lr_from_hr(scale, device):
     """The callable FolderSRDataset(lr_from_hr=...) wants, on the device resize: uint8 HWC array -> uint8 HWC array."""
-    from pesr_amd.resize import imresize_u8
-    return lambda hr: imresize_u8(torch.from_numpy(np.array(hr)).to(device), scale, up=False).cpu().numpy()
+    from pesr_amd.degrade import lr_image_u8
+    return lambda hr: lr_image_u8(torch.from_numpy(np.array(hr)).to(device), scale).cpu().numpy()
 
 
 VALID_DEGRADE_SEED = 20240229      # --degradation classical: the validation images' kernels and noise never change
@@ -188,19 +188,14 @@ def device_degrade_from_hr(scale, spec, device):
     4m (the noise then in its second resize), a spec with a JPEG range compresses it last (section 4l): both take their values from
     the same stream, after the other values."""
     import random
-    from pesr_amd.degrade import degrade_u8, gaussian_kernel, kernel_size, resize_jitter_u8
+    from pesr_amd.degrade import gaussian_kernel, kernel_size, lr_image_u8
     K = kernel_size(scale, spec.sigma_hi)
 
     def make(hr, i):
         d = spec.named(spec.draw(random.Random(VALID_DEGRADE_SEED * 1000003 + i)))
-        lr = degrade_u8(torch.from_numpy(np.array(hr)).to(device), scale, gaussian_kernel(K, d["sigma1"], d["sigma2"], d["theta"]),
-                        0.0 if spec.jitter_hi else d["sigma_n"], d["q"])
-        if spec.jitter_hi:
-            lr = resize_jitter_u8(lr, d["jitter_r"], d["jitter_m1"], d["jitter_m2"], d["sigma_n"], d["q"])
-        if spec.jpeg_hi:
-            from pesr_amd.jpeg import jpeg_u8
-            lr = jpeg_u8(lr, d["jpeg_quality"], spec.jpeg_420)
-        return lr.cpu().numpy()
+        return lr_image_u8(torch.from_numpy(np.array(hr)).to(device), scale, gaussian_kernel(K, d["sigma1"], d["sigma2"], d["theta"]),
+                           d["sigma_n"], d["q"], (d["jitter_r"], d["jitter_m1"], d["jitter_m2"]) if spec.jitter_hi else None,
+                           d.get("jpeg_quality", 0), spec.jpeg_420).cpu().numpy()
     return make
 
 
@@ -365,31 +360,19 @@ def check_limits(args, world):
                          "which this implementation does for even sizes only)")
 
 
-def niqe_model_of(args):
-    """--valid_niqe -> its model (None without the flag); SystemExit naming the flags.  No GPU is touched."""
-    if not args.valid_niqe:
-        return None
-    from pesr_amd import niqe as _niqe
-    model = _niqe.load_model_flag("train.py", "--valid_niqe", args.valid_niqe)
+def scorer_of(args):
+    """The --valid_* flags -> the Scorer of the validation (pesr_amd/quality.py); SystemExit naming the flags.  No GPU is touched."""
+    from pesr_amd.quality import Scorer
+    scorer = Scorer("train.py", args.valid_ssim, args.valid_shave, args.valid_niqe, args.valid_lpips,
+                    flags=("--valid_niqe", "--valid_lpips", "--valid_shave"), size_flags="--valid_shave / --patch_size")
     if args.synthetic:          # (the synthetic validation images are patch-sized; a folder's sizes are known when it is read)
-        side = args.patch_size * args.scale
-        _niqe.check_fits_flag("train.py", "--valid_niqe / --valid_shave / --patch_size", model, side, side, args.valid_shave,
-                              "the synthetic validation images")
-    return model
+        scorer.check_size(args.patch_size * args.scale, args.patch_size * args.scale, "the synthetic validation images")
+    return scorer
 
 
 def lpips_model_of(args):
-    """--valid_lpips -> its model (None without the flag); SystemExit naming the flags.  No GPU is touched."""
-    if not args.valid_lpips:
-        return None
-    from pesr_amd import lpips as _lpips
-    model = _lpips.load_model_flag("train.py", "--valid_lpips", args.valid_lpips)
-    if args.synthetic:
-        side = args.patch_size * args.scale - 2 * args.valid_shave
-        if side < _lpips.MIN_SIDE:
-            raise SystemExit(f"train.py: --valid_lpips / --valid_shave / --patch_size: the synthetic validation images are {max(side, 0)} x "
-                             f"{max(side, 0)} after the shave; LPIPS needs at least {_lpips.MIN_SIDE} x {_lpips.MIN_SIDE}")
-    return model
+    """--valid_lpips -> its model (None without the flag), as scorer_of(args) holds it."""
+    return scorer_of(args).lpips_model
 
 
 def lpips_loss_model_of(args, valid_model=None):
@@ -423,9 +406,8 @@ def lpips_loss_model_of(args, valid_model=None):
 def main(argv=None):
     args = build_parser().parse_args(argv)
     degradation_spec(args)      # (refuses a classical run without its companion flags before anything else starts)
-    niqe_model = niqe_model_of(args)
-    lpips_model = lpips_model_of(args)
-    lpips_loss_model = lpips_loss_model_of(args, lpips_model)
+    scorer = scorer_of(args)
+    lpips_loss_model = lpips_loss_model_of(args, scorer.lpips_model)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -453,7 +435,7 @@ def main(argv=None):
     _ops.set_precision(args.precision)
     from pesr_amd.optim import FlatAdam
     from pesr_amd.step import Trainer
-    from utils import compute_LPIPS, compute_NIQE, compute_PSNR, compute_SSIM
+    from pesr_amd.quality import ScoreError
     from pesr_amd.tile import describe, receptive_halo, tiled_forward
     valid_halo = receptive_halo(args.num_blocks, args.scale) if args.valid_tile_halo == -1 else args.valid_tile_halo
     if args.valid_tile and rank == 0:
@@ -631,7 +613,7 @@ def main(argv=None):
 
         # validation on rank 0 (full images, batch 1, no_grad), reference train.py:281-295
         if rank == 0:
-            psnr, ssim, niqe, lpips_v = [], [], [], []
+            scores = []
             if G_eval is not G:
                 optim_G.refresh_ema()       # the steps of this epoch rewrote the averaged weights through raw pointers
             with torch.no_grad():
@@ -640,39 +622,17 @@ def main(argv=None):
                         sr, _ = tiled_forward(G_eval, lr_img.to(device), args.scale, args.valid_tile, valid_halo)
                     else:
                         sr = G_eval(lr_img.to(device))
-                    hr_img = hr_img.to(device)
-                    psnr.append(compute_PSNR(hr_img, sr, args.valid_shave))
-                    if args.valid_ssim:
-                        ssim.append(compute_SSIM(hr_img, sr, args.valid_shave))
-                    if niqe_model is not None:
-                        try:
-                            niqe.append(compute_NIQE(sr, niqe_model, args.valid_shave))
-                        except ValueError as e:
-                            raise SystemExit(f"train.py: --valid_niqe / --valid_shave: a validation image: {e}")
-                    if lpips_model is not None:
-                        try:        # (of the uint8 values the result would be saved as)
-                            lpips_v.append(compute_LPIPS(sr.clamp(0, 255).round(), hr_img, lpips_model, args.valid_shave))
-                        except ValueError as e:
-                            raise SystemExit(f"train.py: --valid_lpips / --valid_shave: a validation image: {e}")
-            val_psnr = float(np.mean(psnr)) if psnr else 0.0
-            print("Finish valid [%d/%d]. PSNR: %.4fdB%s" % (epoch, args.num_epochs, val_psnr, ema_tag))
-            if tb is not None:
-                tb.add_scalar("Validate PSNR", val_psnr, epoch)
-            if args.valid_ssim:
-                val_ssim = float(np.mean(ssim)) if ssim else 0.0
-                print("Finish valid [%d/%d]. SSIM: %.6f" % (epoch, args.num_epochs, val_ssim))
+                    try:
+                        scores.append(scorer.score(sr, hr_img.to(device)))
+                    except ScoreError as e:
+                        raise SystemExit(f"train.py: {e.flags}: a validation image: {e}")
+            means = scorer.mean(scores, scorer.columns())
+            val_psnr = means["PSNR-Y"]
+            # per column: "Finish valid [e/E]. NAME: value" and the tensorboard scalar "Validate NAME"
+            for line, tag, value in scorer.valid_lines(epoch, args.num_epochs, means, ema_tag):
+                print(line)
                 if tb is not None:
-                    tb.add_scalar("Validate SSIM", val_ssim, epoch)
-            if niqe_model is not None:
-                val_niqe = float(np.mean(niqe)) if niqe else 0.0
-                print("Finish valid [%d/%d]. NIQE: %.6f" % (epoch, args.num_epochs, val_niqe))
-                if tb is not None:
-                    tb.add_scalar("Validate NIQE", val_niqe, epoch)
-            if lpips_model is not None:
-                val_lpips = float(np.mean(lpips_v)) if lpips_v else 0.0
-                print("Finish valid [%d/%d]. LPIPS: %.6f" % (epoch, args.num_epochs, val_lpips))
-                if tb is not None:
-                    tb.add_scalar("Validate LPIPS", val_lpips, epoch)
+                    tb.add_scalar(tag, value, epoch)
             if not gan and val_psnr > best_psnr:
                 best_psnr = val_psnr
                 torch.save(G_eval.state_dict(), os.path.join(check_point, "best_model.pt"))
