@@ -18,7 +18,7 @@ template <int WHICH>
 __global__ __launch_bounds__(256) void bn_reduce_kernel(const float* __restrict__ x, const float* __restrict__ dy,
                                                         const float* __restrict__ mean_invstd, const float* __restrict__ gamma,
                                                         const float* __restrict__ beta, float* __restrict__ part, long M, int C,
-                                                        long rows_per_block, float slope, long dy_sn, long dy_sc, long dy_sp, long HW) {
+                                                        long rows_per_block, float slope) {
     const int C4 = C >> 2;
     const int cw = C4 < 256 ? C4 : 256;
     const int rl = 256 / cw;
@@ -41,13 +41,7 @@ __global__ __launch_bounds__(256) void bn_reduce_kernel(const float* __restrict_
                     const f64x4 vd = __builtin_convertvector(v, f64x4);
                     s0 += vd; s1 += vd * vd;
                 } else {
-                    f32x4 g;
-                    if (dy_sc == 1) g = ((const f32x4*)dy)[rr * C4 + c4];
-                    else {  // dy stored NCHW (flattened classifier input): gather 4 channels
-                        const long n = rr / HW, p = rr - n * HW;
-                        const float* q = dy + n * dy_sn + p * dy_sp + (long)(c4 * 4) * dy_sc;
-                        g = (f32x4){q[0], q[dy_sc], q[2 * dy_sc], q[3 * dy_sc]};
-                    }
+                    const f32x4 g = ((const f32x4*)dy)[rr * C4 + c4];
                     const f32x4 xh = (v - mu) * is;
                     const f32x4 z = ga * xh + be;
                     f32x4 dz;
@@ -167,24 +161,16 @@ __global__ void bn_apply_kernel(const f32x4* __restrict__ x, const float* __rest
 // premasked: dy already is dz = dy * lrelu'(z) (written by the conv kernel that produced it, common.h BnEpi mode 2)
 __global__ void bn_bwd_apply_kernel(const f32x4* __restrict__ x, const float* __restrict__ dy, const float* __restrict__ mean_invstd,
                                     const float* __restrict__ gamma, const float* __restrict__ beta, const float* __restrict__ sums,
-                                    f32x4* __restrict__ dx, long M, int C, float slope, long HW, long dy_sn, long dy_sc, long dy_sp,
-                                    int premasked) {
+                                    f32x4* __restrict__ dx, long M, int C, float slope, int premasked) {
     const int C4 = C >> 2;
     const long total = M * C4;
     const float invM = 1.0f / (float)M;
     for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (long)gridDim.x * blockDim.x) {
         const int c4 = (int)(e % C4);
-        const long rr = e / C4;
+        const f32x4 g = ((const f32x4*)dy)[e];
         const f32x4 mu = ((const f32x4*)mean_invstd)[c4], is = ((const f32x4*)(mean_invstd + C))[c4];
         const f32x4 ga = ((const f32x4*)gamma)[c4], be = ((const f32x4*)beta)[c4];
         const f32x4 sdz = ((const f32x4*)sums)[c4] * invM, sdzx = ((const f32x4*)(sums + C))[c4] * invM;
-        f32x4 g;
-        if (dy_sc == 1) g = ((const f32x4*)dy)[e];
-        else {
-            const long n = rr / HW, p = rr - n * HW;
-            const float* q = dy + n * dy_sn + p * dy_sp + (long)(c4 * 4) * dy_sc;
-            g = (f32x4){q[0], q[dy_sc], q[2 * dy_sc], q[3 * dy_sc]};
-        }
         const f32x4 xh = (x[e] - mu) * is;
         const f32x4 z = ga * xh + be;
         f32x4 dz = g;
@@ -241,16 +227,76 @@ static void bn_grid(long M, long* nb, long* rpb) {
     *rpb = (M + b - 1) / b;
     *nb = (M + *rpb - 1) / *rpb;
 }
+// blocks of an elementwise pass over [M][C / 4] float4 groups (grid-stride loop, 256 threads)
+static int bn_elem_grid(long M, int C) {
+    const long blocks = (M * (C / 4) + 255) / 256;
+    return (int)(blocks < 8192 ? blocks : 8192);
+}
+
+// workspace of the stand-alone passes: part [nb][2][C] (bn_reduce_kernel's per-block sums), sums [2][C] (the backward's reduced sums)
+// and dyt, room for an NHWC copy of an NCHW gradient
+struct BnWs {
+    long nb, rpb;           // bn_grid(M)
+    float *part, *sums;
+    float* dyt;             // null where the workspace given ends before the copy
+    size_t bytes;           // what pesr_bn_ws_bytes reports
+};
+// false: ws is missing or too small for part and sums
+static bool bn_ws_layout(long M, int C, void* ws, size_t ws_bytes, BnWs* w) {
+    bn_grid(M, &w->nb, &w->rpb);
+    const size_t part_bytes = (size_t)w->nb * 2 * C * sizeof(float), sums_bytes = 2 * (size_t)C * sizeof(float);
+    const size_t dyt_off = (part_bytes + sums_bytes + 255) / 256 * 256, copy = (size_t)M * C * sizeof(float);
+    w->bytes = dyt_off + copy;
+    const bool ok = ws && ws_bytes >= dyt_off;
+    w->part = ok ? (float*)ws : nullptr;
+    w->sums = ok ? (float*)((char*)ws + part_bytes) : nullptr;
+    w->dyt = ok && ws_bytes >= dyt_off + copy ? (float*)((char*)ws + dyt_off) : nullptr;
+    return ok;
+}
+
+static void bn_apply_launch(const float* x, const float* mean_invstd, const float* gamma, const float* beta, float* y, long M, int C, long HW,
+                            float slope, int y_nchw, hipStream_t stream) {
+    long ysn = HW * C, ysc = 1, ysp = C;        // (image, channel, pixel) strides of y [N][HW][C]
+    if (y_nchw) { ysc = HW; ysp = 1; }          // ... or [N][C][HW]
+    hipLaunchKernelGGL(bn_apply_kernel, dim3(bn_elem_grid(M, C)), dim3(256), 0, stream, (const f32x4*)x, mean_invstd, gamma, beta, y, M, C, slope,
+                       HW, ysn, ysc, ysp);
+}
+// the gradient as the backward kernels read it, NHWC: an NCHW one is transposed into the workspace once (read in place, a channel-group
+// lane would gather its four channels HW floats apart); with HW == 1 the two layouts coincide.  null: no room for the copy
+static const float* bn_dy_nhwc(const float* dy, int dy_nchw, const BnWs& w, long M, int C, long HW, hipStream_t stream) {
+    if (!dy_nchw || HW == 1) return dy;
+    if (!w.dyt) return nullptr;
+    hipLaunchKernelGGL(nchw_to_nhwc_kernel, dim3((unsigned)((HW + 31) / 32), (unsigned)((C + 31) / 32), (unsigned)(M / HW)), dim3(256), 0, stream,
+                       dy, w.dyt, C, (int)HW);
+    return w.dyt;
+}
+// forward tail: statistics from part [rows][2][C] (mean_invstd, running statistics), then y = lrelu(bn(x))
+static int bn_fwd_tail(const float* part, int rows, const float* x, const float* gamma, const float* beta, float* y, float* mean_invstd,
+                       float* running_mean, float* running_var, long long* num_batches, long M, int C, long HW, float eps, float momentum,
+                       float slope, int y_nchw, hipStream_t stream) {
+    bn_finalize_launch(part, rows, C, M, eps, momentum, mean_invstd, running_mean, running_var, num_batches, stream);
+    bn_apply_launch(x, mean_invstd, gamma, beta, y, M, C, HW, slope, y_nchw, stream);
+    return pesr_launch_status();
+}
+// backward tail: part [rows][2][C] (null: none wanted) -> sums and dgamma / dbeta; then dx from sums - or, with fixed statistics, from
+// zeros, where the batch-statistics terms of the formula vanish
+static int bn_bwd_tail(const float* part, int rows, const float* x, const float* dy, const float* gamma, const float* beta,
+                       const float* mean_invstd, float* sums, float* dx, float* dgamma, float* dbeta, int accumulate, bool batch_stats, long M,
+                       int C, float slope, int premasked, hipStream_t stream) {
+    if (part) bn_bwd_sums_launch(part, rows, C, sums, dbeta, dgamma, accumulate, stream);
+    if (!batch_stats) {
+        hipError_t e = hipMemsetAsync(sums, 0, 2 * (size_t)C * sizeof(float), stream);
+        if (e != hipSuccess) return (int)e;
+    }
+    hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(bn_elem_grid(M, C)), dim3(256), 0, stream, (const f32x4*)x, dy, mean_invstd, gamma, beta,
+                       (const float*)sums, (f32x4*)dx, M, C, slope, premasked);
+    return pesr_launch_status();
+}
 }  // namespace
 
-static size_t bn_ws_base(long M, int C) {
-    long nb, rpb; bn_grid(M, &nb, &rpb);
-    return ((size_t)nb * 2 * C * sizeof(float) + 2 * (size_t)C * sizeof(float) + 2 * (size_t)C * sizeof(double) + 512 + 255) / 256 * 256;
-}
-// + room for an NHWC copy of an NCHW gradient (small tensors only: the layer in front of the classifier)
 size_t pesr_bn_ws_bytes(long M, int C) {
-    const size_t copy = (size_t)M * C * sizeof(float);
-    return bn_ws_base(M, C) + (copy <= ((size_t)64 << 20) ? copy : 0);
+    BnWs w; bn_ws_layout(M, C, nullptr, 0, &w);
+    return w.bytes;
 }
 
 // forward: x [M][C] (M = N*H*W) -> y; saves mean_invstd [2][C]
@@ -258,21 +304,12 @@ int pesr_bn_lrelu_fwd_launch(const float* x, const float* gamma, const float* be
                              float* running_mean, float* running_var, long long* num_batches, long M, int C, long HW, float eps,
                              float momentum, float slope, int y_nchw, void* ws, size_t ws_bytes, hipStream_t stream) {
     if (C % 4) return PESR_EINVAL;
-    long nb, rpb; bn_grid(M, &nb, &rpb);
-    const size_t dsum_bytes = ((size_t)2 * C * sizeof(double) + 255) / 256 * 256;
-    if (!ws || ws_bytes < dsum_bytes + (size_t)nb * 2 * C * sizeof(float)) return PESR_EWORKSPACE;
-    double* dsum = (double*)ws;
-    float* part = (float*)((char*)ws + dsum_bytes);
-    hipLaunchKernelGGL(bn_reduce_kernel<0>, dim3((unsigned)nb), dim3(256), 0, stream, x, (const float*)nullptr, (const float*)nullptr,
-                       (const float*)nullptr, (const float*)nullptr, part, M, C, rpb, slope, 0L, 1L, 0L, HW);
-    bn_finalize_launch(part, (int)nb, C, M, eps, momentum, mean_invstd, running_mean, running_var, num_batches, stream);
-    const long total = M * (C / 4);
-    const int grid = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
-    long ysn = HW * C, ysc = 1, ysp = C;
-    if (y_nchw) { ysn = HW * C; ysc = HW; ysp = 1; }
-    hipLaunchKernelGGL(bn_apply_kernel, dim3(grid), dim3(256), 0, stream, (const f32x4*)x, (const float*)mean_invstd, gamma, beta, y, M, C,
-                       slope, HW, ysn, ysc, ysp);
-    return pesr_launch_status();
+    BnWs w;
+    if (!bn_ws_layout(M, C, ws, ws_bytes, &w)) return PESR_EWORKSPACE;
+    hipLaunchKernelGGL(bn_reduce_kernel<0>, dim3((unsigned)w.nb), dim3(256), 0, stream, x, (const float*)nullptr, (const float*)nullptr,
+                       (const float*)nullptr, (const float*)nullptr, w.part, M, C, w.rpb, slope);
+    return bn_fwd_tail(w.part, (int)w.nb, x, gamma, beta, y, mean_invstd, running_mean, running_var, num_batches, M, C, HW, eps, momentum,
+                       slope, y_nchw, stream);
 }
 
 // conv 3 -> C (no bias) -> BatchNorm (training) -> LeakyReLU with the statistics taken from the conv kernel's epilogue (SURVEY K10's
@@ -294,15 +331,8 @@ int pesr_conv_rgb_bn_lrelu_fwd_launch(const float* x, const float* w, float* z, 
     float* part = (float*)ws;
     int rc = pesr_conv_rgb_in_stats_launch(x, w, z, part, N, H, W, C, stream);
     if (rc) return rc;
-    const long M = (long)N * H * W, HW = (long)H * W;
-    bn_finalize_launch(part, rows, C, M, eps, momentum, mean_invstd, running_mean, running_var, num_batches, stream);
-    const long total = M * (C / 4);
-    const int grid = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
-    long ysn = HW * C, ysc = 1, ysp = C;
-    if (y_nchw) { ysn = HW * C; ysc = HW; ysp = 1; }
-    hipLaunchKernelGGL(bn_apply_kernel, dim3(grid), dim3(256), 0, stream, (const f32x4*)z, (const float*)mean_invstd, gamma, beta, y, M, C,
-                       slope, HW, ysn, ysc, ysp);
-    return pesr_launch_status();
+    return bn_fwd_tail(part, rows, z, gamma, beta, y, mean_invstd, running_mean, running_var, num_batches, (long)N * H * W, C, (long)H * W, eps,
+                       momentum, slope, y_nchw, stream);
 }
 
 // backward: dy is the gradient w.r.t. the LeakyReLU output (NHWC, or NCHW when dy_nchw); dgamma/dbeta may be NULL
@@ -310,33 +340,11 @@ int pesr_bn_lrelu_bwd_launch(const float* x, const float* dy, const float* gamma
                              float* dx, float* dgamma, float* dbeta, long M, int C, long HW, float slope, int dy_nchw, int accumulate,
                              void* ws, size_t ws_bytes, hipStream_t stream) {
     if (C % 4) return PESR_EINVAL;
-    long nb, rpb; bn_grid(M, &nb, &rpb);
-    const size_t part_bytes = (size_t)nb * 2 * C * sizeof(float);
-    const size_t dsum_bytes = ((size_t)2 * C * sizeof(double) + 255) / 256 * 256;
-    if (!ws || ws_bytes < dsum_bytes + part_bytes + 2 * (size_t)C * sizeof(float)) return PESR_EWORKSPACE;
-    double* dsum = (double*)ws;
-    float* part = (float*)((char*)ws + dsum_bytes);
-    float* sums = (float*)((char*)ws + dsum_bytes + part_bytes);
-    long sn = HW * C, sc = 1, sp = C;
-    if (dy_nchw) {
-        const size_t base = bn_ws_base(M, C), copy = (size_t)M * C * sizeof(float);
-        if (ws_bytes >= base + copy && HW > 1) {      // transpose once, then the coalesced NHWC paths
-            float* dyt = (float*)((char*)ws + base);
-            hipLaunchKernelGGL(nchw_to_nhwc_kernel, dim3((unsigned)((HW + 31) / 32), (unsigned)((C + 31) / 32), (unsigned)(M / HW)), dim3(256), 0, stream,
-                               dy, dyt, C, (int)HW);
-            dy = dyt;
-        } else {
-            sn = HW * C; sc = HW; sp = 1;
-        }
-    }
-    hipLaunchKernelGGL(bn_reduce_kernel<1>, dim3((unsigned)nb), dim3(256), 0, stream, x, dy, mean_invstd, gamma, beta, part, M, C, rpb, slope,
-                       sn, sc, sp, HW);
-    bn_bwd_sums_launch(part, (int)nb, C, sums, dbeta, dgamma, accumulate, stream);
-    const long total = M * (C / 4);
-    const int grid = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
-    hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(grid), dim3(256), 0, stream, (const f32x4*)x, dy, mean_invstd, gamma, beta, (const float*)sums,
-                       (f32x4*)dx, M, C, slope, HW, sn, sc, sp, 0);
-    return pesr_launch_status();
+    BnWs w;
+    if (!bn_ws_layout(M, C, ws, ws_bytes, &w)) return PESR_EWORKSPACE;
+    if (!(dy = bn_dy_nhwc(dy, dy_nchw, w, M, C, HW, stream))) return PESR_EWORKSPACE;
+    hipLaunchKernelGGL(bn_reduce_kernel<1>, dim3((unsigned)w.nb), dim3(256), 0, stream, x, dy, mean_invstd, gamma, beta, w.part, M, C, w.rpb, slope);
+    return bn_bwd_tail(w.part, (int)w.nb, x, dy, gamma, beta, mean_invstd, w.sums, dx, dgamma, dbeta, accumulate, true, M, C, slope, 0, stream);
 }
 
 // ---- round 6: the two halves of the BatchNorm whose sums come out of a conv kernel's epilogue (common.h BnEpi) -----------------------
@@ -355,13 +363,7 @@ int pesr_bn_lrelu_bwd_fused_launch(const float* z, const float* gmasked, const f
                                    void* ws, size_t ws_bytes, hipStream_t stream) {
     if (C % 4 || rows < 1 || !part) return PESR_EINVAL;
     if (!ws || ws_bytes < 2 * (size_t)C * sizeof(float)) return PESR_EWORKSPACE;
-    float* sums = (float*)ws;
-    bn_bwd_sums_launch(part, rows, C, sums, dbeta, dgamma, accumulate, stream);
-    const long total = M * (C / 4);
-    const int grid = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
-    hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(grid), dim3(256), 0, stream, (const f32x4*)z, gmasked, mean_invstd, gamma, beta, (const float*)sums,
-                       (f32x4*)dz, M, C, 0.f, HW, HW * C, 1L, (long)C, 1);
-    return pesr_launch_status();
+    return bn_bwd_tail(part, rows, z, gmasked, gamma, beta, mean_invstd, (float*)ws, dz, dgamma, dbeta, accumulate, true, M, C, 0.f, 1, stream);
 }
 
 // ---- eval-mode BatchNorm (running statistics; nn.BatchNorm2d in .eval(), a constructor branch of reference model/basic.py:29) ----
@@ -369,12 +371,7 @@ int pesr_bn_lrelu_bwd_fused_launch(const float* z, const float* gmasked, const f
 int pesr_bn_lrelu_apply_launch(const float* x, const float* gamma, const float* beta, const float* mean_invstd, float* y, long M,
                                int C, long HW, float slope, int y_nchw, hipStream_t stream) {
     if (C % 4) return PESR_EINVAL;
-    const long total = M * (C / 4);
-    const int grid = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
-    long ysn = HW * C, ysc = 1, ysp = C;
-    if (y_nchw) { ysn = HW * C; ysc = HW; ysp = 1; }
-    hipLaunchKernelGGL(bn_apply_kernel, dim3(grid), dim3(256), 0, stream, (const f32x4*)x, mean_invstd, gamma, beta, y, M, C, slope, HW,
-                       ysn, ysc, ysp);
+    bn_apply_launch(x, mean_invstd, gamma, beta, y, M, C, HW, slope, y_nchw, stream);
     return pesr_launch_status();
 }
 
@@ -384,27 +381,15 @@ int pesr_bn_lrelu_bwd_eval_launch(const float* x, const float* dy, const float* 
                                   float* dx, float* dgamma, float* dbeta, long M, int C, long HW, float slope, int dy_nchw, void* ws,
                                   size_t ws_bytes, hipStream_t stream) {
     if (C % 4) return PESR_EINVAL;
-    long nb, rpb; bn_grid(M, &nb, &rpb);
-    const size_t part_bytes = (size_t)nb * 2 * C * sizeof(float);
-    const size_t dsum_bytes = ((size_t)2 * C * sizeof(double) + 255) / 256 * 256;
-    if (!ws || ws_bytes < dsum_bytes + part_bytes + 2 * (size_t)C * sizeof(float)) return PESR_EWORKSPACE;
-    double* dsum = (double*)ws;
-    float* part = (float*)((char*)ws + dsum_bytes);
-    float* sums = (float*)((char*)ws + dsum_bytes + part_bytes);
-    long sn = HW * C, sc = 1, sp = C;
-    if (dy_nchw) { sn = HW * C; sc = HW; sp = 1; }
-    if (dgamma || dbeta) {
-        hipLaunchKernelGGL(bn_reduce_kernel<1>, dim3((unsigned)nb), dim3(256), 0, stream, x, dy, mean_invstd, gamma, beta, part, M, C, rpb,
-                           slope, sn, sc, sp, HW);
-        bn_bwd_sums_launch(part, (int)nb, C, sums, dbeta, dgamma, 0, stream);
-    }
-    hipError_t e = hipMemsetAsync(sums, 0, 2 * (size_t)C * sizeof(float), stream);
-    if (e != hipSuccess) return (int)e;
-    const long total = M * (C / 4);
-    const int grid = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
-    hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(grid), dim3(256), 0, stream, (const f32x4*)x, dy, mean_invstd, gamma, beta, (const float*)sums,
-                       (f32x4*)dx, M, C, slope, HW, sn, sc, sp, 0);
-    return pesr_launch_status();
+    BnWs w;
+    if (!bn_ws_layout(M, C, ws, ws_bytes, &w)) return PESR_EWORKSPACE;
+    if (!(dy = bn_dy_nhwc(dy, dy_nchw, w, M, C, HW, stream))) return PESR_EWORKSPACE;
+    const bool want_sums = dgamma || dbeta;
+    if (want_sums)
+        hipLaunchKernelGGL(bn_reduce_kernel<1>, dim3((unsigned)w.nb), dim3(256), 0, stream, x, dy, mean_invstd, gamma, beta, w.part, M, C, w.rpb,
+                           slope);
+    return bn_bwd_tail(want_sums ? w.part : nullptr, (int)w.nb, x, dy, gamma, beta, mean_invstd, w.sums, dx, dgamma, dbeta, 0, false, M, C, slope, 0,
+                       stream);
 }
 
 // ---- backward OF the training-mode BatchNorm backward (gradient penalty, reference train.py:216-226: the penalty is a function
@@ -501,9 +486,7 @@ int pesr_bn_bwd_bwd_launch(const float* z, const float* du, const float* g, cons
     hipLaunchKernelGGL(bn_bwd2_reduce_kernel, dim3((unsigned)nb), dim3(256), 0, stream, z, du, g, mean_invstd, part, M, C, rpb);
     int rc0 = pesr_reduce_rows_launch(part, dsum, (int)nb, 5 * C, stream);
     if (rc0) return rc0;
-    const long total = M * (C / 4);
-    const int grid = (int)((total + 255) / 256 < 8192 ? (total + 255) / 256 : 8192);
-    hipLaunchKernelGGL(bn_bwd2_apply_kernel, dim3(grid), dim3(256), 0, stream, (const f32x4*)z, (const f32x4*)du, (const f32x4*)g, mean_invstd,
+    hipLaunchKernelGGL(bn_bwd2_apply_kernel, dim3(bn_elem_grid(M, C)), dim3(256), 0, stream, (const f32x4*)z, (const f32x4*)du, (const f32x4*)g, mean_invstd,
                        gamma, (const double*)dsum, (f32x4*)l_du, (f32x4*)l_z, l_gamma, M, C);
     return pesr_launch_status();
 }

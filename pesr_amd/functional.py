@@ -643,6 +643,23 @@ class BnLink:
         self.slope = 0.0
 
 
+def _conv_bn_fwd(x, weight, bias, gamma, beta, running_mean, running_var, num_batches, cache, stride, eps, momentum, slope, y_nchw, training):
+    """(z, y, stats) of conv -> BatchNorm -> activation, by the first route that covers the problem."""
+    if not training:        # running statistics
+        z = _conv_fwd(x, weight, bias, cache, stride)
+        stats = ops.bn_eval_stats(running_mean, running_var, eps)
+        return z, ops.bn_lrelu_eval_fwd(z, gamma, beta, stats, slope, y_nchw), stats
+    bn = (gamma, beta, running_mean, running_var, num_batches, eps, momentum, slope, y_nchw)
+    if bias is None and tuple(weight.shape[2:]) == (3, 3) and ops.conv_rgb_bn_eligible(x.shape[3], weight.shape[0], stride):
+        # the Discriminator's features.0: the statistics come out of the conv kernel's epilogue (no pass over z for them)
+        return ops.conv_rgb_bn_lrelu_fwd(x, weight.detach(), *bn)
+    res = ops.conv3x3_fwd_bn_stats(x, cache.for_fwd(weight, x.shape, stride), None if bias is None else bias.detach(), weight.shape[0], stride)
+    if res is not None:     # the sums came out of the conv kernel's epilogue: finalize + apply
+        return (res[0], *ops.bn_finalize_apply(*res, *bn))
+    z = _conv_fwd(x, weight, bias, cache, stride)
+    return (z, *ops.bn_lrelu_fwd(z, *bn))
+
+
 class ConvBnLReluFn(Function):
     """conv (bias optional) -> BatchNorm2d -> activation given by its negative slope (0.2 LeakyReLU, 0 ReLU, 1 none).
     training = True: batch statistics (and the running-stat update) - the Discriminator's only use; training = False: the
@@ -657,26 +674,8 @@ class ConvBnLReluFn(Function):
                 slope, y_nchw, training, prev_link=None, link=None):
         x = _c(x)
         ctx.prev_link, ctx.link = prev_link, None
-        if training and bias is None and tuple(weight.shape[2:]) == (3, 3) and ops.conv_rgb_bn_eligible(x.shape[3], weight.shape[0], stride):
-            # the Discriminator's features.0: the statistics come out of the conv kernel's epilogue (no pass over z for them)
-            z, y, stats = ops.conv_rgb_bn_lrelu_fwd(x, weight.detach(), gamma.detach(), beta.detach(), running_mean, running_var,
-                                                    num_batches, eps, momentum, slope, y_nchw)
-        else:
-            res = None
-            if training:
-                res = ops.conv3x3_fwd_bn_stats(x, cache.for_fwd(weight, x.shape, stride), None if bias is None else bias.detach(), weight.shape[0], stride)
-            if res is not None:
-                z, part = res
-                y, stats = ops.bn_finalize_apply(z, part, gamma.detach(), beta.detach(), running_mean, running_var, num_batches, eps, momentum,
-                                                 slope, y_nchw)
-            else:
-                z = _conv_fwd(x, weight, bias, cache, stride)
-                if training:
-                    y, stats = ops.bn_lrelu_fwd(z, gamma.detach(), beta.detach(), running_mean, running_var, num_batches, eps,
-                                                momentum, slope, y_nchw)
-                else:
-                    stats = ops.bn_eval_stats(running_mean, running_var, eps)
-                    y = ops.bn_lrelu_eval_fwd(z, gamma.detach(), beta.detach(), stats, slope, y_nchw)
+        z, y, stats = _conv_bn_fwd(x, weight, bias, gamma.detach(), beta.detach(), running_mean, running_var, num_batches, cache, stride, eps,
+                                   momentum, slope, y_nchw, training)
         if link is not None and training and not y_nchw:
             link.z, link.stats, link.gamma, link.beta, link.slope = z, stats, gamma.detach(), beta.detach(), slope
             ctx.link = link
@@ -689,7 +688,6 @@ class ConvBnLReluFn(Function):
         x, z, weight, gamma, beta, stats = ctx.saved_tensors
         gy = _c(gy)
         need_p = ctx.needs_input_grad[3] or ctx.needs_input_grad[4]
-        bwd = ops.bn_lrelu_bwd if ctx.training else ops.bn_lrelu_eval_bwd
         # the gradient that arrives was written by the consumer's input-gradient kernel, already multiplied by lrelu'(bn(z)), and that
         # kernel left the two sums of the BatchNorm backward (BnLink): no reduction pass
         link, part = ctx.link, None
@@ -698,22 +696,18 @@ class ConvBnLReluFn(Function):
                 raise RuntimeError("pesr_amd: the masked gradient a fused input-gradient kernel wrote for this BatchNorm did not arrive as "
                                    "written (its block's output has another consumer?)")
             part, link.part, link.g_ptr = link.part, None, None
-
-            def bwd(z_, gy_, gamma_, beta_, stats_, slope_, nchw_, need_, dgamma_out=None, dbeta_out=None, accumulate=False):   # noqa: F811
-                return ops.bn_lrelu_bwd_fused(z_, gy_, part, gamma_, beta_, stats_, need_, dgamma_out=dgamma_out, dbeta_out=dbeta_out,
-                                              accumulate=accumulate)
         # second use of this block inside one backward pass: the parameter gradients are ADDED to the slices the first use wrote
         # (autograd's fan-in add_ plus the copy of the sum into the flat buffer were two launches per parameter tensor); in-place
         # accumulation assumes every weight gradient is written on one stream
         again = _second_use((gamma, beta, weight), ctx.training and need_p and ctx.needs_input_grad[1] and ctx.bias_ref is None and _SIDE_OFF,
                             (gamma, beta, weight))
+        bn = (z, gy, gamma.detach(), beta.detach(), stats, ctx.slope, ctx.y_nchw)
         if again:
-            dz, _, _ = bwd(z, gy, gamma.detach(), beta.detach(), stats, ctx.slope, ctx.y_nchw, True, dgamma_out=again[0], dbeta_out=again[1],
-                           accumulate=True)
+            dz, _, _ = ops.bn_lrelu_backward(*bn, True, again[0], again[1], accumulate=True, training=ctx.training, part=part)
             dgamma = dbeta = None
         else:
-            dz, dgamma, dbeta = bwd(z, gy, gamma.detach(), beta.detach(), stats, ctx.slope, ctx.y_nchw, need_p,
-                                    dgamma_out=grad_out(gamma) if need_p else None, dbeta_out=grad_out(beta) if need_p else None)
+            dz, dgamma, dbeta = ops.bn_lrelu_backward(*bn, need_p, grad_out(gamma) if need_p else None, grad_out(beta) if need_p else None,
+                                                      training=ctx.training, part=part)
         need_dx = ctx.needs_input_grad[0]
         wpd = _dgrad_pack(weight, ctx.cache, x.shape, ctx.stride) if need_dx else None
         dw, db = _conv_wgrad(x, dz, weight, ctx.bias_ref, ctx.stride, ctx.cache.ps, ctx.needs_input_grad[1],

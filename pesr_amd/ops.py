@@ -852,13 +852,19 @@ def maxpool2x2_bwd(x: torch.Tensor, dy: torch.Tensor, relu_in: bool) -> torch.Te
 # ------------------------------------------------------------------------------------------------
 # BatchNorm(train) + LeakyReLU
 # ------------------------------------------------------------------------------------------------
+def _bn_y(x, y_nchw):
+    """The output of a BatchNorm + activation over x [N,H,W,C]: NHWC, or NCHW (the flatten in front of the classifier)."""
+    N, H, W, C = x.shape
+    return torch.empty((N, C, H, W) if y_nchw else (N, H, W, C), dtype=torch.float32, device=x.device)
+
+
 def bn_lrelu_fwd(x, gamma, beta, running_mean, running_var, num_batches, eps=1e-5, momentum=0.1, slope=0.2,
                  y_nchw=False):
     _chk(x, "bn_lrelu_fwd.x")
     N, H, W, C = x.shape
     L = _lib.lib()
     ws = workspace(L.pesr_bn_workspace_bytes(N * H * W, C), x.device)
-    y = torch.empty((N, C, H, W) if y_nchw else (N, H, W, C), dtype=torch.float32, device=x.device)
+    y = _bn_y(x, y_nchw)
     stats = torch.empty((2, C), dtype=torch.float32, device=x.device)
     rc = L.pesr_bn_lrelu_fwd(_p(x), _p(gamma), _p(beta), _p(y), _p(stats), _p(running_mean), _p(running_var),
                              _p(num_batches), N, H, W, C, eps, momentum, slope, int(y_nchw), _p(ws), ws.numel(), _stream())
@@ -882,7 +888,7 @@ def conv_rgb_bn_lrelu_fwd(x, w_oihw, gamma, beta, running_mean, running_var, num
     L = _lib.lib()
     ws = workspace(L.pesr_conv3x3_rgb_bn_workspace_bytes(N, H, W, C), x.device)
     z = torch.empty((N, H, W, C), dtype=torch.float32, device=x.device)
-    y = torch.empty((N, C, H, W) if y_nchw else (N, H, W, C), dtype=torch.float32, device=x.device)
+    y = _bn_y(z, y_nchw)
     stats = torch.empty((2, C), dtype=torch.float32, device=x.device)
     _conv_flops(N, H, W, Cin, C, _RGB_VALU)
     rc = L.pesr_conv3x3_rgb_bn_lrelu_fwd(_p(x), _p(w_oihw), _p(z), _p(gamma), _p(beta), _p(y), _p(stats), _p(running_mean), _p(running_var),
@@ -918,34 +924,43 @@ def _fuse_struct(mode, part, z=None, stats=None, gamma=None, beta=None, slope=0.
     return f
 
 
+def _conv3x3_bn(kind, src, wp, bias, N, H, W, Cin, cout, stride, mode, **bn):
+    """A conv [N,H,W,Cin] -> cout whose kernel leaves BatchNorm sums: kind "fwd" runs it on src = x, kind "dgrad" its input gradient on
+    src = dy -> (out, part [rows, 2, channels of out]) or None when the fused form does not cover this problem / packing."""
+    fwd = kind == "fwd"
+    four = isinstance(wp, Wino4Packed)
+    if not four and not torch.is_tensor(wp):
+        return None
+    ci, co = (Cin, cout) if fwd else (cout, Cin)        # channels of src and of out; the F(4,3) kernel (stride 1) runs ci -> co either way
+    rows = conv_bn_rows(2, N, H, W, ci, co, 1) if four else conv_bn_rows(0 if fwd else 1, N, H, W, Cin, cout, stride)
+    if rows == 0:
+        return None
+    OH, OW = (H - 1) // stride + 1, (W - 1) // stride + 1
+    oshape = (N, OH, OW, co) if fwd else (N, H, W, co)
+    L = _lib.lib()
+    out = torch.empty(oshape, dtype=torch.float32, device=src.device)
+    part = torch.empty((rows, 2, co), dtype=torch.float32, device=src.device)
+    f = _fuse_struct(mode, part, **bn)
+    nws = L.pesr_conv3x3_workspace_bytes(*oshape) if fwd or stride == 1 else 0
+    ws = workspace(nws, src.device) if nws else None
+    _conv_flops(N, OH, OW, Cin, cout, _conv_family(wp))
+    br = KERNEL_EVENTS.begin(kind, N, H, W, Cin, cout, stride)
+    if four:
+        rc = L.pesr_conv3x3_wino4_bn(_p(src), _p(wp.t), _p(bias), _p(out), N, H, W, ci, co, _p(ws), nws, ctypes.byref(f), _stream())
+    elif fwd:
+        rc = L.pesr_conv3x3_fwd_bn(_p(src), _p(wp), _p(bias), _p(out), N, H, W, Cin, cout, stride, _p(ws), nws, ctypes.byref(f), _stream())
+    else:
+        rc = L.pesr_conv3x3_dgrad_bn(_p(src), _p(wp), _p(out), N, H, W, Cin, cout, stride, _p(ws), nws, ctypes.byref(f), _stream())
+    KERNEL_EVENTS.end(br)
+    _lib.check(rc, f"pesr_conv3x3_{'wino4' if four else kind}_bn[{N}x{H}x{W}x{Cin}{'->' if fwd else '<-'}{cout},s{stride}]")
+    return out, part
+
+
 def conv3x3_fwd_bn_stats(x: torch.Tensor, wp, bias: Optional[torch.Tensor], cout: int, stride: int = 1):
     """z = conv(x) (+ bias) with the per-pixel-tile sums of z and z^2 left by the kernel's epilogue -> (z, part [rows, 2, cout]) or None when
     the fused form does not cover this problem / packing (the caller then runs conv3x3_fwd + bn_lrelu_fwd)."""
     _chk(x, "conv3x3_fwd_bn_stats.x")
-    N, H, W, Cin = x.shape
-    four = isinstance(wp, Wino4Packed)
-    if not four and not torch.is_tensor(wp):
-        return None
-    rows = conv_bn_rows(2, N, H, W, Cin, cout, 1) if four else conv_bn_rows(0, N, H, W, Cin, cout, stride)
-    if rows == 0:
-        return None
-    OH, OW = (H - 1) // stride + 1, (W - 1) // stride + 1
-    L = _lib.lib()
-    z = torch.empty((N, OH, OW, cout), dtype=torch.float32, device=x.device)
-    part = torch.empty((rows, 2, cout), dtype=torch.float32, device=x.device)
-    f = _fuse_struct(BN_FWD_STATS, part)
-    nws = L.pesr_conv3x3_workspace_bytes(N, OH, OW, cout)
-    ws = workspace(nws, x.device) if nws else None
-    fam = _conv_family(wp)
-    _conv_flops(N, OH, OW, Cin, cout, fam)
-    br = KERNEL_EVENTS.begin("fwd", N, H, W, Cin, cout, stride)
-    if four:
-        rc = L.pesr_conv3x3_wino4_bn(_p(x), _p(wp.t), _p(bias), _p(z), N, H, W, Cin, cout, _p(ws), nws, ctypes.byref(f), _stream())
-    else:
-        rc = L.pesr_conv3x3_fwd_bn(_p(x), _p(wp), _p(bias), _p(z), N, H, W, Cin, cout, stride, _p(ws), nws, ctypes.byref(f), _stream())
-    KERNEL_EVENTS.end(br)
-    _lib.check(rc, f"pesr_conv3x3_{'wino4' if four else 'fwd'}_bn[{N}x{H}x{W}x{Cin}->{cout},s{stride}]")
-    return z, part
+    return _conv3x3_bn("fwd", x, wp, bias, *x.shape, cout, stride, BN_FWD_STATS)
 
 
 def bn_finalize_apply(z, part, gamma, beta, running_mean, running_var, num_batches, eps=1e-5, momentum=0.1, slope=0.2, y_nchw=False):
@@ -955,7 +970,7 @@ def bn_finalize_apply(z, part, gamma, beta, running_mean, running_var, num_batch
     stats = torch.empty((2, C), dtype=torch.float32, device=z.device)
     _lib.check(L.pesr_bn_finalize(_p(part), part.shape[0], C, N * H * W, eps, momentum, _p(stats), _p(running_mean), _p(running_var),
                                   _p(num_batches), _stream()), "pesr_bn_finalize")
-    y = torch.empty((N, C, H, W) if y_nchw else (N, H, W, C), dtype=torch.float32, device=z.device)
+    y = _bn_y(z, y_nchw)
     _lib.check(L.pesr_bn_lrelu_eval_fwd(_p(z), _p(gamma), _p(beta), _p(stats), _p(y), N, H, W, C, slope, int(y_nchw), _stream()), "pesr_bn_lrelu_eval_fwd")
     return y, stats
 
@@ -964,64 +979,48 @@ def conv3x3_dgrad_bn_sums(dy: torch.Tensor, wpd, in_shape, stride, z, stats, gam
     """The input gradient dx of a conv whose INPUT was y = lrelu(bn(z)): the kernel stores g' = dx * lrelu'(bn(z)) and leaves the sums of g'
     and g' * xhat per pixel tile -> (g' [in_shape], part [rows, 2, C]) or None when the fused form does not cover the problem / packing."""
     _chk(dy, "conv3x3_dgrad_bn_sums.dy")
-    N, H, W, Cin = in_shape
-    cout = dy.shape[3]
-    four = isinstance(wpd, Wino4Packed)
-    if not four and not torch.is_tensor(wpd):
-        return None
-    rows = conv_bn_rows(2, N, H, W, cout, Cin, 1) if four else conv_bn_rows(1, N, H, W, Cin, cout, stride)
-    if rows == 0:
-        return None
     assert tuple(z.shape) == tuple(in_shape) and z.is_contiguous()
+    return _conv3x3_bn("dgrad", dy, wpd, None, *in_shape, dy.shape[3], stride, BN_BWD_MASK_SUMS, z=z, stats=stats, gamma=gamma, beta=beta,
+                       slope=slope)
+
+
+def _bn_param_grads(need_param_grads, dgamma_out, dbeta_out, C, device):
+    """(dgamma, dbeta) [C]: the caller's tensors where given, fresh ones else; (None, None) when not wanted."""
+    if not need_param_grads:
+        return None, None
+    return _out(dgamma_out, (C,), device), _out(dbeta_out, (C,), device)
+
+
+def bn_lrelu_backward(x, dy, gamma, beta, stats, slope=0.2, dy_nchw=False, need_param_grads=True, dgamma_out=None, dbeta_out=None,
+                      accumulate=False, training=True, part=None):
+    """Backward of y = lrelu(bn(x)) -> (dx, dgamma, dbeta).  training: batch statistics (bn_lrelu_bwd), else the running ones
+    (bn_lrelu_eval_bwd).  part: dy already is the masked gradient and part holds the sums its conv kernel left (bn_lrelu_bwd_fused).
+    accumulate: add to dgamma_out / dbeta_out (which then must be given) instead of overwriting them."""
+    fused = part is not None
+    fn = "bn_lrelu_bwd_fused" if fused else "bn_lrelu_bwd" if training else "bn_lrelu_eval_bwd"
+    _chk(dy, fn + (".g" if fused else ".dy"))
+    assert not accumulate or (dgamma_out is not None and dbeta_out is not None and (fused or training))
+    N, H, W, C = x.shape
     L = _lib.lib()
-    g = torch.empty((N, H, W, Cin), dtype=torch.float32, device=dy.device)
-    part = torch.empty((rows, 2, Cin), dtype=torch.float32, device=dy.device)
-    f = _fuse_struct(BN_BWD_MASK_SUMS, part, z, stats, gamma, beta, slope)
-    nws = L.pesr_conv3x3_workspace_bytes(N, H, W, Cin) if stride == 1 else 0
-    ws = workspace(nws, dy.device) if nws else None
-    fam = _conv_family(wpd)
-    _conv_flops(N, (H - 1) // stride + 1, (W - 1) // stride + 1, Cin, cout, fam)
-    br = KERNEL_EVENTS.begin("dgrad", N, H, W, Cin, cout, stride)
-    if four:
-        rc = L.pesr_conv3x3_wino4_bn(_p(dy), _p(wpd.t), None, _p(g), N, H, W, cout, Cin, _p(ws), nws, ctypes.byref(f), _stream())
-    else:
-        rc = L.pesr_conv3x3_dgrad_bn(_p(dy), _p(wpd), _p(g), N, H, W, Cin, cout, stride, _p(ws), nws, ctypes.byref(f), _stream())
-    KERNEL_EVENTS.end(br)
-    _lib.check(rc, f"pesr_conv3x3_{'wino4' if four else 'dgrad'}_bn[{N}x{H}x{W}x{Cin}<-{cout},s{stride}]")
-    return g, part
+    ws = workspace(2 * C * 4 + 256 if fused else L.pesr_bn_workspace_bytes(N * H * W, C), x.device)
+    dx = torch.empty_like(x)
+    dgamma, dbeta = _bn_param_grads(need_param_grads, dgamma_out, dbeta_out, C, x.device)
+    sums = (_p(part), part.shape[0]) if fused else ()
+    how = (int(accumulate),) if fused else (slope, int(dy_nchw), int(accumulate)) if training else (slope, int(dy_nchw))
+    rc = getattr(L, "pesr_" + fn)(_p(x), _p(dy), *sums, _p(gamma), _p(beta), _p(stats), _p(dx), _p(dgamma), _p(dbeta), N, H, W, C, *how,
+                                  _p(ws), ws.numel(), _stream())
+    _lib.check(rc, "pesr_" + fn)
+    return dx, dgamma, dbeta
 
 
 def bn_lrelu_bwd_fused(z, g_masked, part, gamma, beta, stats, need_param_grads=True, dgamma_out=None, dbeta_out=None, accumulate=False):
     """BatchNorm backward from the sums the producing conv kernel left (conv3x3_dgrad_bn_sums): -> (dz, dgamma, dbeta)."""
-    _chk(g_masked, "bn_lrelu_bwd_fused.g")
-    assert not accumulate or (dgamma_out is not None and dbeta_out is not None)
-    N, H, W, C = z.shape
-    L = _lib.lib()
-    ws = workspace(2 * C * 4 + 256, z.device)
-    dz = torch.empty_like(z)
-    dgamma = _out(dgamma_out, (C,), z.device) if need_param_grads else None
-    dbeta = _out(dbeta_out, (C,), z.device) if need_param_grads else None
-    rc = L.pesr_bn_lrelu_bwd_fused(_p(z), _p(g_masked), _p(part), part.shape[0], _p(gamma), _p(beta), _p(stats), _p(dz), _p(dgamma), _p(dbeta),
-                                   N, H, W, C, int(accumulate), _p(ws), ws.numel(), _stream())
-    _lib.check(rc, "pesr_bn_lrelu_bwd_fused")
-    return dz, dgamma, dbeta
+    return bn_lrelu_backward(z, g_masked, gamma, beta, stats, 0.0, False, need_param_grads, dgamma_out, dbeta_out, accumulate, True, part)
 
 
 def bn_lrelu_bwd(x, dy, gamma, beta, stats, slope=0.2, dy_nchw=False, need_param_grads=True, dgamma_out=None, dbeta_out=None,
                  accumulate=False):
-    """accumulate: add to dgamma_out / dbeta_out (which then must be given) instead of overwriting them."""
-    _chk(dy, "bn_lrelu_bwd.dy")
-    assert not accumulate or (dgamma_out is not None and dbeta_out is not None)
-    N, H, W, C = x.shape
-    L = _lib.lib()
-    ws = workspace(L.pesr_bn_workspace_bytes(N * H * W, C), x.device)
-    dx = torch.empty_like(x)
-    dgamma = _out(dgamma_out, (C,), x.device) if need_param_grads else None
-    dbeta = _out(dbeta_out, (C,), x.device) if need_param_grads else None
-    rc = L.pesr_bn_lrelu_bwd(_p(x), _p(dy), _p(gamma), _p(beta), _p(stats), _p(dx), _p(dgamma), _p(dbeta), N, H, W, C, slope,
-                             int(dy_nchw), int(accumulate), _p(ws), ws.numel(), _stream())
-    _lib.check(rc, "pesr_bn_lrelu_bwd")
-    return dx, dgamma, dbeta
+    return bn_lrelu_backward(x, dy, gamma, beta, stats, slope, dy_nchw, need_param_grads, dgamma_out, dbeta_out, accumulate)
 
 
 def bn_bwd_bwd(z, du, g, gamma, stats, need_du=True, need_z=True, need_gamma=True):
@@ -1047,24 +1046,14 @@ def bn_eval_stats(running_mean, running_var, eps=1e-5):
 def bn_lrelu_eval_fwd(x, gamma, beta, stats, slope=0.2, y_nchw=False):
     _chk(x, "bn_lrelu_eval_fwd.x")
     N, H, W, C = x.shape
-    y = torch.empty((N, C, H, W) if y_nchw else (N, H, W, C), dtype=torch.float32, device=x.device)
+    y = _bn_y(x, y_nchw)
     rc = _lib.lib().pesr_bn_lrelu_eval_fwd(_p(x), _p(gamma), _p(beta), _p(stats), _p(y), N, H, W, C, slope, int(y_nchw), _stream())
     _lib.check(rc, "pesr_bn_lrelu_eval_fwd")
     return y
 
 
 def bn_lrelu_eval_bwd(x, dy, gamma, beta, stats, slope=0.2, dy_nchw=False, need_param_grads=True, dgamma_out=None, dbeta_out=None):
-    _chk(dy, "bn_lrelu_eval_bwd.dy")
-    N, H, W, C = x.shape
-    L = _lib.lib()
-    ws = workspace(L.pesr_bn_workspace_bytes(N * H * W, C), x.device)
-    dx = torch.empty_like(x)
-    dgamma = _out(dgamma_out, (C,), x.device) if need_param_grads else None
-    dbeta = _out(dbeta_out, (C,), x.device) if need_param_grads else None
-    rc = L.pesr_bn_lrelu_eval_bwd(_p(x), _p(dy), _p(gamma), _p(beta), _p(stats), _p(dx), _p(dgamma), _p(dbeta), N, H, W, C, slope,
-                                  int(dy_nchw), _p(ws), ws.numel(), _stream())
-    _lib.check(rc, "pesr_bn_lrelu_eval_bwd")
-    return dx, dgamma, dbeta
+    return bn_lrelu_backward(x, dy, gamma, beta, stats, slope, dy_nchw, need_param_grads, dgamma_out, dbeta_out, training=False)
 
 
 # ------------------------------------------------------------------------------------------------

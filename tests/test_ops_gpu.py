@@ -164,6 +164,53 @@ def test_bn_lrelu(N, C, H, W, nchw):
     _close(_nchw(dx), xr.grad, 5e-5, "bn dx"); _close(dg.cpu(), gr.grad, 5e-5, "dgamma"); _close(db.cpu(), br.grad, 5e-5, "dbeta")
 
 
+# C = 8 and 36 leave the NCHW -> NHWC transposer's 32-channel tile ragged, HW = 15 and 35 its pixel tile; (4, 512, 2, 2) is the
+# Discriminator's last block at patch size 8; with HW = 1 the two layouts coincide
+_BN_EVAL_CASES = [(2, 8, 3, 5, False), (2, 8, 3, 5, True), (3, 36, 5, 7, True), (4, 512, 2, 2, True), (2, 64, 1, 1, True)]
+
+
+def _bn_case(N, C, H, W):
+    """x, gamma, beta, running mean in [-0.2, 0.2], running var in [0.5, 1.5], dy - all NCHW on the CPU."""
+    return (_rand(N, C, H, W, seed=1, lo=-2, hi=3), _rand(C, seed=2, lo=0.5, hi=1.5), _rand(C, seed=3, lo=-0.3, hi=0.3),
+            _rand(C, seed=5, lo=-0.2, hi=0.2), _rand(C, seed=6, lo=0.5, hi=1.5), _rand(N, C, H, W, seed=4))
+
+
+@pytest.mark.parametrize("N,C,H,W,nchw", _BN_EVAL_CASES)
+def test_bn_lrelu_eval(N, C, H, W, nchw):
+    """Eval-mode BatchNorm (running statistics) + LeakyReLU, forward and backward, against torch on the CPU in double; nchw: y is written
+    and dy arrives NCHW-contiguous."""
+    from pesr_amd import ops
+    x, gamma, beta, rm, rv, dy = _bn_case(N, C, H, W)
+    xr, gr, br = (t.double().requires_grad_(True) for t in (x, gamma, beta))
+    ref = F.leaky_relu(F.batch_norm(xr, rm.double(), rv.double(), gr, br, False, 0.1, 1e-5), 0.2)
+    ref.backward(dy.double())
+    stats = ops.bn_eval_stats(rm.cuda(), rv.cuda(), 1e-5)
+    xg, gg, bg = _nhwc(x), gamma.cuda(), beta.cuda()
+    y = ops.bn_lrelu_eval_fwd(xg, gg, bg, stats, 0.2, y_nchw=nchw)
+    _close((y.cpu() if nchw else _nchw(y)).double(), ref.detach(), 2e-5, "bn eval fwd")
+    dyg = dy.cuda().contiguous() if nchw else _nhwc(dy)
+    dx, dg, db = ops.bn_lrelu_eval_bwd(xg, dyg, gg, bg, stats, 0.2, dy_nchw=nchw)
+    _close(_nchw(dx).double(), xr.grad, 5e-5, "bn eval dx")
+    _close(dg.cpu().double(), gr.grad, 5e-5, "bn eval dgamma"); _close(db.cpu().double(), br.grad, 5e-5, "bn eval dbeta")
+    dx2, dg2, db2 = ops.bn_lrelu_eval_bwd(xg, dyg, gg, bg, stats, 0.2, dy_nchw=nchw, need_param_grads=False)
+    assert torch.equal(dx2, dx) and dg2 is None and db2 is None
+
+
+@pytest.mark.parametrize("N,C,H,W", [c[:4] for c in _BN_EVAL_CASES if c[4]])
+def test_bn_backward_does_not_depend_on_the_gradients_layout(N, C, H, W):
+    """The training and the eval backward get the same gradient NCHW-contiguous (dy_nchw=True) and NHWC: the values and the order of the
+    additions are the same, so dx, dgamma and dbeta are the same bits."""
+    from pesr_amd import ops
+    x, gamma, beta, rm, rv, dy = _bn_case(N, C, H, W)
+    xg, gg, bg = _nhwc(x), gamma.cuda(), beta.cuda()
+    _, train_stats = ops.bn_lrelu_fwd(xg, gg, bg, torch.zeros(C).cuda(), torch.ones(C).cuda(), torch.zeros((), dtype=torch.long).cuda())
+    for name, bwd, stats in (("train", ops.bn_lrelu_bwd, train_stats), ("eval", ops.bn_lrelu_eval_bwd, ops.bn_eval_stats(rm.cuda(), rv.cuda(), 1e-5))):
+        a = bwd(xg, dy.cuda().contiguous(), gg, bg, stats, 0.2, dy_nchw=True)
+        b = bwd(xg, _nhwc(dy), gg, bg, stats, 0.2, dy_nchw=False)
+        for what, u, v in zip(("dx", "dgamma", "dbeta"), a, b):
+            assert torch.equal(u, v), f"{name} backward, {what}: the NCHW and the NHWC gradient give different bits"
+
+
 @pytest.mark.parametrize("N,H,W,C,nchw", [(16, 192, 192, 64, False), (2, 37, 50, 64, False), (3, 9, 33, 32, True), (1, 8, 32, 256, False)])
 def test_conv_rgb_bn_lrelu_fused_statistics(N, H, W, C, nchw):
     """The 3 -> C conv whose kernel leaves the BatchNorm partial sums (the Discriminator's features.0, reference model/pesr.py:53 +
