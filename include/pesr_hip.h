@@ -384,6 +384,25 @@ int pesr_psnr_y(const float* a, const float* b, double* out2, int H, int W, int 
 int pesr_ssim_y(const float* a, const float* b, double* out, int N, int H, int W, int a_nhwc, int b_nhwc, int shave,
                 double* map_or_null, void* workspace, size_t ws_bytes, void* stream);
 
+/* ---- SSIM-Y as a training loss (docs/modes.md section 4p), N image pairs [N][3][H][W] ------- */
+/* The score of pesr_ssim_y on the UNQUANTISED luma: Y = ((r*(65.738/256) + g*(129.057/256)) + b*(25.064/256)) + 16 in double from the
+ * fp32 values, nothing clipped or rounded (so not the metric's bits, even on integer images); window, "valid" region, separable
+ * filtering and the map's expression order as there; no shave.  score: N device doubles, the mean of each pair's
+ * [H-10][W-10] map.  coef_or_null: when non-null, double [N][3][H-10][W-10], the derivatives of each window's value with respect
+ * to its moments mean(x), mean(x*x), mean(x*y) (the raw moments held fixed) - what pesr_ssim_loss_bwd reads.  The workspace holds one
+ * double per workgroup: 8 * N * ceil((H-10)/16) * ceil((W-10)/16) bytes are enough, less -> PESR_EWORKSPACE.  PESR_EINVAL (nothing
+ * launched): a null a, b or score, N < 1 or N > 65535, a side below 11, score, coef or the workspace not on an 8-byte boundary.
+ * Float64 without fused multiply-add, no atomics: bit-identical to the ordered float64 host restatement and on every call. */
+int pesr_ssim_loss_fwd(const float* a, const float* b, double* score, int N, int H, int W, int a_nhwc, int b_nhwc,
+                       double* coef_or_null, void* workspace, size_t ws_bytes, void* stream);
+/* Its gradient with respect to a.  coef: what the forward wrote for the same a and b; g: N device doubles, dL/dscore of each pair;
+ * ga: fp32 in a's layout ([N][H][W][3] when a_nhwc).  With T[m] the transpose of the valid filter applied to map m, x and y the lumas:
+ *     dY = (g[n] / ((H-10) (W-10))) * ((T[ca] + (2 x) T[cb]) + y T[cc]),  ga_c = (float)(dY * k_c),  k = the three luma weights.
+ * Every input element is read once, every gradient element written once; no workspace, no atomics; b gets no gradient.  PESR_EINVAL
+ * (nothing launched): a null pointer, N < 1 or N > 65535, a side below 11, coef or g not on an 8-byte boundary, ga not on 4. */
+int pesr_ssim_loss_bwd(const float* a, const float* b, const double* coef, const double* g, float* ga, int N, int H, int W,
+                       int a_nhwc, int b_nhwc, void* stream);
+
 /* ---- NIQE block statistics (docs/modes.md section 4k), N images [N][3][H][W] (nhwc: [N][H][W][3]) ------- */
 /* The device half of the no-reference score of Mittal et al. as section 4k restates it.  RGB clipped to 0..255 and rounded; luma
  * 0 = MATLAB's rgb2gray, floor(((r*0.298936021293775 + g*0.587043074451121) + b*0.114020904255103) + 0.5), luma 1 = the Y of the

@@ -96,6 +96,8 @@ SIGNATURES.update({
     "pesr_resize_to_u8_pass": (c_int, [_P, _P, _P, _P, c_int, c_int, _P, c_long, _P]),
     "pesr_psnr_y": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, _P, c_size_t, _P]),
     "pesr_ssim_y": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, c_size_t, _P]),
+    "pesr_ssim_loss_fwd": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P, c_size_t, _P]),
+    "pesr_ssim_loss_bwd": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P]),
     "pesr_niqe_stats": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, c_size_t, _P]),
     "pesr_lpips_layer": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, _P, _P, c_size_t, _P]),
     "pesr_lpips_layer2": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, _P, _P, c_size_t, _P]),

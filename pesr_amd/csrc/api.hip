@@ -379,6 +379,16 @@ PESR_API int pesr_ssim_y(const float* a, const float* b, double* out, int N, int
     return pesr_ssim_y_launch(a, b, out, N, H, W, a_nhwc, b_nhwc, shave, map_or_null, workspace, ws_bytes, (hipStream_t)stream);
 }
 
+PESR_API int pesr_ssim_loss_fwd(const float* a, const float* b, double* score, int N, int H, int W, int a_nhwc, int b_nhwc,
+                                double* coef_or_null, void* workspace, size_t ws_bytes, void* stream) {
+    return pesr_ssim_loss_fwd_launch(a, b, score, N, H, W, a_nhwc, b_nhwc, coef_or_null, workspace, ws_bytes, (hipStream_t)stream);
+}
+
+PESR_API int pesr_ssim_loss_bwd(const float* a, const float* b, const double* coef, const double* g, float* ga, int N, int H, int W,
+                                int a_nhwc, int b_nhwc, void* stream) {
+    return pesr_ssim_loss_bwd_launch(a, b, coef, g, ga, N, H, W, a_nhwc, b_nhwc, (hipStream_t)stream);
+}
+
 PESR_API int pesr_niqe_stats(const float* img, int N, int H, int W, int nhwc, int shave, int B, int luma, double* stats,
                              double* mscn1_or_null, double* mscn2_or_null, void* workspace, size_t ws_bytes, void* stream) {
     return pesr_niqe_stats_launch(img, N, H, W, nhwc, shave, B, luma, stats, mscn1_or_null, mscn2_or_null, workspace, ws_bytes,

@@ -218,6 +218,12 @@ int pesr_psnr_y_launch(const float* a, const float* b, double* out2, int H, int 
 int pesr_ssim_y_launch(const float* a, const float* b, double* out, int N, int H, int W, int a_nhwc, int b_nhwc, int shave,
                        double* map, void* ws, size_t ws_bytes, hipStream_t stream);
 
+// SSIM-Y on the unquantised luma as a training loss, and its gradient with respect to a (ssim_loss.hip, docs/modes.md section 4p)
+int pesr_ssim_loss_fwd_launch(const float* a, const float* b, double* score, int N, int H, int W, int a_nhwc, int b_nhwc, double* coef,
+                              void* ws, size_t ws_bytes, hipStream_t stream);
+int pesr_ssim_loss_bwd_launch(const float* a, const float* b, const double* coef, const double* g, float* ga, int N, int H, int W,
+                              int a_nhwc, int b_nhwc, hipStream_t stream);
+
 // NIQE block statistics: luma, crop, two scales, MSCN maps, 26 sums per block and scale (niqe.hip)
 int pesr_niqe_stats_launch(const float* img, int N, int H, int W, int nhwc, int shave, int B, int luma, double* stats, double* mscn1,
                            double* mscn2, void* ws, size_t ws_bytes, hipStream_t stream);

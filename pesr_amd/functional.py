@@ -1055,6 +1055,33 @@ def lpips_layer(fa, fb, w):
     return LpipsLayerFn.apply(fa, fb, w)
 
 
+# ------------------------------------------------------------------------------------------------
+# SSIM-Y on the unquantised luma as a loss                     docs/modes.md section 4p
+# ------------------------------------------------------------------------------------------------
+class SsimLossFn(Function):
+    """(sr, hr) [N, 3, H, W] -> float64 [N], ops.ssim_loss_fwd; only sr gets a gradient: ops.ssim_loss_bwd on the saved images and the
+    saved per-window coefficients.  When sr needs no gradient the coefficients are never written."""
+
+    @staticmethod
+    def forward(ctx, a, b):
+        need = ctx.needs_input_grad[0]
+        score, coef = ops.ssim_loss_fwd(a, b, need)
+        if need:
+            ctx.save_for_backward(a, b, coef)
+        return score
+
+    @staticmethod
+    def backward(ctx, g):
+        if not ctx.needs_input_grad[0]:
+            return None, None
+        a, b, coef = ctx.saved_tensors
+        return ops.ssim_loss_bwd(a, b, coef, _c(g)), None
+
+
+def ssim_loss(sr, hr):
+    return SsimLossFn.apply(sr, hr)
+
+
 class VggTailFn(Function):
     """conv4_1 .. conv5_4 (+ pool4) of vgg19 features[:35] (reference model/vgg.py:8-10,19-26) for the sr AND the hr branch in one
     batch: forward on cat(a, b) - one launch per layer over 2B images instead of two over B -, backward on the sr half only (the

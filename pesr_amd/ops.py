@@ -1227,6 +1227,47 @@ def ssim_y(a: torch.Tensor, b: torch.Tensor, shave: int = 0, return_map: bool = 
     return (out, smap) if return_map else out
 
 
+def _ssim_loss_pair(what: str, a: torch.Tensor, b: torch.Tensor):
+    (ta, la), (tb, lb) = (_image_layout(t, f"{what}: expected [N, 3, H, W] float32 GPU tensors", 1) for t in (a, b))
+    if ta.shape != tb.shape:
+        raise ValueError(f"{what}: the two tensors differ in shape: {tuple(ta.shape)} and {tuple(tb.shape)}")
+    N, H, W = ta.shape[0], ta.shape[2], ta.shape[3]
+    if H < 11 or W < 11:
+        raise ValueError(f"{what}: a {H} x {W} image is smaller than the 11 x 11 window")
+    return ta, la, tb, lb, N, H, W
+
+
+def ssim_loss_fwd(a: torch.Tensor, b: torch.Tensor, need_grad: bool = False):
+    """SSIM-Y on the unquantised luma (docs/modes.md section 4p) of N image pairs [N, 3, H, W], each NCHW-contiguous or channels_last
+    -> (device double [N], the mean of each pair's map; coef).  coef is None unless need_grad: then the double [N, 3, H-10, W-10] of
+    each window's derivatives with respect to mean(x), mean(x*x) and mean(x*y), what ssim_loss_bwd reads."""
+    ta, la, tb, lb, N, H, W = _ssim_loss_pair("ssim_loss_fwd", a, b)
+    Ho, Wo = H - 10, W - 10
+    score = torch.empty(N, dtype=torch.float64, device=ta.device)
+    coef = torch.empty((N, 3, Ho, Wo), dtype=torch.float64, device=ta.device) if need_grad else None
+    ws = workspace(8 * N * ((Ho + 15) // 16) * ((Wo + 15) // 16), ta.device)
+    rc = _lib.lib().pesr_ssim_loss_fwd(ta.data_ptr(), tb.data_ptr(), score.data_ptr(), N, H, W, la, lb,
+                                       coef.data_ptr() if need_grad else None, ws.data_ptr(), ws.numel(), _stream())
+    _lib.check(rc, "pesr_ssim_loss_fwd")
+    return score, coef
+
+
+def ssim_loss_bwd(a: torch.Tensor, b: torch.Tensor, coef: torch.Tensor, g: torch.Tensor) -> torch.Tensor:
+    """The gradient of ssim_loss_fwd(a, b)'s score with respect to a (docs/modes.md section 4p).  coef: what the forward returned for the
+    same pair; g: device double [N], dL/dscore of each pair -> fp32 [N, 3, H, W] with a's strides.  b gets none."""
+    ta, la, tb, lb, N, H, W = _ssim_loss_pair("ssim_loss_bwd", a, b)
+    if not torch.is_tensor(coef) or not coef.is_cuda or coef.dtype != torch.float64 or tuple(coef.shape) != (N, 3, H - 10, W - 10) \
+            or not coef.is_contiguous():
+        raise _lib.PesrHipError(f"ssim_loss_bwd.coef: expected a contiguous float64 GPU tensor [{N}, 3, {H - 10}, {W - 10}]")
+    if not torch.is_tensor(g) or not g.is_cuda or g.dtype != torch.float64 or tuple(g.shape) != (N,) or not g.is_contiguous():
+        raise _lib.PesrHipError(f"ssim_loss_bwd.g: expected a contiguous float64 GPU tensor [{N}]")
+    ga = torch.empty_like(ta)                  # (preserve_format: ta is dense in one of the two layouts, so these are its strides)
+    rc = _lib.lib().pesr_ssim_loss_bwd(ta.data_ptr(), tb.data_ptr(), coef.data_ptr(), g.data_ptr(), ga.data_ptr(), N, H, W, la, lb,
+                                       _stream())
+    _lib.check(rc, "pesr_ssim_loss_bwd")
+    return ga
+
+
 LPIPS_CHANNELS = (64, 128, 256, 512)
 
 

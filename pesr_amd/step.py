@@ -74,8 +74,14 @@ def _img(x: torch.Tensor) -> torch.Tensor:
 class Trainer:
     def __init__(self, G, D=None, vgg=None, optim_G=None, optim_D=None, *, gan_type="RSGAN", focal_loss=True, fl_gamma=1.0,
                  alpha_vgg=50.0, alpha_gan=1.0, alpha_tv=1e-6, alpha_l1=0.0, world_size=1, gradient_penalty=False,
-                 lpips_model=None, alpha_lpips=0.0):
+                 lpips_model=None, alpha_lpips=0.0, alpha_ssim=0.0):
         self.G, self.D, self.vgg = G, D, vgg
+        # 1 - SSIM-Y as a term of the generator's loss in both phases (docs/modes.md section 4p): on only with a positive weight; off,
+        # both steps launch exactly what they launch without the argument
+        self.alpha_ssim = float(alpha_ssim)
+        if self.alpha_ssim < 0:
+            raise ValueError(f"alpha_ssim must be >= 0, got {alpha_ssim}")
+        self.use_ssim = self.alpha_ssim > 0
         # LPIPS as a term of the generator's loss (docs/modes.md section 4o): on only with a model AND a positive weight; off, gan_step
         # launches exactly what it launches without the two arguments
         self.lpips_model, self.alpha_lpips = lpips_model, float(alpha_lpips)
@@ -107,10 +113,18 @@ class Trainer:
     def pretrain_step(self, lr, hr):
         sr = self.G(lr)
         self.optim_G.zero_grad()
-        loss = PF.l1_loss(nhwc(sr), _img(hr))
-        loss.backward()
+        l1 = PF.l1_loss(nhwc(sr), _img(hr))
+        ssim_loss = self._ssim_term(sr, hr) if self.use_ssim else None
+        (l1 if ssim_loss is None else l1 + ssim_loss).backward()
         self.optim_G.step()
-        return {"l1": loss.detach()}
+        logs = {"l1": l1.detach()}
+        if ssim_loss is not None:
+            logs["ssim"] = ssim_loss.detach()
+        return logs
+
+    def _ssim_term(self, sr, hr):
+        """alpha_ssim * (1 - the batch mean of the SSIM-Y score): a batch mean like l1, so no world_size factor (float64 [B] -> fp32 scalar)"""
+        return (1 - PF.ssim_loss(sr, hr).mean()).float() * self.alpha_ssim
 
     # ---- reference train.py:194-259 -----------------------------------------------------------------
     def _gradient_penalty(self, hr_cl, sr, u):
@@ -184,6 +198,7 @@ class Trainer:
         if self.use_lpips:       # a batch mean like l1 and vgg: no world_size factor (float64 [B] -> fp32 scalar)
             from .lpips import lpips_loss as _lpips_loss
             lpips_loss = _lpips_loss(sr, hr_cl, self.lpips_model).mean().float() * self.alpha_lpips
+        ssim_loss = self._ssim_term(sr, hr_cl) if self.use_ssim else None
         self.optim_D.step()
 
         # generator phase
@@ -211,6 +226,8 @@ class Trainer:
         total_G_loss = l1_loss + vgg_loss + G_loss + tv_local * float(self.world_size)
         if lpips_loss is not None:
             total_G_loss = total_G_loss + lpips_loss
+        if ssim_loss is not None:
+            total_G_loss = total_G_loss + ssim_loss
         total_G_loss.backward()
         self.optim_G.step()
         logs = {"l1": l1_loss.detach(), "vgg": vgg_loss.detach(), "g": G_loss.detach(), "tv": tv_local.detach(),
@@ -219,6 +236,8 @@ class Trainer:
             logs["gp"] = gp.detach()
         if lpips_loss is not None:
             logs["lpips"] = lpips_loss.detach()
+        if ssim_loss is not None:
+            logs["ssim"] = ssim_loss.detach()
         return logs
 
     # ---- the GAN step as ONE hipGraph ------------------------------------------------------------------------------------

@@ -129,6 +129,10 @@ def build_parser():
     p.add_argument("--alpha_lpips", type=float, default=0.0,
                    help="weight of the LPIPS term of the generator's loss; 0 (default) = off, and the step is then what it is without "
                         "the flag; > 0 needs --lpips_loss, --phase train and (--patch_size * --scale) % 16 == 0")
+    p.add_argument("--alpha_ssim", type=float, default=0.0,
+                   help="weight of the (1 - SSIM-Y) term of the generator's loss, in both phases (docs/modes.md section 4p: the SSIM of "
+                        "--valid_ssim on the unquantised luma, differentiated on the GPU); 0 (default) = off, and the step is then what "
+                        "it is without the flag; > 0 needs (--patch_size * --scale) >= 11")
     p.add_argument("--valid_tile", type=int, default=0,
                    help="validate every image as batches of overlapping tiles (docs/modes.md section 4h): the side of the square of LR "
                         "pixels a tile owns; 0 (default) = off, one Generator call on the whole image")
@@ -403,11 +407,22 @@ def lpips_loss_model_of(args, valid_model=None):
     return model
 
 
+def check_alpha_ssim(args):
+    """--alpha_ssim; SystemExit naming the flag.  No GPU is touched."""
+    if not args.alpha_ssim >= 0:
+        raise SystemExit(f"train.py: --alpha_ssim {args.alpha_ssim} must be >= 0 (0 = off)")
+    side = args.patch_size * args.scale
+    if args.alpha_ssim > 0 and side < 11:
+        raise SystemExit(f"train.py: --alpha_ssim {args.alpha_ssim}: (--patch_size * --scale) = {args.patch_size} * {args.scale} = {side} is "
+                         "smaller than the 11 x 11 window of the SSIM")
+
+
 def main(argv=None):
     args = build_parser().parse_args(argv)
     degradation_spec(args)      # (refuses a classical run without its companion flags before anything else starts)
     scorer = scorer_of(args)
     lpips_loss_model = lpips_loss_model_of(args, scorer.lpips_model)
+    check_alpha_ssim(args)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -476,7 +491,8 @@ def main(argv=None):
     scheduler_D = lr_scheduler.StepLR(optim_D, step_size=args.lr_step, gamma=0.5) if gan else None
     trainer = Trainer(G, D, vgg, optim_G, optim_D, gan_type=args.gan_type, focal_loss=args.focal_loss, fl_gamma=args.fl_gamma,
                       alpha_vgg=args.alpha_vgg, alpha_gan=args.alpha_gan, alpha_tv=args.alpha_tv, alpha_l1=args.alpha_l1,
-                      world_size=world, gradient_penalty=args.GP, lpips_model=lpips_loss_model, alpha_lpips=args.alpha_lpips)
+                      world_size=world, gradient_penalty=args.GP, lpips_model=lpips_loss_model, alpha_lpips=args.alpha_lpips,
+                      alpha_ssim=args.alpha_ssim)
 
     check_point = os.path.join(args.check_point, args.phase)
     # what checkpoint.rng_snapshot / rng_restore get besides the process-wide streams: the GPU input pipeline's crop stream, or the
@@ -507,6 +523,8 @@ def main(argv=None):
     keys = ("l1", "vgg", "g", "tv", "d") if gan else ("l1",)
     if trainer.use_lpips:
         keys += ("lpips",)
+    if trainer.use_ssim:
+        keys += ("ssim",)
     graphed, graph_shapes, eager_at_shape = None, None, 0
     use_graph = device.type == "cuda" and (world == 1 if args.hip_graph == "auto" else str2bool(args.hip_graph))
     # data-parallel schedule: fixed by flag, or measured once (inside the first epoch that is long enough for it)
@@ -607,9 +625,10 @@ def main(argv=None):
             print("Epoch [%d/%d] lr %g  " % (epoch, args.num_epochs, cur_lr) + "  ".join("%s %.4f" % kv for kv in zip(keys, avg)))
             if tb is not None:
                 tb.add_scalar("Learning rate", cur_lr, epoch)
-                names = {"l1": "L1 Loss", "vgg": "VGG Loss", "g": "G Loss", "tv": "TV Loss", "d": "D Loss", "lpips": "LPIPS Loss"}
+                names = {"l1": "L1 Loss", "vgg": "VGG Loss", "g": "G Loss", "tv": "TV Loss", "d": "D Loss", "lpips": "LPIPS Loss",
+                         "ssim": "SSIM Loss"}
                 for k, v in zip(keys, avg):
-                    tb.add_scalar(names[k] if gan else "Pretrain Loss", v, epoch)
+                    tb.add_scalar(names[k] if gan or k != "l1" else "Pretrain Loss", v, epoch)
 
         # validation on rank 0 (full images, batch 1, no_grad), reference train.py:281-295
         if rank == 0:
