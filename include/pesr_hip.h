@@ -403,6 +403,34 @@ int pesr_ssim_loss_fwd(const float* a, const float* b, double* score, int N, int
 int pesr_ssim_loss_bwd(const float* a, const float* b, const double* coef, const double* g, float* ga, int N, int H, int W,
                        int a_nhwc, int b_nhwc, void* stream);
 
+/* ---- Texture loss: patch-wise Gram matrices (docs/modes.md section 4q), features f [N][H][W][C] fp32 ------- */
+/* Patches of ph x pw pixels tile the map (H % ph == 0, W % pw == 0; ph = H, pw = W is the whole-map Gram of Gatys / Johnson):
+ * P = (H / ph) (W / pw) per image, row-major; K = ph pw pixels each.  G [N][P][C][C] fp32,
+ *     G[n][p][c][c'] = s * sum_k f[n][k][c] f[n][k][c'],   s = 1 / (C K),
+ * on the fp32 MFMA (a k-ordered fmaf chain per element), scaled once at the end; bit-for-bit symmetric, and the same bits on every
+ * call (no atomics).  Long patches are cut into pesr_gram_splits(...) slices of K whose sums go through the workspace
+ * ([S][N P][C][C] floats = pesr_gram_workspace_bytes(...), 0 when S == 1) and are added in ascending order.  Both planners are pure
+ * host functions of the shape; pesr_gram_splits returns 0 for a shape the kernels do not take.  PESR_EINVAL (nothing launched): a
+ * null f or G, N < 1, a side < 1, C not 64, 128 or 256, a patch that does not divide the map, f, G or the workspace not on a
+ * 16-byte boundary; PESR_EWORKSPACE: S > 1 and a missing or smaller workspace.  64-bit offsets. */
+int pesr_gram_splits(int N, int H, int W, int C, int ph, int pw);
+size_t pesr_gram_workspace_bytes(int N, int H, int W, int C, int ph, int pw);
+int pesr_gram_fwd(const float* f, float* G, int N, int H, int W, int C, int ph, int pw, void* workspace, size_t ws_bytes, void* stream);
+/* The squared distance of two such tensors ga, gb [N][P][C][C]: d = (double)ga - (double)gb (exact), t[n] = (sum_p sum_cc' d^2) / P as
+ * N device doubles (fixed summation tree, no fused multiply-add, no atomics); dg_or_null: when non-null, fp32 [N][P][C][C], (float)d -
+ * what pesr_gram_bwd reads.  The workspace holds one double per workgroup: pesr_gram_loss_workspace_bytes(N, P, C), less ->
+ * PESR_EWORKSPACE.  PESR_EINVAL: a null ga, gb or t, N < 1 or N > 65535, P < 1, C as above, ga, gb or dg not on a 16-byte boundary,
+ * t or the workspace not on 8. */
+size_t pesr_gram_loss_workspace_bytes(int N, int P, int C);
+int pesr_gram_loss(const float* ga, const float* gb, double* t, float* dg_or_null, int N, int P, int C, void* workspace,
+                   size_t ws_bytes, void* stream);
+/* The gradient of sum_n g[n] t[n] with respect to the f that ga was made from: dg a SYMMETRIC [N][P][C][C] (pesr_gram_loss's), g N
+ * device doubles, gf fp32 [N][H][W][C],
+ *     gf[n][k][c] = (float)(g[n] * 4 s / P) * sum_c' f[n][k][c'] dg[n][p(k)][c'][c]
+ * on the fp32 MFMA; every element written once, no workspace, no atomics; not masked by f > 0.  Shape errors as pesr_gram_fwd;
+ * f, dg and gf on 16-byte boundaries, g on 8. */
+int pesr_gram_bwd(const float* f, const float* dg, const double* g, float* gf, int N, int H, int W, int C, int ph, int pw, void* stream);
+
 /* ---- NIQE block statistics (docs/modes.md section 4k), N images [N][3][H][W] (nhwc: [N][H][W][3]) ------- */
 /* The device half of the no-reference score of Mittal et al. as section 4k restates it.  RGB clipped to 0..255 and rounded; luma
  * 0 = MATLAB's rgb2gray, floor(((r*0.298936021293775 + g*0.587043074451121) + b*0.114020904255103) + 0.5), luma 1 = the Y of the

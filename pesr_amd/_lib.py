@@ -98,6 +98,12 @@ SIGNATURES.update({
     "pesr_ssim_y": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, c_size_t, _P]),
     "pesr_ssim_loss_fwd": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P, _P, c_size_t, _P]),
     "pesr_ssim_loss_bwd": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P]),
+    "pesr_gram_splits": (c_int, [c_int, c_int, c_int, c_int, c_int, c_int]),
+    "pesr_gram_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int]),
+    "pesr_gram_fwd": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P, c_size_t, _P]),
+    "pesr_gram_loss_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "pesr_gram_loss": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, _P, c_size_t, _P]),
+    "pesr_gram_bwd": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
     "pesr_niqe_stats": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, c_size_t, _P]),
     "pesr_lpips_layer": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, _P, _P, c_size_t, _P]),
     "pesr_lpips_layer2": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, _P, _P, c_size_t, _P]),

@@ -389,6 +389,29 @@ PESR_API int pesr_ssim_loss_bwd(const float* a, const float* b, const double* co
     return pesr_ssim_loss_bwd_launch(a, b, coef, g, ga, N, H, W, a_nhwc, b_nhwc, (hipStream_t)stream);
 }
 
+PESR_API int pesr_gram_splits(int N, int H, int W, int C, int ph, int pw) { return pesr_gram_splits_host(N, H, W, C, ph, pw); }
+
+PESR_API size_t pesr_gram_workspace_bytes(int N, int H, int W, int C, int ph, int pw) {
+    return pesr_gram_workspace_bytes_host(N, H, W, C, ph, pw);
+}
+
+PESR_API size_t pesr_gram_loss_workspace_bytes(int N, int P, int C) { return pesr_gram_loss_workspace_bytes_host(N, P, C); }
+
+PESR_API int pesr_gram_fwd(const float* f, float* G, int N, int H, int W, int C, int ph, int pw, void* workspace, size_t ws_bytes,
+                           void* stream) {
+    return pesr_gram_fwd_launch(f, G, N, H, W, C, ph, pw, workspace, ws_bytes, (hipStream_t)stream);
+}
+
+PESR_API int pesr_gram_loss(const float* ga, const float* gb, double* t, float* dg_or_null, int N, int P, int C, void* workspace,
+                            size_t ws_bytes, void* stream) {
+    return pesr_gram_loss_launch(ga, gb, t, dg_or_null, N, P, C, workspace, ws_bytes, (hipStream_t)stream);
+}
+
+PESR_API int pesr_gram_bwd(const float* f, const float* dg, const double* g, float* gf, int N, int H, int W, int C, int ph, int pw,
+                           void* stream) {
+    return pesr_gram_bwd_launch(f, dg, g, gf, N, H, W, C, ph, pw, (hipStream_t)stream);
+}
+
 PESR_API int pesr_niqe_stats(const float* img, int N, int H, int W, int nhwc, int shave, int B, int luma, double* stats,
                              double* mscn1_or_null, double* mscn2_or_null, void* workspace, size_t ws_bytes, void* stream) {
     return pesr_niqe_stats_launch(img, N, H, W, nhwc, shave, B, luma, stats, mscn1_or_null, mscn2_or_null, workspace, ws_bytes,

@@ -224,6 +224,17 @@ int pesr_ssim_loss_fwd_launch(const float* a, const float* b, double* score, int
 int pesr_ssim_loss_bwd_launch(const float* a, const float* b, const double* coef, const double* g, float* ga, int N, int H, int W,
                               int a_nhwc, int b_nhwc, hipStream_t stream);
 
+// Texture loss: patch-wise Gram matrices of NHWC features, their squared distance, the gradient (gram.hip, docs/modes.md section 4q)
+int pesr_gram_splits_host(int N, int H, int W, int C, int ph, int pw);
+size_t pesr_gram_workspace_bytes_host(int N, int H, int W, int C, int ph, int pw);
+size_t pesr_gram_loss_workspace_bytes_host(int N, int P, int C);
+int pesr_gram_fwd_launch(const float* f, float* G, int N, int H, int W, int C, int ph, int pw, void* ws, size_t ws_bytes,
+                         hipStream_t stream);
+int pesr_gram_loss_launch(const float* ga, const float* gb, double* t, float* dg, int N, int P, int C, void* ws, size_t ws_bytes,
+                          hipStream_t stream);
+int pesr_gram_bwd_launch(const float* f, const float* dg, const double* g, float* gf, int N, int H, int W, int C, int ph, int pw,
+                         hipStream_t stream);
+
 // NIQE block statistics: luma, crop, two scales, MSCN maps, 26 sums per block and scale (niqe.hip)
 int pesr_niqe_stats_launch(const float* img, int N, int H, int W, int nhwc, int shave, int B, int luma, double* stats, double* mscn1,
                            double* mscn2, void* ws, size_t ws_bytes, hipStream_t stream);

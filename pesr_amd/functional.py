@@ -1082,6 +1082,36 @@ def ssim_loss(sr, hr):
     return SsimLossFn.apply(sr, hr)
 
 
+# ------------------------------------------------------------------------------------------------
+# texture loss of one tapped layer: patch-wise Gram matrices    docs/modes.md section 4q
+# ------------------------------------------------------------------------------------------------
+class TextureLayerFn(Function):
+    """(fa, fb) NHWC [N, H, W, C] -> float64 [N]: ops.gram of both, ops.gram_loss; only fa gets a gradient (fb is the no_grad hr pass):
+    ops.gram_bwd on the saved fa and the saved difference dG, which is never written when fa needs no gradient.  Like LpipsLayerFn's,
+    the gradient is NOT masked by fa > 0: the tap's own conv masks the sum of its consumers' gradients."""
+
+    @staticmethod
+    def forward(ctx, fa, fb, patch):
+        need = ctx.needs_input_grad[0]
+        fa, fb = _c(fa), _c(fb)
+        t, dg = ops.gram_loss(ops.gram(fa, patch), ops.gram(fb, patch), need)
+        ctx.patch = patch
+        if need:
+            ctx.save_for_backward(fa, dg)
+        return t
+
+    @staticmethod
+    def backward(ctx, g):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None
+        fa, dg = ctx.saved_tensors
+        return ops.gram_bwd(fa, dg, _c(g), ctx.patch), None, None
+
+
+def texture_layer(fa, fb, patch=0):
+    return TextureLayerFn.apply(fa, fb, patch)
+
+
 class VggTailFn(Function):
     """conv4_1 .. conv5_4 (+ pool4) of vgg19 features[:35] (reference model/vgg.py:8-10,19-26) for the sr AND the hr branch in one
     batch: forward on cat(a, b) - one launch per layer over 2B images instead of two over B -, backward on the sr half only (the

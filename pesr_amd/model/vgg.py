@@ -77,38 +77,53 @@ class VGG(nn.Module):
                 i += 1
         return out
 
-    def _run(self, h, lo, hi, prev_relu=False):
+    # the texture loss's taps (pesr_amd/texture.py, docs/modes.md section 4q): relu1_1, relu2_1, relu3_1 as indices of `features`,
+    # all in front of TAIL_START
+    TAPS = (1, 6, 11)
+
+    def _run(self, h, lo, hi, prev_relu=False, taps=None):
+        """features[lo:hi].  taps: None, or a list that receives the NHWC outputs of the ReLUs at TAPS.  A tapped output has two
+        consumers, so its conv masks the sum of their gradients itself (relu_grad_by_consumer = False) and the next layer does not
+        (relu_in = False) - the rule of LpipsModel.features_grad; the forward values do not depend on it."""
+        i = lo
         for kind, m, has_relu in self._steps(lo, hi):
             if kind == "conv":
+                tap = taps is not None and has_relu and (i + 1) in self.TAPS
+                by_consumer = has_relu and not tap
                 h = m(h, act=ops.ACT_RELU if has_relu else ops.ACT_NONE, relu_in=prev_relu,
-                      relu_grad_by_consumer=has_relu)   # every ReLU here feeds a conv or a pool that masks for it
-                prev_relu = has_relu
+                      relu_grad_by_consumer=by_consumer)   # every other ReLU here feeds a conv or a pool that masks for it
+                prev_relu = by_consumer
+                if tap:
+                    taps.append(nhwc(h))
+                i += 2 if has_relu else 1
             else:
                 h = m(h, relu_in=prev_relu)
                 prev_relu = False
+                i += 1
         return h
 
     def features(self, x):
         """sub_mean -> vgg19.features[:35] of one image batch (reference model/vgg.py:19-22 `_forward`)."""
         return self._run(self.sub_mean(x), 0, len(self.vgg))
 
-    def forward(self, sr, hr):
+    def forward(self, sr, hr, taps=False):
         """(features(sr), features(hr) without gradient) - reference model/vgg.py:24-26.  The two passes share conv4_1 .. conv5_4 as
         ONE batch (functional.VggTailFn; round 4): behind the third max-pool the feature maps are 24 x 24 and 12 x 12 at the training
         shape, a batch of 16 leaves those launches at 128 - 240 workgroups (split-K, 40 % of the matrix pipe on the 12 x 12 ones), and
         vgg19 has no BatchNorm that would tie samples together: 2076 -> 1768 us per step for these eight layers' forwards
         (profiles/r04_merge_probe.txt).  The input gradient runs on the sr half only.  Not in the bf16 mode (its oracle mirrors the
-        per-pass dispatch), not when the tail's weights are trainable, not for unequal shapes."""
+        per-pass dispatch), not when the tail's weights are trainable, not for unequal shapes.
+        taps=True: -> (features(sr), features(hr), taps_sr, taps_hr), the NHWC outputs of the ReLUs at TAPS of both passes (the hr
+        ones without gradient) from the same two trunk passes; the two feature tensors are the bits of the taps=False call."""
         n = len(self.vgg)
         merge = (sr.shape == hr.shape and n > self.TAIL_START and ops.PRECISION == "fp32" and sr.is_cuda
                  and not any(p.requires_grad for p in self.vgg[self.TAIL_START:].parameters()))
-        if not merge:
-            vgg_sr = self.features(sr)
-            with torch.no_grad():
-                vgg_hr = self.features(hr.detach())
-            return vgg_sr, vgg_hr
-        a = self._run(self.sub_mean(sr), 0, self.TAIL_START)
+        taps_sr, taps_hr = ([], []) if taps else (None, None)
+        split = self.TAIL_START if merge else n
+        a = self._run(self.sub_mean(sr), 0, split, taps=taps_sr)
         with torch.no_grad():
-            b = self._run(self.sub_mean(hr.detach()), 0, self.TAIL_START)
-        fa, fb = PF.VggTailFn.apply(nhwc(a), nhwc(b), self._steps(self.TAIL_START, n))
-        return nchw(fa), nchw(fb)
+            b = self._run(self.sub_mean(hr.detach()), 0, split, taps=taps_hr)
+        if merge:
+            fa, fb = PF.VggTailFn.apply(nhwc(a), nhwc(b), self._steps(self.TAIL_START, n))
+            a, b = nchw(fa), nchw(fb)
+        return (a, b, taps_sr, taps_hr) if taps else (a, b)

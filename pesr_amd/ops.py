@@ -1328,6 +1328,90 @@ def lpips_layer_bwd(fa: torch.Tensor, fb: torch.Tensor, w: torch.Tensor, g: torc
 
 
 # ------------------------------------------------------------------------------------------------
+# texture loss: patch-wise Gram matrices (docs/modes.md section 4q)
+# ------------------------------------------------------------------------------------------------
+GRAM_CHANNELS = (64, 128, 256)
+
+
+def _gram_patch(what: str, H: int, W: int, patch):
+    """patch: 0 (the whole map), a side, or (ph, pw) -> (ph, pw); PesrHipError unless it tiles the H x W map."""
+    ph, pw = (patch, patch) if isinstance(patch, int) else (int(patch[0]), int(patch[1]))
+    ph, pw = (ph or H), (pw or W)
+    if ph < 1 or pw < 1 or H % ph or W % pw:
+        raise _lib.PesrHipError(f"{what}: a {ph} x {pw} patch does not tile a {H} x {W} map")
+    return ph, pw
+
+
+def _chk_gram_feat(what: str, f: torch.Tensor):
+    if not torch.is_tensor(f) or not f.is_cuda or f.dtype != torch.float32 or f.dim() != 4 or not f.is_contiguous() or f.shape[0] < 1:
+        raise _lib.PesrHipError(f"{what}: expected contiguous [N, H, W, C] float32 GPU tensors (NHWC features; there is no CPU path)")
+    if f.shape[3] not in GRAM_CHANNELS:
+        raise _lib.PesrHipError(f"{what}: C = {f.shape[3]}, the Gram kernels take C in {GRAM_CHANNELS}")
+    return tuple(f.shape)
+
+
+def gram_plan(N: int, H: int, W: int, C: int, ph: int, pw: int) -> dict:
+    """What pesr_gram_fwd does with this shape (a host-only question): {"splits": the number of K slices, 1 = the kernel writes G
+    itself; "workspace_bytes": the partial sums' slabs, 0 without a split; "patches": P; "pixels": K}.  ValueError for a shape the
+    kernels do not take."""
+    s = _memo("pesr_gram_splits", N, H, W, C, ph, pw)
+    if s < 1:
+        raise ValueError(f"gram_plan: no Gram kernel for N {N}, {H} x {W} x {C}, patch {ph} x {pw}")
+    return {"splits": s, "workspace_bytes": int(_lib.lib().pesr_gram_workspace_bytes(N, H, W, C, ph, pw)),
+            "patches": (H // ph) * (W // pw), "pixels": ph * pw}
+
+
+def gram(f: torch.Tensor, patch=0) -> torch.Tensor:
+    """Patch-wise Gram matrices of NHWC features f [N, H, W, C] (C in GRAM_CHANNELS): fp32 [N, P, C, C],
+    G[n, p] = F_p^T F_p / (C K) over the K pixels of patch p, on the fp32 MFMA; bit-for-bit symmetric and reproducible.  patch: 0 = the
+    whole map, a side, or (ph, pw); it must tile the map."""
+    N, H, W, C = _chk_gram_feat("gram", f)
+    ph, pw = _gram_patch("gram", H, W, patch)
+    plan = gram_plan(N, H, W, C, ph, pw)
+    G = torch.empty((N, plan["patches"], C, C), dtype=torch.float32, device=f.device)
+    ws = workspace(plan["workspace_bytes"], f.device)
+    rc = _lib.lib().pesr_gram_fwd(_p(f), _p(G), N, H, W, C, ph, pw, _p(ws), ws.numel(), _stream())
+    _lib.check(rc, "pesr_gram_fwd")
+    return G
+
+
+def gram_loss(ga: torch.Tensor, gb: torch.Tensor, need_grad: bool = False):
+    """(ga, gb) fp32 [N, P, C, C] -> (device double [N]: sum over patches and entries of (ga - gb)^2, divided by P, the difference
+    taken in double; dG).  dG is None unless need_grad: then fp32 [N, P, C, C], the difference rounded once, what gram_bwd reads."""
+    for t in (ga, gb):
+        if not torch.is_tensor(t) or not t.is_cuda or t.dtype != torch.float32 or t.dim() != 4 or not t.is_contiguous() \
+                or t.shape[0] < 1 or t.shape[2] != t.shape[3]:
+            raise _lib.PesrHipError("gram_loss: expected contiguous [N, P, C, C] float32 GPU tensors (there is no CPU path)")
+    if tuple(ga.shape) != tuple(gb.shape):
+        raise _lib.PesrHipError(f"gram_loss: the two tensors differ in shape: {tuple(ga.shape)} and {tuple(gb.shape)}")
+    N, P, C = ga.shape[0], ga.shape[1], ga.shape[2]
+    if C not in GRAM_CHANNELS:
+        raise _lib.PesrHipError(f"gram_loss: C = {C}, the Gram kernels take C in {GRAM_CHANNELS}")
+    t = torch.empty(N, dtype=torch.float64, device=ga.device)
+    dg = torch.empty_like(ga) if need_grad else None
+    ws = workspace(int(_lib.lib().pesr_gram_loss_workspace_bytes(N, P, C)), ga.device)
+    rc = _lib.lib().pesr_gram_loss(_p(ga), _p(gb), _p(t), _p(dg), N, P, C, _p(ws), ws.numel(), _stream())
+    _lib.check(rc, "pesr_gram_loss")
+    return t, dg
+
+
+def gram_bwd(f: torch.Tensor, dg: torch.Tensor, g: torch.Tensor, patch=0) -> torch.Tensor:
+    """The gradient of sum_n g[n] t[n] (gram_loss of gram(f, patch) against anything) with respect to f: fp32 [N, H, W, C],
+    g[n] (4 / (C K P)) F dG per patch.  dg: gram_loss's symmetric fp32 [N, P, C, C]; g: device double [N].  Not masked by f > 0."""
+    N, H, W, C = _chk_gram_feat("gram_bwd", f)
+    ph, pw = _gram_patch("gram_bwd", H, W, patch)
+    P = (H // ph) * (W // pw)
+    if not torch.is_tensor(dg) or not dg.is_cuda or dg.dtype != torch.float32 or tuple(dg.shape) != (N, P, C, C) or not dg.is_contiguous():
+        raise _lib.PesrHipError(f"gram_bwd.dg: expected a contiguous float32 GPU tensor [{N}, {P}, {C}, {C}]")
+    if not torch.is_tensor(g) or not g.is_cuda or g.dtype != torch.float64 or tuple(g.shape) != (N,) or not g.is_contiguous():
+        raise _lib.PesrHipError(f"gram_bwd.g: expected a contiguous float64 GPU tensor [{N}]")
+    gf = torch.empty_like(f)
+    rc = _lib.lib().pesr_gram_bwd(_p(f), _p(dg), _p(g), _p(gf), N, H, W, C, ph, pw, _stream())
+    _lib.check(rc, "pesr_gram_bwd")
+    return gf
+
+
+# ------------------------------------------------------------------------------------------------
 # tiled inference (docs/modes.md section 4h; the plan and the driver are pesr_amd/tile.py)
 # ------------------------------------------------------------------------------------------------
 def _tile_desc(desc, cols: int, device):

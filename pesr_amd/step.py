@@ -74,8 +74,17 @@ def _img(x: torch.Tensor) -> torch.Tensor:
 class Trainer:
     def __init__(self, G, D=None, vgg=None, optim_G=None, optim_D=None, *, gan_type="RSGAN", focal_loss=True, fl_gamma=1.0,
                  alpha_vgg=50.0, alpha_gan=1.0, alpha_tv=1e-6, alpha_l1=0.0, world_size=1, gradient_penalty=False,
-                 lpips_model=None, alpha_lpips=0.0, alpha_ssim=0.0):
+                 lpips_model=None, alpha_lpips=0.0, alpha_ssim=0.0, alpha_texture=0.0, texture_patch=16):
         self.G, self.D, self.vgg = G, D, vgg
+        # the texture loss, Gram matrices of three VGG19 taps (docs/modes.md section 4q), as a term of gan_step's generator loss: on
+        # only with a positive weight; off, the VGG is called without taps and the step launches exactly what it launches without the
+        # two arguments.  texture_patch: the side of the patches in each tap's own pixels, 0 = the whole map
+        self.alpha_texture, self.texture_patch = float(alpha_texture), int(texture_patch)
+        if not self.alpha_texture >= 0:
+            raise ValueError(f"alpha_texture must be >= 0, got {alpha_texture}")
+        if self.texture_patch < 0:
+            raise ValueError(f"texture_patch must be >= 0 (0 = the whole map), got {texture_patch}")
+        self.use_texture = self.alpha_texture > 0
         # 1 - SSIM-Y as a term of the generator's loss in both phases (docs/modes.md section 4p): on only with a positive weight; off,
         # both steps launch exactly what they launch without the argument
         self.alpha_ssim = float(alpha_ssim)
@@ -191,7 +200,13 @@ class Trainer:
         # gradients that optim_D.step() has to wait for.  Same graph, same values; only the launch order differs.
         sr_nhwc, hr_nhwc = nhwc(sr), nhwc(hr_cl)
         l1_loss = PF.l1_loss(sr_nhwc, hr_nhwc) * self.alpha_l1
-        vgg_sr, vgg_hr = self.vgg(sr, hr_cl)
+        texture_loss = None
+        if self.use_texture:     # the taps come out of the same two trunk passes; a batch mean like l1 and vgg: no world_size factor
+            from .texture import texture_from_taps
+            vgg_sr, vgg_hr, taps_sr, taps_hr = self.vgg(sr, hr_cl, taps=True)
+            texture_loss = texture_from_taps(taps_sr, taps_hr, self.texture_patch).mean().float() * self.alpha_texture
+        else:
+            vgg_sr, vgg_hr = self.vgg(sr, hr_cl)
         vgg_loss = PF.mse_loss(nhwc(vgg_sr), nhwc(vgg_hr)) * self.alpha_vgg
         tv_local = PF.tv_loss(sr_nhwc) * self.alpha_tv
         lpips_loss = None
@@ -228,6 +243,8 @@ class Trainer:
             total_G_loss = total_G_loss + lpips_loss
         if ssim_loss is not None:
             total_G_loss = total_G_loss + ssim_loss
+        if texture_loss is not None:
+            total_G_loss = total_G_loss + texture_loss
         total_G_loss.backward()
         self.optim_G.step()
         logs = {"l1": l1_loss.detach(), "vgg": vgg_loss.detach(), "g": G_loss.detach(), "tv": tv_local.detach(),
@@ -238,6 +255,8 @@ class Trainer:
             logs["lpips"] = lpips_loss.detach()
         if ssim_loss is not None:
             logs["ssim"] = ssim_loss.detach()
+        if texture_loss is not None:
+            logs["texture"] = texture_loss.detach()
         return logs
 
     # ---- the GAN step as ONE hipGraph ------------------------------------------------------------------------------------

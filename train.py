@@ -133,6 +133,13 @@ def build_parser():
                    help="weight of the (1 - SSIM-Y) term of the generator's loss, in both phases (docs/modes.md section 4p: the SSIM of "
                         "--valid_ssim on the unquantised luma, differentiated on the GPU); 0 (default) = off, and the step is then what "
                         "it is without the flag; > 0 needs (--patch_size * --scale) >= 11")
+    p.add_argument("--alpha_texture", type=float, default=0.0,
+                   help="weight of the texture loss of the generator's loss (docs/modes.md section 4q: the distance between patch-wise "
+                        "Gram matrices of relu1_1 / relu2_1 / relu3_1 of the VGG19 trunk that --alpha_vgg runs anyway); 0 (default) = "
+                        "off, and the step is then what it is without the flag; > 0 needs --phase train")
+    p.add_argument("--texture_patch", type=int, default=16,
+                   help="side of the texture loss's patches, in each tap's own pixels (EnhanceNet: 16); it must divide the three tap "
+                        "sizes (--patch_size * --scale, a half and a quarter of it); 0 = the whole map (Gatys / Johnson)")
     p.add_argument("--valid_tile", type=int, default=0,
                    help="validate every image as batches of overlapping tiles (docs/modes.md section 4h): the side of the square of LR "
                         "pixels a tile owns; 0 (default) = off, one Generator call on the whole image")
@@ -417,12 +424,30 @@ def check_alpha_ssim(args):
                          "smaller than the 11 x 11 window of the SSIM")
 
 
+def check_alpha_texture(args):
+    """--alpha_texture / --texture_patch; SystemExit naming the flag.  No GPU is touched."""
+    if not args.alpha_texture >= 0:
+        raise SystemExit(f"train.py: --alpha_texture {args.alpha_texture} must be >= 0 (0 = off)")
+    if args.alpha_texture == 0:
+        return
+    if args.phase != "train":
+        raise SystemExit(f"train.py: --alpha_texture {args.alpha_texture} needs --phase train: the texture loss reads taps of the VGG19 "
+                         f"trunk, and no VGG runs in --phase {args.phase}")
+    from pesr_amd.texture import check_patch
+    side = args.patch_size * args.scale
+    why = check_patch(side, side, args.texture_patch)
+    if why:
+        raise SystemExit(f"train.py: --alpha_texture {args.alpha_texture}: --texture_patch {args.texture_patch} with (--patch_size * "
+                         f"--scale) = {args.patch_size} * {args.scale} = {side}: {why}; --texture_patch 0 takes the whole map of every tap")
+
+
 def main(argv=None):
     args = build_parser().parse_args(argv)
     degradation_spec(args)      # (refuses a classical run without its companion flags before anything else starts)
     scorer = scorer_of(args)
     lpips_loss_model = lpips_loss_model_of(args, scorer.lpips_model)
     check_alpha_ssim(args)
+    check_alpha_texture(args)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -492,7 +517,7 @@ def main(argv=None):
     trainer = Trainer(G, D, vgg, optim_G, optim_D, gan_type=args.gan_type, focal_loss=args.focal_loss, fl_gamma=args.fl_gamma,
                       alpha_vgg=args.alpha_vgg, alpha_gan=args.alpha_gan, alpha_tv=args.alpha_tv, alpha_l1=args.alpha_l1,
                       world_size=world, gradient_penalty=args.GP, lpips_model=lpips_loss_model, alpha_lpips=args.alpha_lpips,
-                      alpha_ssim=args.alpha_ssim)
+                      alpha_ssim=args.alpha_ssim, alpha_texture=args.alpha_texture, texture_patch=args.texture_patch)
 
     check_point = os.path.join(args.check_point, args.phase)
     # what checkpoint.rng_snapshot / rng_restore get besides the process-wide streams: the GPU input pipeline's crop stream, or the
@@ -525,6 +550,8 @@ def main(argv=None):
         keys += ("lpips",)
     if trainer.use_ssim:
         keys += ("ssim",)
+    if trainer.use_texture:
+        keys += ("texture",)
     graphed, graph_shapes, eager_at_shape = None, None, 0
     use_graph = device.type == "cuda" and (world == 1 if args.hip_graph == "auto" else str2bool(args.hip_graph))
     # data-parallel schedule: fixed by flag, or measured once (inside the first epoch that is long enough for it)
@@ -626,7 +653,7 @@ def main(argv=None):
             if tb is not None:
                 tb.add_scalar("Learning rate", cur_lr, epoch)
                 names = {"l1": "L1 Loss", "vgg": "VGG Loss", "g": "G Loss", "tv": "TV Loss", "d": "D Loss", "lpips": "LPIPS Loss",
-                         "ssim": "SSIM Loss"}
+                         "ssim": "SSIM Loss", "texture": "Texture Loss"}
                 for k, v in zip(keys, avg):
                     tb.add_scalar(names[k] if gan or k != "l1" else "Pretrain Loss", v, epoch)
 
