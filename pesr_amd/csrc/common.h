@@ -61,6 +61,15 @@ __device__ __forceinline__ double wave_sum_d(double v) {
     for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
     return v;
 }
+// Fixed-order sum over a workgroup of 256 lanes: wave_sum_d, lane 0 of each wave to red[4] (LDS), one barrier, waves 0..3 in order.
+// Every lane returns the same bits.  red must not have been read since the last barrier: a kernel that uses it again puts a
+// barrier in between itself.
+__device__ __forceinline__ double block_sum_d(double v, double* red) {
+    const double w = wave_sum_d(v);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = w;
+    __syncthreads();
+    return ((red[0] + red[1]) + red[2]) + red[3];
+}
 
 // Column sum over `rows` partial rows in increasing order, in double - eight loads in flight at a time (as a plain loop hipcc emits one
 // load, one s_waitcnt vmcnt(0) and one add per iteration: `rows` dependent round trips on a single thread that its whole block waits for).

@@ -93,10 +93,8 @@ __global__ __launch_bounds__(256) void convk_bgrad_kernel(const float* __restric
     const int co = blockIdx.x;
     double acc = 0.0;
     for (long q = threadIdx.x; q < P; q += 256) acc += (double)dy[q * Cout + co];
-    const double wsum = wave_sum_d(acc);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = wsum;
-    __syncthreads();
-    if (threadIdx.x == 0) db[co] = (float)(((red[0] + red[1]) + red[2]) + red[3]);
+    const double t = block_sum_d(acc, red);
+    if (threadIdx.x == 0) db[co] = (float)t;
 }
 }  // namespace
 

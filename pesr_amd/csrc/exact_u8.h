@@ -1,6 +1,7 @@
 // The pinned float64 arithmetic and byte-image access that the exact kernels share (resize.hip, resize_to.hip, degrade.hip, jpeg.hip,
-// niqe.hip, ssim.hip): each of them promises bit equality with a float64 restatement on the host, and every operation that promise
-// rests on is here once.  Include it after common.h, under the including file's own `#pragma clang fp contract(off)`.
+// niqe.hip, ssim.hip with the SSIM-Y score and loss): each of them promises bit equality with a float64 restatement on the host, and
+// every operation that promise rests on is here once.  Include it after common.h, under the including file's own
+// `#pragma clang fp contract(off)`.
 #pragma once
 #pragma clang fp contract(off)
 
@@ -31,6 +32,16 @@ __device__ __forceinline__ double exact_round8(double v) {
 // four of them as the bytes of a dword, lowest first
 __device__ __forceinline__ unsigned exact_round8x4(double a0, double a1, double a2, double a3) {
     return (unsigned)exact_round8(a0) | ((unsigned)exact_round8(a1) << 8) | ((unsigned)exact_round8(a2) << 16) | ((unsigned)exact_round8(a3) << 24);
+}
+
+// The 8-bit BT.601 luma of one RGB pixel, the Y of the PSNR-Y, SSIM-Y and NIQE's mode 1: each channel clipped to 0..255 and rounded
+// (to even), weighed in double, + 16, clipped and rounded again.  An integer in 0..255.  loss.hip's luma_u8 is the same steps under
+// that file's default contraction (psnr_y_kernel predates this header) and stays there.
+__device__ __forceinline__ double exact_clip8(float v) { return rint(fmin(fmax((double)v, 0.0), 255.0)); }
+__device__ __forceinline__ double exact_luma601_u8(float pr, float pg, float pb) {
+    const double r = exact_clip8(pr), g = exact_clip8(pg), b = exact_clip8(pb);
+    const double y = ((r * (65.738 / 256) + g * (129.057 / 256)) + b * (25.064 / 256)) + 16.0;
+    return rint(fmin(fmax(y, 0.0), 255.0));
 }
 
 // symmetric reflection ... 1 0 | 0 1 ... n-1 | n-1 n-2 ... (period 2n), for any j

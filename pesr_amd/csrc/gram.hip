@@ -18,7 +18,7 @@
 //
 // Distance: d = (double)Gsr - (double)Ghr (exact), dG = (float)d (one rounding; written only when asked for), t[n] = (sum d^2) / P
 // in double: a lane adds its elements in ascending address order, wave_sum_d's tree, the four waves in order, one partial per
-// workgroup; gram_loss_final_kernel adds an image's partials (lane t: t, t + 256, ... ascending; the same tree).
+// workgroup (block_sum_d); reduce.hip's mean_partials_kernel adds an image's partials in its fixed order and divides by P.
 //
 // Backward, gF[k][c] = (float)(g[n] 4 s / P) * sum_c' F[k][c'] dG[c'][c]: one workgroup per (image, patch, run of 64 pixels; 32 at
 // C = 256).  The operand indexed [pixel][c'] has its pixel on the lane, which memory does not give contiguously: the run's rows are
@@ -141,23 +141,8 @@ __global__ __launch_bounds__(GR_THREADS) void gram_loss_kernel(const float* __re
         if (dg) *(f32x4*)(dg + img + e) = o;
     }
     __shared__ double red[GR_THREADS / 64];
-    const double w = wave_sum_d(s);
-    if ((tid & 63) == 0) red[tid >> 6] = w;
-    __syncthreads();
-    if (tid == 0) part[(long)blockIdx.y * gridDim.x + blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
-}
-
-// one workgroup per image
-__global__ __launch_bounds__(GR_THREADS) void gram_loss_final_kernel(const double* __restrict__ part, double* __restrict__ out, int nb,
-                                                                     double patches) {
-    const double* p = part + (long)blockIdx.x * nb;
-    double s = 0.0;
-    for (int k = threadIdx.x; k < nb; k += GR_THREADS) s += p[k];
-    __shared__ double red[GR_THREADS / 64];
-    const double w = wave_sum_d(s);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = w;
-    __syncthreads();
-    if (threadIdx.x == 0) out[blockIdx.x] = (((red[0] + red[1]) + red[2]) + red[3]) / patches;
+    const double t = block_sum_d(s, red);
+    if (tid == 0) part[(long)blockIdx.y * gridDim.x + blockIdx.x] = t;
 }
 
 // grid.x = N * P * runs: block b is pixel run b % runs of patch b / runs
@@ -307,8 +292,7 @@ int pesr_gram_loss_launch(const float* ga, const float* gb, double* t, float* dg
     const int nb = gram_loss_blocks(per);
     if (!ws || ws_bytes < sizeof(double) * (size_t)N * nb) return PESR_EWORKSPACE;
     hipLaunchKernelGGL(gram_loss_kernel, dim3(nb, N), dim3(GR_THREADS), 0, stream, ga, gb, dg, (double*)ws, per);
-    hipLaunchKernelGGL(gram_loss_final_kernel, dim3(N), dim3(GR_THREADS), 0, stream, (const double*)ws, t, nb, (double)P);
-    return pesr_launch_status();
+    return pesr_mean_partials_launch((const double*)ws, t, N, nb, (double)P, stream);
 }
 
 int pesr_gram_bwd_launch(const float* f, const float* dg, const double* g, float* gf, int N, int H, int W, int C, int ph, int pw,

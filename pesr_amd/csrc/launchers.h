@@ -114,6 +114,9 @@ int pesr_adam_launch(float* p, const float* g, float* m, float* v, long n, float
 
 // dsum[col] = sum_k part[k*ncols + col] in double, fixed order (reduce.hip)
 int pesr_reduce_rows_launch(const float* part, double* dsum, int nb, int ncols, hipStream_t stream);
+// out[n] = (sum of part[n*per .. n*per + per - 1]) / count for n < N, float64, fixed order (reduce.hip): the second stage of the SSIM
+// score, the SSIM loss, the LPIPS head and the Gram distance
+int pesr_mean_partials_launch(const double* part, double* out, int N, long per, double count, hipStream_t stream);
 
 // fixed-order split-K reduce of the direct wgrad kernel: slab [split][9][Cout][Cin] -> dw OIHW (+ bias partials -> db)
 int pesr_wgrad_reduce_launch(const float* slab, float* dw, int split, int Cout, int Cin, float alpha, int ps, const float* bias_part,
@@ -214,11 +217,11 @@ int pesr_resize_to_u8_pass_launch(const unsigned char* src, unsigned char* dst, 
 int pesr_psnr_y_launch(const float* a, const float* b, double* out2, int H, int W, int a_nhwc, int b_nhwc, void* ws, size_t ws_bytes,
                        hipStream_t stream);
 
-// SSIM on the Y channel with a border shave (ssim.hip)
+// SSIM on the Y channel with a border shave (ssim.hip, docs/modes.md section 4g)
 int pesr_ssim_y_launch(const float* a, const float* b, double* out, int N, int H, int W, int a_nhwc, int b_nhwc, int shave,
                        double* map, void* ws, size_t ws_bytes, hipStream_t stream);
 
-// SSIM-Y on the unquantised luma as a training loss, and its gradient with respect to a (ssim_loss.hip, docs/modes.md section 4p)
+// SSIM-Y on the unquantised luma as a training loss, and its gradient with respect to a (ssim.hip, docs/modes.md section 4p)
 int pesr_ssim_loss_fwd_launch(const float* a, const float* b, double* score, int N, int H, int W, int a_nhwc, int b_nhwc, double* coef,
                               void* ws, size_t ws_bytes, hipStream_t stream);
 int pesr_ssim_loss_bwd_launch(const float* a, const float* b, const double* coef, const double* g, float* ga, int N, int H, int W,

@@ -94,6 +94,8 @@ int pesr_loss_mse_launch(const float* a, const float* b, float* grad, float* out
 // clipped and rounded again, and the squared differences are summed.  Every term is an integer-valued double, so the sum
 // is exact whatever its order: the result is bit-identical to the host computation.
 // Element (n = 0, c, y, x) of a logical NCHW tensor lives at c*sc + (y*W + x)*sp.
+// luma_u8 is exact_u8.h's exact_luma601_u8 step for step, compiled under this file's default contraction (that header switches
+// contraction off for whatever includes it, which would change psnr_y_kernel's code): it stays a copy.
 // ------------------------------------------------------------------------------------------------
 __device__ __forceinline__ double luma_u8(const float* p, long sc) {
     const double r = rint(fmin(fmax((double)p[0], 0.0), 255.0));
@@ -110,10 +112,8 @@ __global__ __launch_bounds__(256) void psnr_y_kernel(const float* __restrict__ a
         s += d * d;
     }
     __shared__ double red[4];
-    const double w = wave_sum_d(s);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = w;
-    __syncthreads();
-    if (threadIdx.x == 0) part[blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
+    const double t = block_sum_d(s, red);
+    if (threadIdx.x == 0) part[blockIdx.x] = t;
 }
 __global__ void psnr_final_kernel(const double* __restrict__ part, double* __restrict__ out, int nb, double inv_n) {
     if (threadIdx.x == 0) {

@@ -15,8 +15,8 @@
 //   per channel    t = a_k / (na + 1e-10) - b_k / (nb + 1e-10);  acc = acc + w_k * (t * t), k ascending, then across lanes
 //   workgroup      256 lanes = 4 waves own 64 consecutive pixels of one image, wave v pixels 16 v .. 16 v + 15 in ascending order:
 //                  s = s + d(p); then ((s0 + s1) + s2) + s3 -> one partial per workgroup in the workspace
-//   image          lpips_final_kernel: lane t adds partials t, t + 256, ... ascending, wave_sum_d (off = 32 .. 1), ((r0 + r1) + r2) + r3,
-//                  / (H * W).
+//   image          mean_partials_kernel (reduce.hip): lane t adds partials t, t + 256, ... ascending, wave_sum_d (off = 32 .. 1),
+//                  ((r0 + r1) + r2) + r3, / (H * W).
 // No atomics; the order is a function of (H, W, C) alone, so the score has the same bits on every call, with or without the map.
 // The IEEE double division and square root are correctly rounded (their expansions are the only fused operations in this file's code).
 //
@@ -152,23 +152,10 @@ __global__ __launch_bounds__(LPIPS_THREADS) void lpips_layer_kernel(const float*
             }
         }
     }
-    __shared__ double red[LPIPS_THREADS / 64];
+    __shared__ double red[LPIPS_THREADS / 64];                      // block_sum_d without its wave_sum_d: s is the wave's sum already
     if (lane == 0) red[wv] = s;
     __syncthreads();
     if (tid == 0) part[(long)n * gridDim.x + blockIdx.x] = ((red[0] + red[1]) + red[2]) + red[3];
-}
-
-// one workgroup per image pair: lane t adds partials t, t + 256, ... in ascending order, then the fixed tree of wave_sum_d
-__global__ __launch_bounds__(LPIPS_THREADS) void lpips_final_kernel(const double* __restrict__ part, double* __restrict__ out, long groups,
-                                                                     double count) {
-    const double* p = part + blockIdx.x * groups;
-    double s = 0.0;
-    for (long k = threadIdx.x; k < groups; k += LPIPS_THREADS) s = s + p[k];
-    __shared__ double red[LPIPS_THREADS / 64];
-    const double ws = wave_sum_d(s);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = ws;
-    __syncthreads();
-    if (threadIdx.x == 0) out[blockIdx.x] = (((red[0] + red[1]) + red[2]) + red[3]) / count;
 }
 
 // grid (ceil(HW / 64), N): the forward's loads and norms, then the gradient of fa (the order is in this file's header)
@@ -287,8 +274,7 @@ int pesr_lpips_layer2_launch(const float* fa, const float* fb, const float* w, d
     case 256: hipLaunchKernelGGL(lpips_layer_kernel<256>, grid, block, 0, stream, fa, fb, w, part, map, HW); break;
     default: hipLaunchKernelGGL(lpips_layer_kernel<512>, grid, block, 0, stream, fa, fb, w, part, map, HW); break;
     }
-    hipLaunchKernelGGL(lpips_final_kernel, dim3(N), block, 0, stream, (const double*)part, out, groups, (double)HW);
-    return pesr_launch_status();
+    return pesr_mean_partials_launch(part, out, N, groups, (double)HW, stream);
 }
 
 // [a; b] in one tensor: b's features start N * H * W * C floats behind a's, a multiple of 256 bytes

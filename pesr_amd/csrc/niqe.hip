@@ -44,14 +44,13 @@ __device__ __forceinline__ constexpr double niqe_w2(int t) {
     return d == 0 ? 111.0 / 256 : d == 1 ? 29.0 / 256 : d == 2 ? -9.0 / 256 : -3.0 / 256;
 }
 
-// mode 0: floor(((r*0.2989.. + g*0.5870..) + b*0.1140..) + 0.5), MATLAB's rgb2gray; mode 1: ssim.hip's Y.  Integers in 0..255.
+// mode 0: floor(((r*0.2989.. + g*0.5870..) + b*0.1140..) + 0.5), MATLAB's rgb2gray; mode 1: exact_u8.h's Y.  Integers in 0..255.
 __device__ __forceinline__ double niqe_luma(float pr, float pg, float pb, int mode) {
-    const double r = rint(fmin(fmax((double)pr, 0.0), 255.0));
-    const double g = rint(fmin(fmax((double)pg, 0.0), 255.0));
-    const double b = rint(fmin(fmax((double)pb, 0.0), 255.0));
-    if (mode == 0) return floor(((r * 0.298936021293775 + g * 0.587043074451121) + b * 0.114020904255103) + 0.5);
-    const double y = ((r * (65.738 / 256) + g * (129.057 / 256)) + b * (25.064 / 256)) + 16.0;
-    return rint(fmin(fmax(y, 0.0), 255.0));
+    if (mode == 0) {
+        const double r = exact_clip8(pr), g = exact_clip8(pg), b = exact_clip8(pb);
+        return floor(((r * 0.298936021293775 + g * 0.587043074451121) + b * 0.114020904255103) + 0.5);
+    }
+    return exact_luma601_u8(pr, pg, pb);
 }
 
 // grid (ceil(Hc*Wc / 256), 1, N).  Element (c, y, x) of image n lives at n*3*H*W + c*sc + (y*W + x)*sp.

@@ -12,15 +12,7 @@
 #include "launchers.h"
 
 namespace {
-constexpr int SN_NT = 256;
-
-__device__ __forceinline__ double block_sum_d(double v, double* red) {      // fixed order: waves 0..3
-    const double w = wave_sum_d(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = w;
-    __syncthreads();
-    return ((red[0] + red[1]) + red[2]) + red[3];
-}
+constexpr int SN_NT = 256;                // the workgroup of common.h's block_sum_d, which each kernel below calls once
 
 // t[j] = sum_i W[i][j] u[i]  (one thread per column j: coalesced rows); part[block] = sum_j t[j]^2 of the block's columns
 __global__ __launch_bounds__(SN_NT) void sn_wtu_kernel(const float* __restrict__ W, const float* __restrict__ u, float* __restrict__ t,

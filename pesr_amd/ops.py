@@ -1207,45 +1207,47 @@ SSIM_WINDOW = (0.00102838008447911, 0.007598758135239185, 0.03600077212843083, 0
                0.00102838008447911)
 
 
+def _ssim_loss_pair(what: str, a: torch.Tensor, b: torch.Tensor, shave=None):
+    """The checks of ssim_y (with its shave) and of the loss's two halves (shave None) -> the tensors, their layouts, N, H, W and the
+    size Ho x Wo of the map."""
+    (ta, la), (tb, lb) = (_image_layout(t, f"{what}: expected [N, 3, H, W] float32 GPU tensors", 1) for t in (a, b))
+    if ta.shape != tb.shape:
+        raise ValueError(f"{what}: the two tensors differ in shape: {tuple(ta.shape)} and {tuple(tb.shape)}")
+    N, H, W = ta.shape[0], ta.shape[2], ta.shape[3]
+    Ho, Wo = H - 2 * (shave or 0) - 10, W - 2 * (shave or 0) - 10
+    if (shave or 0) < 0 or Ho < 1 or Wo < 1:
+        why = "is smaller than" if shave is None else f"with shave {shave} leaves less than"
+        raise ValueError(f"{what}: a {H} x {W} image {why} the 11 x 11 window")
+    return ta, la, tb, lb, N, H, W, Ho, Wo
+
+
+def _ssim_workspace(N: int, Ho: int, Wo: int, device):
+    """One double per tile of the map; counted with 16 x 16 tiles, which is no fewer than either kernel's tile gives."""
+    return workspace(8 * N * ((Ho + 15) // 16) * ((Wo + 15) // 16), device)
+
+
 def ssim_y(a: torch.Tensor, b: torch.Tensor, shave: int = 0, return_map: bool = False):
     """Y-channel SSIM of N image pairs [N, 3, H, W] (each NCHW-contiguous or channels_last), a border of `shave` pixels ignored
     -> device double [N], the mean of each pair's map; with return_map also the [N, H-2*shave-10, W-2*shave-10] double map."""
-    (ta, la), (tb, lb) = (_image_layout(t, "ssim_y: expected [N, 3, H, W] float32 GPU tensors", 1) for t in (a, b))
-    if ta.shape != tb.shape:
-        raise ValueError(f"ssim_y: the two tensors differ in shape: {tuple(ta.shape)} and {tuple(tb.shape)}")
     shave = int(shave)
-    N, H, W = ta.shape[0], ta.shape[2], ta.shape[3]
-    Ho, Wo = H - 2 * shave - 10, W - 2 * shave - 10
-    if shave < 0 or Ho < 1 or Wo < 1:
-        raise ValueError(f"ssim_y: a {H} x {W} image with shave {shave} leaves less than the 11 x 11 window")
+    ta, la, tb, lb, N, H, W, Ho, Wo = _ssim_loss_pair("ssim_y", a, b, shave)
     out = torch.empty(N, dtype=torch.float64, device=ta.device)
     smap = torch.empty((N, Ho, Wo), dtype=torch.float64, device=ta.device) if return_map else None
-    ws = workspace(8 * N * ((Ho + 15) // 16) * ((Wo + 15) // 16), ta.device)
+    ws = _ssim_workspace(N, Ho, Wo, ta.device)
     rc = _lib.lib().pesr_ssim_y(ta.data_ptr(), tb.data_ptr(), out.data_ptr(), N, H, W, la, lb, shave,
                                 smap.data_ptr() if return_map else None, ws.data_ptr(), ws.numel(), _stream())
     _lib.check(rc, "pesr_ssim_y")
     return (out, smap) if return_map else out
 
 
-def _ssim_loss_pair(what: str, a: torch.Tensor, b: torch.Tensor):
-    (ta, la), (tb, lb) = (_image_layout(t, f"{what}: expected [N, 3, H, W] float32 GPU tensors", 1) for t in (a, b))
-    if ta.shape != tb.shape:
-        raise ValueError(f"{what}: the two tensors differ in shape: {tuple(ta.shape)} and {tuple(tb.shape)}")
-    N, H, W = ta.shape[0], ta.shape[2], ta.shape[3]
-    if H < 11 or W < 11:
-        raise ValueError(f"{what}: a {H} x {W} image is smaller than the 11 x 11 window")
-    return ta, la, tb, lb, N, H, W
-
-
 def ssim_loss_fwd(a: torch.Tensor, b: torch.Tensor, need_grad: bool = False):
     """SSIM-Y on the unquantised luma (docs/modes.md section 4p) of N image pairs [N, 3, H, W], each NCHW-contiguous or channels_last
     -> (device double [N], the mean of each pair's map; coef).  coef is None unless need_grad: then the double [N, 3, H-10, W-10] of
     each window's derivatives with respect to mean(x), mean(x*x) and mean(x*y), what ssim_loss_bwd reads."""
-    ta, la, tb, lb, N, H, W = _ssim_loss_pair("ssim_loss_fwd", a, b)
-    Ho, Wo = H - 10, W - 10
+    ta, la, tb, lb, N, H, W, Ho, Wo = _ssim_loss_pair("ssim_loss_fwd", a, b)
     score = torch.empty(N, dtype=torch.float64, device=ta.device)
     coef = torch.empty((N, 3, Ho, Wo), dtype=torch.float64, device=ta.device) if need_grad else None
-    ws = workspace(8 * N * ((Ho + 15) // 16) * ((Wo + 15) // 16), ta.device)
+    ws = _ssim_workspace(N, Ho, Wo, ta.device)
     rc = _lib.lib().pesr_ssim_loss_fwd(ta.data_ptr(), tb.data_ptr(), score.data_ptr(), N, H, W, la, lb,
                                        coef.data_ptr() if need_grad else None, ws.data_ptr(), ws.numel(), _stream())
     _lib.check(rc, "pesr_ssim_loss_fwd")
@@ -1255,10 +1257,10 @@ def ssim_loss_fwd(a: torch.Tensor, b: torch.Tensor, need_grad: bool = False):
 def ssim_loss_bwd(a: torch.Tensor, b: torch.Tensor, coef: torch.Tensor, g: torch.Tensor) -> torch.Tensor:
     """The gradient of ssim_loss_fwd(a, b)'s score with respect to a (docs/modes.md section 4p).  coef: what the forward returned for the
     same pair; g: device double [N], dL/dscore of each pair -> fp32 [N, 3, H, W] with a's strides.  b gets none."""
-    ta, la, tb, lb, N, H, W = _ssim_loss_pair("ssim_loss_bwd", a, b)
-    if not torch.is_tensor(coef) or not coef.is_cuda or coef.dtype != torch.float64 or tuple(coef.shape) != (N, 3, H - 10, W - 10) \
+    ta, la, tb, lb, N, H, W, Ho, Wo = _ssim_loss_pair("ssim_loss_bwd", a, b)
+    if not torch.is_tensor(coef) or not coef.is_cuda or coef.dtype != torch.float64 or tuple(coef.shape) != (N, 3, Ho, Wo) \
             or not coef.is_contiguous():
-        raise _lib.PesrHipError(f"ssim_loss_bwd.coef: expected a contiguous float64 GPU tensor [{N}, 3, {H - 10}, {W - 10}]")
+        raise _lib.PesrHipError(f"ssim_loss_bwd.coef: expected a contiguous float64 GPU tensor [{N}, 3, {Ho}, {Wo}]")
     if not torch.is_tensor(g) or not g.is_cuda or g.dtype != torch.float64 or tuple(g.shape) != (N,) or not g.is_contiguous():
         raise _lib.PesrHipError(f"ssim_loss_bwd.g: expected a contiguous float64 GPU tensor [{N}]")
     ga = torch.empty_like(ta)                  # (preserve_format: ta is dense in one of the two layouts, so these are its strides)

@@ -9,44 +9,19 @@ score_ordered, coef_ordered and grad_ordered perform the device kernels' IEEE op
 order down), the reduction tree of the score and the one rounding to float32 of the gradient included: the device results are compared
 with them bit for bit.  grad_exact is torch.autograd on a float64 statement of the definition and knows nothing of that order.
 """
-import math
-
 import numpy as np
 
-C1 = (0.01 * 255) * (0.01 * 255)
-C2 = (0.03 * 255) * (0.03 * 255)
-TAPS = 11
+from ssim_oracle import C1, C2, TAPS, _filter, window      # section 4g's window, constants and passes: one statement of them
+
 HALO = TAPS - 1
 KY = (65.738 / 256, 129.057 / 256, 25.064 / 256)
 TILE_H, TILE_W, LANES, WAVE = 16, 32, 256, 64          # the forward's tile of the map and its workgroup: the score's summation order
-
-
-def window():
-    """g[k] = exp(-(k-5)^2 / 4.5) / sum, the sum accumulated in ascending k."""
-    raw = [math.exp(-((k - 5) * (k - 5)) / 4.5) for k in range(TAPS)]
-    total = 0.0
-    for v in raw:
-        total = total + v
-    return [v / total for v in raw]
 
 
 def luma(img):
     """[3, H, W] floats -> float64 Y [H, W], neither clipped nor rounded."""
     rgb = np.asarray(img).astype(np.float64)
     return ((rgb[0] * KY[0] + rgb[1] * KY[1]) + rgb[2] * KY[2]) + 16.0
-
-
-def _filter(v, g):
-    """Separable "valid" filtering of [H, W]: along the height, then along the width, k ascending."""
-    ho = v.shape[0] - HALO
-    wo = v.shape[1] - HALO
-    acc = np.zeros((ho, v.shape[1]))
-    for k in range(TAPS):
-        acc = acc + g[k] * v[k:k + ho, :]
-    out = np.zeros((ho, wo))
-    for k in range(TAPS):
-        out = out + g[k] * acc[:, k:k + wo]
-    return out
 
 
 def _windows(a, b):

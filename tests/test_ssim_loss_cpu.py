@@ -1,6 +1,7 @@
 """CPU: SSIM-Y as a training loss (docs/modes.md section 4p) - the ordered restatement of the gradient (tests/ssim_loss_oracle.py)
 against torch.autograd on the float64 definition, the closed forms of the score, the constants and the absence of fused multiply-adds
-in ssim_loss.hip, the refusals of the two C entry points, of train.py --alpha_ssim and of the Trainer."""
+in ssim.hip (the loss's kernels beside the score's), the refusals of the two C entry points, of train.py --alpha_ssim and of the
+Trainer."""
 import importlib.util
 import os
 import re
@@ -90,20 +91,21 @@ def test_score_ordered_is_the_mean_of_the_map():
 def test_kernel_literals_are_the_restatements():
     from pesr_amd import ops
     assert list(ops.SSIM_WINDOW) == O.window()
-    src = open(os.path.join(ROOT, "pesr_amd", "csrc", "ssim_loss.hip")).read()
-    body = src[src.index("constexpr double ssim_loss_g"):]
+    src = open(os.path.join(ROOT, "pesr_amd", "csrc", "ssim.hip")).read()
+    body = src[src.index("constexpr double ssim_g"):]
     body = body[:body.index("}")]
     assert [float(v) for v in re.findall(r"[:?]\s*(0\.\d+)", body)] == O.window()[5::-1]      # d = 0 .. 5 from the centre outwards
     assert "65.738 / 256" in src and "129.057 / 256" in src and "25.064 / 256" in src
-    tile = re.search(r"SL_TH = (\d+), SL_TW = (\d+)", src)
+    tile = re.search(r"SsimLossTile = SsimTile<(\d+), (\d+),", src)
     assert (int(tile.group(1)), int(tile.group(2))) == (O.TILE_H, O.TILE_W)                   # the score's summation order
 
 
 def test_kernels_have_no_fused_multiply_add_outside_the_divisions():
-    """As tests/test_ssim_cpu.py for ssim.hip: every v_fma_f64 / v_fmac_f64 belongs to the expansion of an IEEE double division."""
+    """As tests/test_ssim_cpu.py, for the file with all three kernels in it (one division in the score, six in the loss's forward, one
+    in its backward): every v_fma_f64 / v_fmac_f64 belongs to the expansion of an IEEE double division."""
     from pesr_amd import build
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    cmd = [hipcc] + build.HIPCC_FLAGS + ["-S", "--cuda-device-only", os.path.join(build.CSRC, "ssim_loss.hip"), "-o", "-"]
+    cmd = [hipcc] + build.HIPCC_FLAGS + ["-S", "--cuda-device-only", os.path.join(build.CSRC, "ssim.hip"), "-o", "-"]
     asm = subprocess.run(cmd, check=True, capture_output=True, text=True).stdout
     count = lambda pat: len(re.findall(pat, asm))
     divs = count(r"\bv_div_fixup_f64\b")

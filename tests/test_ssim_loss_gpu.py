@@ -1,6 +1,6 @@
 """GPU: SSIM-Y as a training loss (docs/modes.md section 4p).
 
-Score, coefficient maps and gradient of pesr_amd/csrc/ssim_loss.hip against tests/ssim_loss_oracle.py BIT FOR BIT: the kernels' order
+Score, coefficient maps and gradient of pesr_amd/csrc/ssim.hip's loss kernels against tests/ssim_loss_oracle.py BIT FOR BIT: the kernels' order
 of operations is fixed and nothing is fused, so kernel and restatement perform the same IEEE operations, the score's summation tree and
 the gradient's one rounding to float32 included.  How far the ordered gradient is from autograd on the definition is bounded on the CPU
 (tests/test_ssim_loss_cpu.py).  Then the layouts, the margins, and the training steps with the term off, on and captured."""
@@ -75,6 +75,17 @@ def test_special_inputs_bit_for_bit(h, w):
             assert np.isfinite(grad).all()
             if kind == "same":
                 assert score.tolist() == [1.0] * n
+
+
+def test_score_of_more_partials_than_lanes_bit_for_bit():
+    """267 x 491: a 257 x 481 map, 17 x 16 = 272 tiles per image, so the mean of an image's partials (reduce.hip, shared with the SSIM-Y
+    score, the LPIPS head and the Gram distance) takes a second round of its lane loop, a tail of 16.  No smaller shape above does."""
+    from pesr_amd import ops
+    n, h, w = 2, 267, 491
+    assert -(-(h - 10) // O.TILE_H) * -(-(w - 10) // O.TILE_W) == O.LANES + 16
+    a, b, _ = C.case("noise", n, h, w)
+    score, _ = ops.ssim_loss_fwd(_dev(a), _dev(b))
+    _same_bits(score, O.score_ordered(a, b), f"noise {n} x {h} x {w}: score")
 
 
 def test_margins_come_back_intact():
