@@ -69,8 +69,9 @@ PESR_API long pesr_conv3x3_bn_rows(int which, int N, int H, int W, int Cin, int 
             rc = pesr_conv3x3_s2_dgrad_launch(nullptr, nullptr, nullptr, nullptr, N, H, W, Cout, Cin, 1.f, nullptr, &a);
         }
     } else if (which == 2) {
-        rc = pesr_conv3x3_wino4_launch(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, N, H, W, Cin, Cout, 1.f, PESR_ACT_NONE, 0.f, 0, 0, nullptr, 0,
-                                       nullptr, &a);
+        const size_t wsb = pesr_conv3x3_workspace_bytes(N, H, W, Cout);
+        rc = pesr_conv3x3_wino4_launch(nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, N, H, W, Cin, Cout, 1.f, PESR_ACT_NONE, 0.f, 0, 0,
+                                       wsb ? (void*)8 : nullptr, wsb, nullptr, &a);
     }
     return rc ? 0 : a.rows_out;
 }

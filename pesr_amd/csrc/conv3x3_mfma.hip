@@ -698,7 +698,8 @@ static int launch_cfg(ConvArgs& a, int hext, int wext, hipStream_t stream, int t
     a.bn_rows = (a.cout_store % 4 == 0 && NT % (WAVES_N * WN * 4) == 0 && !a.ps)
                     ? (a.ksplit == 1 ? (long)a.N * a.tiles_y * a.tiles_x : pesr_conv_splitk_finish_bn_rows(a.cout_store, a.ksplit)) : 0;
     if (a.dry) return PESR_OK;
-    if (a.bn_mode && (a.bn_rows == 0 || a.bn_row0 + a.bn_rows > a.bn_cap || !g_bn_epi.part)) return PESR_EINVAL;
+    // (equality: the caller finalizes over the rows it allocated - a row this launch does not write would be summed uninitialised)
+    if (a.bn_mode && (a.bn_rows == 0 || a.bn_row0 + a.bn_rows != a.bn_cap || !g_bn_epi.part)) return PESR_EINVAL;
     const size_t out_bytes = (size_t)a.N * a.OH * a.OW * a.cout_store * sizeof(float);
     const float* bias = a.bias; const float* skip = a.skip; const float* mask = a.mask;
     BnEpi a_bn = g_bn_epi;
@@ -747,7 +748,7 @@ static int launch_s2dgrad4(ConvArgs4& a4, const int* hext, const int* wext, hipS
     }
     a4.c[0].bn_rows = rows_ok ? rows : 0;
     if (a4.c[0].dry) return PESR_OK;
-    if (a4.c[0].bn_mode && (!rows_ok || rows > a4.c[0].bn_cap || !g_bn_epi.part)) return PESR_EINVAL;
+    if (a4.c[0].bn_mode && (!rows_ok || rows != a4.c[0].bn_cap || !g_bn_epi.part)) return PESR_EINVAL;
     if (gmax == 0) return PESR_OK;
     auto kern = conv3x3_s2dgrad4_kernel<WAVES_M, WAVES_N, WM, WN, HL>;
     static PesrDeviceOnce attr_once;

@@ -25,11 +25,49 @@
 // The 16-byte k-groups of a V entry are XOR-swizzled by ((x-tile >> 1) ^ row term) so that the ds_read_b128 fragment reads
 // are bank-conflict free for TXT = 12 (48-wide images: row term 2 * (halo row & 1)) and TXT = 8 / 16 / 24 (no row term).
 // Layers with too few tiles split the Cin chunks over workgroups (raw partial sums + the direct kernel's finish kernel).
+#include <cstdlib>
 #include <mutex>
+#include <type_traits>
 #include "common.h"
 #include "launchers.h"
 #include "conv_epilogue.h"
 #include "wino4_pack.h"
+
+// ---- timing-only builds (scripts/wino4_loop.py builds them into libraries of their own; every macro is off in the product, and the
+// file then compiles to the code it compiled to without them) ---------------------------------------------------------------------
+//   W4_STAMPS         s_memtime (shader clocks; each XCD counts from a base of its own, so only differences inside a wave mean anything)
+//                     per wave at kernel entry, end of prologue, arrival at / release from every chunk barrier, arrival at and release
+//                     from the exchange barrier, last store issued, stores acknowledged, and s_memrealtime (100 MHz) at both ends for
+//                     the clock: kept in LDS behind the exchange slots, copied to g_w4_stamps with vector stores at the end; read back
+//                     by pesr_debug_w4_stamps()
+//   W4_NO_XFORM       no staging transform and no LDS stores (the staged loads are still waited for)
+//   W4_NO_STLOAD      no staging loads
+//   W4_NO_BARRIER     no barrier per chunk
+//   W4_NO_AREAD       no A-fragment reads (the registers are reused)
+//   W4_NO_WLOAD       no weight loads
+//   W4_NO_EXCHANGE    no epilogue exchange (no LDS stores, barrier or reads: every wave stores what it has)
+//   W4_MFMA_ONLY      the five loop ablations together: nothing but the MFMAs (and the fences around them)
+//   W4_NO_FENCES      no sched_barrier pairs around the groups of 12 MFMAs (this one computes the right result)
+// All but the last give WRONG results.
+#ifdef W4_MFMA_ONLY
+#define W4_NO_XFORM
+#define W4_NO_STLOAD
+#define W4_NO_BARRIER
+#define W4_NO_AREAD
+#define W4_NO_WLOAD
+#endif
+#ifdef W4_STAMPS
+constexpr int W4_ST_SLOTS = 48, W4_ST_WGS = 2048, W4_ST_LDS = 2 * 9 * 2 * 4 * 64 * 16;   // the stamps' LDS lies behind the exchange slots
+__device__ unsigned long long g_w4_stamps[W4_ST_WGS * 8 * W4_ST_SLOTS];
+PESR_API int pesr_debug_w4_stamps(unsigned long long* out, int wgs) {
+    if (wgs < 1 || wgs > W4_ST_WGS) return PESR_EINVAL;
+    return (int)hipMemcpyFromSymbol(out, HIP_SYMBOL(g_w4_stamps), (size_t)wgs * 8 * W4_ST_SLOTS * sizeof(unsigned long long));
+}
+#define W4_STAMP(K) { const unsigned long long t_ = __builtin_amdgcn_s_memtime(); if (lane == 0) w4_st[K] = t_; }
+#define W4_STAMP_REAL(K) { const unsigned long long t_ = __builtin_amdgcn_s_memrealtime(); if (lane == 0) w4_st[K] = t_; }
+#else
+#define W4_STAMP(K)
+#endif
 
 struct Wino4Args {
     const float* x;     // [N][H][W][Cin]
@@ -72,7 +110,10 @@ constexpr int W4_BN = 64, W4_MG = 9;
 // BNF: the instantiation carries the BatchNorm-sums epilogue (common.h BnEpi; the Discriminator's layers).  false: none of that code -
 // the Generator's / VGG's kernels keep the register allocation they had (with it, the 18 prefetched z values of mode 2 cost the
 // 48-wide instantiation 52 bytes of scratch in its epilogue).
-template <bool DENSE, int TXTC, bool BNF = false>
+// LOOP: the chunk loop of wino4_loop.md (docs/experiments): the last chunk peeled off, so that it stages and prefetches nothing, and the
+// first fragment read of a chunk issued in front of its staging loads.  false: the loop as it was before, selected by PESR_WINO4_LOOP=0
+// (same products, same order of additions: tests/test_wino4_loop_gpu.py compares the two with torch.equal).
+template <bool DENSE, int TXTC, bool BNF = false, bool LOOP = true>
 __global__ __launch_bounds__(512) void conv3x3_wino4_kernel(const Wino4Args a, const BnEpi bn_arg) {
     (void)bn_arg;                                          // BatchNorm sums from the epilogue (common.h BnEpi): read through pesr_bn_epi() behind the main loop
     static_assert(!(DENSE && TXTC), "the constant-row-length form is for the non-dense layout");
@@ -89,6 +130,13 @@ __global__ __launch_bounds__(512) void conv3x3_wino4_kernel(const Wino4Args a, c
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int r = lane & 15, g = lane >> 4;
     const int cb = wave & 3, xt = wave >> 2;               // channel block, xi group
+#ifdef W4_STAMPS
+    unsigned long long* const w4_st = (unsigned long long*)(smem + W4_ST_LDS) + wave * W4_ST_SLOTS;
+#endif
+#ifdef W4_STAMPS
+    W4_STAMP_REAL(38)
+#endif
+    W4_STAMP(0)
     // xi plane of this wave's local index xl
     auto xi_of = [&](int xl) -> int { return xt * 3 + xl; };
 
@@ -188,11 +236,23 @@ __global__ __launch_bounds__(512) void conv3x3_wino4_kernel(const Wino4Args a, c
     // at the top of a chunk and stored a third in, item 1 is loaded right there and stored two thirds in.
     u32x4 sx[6];
     auto stage_load = [&](int u, int cc) {
+#ifdef W4_NO_STLOAD
+        (void)u; (void)cc;
+#pragma unroll
+        for (int j = 0; j < 6; ++j) asm volatile("" : "+v"(sx[j]));
+#else
         const int so = __builtin_amdgcn_readfirstlane(chunk_off(cc));
 #pragma unroll
         for (int j = 0; j < 6; ++j) sx[j] = __builtin_amdgcn_raw_buffer_load_b128(x_rsrc, st_off[u][j], so, 0);
+#endif
     };
     auto stage_store = [&](int u, char* vdst) {
+#ifdef W4_NO_XFORM
+        (void)u; (void)vdst;
+#pragma unroll
+        for (int j = 0; j < 6; ++j) asm volatile("" ::"v"(sx[j]));
+        return;
+#endif
         if (st_dst[u] >= 0) {
             const f32x4 d0 = __builtin_bit_cast(f32x4, sx[0]), d1 = __builtin_bit_cast(f32x4, sx[1]),
                         d2 = __builtin_bit_cast(f32x4, sx[2]), d3 = __builtin_bit_cast(f32x4, sx[3]),
@@ -220,7 +280,15 @@ __global__ __launch_bounds__(512) void conv3x3_wino4_kernel(const Wino4Args a, c
         for (int i = 0; i < W4_MG; ++i) acc[xl][i] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
     f32x4 fa[2][3], fb[3];
-    // the xor of the odd-ky reads is redone at every use: hoisted out of the loop it would cost nine more live registers
+    // The key's row term is there for rows of 12 x-tiles only (row_key: TXT % 8 == 4), and those run on TXTC = 12.  The LOOP form uses
+    // that: no xor at all for the other row lengths, and for 12 the nine offsets of the odd ky live in registers of their own, kept up
+    // with a_off - 27 v_xor fewer per chunk and wave, and hipcc allocates 228 VGPRs instead of 246 (G body 171.1 -> 167.2 us with bias +
+    // ReLU, 173.8 -> 169.7 with the skip, 174.2 -> 169.8 with the mask: docs/experiments/wino4_loop.md).
+    // The form before redoes the xor at every use: hoisted out of ITS loop it cost nine more live registers of the 254.
+    constexpr bool ODD = LOOP && !DENSE;
+    constexpr int KX = TXTC == 12 ? 32 : 0;
+    static_assert(TXTC == 0 || TXTC == 12 || TXTC == 24, "KX: the row term of the key for a constant row length");
+    int a_odd[W4_MG];
     auto opaque = [](int v) -> int { asm volatile("" : "+s"(v)); return v; };
     auto a_key = [&](const int i, const int ky) -> int {   // fragment offset of m-tile i for the V row ky below the tile row
         if (DENSE) {
@@ -228,10 +296,14 @@ __global__ __launch_bounds__(512) void conv3x3_wino4_kernel(const Wino4Args a, c
             const unsigned tab = ky == 1 ? ktab1 : ktab2;
             return a_off[i] ^ (int)((tab >> (2 * i)) & 0x30u);
         }
+        if (ODD) return ((ky & 1) && KX) ? a_odd[i] : a_off[i];
         return (ky & 1) ? (a_off[i] ^ opaque(kxor)) : a_off[i];
     };
     // Fragment reads through 32-bit LDS addresses (a_off carries the dynamic-LDS base, added once): written as `smem + offset`
     // every read paid a v_add_u32 of the base's relocation - a literal 0 hipcc cannot fold (36 per chunk and wave).
+#ifdef W4_NO_AREAD
+#define W4_READ_A(FA, VB, KY, XL, GRP) { (void)(VB); }
+#else
 #define W4_READ_A(FA, VB, KY, XL, GRP)                                                                   \
     {                                                                                                    \
         const unsigned vb_ = TXTC ? (unsigned)((KY) * v_row + (XL) * plane)                              \
@@ -239,7 +311,18 @@ __global__ __launch_bounds__(512) void conv3x3_wino4_kernel(const Wino4Args a, c
         _Pragma("unroll") for (int i = 0; i < 3; ++i)                                                    \
             FA[i] = *(const __attribute__((address_space(3))) f32x4*)(size_t)((unsigned)a_key((GRP) * 3 + i, KY) + vb_); \
     }
-#define W4_MFMA(FA, FB, XL, GRP)                                                                         \
+#endif
+#ifdef W4_NO_WLOAD
+#define W4_LDB(DST, KY, XL, CC) { (void)(CC); }
+#else
+#define W4_LDB(DST, KY, XL, CC) DST = ldb(KY, XL, CC);
+#endif
+#ifdef W4_NO_FENCES
+#define W4_FENCE()
+#else
+#define W4_FENCE() __builtin_amdgcn_sched_barrier(0);
+#endif
+#define W4_MFMA(FA, FB, XL, GRP)                                                                        \
     _Pragma("unroll") for (int kk = 0; kk < 4; ++kk)                                                     \
         _Pragma("unroll") for (int i = 0; i < 3; ++i)                                                    \
             acc[XL][(GRP) * 3 + i] = __builtin_amdgcn_mfma_f32_16x16x4f32(FB[kk], FA[i][kk], acc[XL][(GRP) * 3 + i], 0, 0, 0);
@@ -251,57 +334,96 @@ __global__ __launch_bounds__(512) void conv3x3_wino4_kernel(const Wino4Args a, c
         stage_load(0, CB);
 #pragma unroll
         for (int j = 0; j < 6; ++j) sy[j] = __builtin_amdgcn_raw_buffer_load_b128(x_rsrc, st_off[1][j], so, 0);
-        fb[0] = ldb(0, 0, CB);
-        fb[1] = ldb(0, 1, CB);
+#if defined(W4_NO_WLOAD) || defined(W4_NO_AREAD)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) { asm volatile("" : "=v"(fb[j])); asm volatile("" : "=v"(fa[0][j])); asm volatile("" : "=v"(fa[1][j])); }
+#endif
+        W4_LDB(fb[0], 0, 0, CB)
+        W4_LDB(fb[1], 0, 1, CB)
         compute_a_off();
+        if (ODD && KX) {
+#pragma unroll
+            for (int i = 0; i < W4_MG; ++i) a_odd[i] = a_off[i] ^ KX;
+        }
         stage_store(0, smem);
 #pragma unroll
         for (int j = 0; j < 6; ++j) sx[j] = sy[j];
         stage_store(1, smem);
     }
     __syncthreads();
+    W4_STAMP(1)
 
+    // One chunk, as a macro so that the loop and the peeled copy are the same text (and the LOOP = false kernels the same instructions as
+    // before).  LAST: the peeled last chunk of the LOOP form, which has no successor - it stages nothing and fetches no weights beyond its
+    // own.  The loop itself has no branch: with the prefetch under `if (more)` the staging registers and weight fragments had two
+    // definitions merging at the loop header, and hipcc could not count the outstanding loads exactly.  So the form before (LOOP = false)
+    // lets the last chunk "prefetch" itself again (loads, transforms and LDS stores nobody consumes), and the LOOP form runs the loop over
+    // all chunks but the last and the body once more behind it: the loop waits for vmcnt(8), (8), (2) .. as before, the copy ends on
+    // vmcnt(1), (0) (docs/experiments/wino4_loop.md).  In the body: the weight slab s + 2 (of this chunk, or the first ones of the next)
+    // is fetched at the top of slab s; each group's sched_barrier pair keeps the next group's fragment reads ahead of its 12 MFMAs (hipcc
+    // sinks them next to their use); a third / two thirds in, the staged loads have landed and are transformed into the other V buffer
+    // under the MFMAs, at raised priority - a staging wave's VALU instructions and LDS stores then issue ahead of the other wave's MFMAs
+    // instead of between them (G body 172.0 -> 171.2 us with bias + ReLU, 176.0 -> 174.3 with the skip, 177.3 -> 175.2 with the mask).
+    // LOOP: the chunk's first fragment read goes in front of the six staging loads - every wave comes out of the barrier waiting for it.
+#ifdef W4_NO_BARRIER
+#define W4_CHUNK_BARRIER()
+#else
+#define W4_CHUNK_BARRIER() __syncthreads();
+#endif
+#define W4_CHUNK(c, LAST)                                                                                                                                                   \
+        char* const vcur = smem + (c & 1) * v_bytes;                                                                                                                        \
+        char* const vnext = smem + ((c & 1) ^ 1) * v_bytes;                                                                                                                 \
+        const int cn = CB + (LOOP ? c + 1 : (c + 1 < C16 ? c + 1 : c));                                                                                                     \
+        if (LOOP) {                                                                                                                                                         \
+            W4_READ_A(fa[0], vcur, 0, 0, 0)                                                                                                                                 \
+            W4_FENCE()                                                                                                                                                      \
+            if (!LAST) stage_load(0, cn);                                                                                                                                   \
+        } else {                                                                                                                                                            \
+            stage_load(0, cn);                                                                                                                                              \
+            W4_READ_A(fa[0], vcur, 0, 0, 0)                                                                                                                                 \
+        }                                                                                                                                                                   \
+_Pragma("unroll")                                                                                                                                                           \
+        for (int s = 0; s < NSLAB; ++s) {                                                                                                                                   \
+            const int ky = s / NXL, xl = s - ky * NXL;                                                                                                                      \
+            {                                                                                                                                                               \
+                if (s + 2 < NSLAB) W4_LDB(fb[(s + 2) % 3], (s + 2) / NXL, (s + 2) % NXL, CB + c)                                                                            \
+                else if (!LAST) W4_LDB(fb[(s + 2) % 3], 0, s + 2 - NSLAB, cn)                                                                                               \
+            }                                                                                                                                                               \
+_Pragma("unroll")                                                                                                                                                           \
+            for (int grp = 0; grp < 3; ++grp) {                                                                                                                             \
+                const int t = s * 3 + grp, cur = t & 1;                                                                                                                     \
+                if (grp < 2) W4_READ_A(fa[cur ^ 1], vcur, ky, xl, grp + 1)                                                                                                  \
+                else if (s + 1 < NSLAB) W4_READ_A(fa[cur ^ 1], vcur, (s + 1) / NXL, (s + 1) % NXL, 0)                                                                       \
+                W4_FENCE()                                                                                                                                                  \
+                W4_MFMA(fa[cur], fb[s % 3], xl, grp)                                                                                                                        \
+                W4_FENCE()                                                                                                                                                  \
+            }                                                                                                                                                               \
+            if (!LAST) {                                                                                                                                                    \
+                if (s == 2) { __builtin_amdgcn_s_setprio(3); stage_store(0, vnext); stage_load(1, cn); __builtin_amdgcn_sched_barrier(0); __builtin_amdgcn_s_setprio(0); }  \
+                if (s == 6) { __builtin_amdgcn_s_setprio(3); stage_store(1, vnext); __builtin_amdgcn_sched_barrier(0); __builtin_amdgcn_s_setprio(0); }                     \
+            }                                                                                                                                                               \
+        }                                                                                                                                                                   \
+        if (TXTC && !LAST) {                                                                                                                                                \
+            const int dv = (c & 1) ? -v_bytes : v_bytes;                                                                                                                    \
+_Pragma("unroll")                                                                                                                                                           \
+            for (int i = 0; i < W4_MG; ++i) { a_off[i] += dv; if (ODD && KX) a_odd[i] += dv; }                                                                              \
+        }                                                                                                                                                                   \
+        W4_STAMP(2 + 2 * (c < 16 ? c : 15))                                                                                                                                 \
+        W4_CHUNK_BARRIER()                                                                                                                                                  \
+        W4_STAMP(3 + 2 * (c < 16 ? c : 15))
+    if (LOOP) {
 #pragma unroll 1
-    for (int c = 0; c < C16; ++c) {
-        char* const vcur = smem + (c & 1) * v_bytes;      // (TXTC: the fragment offsets carry the buffer, moved below)
-        char* const vnext = smem + ((c & 1) ^ 1) * v_bytes;
-        // No branch in the loop: the last chunk "prefetches" itself again (loads, transforms and LDS stores nobody consumes).  With
-        // the prefetch under `if (more)` the staging registers and weight fragments had two definitions merging at the loop header,
-        // and hipcc could not count the outstanding loads exactly.
-        const int cn = CB + (c + 1 < C16 ? c + 1 : c);
-        stage_load(0, cn);                                 // lands while this chunk computes
-        W4_READ_A(fa[0], vcur, 0, 0, 0)
-#pragma unroll
-        for (int s = 0; s < NSLAB; ++s) {                  // slab s = (ky, xl)
-            const int ky = s / NXL, xl = s - ky * NXL;
-            // weight slab s + 2 (of this chunk, or the first ones of the next)
-            {
-                if (s + 2 < NSLAB) fb[(s + 2) % 3] = ldb((s + 2) / NXL, (s + 2) % NXL, CB + c);
-                else fb[(s + 2) % 3] = ldb(0, s + 2 - NSLAB, cn);
-            }
-#pragma unroll
-            for (int grp = 0; grp < 3; ++grp) {
-                const int t = s * 3 + grp, cur = t & 1;
-                if (grp < 2) W4_READ_A(fa[cur ^ 1], vcur, ky, xl, grp + 1)
-                else if (s + 1 < NSLAB) W4_READ_A(fa[cur ^ 1], vcur, (s + 1) / NXL, (s + 1) % NXL, 0)
-                __builtin_amdgcn_sched_barrier(0);         // keep the prefetch ahead of the MFMA group (hipcc sinks it next to its use)
-                W4_MFMA(fa[cur], fb[s % 3], xl, grp)
-                __builtin_amdgcn_sched_barrier(0);
-            }
-            // A third / two thirds in, the staged loads have landed: transform them into the other V buffer under the MFMAs.
-            // (raised priority while a wave stages: its VALU instructions and LDS stores issue ahead of the other wave's MFMAs instead of
-            // between them - G body 172.0 -> 171.2 us with bias + ReLU, 176.0 -> 174.3 with the skip, 177.3 -> 175.2 with the mask)
-            if (s == 2) { __builtin_amdgcn_s_setprio(3); stage_store(0, vnext); stage_load(1, cn); __builtin_amdgcn_sched_barrier(0); __builtin_amdgcn_s_setprio(0); }
-            if (s == 6) { __builtin_amdgcn_s_setprio(3); stage_store(1, vnext); __builtin_amdgcn_sched_barrier(0); __builtin_amdgcn_s_setprio(0); }
-        }
-        if (TXTC) {
-            const int dv = (c & 1) ? -v_bytes : v_bytes;
-#pragma unroll
-            for (int i = 0; i < W4_MG; ++i) a_off[i] += dv;
-        }
-        __syncthreads();                                   // V[next] complete and visible; everyone is done with V[cur]
+        for (int c = 0; c + 1 < C16; ++c) { W4_CHUNK(c, false) }
+        { const int c = C16 - 1; W4_CHUNK(c, true) }
+    } else {
+#pragma unroll 1
+        for (int c = 0; c < C16; ++c) { W4_CHUNK(c, false) }
     }
 #undef W4_READ_A
+#undef W4_LDB
+#undef W4_CHUNK
+#undef W4_CHUNK_BARRIER
+#undef W4_FENCE
 #undef W4_MFMA
     // ---- epilogue ------------------------------------------------------------------------------------------------------------
     // With the weights as the MFMA's A operand a lane holds, per m-tile i, FOUR CONSECUTIVE CHANNELS (cb*16 + 4g ..) of x-tile
@@ -319,11 +441,15 @@ __global__ __launch_bounds__(512) void conv3x3_wino4_kernel(const Wino4Args a, c
         if (xt == 0) {
             const f32x4 sm = q1 + q2, df = q1 - q2;
             keep[i][0] = q0 + sm; keep[i][1] = df;
+#ifndef W4_NO_EXCHANGE
             *(f32x4*)slot(0, i, 0) = sm; *(f32x4*)slot(0, i, 1) = df;
+#endif
         } else {
             const f32x4 sm = q0 + q1, df = q0 - q1;
             keep[i][0] = 4.0f * sm; keep[i][1] = 8.0f * df + q2;
+#ifndef W4_NO_EXCHANGE
             *(f32x4*)slot(1, i, 0) = sm; *(f32x4*)slot(1, i, 1) = 2.0f * df;
+#endif
         }
     }
     const size_t img_out = (size_t)img * a.H * a.W;
@@ -348,7 +474,11 @@ __global__ __launch_bounds__(512) void conv3x3_wino4_kernel(const Wino4Args a, c
         if (!ok) *idx = 0;
         return ok;
     };
+    W4_STAMP(34)
+#ifndef W4_NO_EXCHANGE
     __syncthreads();
+#endif
+    W4_STAMP(35)
     // BatchNorm mode 2 reads z at every output element: all 18 loads of a lane are issued here, right behind the exchange barrier (in
     // front of it the barrier's vmcnt(0) would wait for them with nothing to overlap - conv3x3_mfma.hip measured both)
     const BnEpi* const bn = pesr_bn_epi((unsigned)((sizeof(Wino4Args) + 7) & ~(size_t)7));
@@ -388,7 +518,11 @@ __global__ __launch_bounds__(512) void conv3x3_wino4_kernel(const Wino4Args a, c
             const int i = ib + (e >> 1), k = e & 1;
             ok[e] = out_index(i, k, &idx[e]);
             // same order of additions as a sequential y = (xi 0..2 part) + (xi 3..5 part)
+#ifdef W4_NO_EXCHANGE
+            v[e] = keep[i][k];
+#else
             v[e] = xt == 0 ? keep[i][k] + *(const f32x4*)slot(1, i, k) : *(const f32x4*)slot(0, i, k) + keep[i][k];
+#endif
             if (a.ksplit == 1) {
                 if (a.mask) mkv[e] = *(const f32x4*)(a.mask + idx[e]);
                 if (a.skip) skv[e] = *(const f32x4*)(a.skip + idx[e]);
@@ -413,6 +547,13 @@ __global__ __launch_bounds__(512) void conv3x3_wino4_kernel(const Wino4Args a, c
             *(f32x4*)(a.y + idx[e]) = o;
         }
     }
+#ifdef W4_STAMPS
+    W4_STAMP(36)
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    W4_STAMP(37)
+    W4_STAMP_REAL(39)
+    if (blockIdx.x < W4_ST_WGS && lane < W4_ST_SLOTS) g_w4_stamps[(blockIdx.x * 8 + wave) * W4_ST_SLOTS + lane] = w4_st[lane];
+#endif
     if (bn_on) {
         // a lane's 18 outputs are pixels of ITS four channels (co .. co + 3): the 16 r-lanes x 2 xi-half waves of a (cb, g) pair
         // meet through LDS and are added in double, in the fixed order (xt, r)
@@ -542,14 +683,16 @@ int pesr_conv3x3_wino4_launch(const float* x, const float* wp, const float* bias
                               void* ws, size_t ws_bytes, hipStream_t stream, PesrBnFuseArgs* fuse) {
     W4Plan p;
     if (fuse) fuse->rows_out = 0;
-    if (!w4_plan(N, H, W, Cin, Cout, (ws != nullptr || (fuse && fuse->dry)) && !ps, (fuse && fuse->dry) ? (size_t)-1 : ws_bytes, !ps && !ps_in, &p)) return PESR_EINVAL;
+    // (a dry call plans with the workspace it is given too: pesr_conv3x3_bn_rows passes what ops.py passes, pesr_conv3x3_workspace_bytes)
+    if (!w4_plan(N, H, W, Cin, Cout, ws != nullptr && !ps, ws_bytes, !ps && !ps_in, &p)) return PESR_EINVAL;
     // BatchNorm sums: one row per pixel tile from the epilogue; with split-K from the finish kernel that sums the slabs (one row per finish
     // workgroup); not with a shuffled store
     const long bn_rows = ps ? 0 : (p.ksplit == 1 ? p.tiles / p.n_tiles : pesr_conv_splitk_finish_bn_rows(Cout, p.ksplit));
     if (fuse) {
         fuse->rows_out = bn_rows;
         if (fuse->dry) return PESR_OK;
-        if (fuse->mode && (bn_rows == 0 || bn_rows > fuse->rows || !fuse->part)) return PESR_EINVAL;
+        // equality: the caller finalizes over the rows it allocated, and a row this launch does not write would be summed uninitialised
+        if (fuse->mode && (bn_rows == 0 || bn_rows != fuse->rows || !fuse->part)) return PESR_EINVAL;
         if (fuse->mode == 2 && (mask || skip || bias || act != PESR_ACT_NONE)) return PESR_EINVAL;
     }
     if (ps && (Cout % 256 || skip || mask)) return PESR_EINVAL;    // a 64-channel n-tile must stay inside one sub-pixel plane
@@ -561,6 +704,7 @@ int pesr_conv3x3_wino4_launch(const float* x, const float* wp, const float* bias
     a.TR = p.TR; a.TXT = p.TXT; a.HT = p.TR + 2;
     a.tiles_x = p.tiles_x; a.tiles_y = p.tiles_y; a.n_tiles = p.n_tiles;
     a.row_key = (p.TXT % 8 == 4) ? 2 : 0;
+    if (!p.dense && p.TXT != 12 && a.row_key) return PESR_EINVAL;   // the LOOP form relies on it: a row term only on the TXTC = 12 kernels
     a.ksplit = p.ksplit; a.chunks_per_split = p.chunks_per_split; a.slab = (float*)ws;
     a.stack = p.stack; a.stack_n = N; a.v_row = p.v_row;
     if (p.stack) a.N = 1;
@@ -570,27 +714,33 @@ int pesr_conv3x3_wino4_launch(const float* x, const float* wp, const float* bias
         bn.beta = fuse->beta; bn.slope = fuse->slope;
         if (p.ksplit > 1) { bn_fin = bn; bn = BnEpi{}; }      // the conv kernel stores raw partial sums: the finish kernel does the BatchNorm part
     }
-    static PesrDeviceOnce attr_once;
-    attr_once([&] {
-        (void)hipFuncSetAttribute((const void*)conv3x3_wino4_kernel<false, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void*)conv3x3_wino4_kernel<false, 12>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void*)conv3x3_wino4_kernel<false, 24>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void*)conv3x3_wino4_kernel<true, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void*)conv3x3_wino4_kernel<false, 0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void*)conv3x3_wino4_kernel<false, 12, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void*)conv3x3_wino4_kernel<false, 24, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void*)conv3x3_wino4_kernel<true, 0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    });
+    // PESR_WINO4_LOOP=0: the chunk loop as it was before the LOOP form (read at every launch: an A/B switch, and the bit-identity test's)
+    const char* const loop_env = getenv("PESR_WINO4_LOOP");
+    const bool loop = !(loop_env && loop_env[0] == '0' && !loop_env[1]);
+    size_t lds = p.lds;
+#ifdef W4_STAMPS
+    if (p.lds > (size_t)W4_ST_LDS) return PESR_EINVAL;
+    lds = (size_t)W4_ST_LDS + 8 * W4_ST_SLOTS * sizeof(unsigned long long);
+#endif
     const dim3 grid((unsigned)(p.tiles * p.ksplit));
+    static PesrDeviceOnce attr_once[16];
+#define W4_LAUNCH(ID, ...)                                                                                                  \
+    {                                                                                                                       \
+        attr_once[ID]([&] { (void)hipFuncSetAttribute((const void*)conv3x3_wino4_kernel<__VA_ARGS__>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); }); \
+        hipLaunchKernelGGL((conv3x3_wino4_kernel<__VA_ARGS__>), grid, dim3(512), lds, stream, a, bn);                        \
+    }
+#define W4_LAUNCH_LOOP(ID, ...) { if (loop) W4_LAUNCH(2 * (ID), __VA_ARGS__, true) else W4_LAUNCH(2 * (ID) + 1, __VA_ARGS__, false) }
     if (bn.mode) {
-        if (p.dense) hipLaunchKernelGGL((conv3x3_wino4_kernel<true, 0, true>), grid, dim3(512), p.lds, stream, a, bn);
-        else if (p.TXT == 12) hipLaunchKernelGGL((conv3x3_wino4_kernel<false, 12, true>), grid, dim3(512), p.lds, stream, a, bn);
-        else if (p.TXT == 24) hipLaunchKernelGGL((conv3x3_wino4_kernel<false, 24, true>), grid, dim3(512), p.lds, stream, a, bn);
-        else hipLaunchKernelGGL((conv3x3_wino4_kernel<false, 0, true>), grid, dim3(512), p.lds, stream, a, bn);
-    } else if (p.dense) hipLaunchKernelGGL((conv3x3_wino4_kernel<true, 0>), grid, dim3(512), p.lds, stream, a, bn);
-    else if (p.TXT == 12) hipLaunchKernelGGL((conv3x3_wino4_kernel<false, 12>), grid, dim3(512), p.lds, stream, a, bn);
-    else if (p.TXT == 24) hipLaunchKernelGGL((conv3x3_wino4_kernel<false, 24>), grid, dim3(512), p.lds, stream, a, bn);
-    else hipLaunchKernelGGL((conv3x3_wino4_kernel<false, 0>), grid, dim3(512), p.lds, stream, a, bn);
+        if (p.dense) W4_LAUNCH_LOOP(0, true, 0, true)
+        else if (p.TXT == 12) W4_LAUNCH_LOOP(1, false, 12, true)
+        else if (p.TXT == 24) W4_LAUNCH_LOOP(2, false, 24, true)
+        else W4_LAUNCH_LOOP(3, false, 0, true)
+    } else if (p.dense) W4_LAUNCH_LOOP(4, true, 0, false)
+    else if (p.TXT == 12) W4_LAUNCH_LOOP(5, false, 12, false)
+    else if (p.TXT == 24) W4_LAUNCH_LOOP(6, false, 24, false)
+    else W4_LAUNCH_LOOP(7, false, 0, false)
+#undef W4_LAUNCH_LOOP
+#undef W4_LAUNCH
     if (p.ksplit > 1 && bn_fin.mode)
         return pesr_conv_splitk_finish_bn_launch((const float*)ws, bias, y, (long)N * H * W * Cout, Cout, p.ksplit, alpha, bn_fin, stream);
     if (p.ksplit > 1)
