@@ -431,6 +431,34 @@ int pesr_gram_loss(const float* ga, const float* gb, double* t, float* dg_or_nul
  * f, dg and gf on 16-byte boundaries, g on 8. */
 int pesr_gram_bwd(const float* f, const float* dg, const double* g, float* gf, int N, int H, int W, int C, int ph, int pw, void* stream);
 
+/* ---- Contextual loss (docs/modes.md section 4r), features as P points of C channels per image: [N][P][C] fp32 ------- */
+/* N in 1 .. 65535, P in 1 .. 4096, C in {64, 128, 256}: anything else -> PESR_EINVAL with nothing launched, as do a null pointer and a
+ * misaligned one (feature-sized arrays on 16-byte boundaries, doubles on 8, the rest on 4).  fp32 MFMA for the two GEMMs, doubles for
+ * the sums, no atomics, fixed summation orders: the same call gives the same bits.  64-bit offsets (D is [N][P][P]).
+ * The four planners are pure host functions of the shape and return 0 for a shape the kernels do not take: the row blocks (of 64 rows)
+ * of the distance and the row kernels, the column pieces (of 64 columns) that the distance kernel stages, the workspace that
+ * pesr_cx_fwd and pesr_cx_bwd want (less -> PESR_EWORKSPACE), and the bytes that a forward keeps for its backward. */
+int pesr_cx_row_blocks(int N, int P, int C);
+int pesr_cx_col_pieces(int N, int P, int C);
+size_t pesr_cx_workspace_bytes(int N, int P, int C);
+size_t pesr_cx_saved_bytes(int N, int P, int C);
+/* mu [N][C] = the mean of fb's points (double sum, one rounding); xh = (fa - mu) r, yh = (fb - mu) r with
+ * r = (float)(1 / sqrt(sum_c (f - mu)^2 + 1e-12)), the sum in double; inv [N][P] = r of fa's points. */
+int pesr_cx_normalize(const float* fa, const float* fb, float* mu, float* xh, float* yh, float* inv, int N, int P, int C, void* stream);
+/* D [N][P][P] = fma(-0.5, xh_i . yh_j, 0.5) with the dot product on the MFMA (a channel-ordered fmaf chain); m [N][P] = min_k D_ik and
+ * b [N][P] (int32) its lowest index, bit for bit from the stored D. */
+int pesr_cx_dist(const float* xh, const float* yh, float* D, float* m, int* b, int N, int P, int C, void* stream);
+/* w_ik = expf(fma(-D_ik, 1 / (m_i + 1e-5), 1) (float)(1 / h)); S [N][P] = sum_k w_ik (double, rounded once); c_ik = w_ik (1 / S_i);
+ * cmax [N][P] = max_i c_ij and a [N][P] (int32) its lowest index; CX [N] = (sum_j cmax_j) / P and L [N] = -log CX as doubles.  h > 0. */
+int pesr_cx_fwd(const float* D, const float* m, double h, float* S, int* a, float* cmax, double* CX, double* L, int N, int P, int C,
+                void* workspace, size_t ws_bytes, void* stream);
+/* The gradient of sum_n gL[n] L[n] with respect to fa, with a and b held fixed: gf [N][P][C] fp32.  E = dL/dD is formed from D on the fly
+ * (section 4r), g_xh = -E yh / 2 on the MFMA, gf = (g_xh - xh (xh . g_xh)) inv.  gL[n] == 0 -> image n all zero.  e_or_null [N][P][P] and
+ * gxh_or_null [N][P][C]: when non-null they receive E and g_xh (for tests; nothing else reads them).  Not masked by fa > 0. */
+int pesr_cx_bwd(const float* D, const float* m, const int* b, const float* S, const int* a, const float* cmax, const double* CX,
+                const double* gL, const float* xh, const float* yh, const float* inv, double h, float* gf, float* e_or_null,
+                float* gxh_or_null, int N, int P, int C, void* workspace, size_t ws_bytes, void* stream);
+
 /* ---- NIQE block statistics (docs/modes.md section 4k), N images [N][3][H][W] (nhwc: [N][H][W][3]) ------- */
 /* The device half of the no-reference score of Mittal et al. as section 4k restates it.  RGB clipped to 0..255 and rounded; luma
  * 0 = MATLAB's rgb2gray, floor(((r*0.298936021293775 + g*0.587043074451121) + b*0.114020904255103) + 0.5), luma 1 = the Y of the

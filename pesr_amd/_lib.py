@@ -7,7 +7,7 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import c_float, c_int, c_long, c_size_t, c_void_p
+from ctypes import c_double, c_float, c_int, c_long, c_size_t, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("PESR_HIP_LIB") or os.path.join(_HERE, "libpesr_hip.so")   # override: experiment builds only
@@ -104,6 +104,14 @@ SIGNATURES.update({
     "pesr_gram_loss_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "pesr_gram_loss": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, _P, c_size_t, _P]),
     "pesr_gram_bwd": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
+    "pesr_cx_row_blocks": (c_int, [c_int, c_int, c_int]),
+    "pesr_cx_col_pieces": (c_int, [c_int, c_int, c_int]),
+    "pesr_cx_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "pesr_cx_saved_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "pesr_cx_normalize": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, _P]),
+    "pesr_cx_dist": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, _P]),
+    "pesr_cx_fwd": (c_int, [_P, _P, c_double, _P, _P, _P, _P, _P, c_int, c_int, c_int, _P, c_size_t, _P]),
+    "pesr_cx_bwd": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_double, _P, _P, _P, c_int, c_int, c_int, _P, c_size_t, _P]),
     "pesr_niqe_stats": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, c_size_t, _P]),
     "pesr_lpips_layer": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, _P, _P, c_size_t, _P]),
     "pesr_lpips_layer2": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, _P, _P, c_size_t, _P]),

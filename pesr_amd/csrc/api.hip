@@ -413,6 +413,35 @@ PESR_API int pesr_gram_bwd(const float* f, const float* dg, const double* g, flo
     return pesr_gram_bwd_launch(f, dg, g, gf, N, H, W, C, ph, pw, (hipStream_t)stream);
 }
 
+PESR_API int pesr_cx_row_blocks(int N, int P, int C) { return pesr_cx_row_blocks_host(N, P, C); }
+
+PESR_API int pesr_cx_col_pieces(int N, int P, int C) { return pesr_cx_col_pieces_host(N, P, C); }
+
+PESR_API size_t pesr_cx_workspace_bytes(int N, int P, int C) { return pesr_cx_workspace_bytes_host(N, P, C); }
+
+PESR_API size_t pesr_cx_saved_bytes(int N, int P, int C) { return pesr_cx_saved_bytes_host(N, P, C); }
+
+PESR_API int pesr_cx_normalize(const float* fa, const float* fb, float* mu, float* xh, float* yh, float* inv, int N, int P, int C,
+                               void* stream) {
+    return pesr_cx_normalize_launch(fa, fb, mu, xh, yh, inv, N, P, C, (hipStream_t)stream);
+}
+
+PESR_API int pesr_cx_dist(const float* xh, const float* yh, float* D, float* m, int* b, int N, int P, int C, void* stream) {
+    return pesr_cx_dist_launch(xh, yh, D, m, b, N, P, C, (hipStream_t)stream);
+}
+
+PESR_API int pesr_cx_fwd(const float* D, const float* m, double h, float* S, int* a, float* cmax, double* CX, double* L, int N, int P,
+                         int C, void* workspace, size_t ws_bytes, void* stream) {
+    return pesr_cx_fwd_launch(D, m, h, S, a, cmax, CX, L, N, P, C, workspace, ws_bytes, (hipStream_t)stream);
+}
+
+PESR_API int pesr_cx_bwd(const float* D, const float* m, const int* b, const float* S, const int* a, const float* cmax, const double* CX,
+                         const double* gL, const float* xh, const float* yh, const float* inv, double h, float* gf, float* e_or_null,
+                         float* gxh_or_null, int N, int P, int C, void* workspace, size_t ws_bytes, void* stream) {
+    return pesr_cx_bwd_launch(D, m, b, S, a, cmax, CX, gL, xh, yh, inv, h, gf, e_or_null, gxh_or_null, N, P, C, workspace, ws_bytes,
+                              (hipStream_t)stream);
+}
+
 PESR_API int pesr_niqe_stats(const float* img, int N, int H, int W, int nhwc, int shave, int B, int luma, double* stats,
                              double* mscn1_or_null, double* mscn2_or_null, void* workspace, size_t ws_bytes, void* stream) {
     return pesr_niqe_stats_launch(img, N, H, W, nhwc, shave, B, luma, stats, mscn1_or_null, mscn2_or_null, workspace, ws_bytes,

@@ -238,6 +238,20 @@ int pesr_gram_loss_launch(const float* ga, const float* gb, double* t, float* dg
 int pesr_gram_bwd_launch(const float* f, const float* dg, const double* g, float* gf, int N, int H, int W, int C, int ph, int pw,
                          hipStream_t stream);
 
+// Contextual loss: normalised points, their distances with row minima, CX and -log CX, the gradient (cx.hip, docs/modes.md section 4r)
+int pesr_cx_row_blocks_host(int N, int P, int C);
+int pesr_cx_col_pieces_host(int N, int P, int C);
+size_t pesr_cx_workspace_bytes_host(int N, int P, int C);
+size_t pesr_cx_saved_bytes_host(int N, int P, int C);
+int pesr_cx_normalize_launch(const float* fa, const float* fb, float* mu, float* xh, float* yh, float* inv, int N, int P, int C,
+                             hipStream_t stream);
+int pesr_cx_dist_launch(const float* xh, const float* yh, float* D, float* m, int* b, int N, int P, int C, hipStream_t stream);
+int pesr_cx_fwd_launch(const float* D, const float* m, double h, float* S, int* a, float* M, double* CX, double* L, int N, int P, int C,
+                       void* ws, size_t ws_bytes, hipStream_t stream);
+int pesr_cx_bwd_launch(const float* D, const float* m, const int* b, const float* S, const int* a, const float* M, const double* CX,
+                       const double* gL, const float* xh, const float* yh, const float* inv, double h, float* gf, float* e_out,
+                       float* gxh_out, int N, int P, int C, void* ws, size_t ws_bytes, hipStream_t stream);
+
 // NIQE block statistics: luma, crop, two scales, MSCN maps, 26 sums per block and scale (niqe.hip)
 int pesr_niqe_stats_launch(const float* img, int N, int H, int W, int nhwc, int shave, int B, int luma, double* stats, double* mscn1,
                            double* mscn2, void* ws, size_t ws_bytes, hipStream_t stream);

@@ -13,7 +13,9 @@
 // gradients.  RCCL's all-reduce keeps workgroups resident for the whole transfer, and ONE held compute unit costs every
 // 256-workgroup conv kernel a second round (x 1.82, profiles/r03_cu_contention.txt).  The flag words count epochs upwards (waits are
 // ">="), so nothing is ever reset.  Primitives verified on this runtime with two processes on one GPU: scripts/ipc_probe.py.
+#include <chrono>
 #include <cstring>
+#include <thread>
 #include "common.h"
 
 namespace {
@@ -87,14 +89,40 @@ PESR_API int pesr_peer_free(void* ptr) { return (int)hipFree(ptr); }
 // Abandon an exchange that does not complete: every wait of THIS rank's streams is a ">= epoch" on a word of its own flag block, so
 // filling the block with 0xffffffff (on a stream of its own: the stuck ones cannot be used) lets all of them run out.  The copies
 // then move whatever the peers' buffers hold - the caller discards the result and the transport.
+// A process has few hardware queues (GPU_MAX_HW_QUEUES, 4 by default) and every stream is given one of them, the least used at the
+// time: a fresh stream can land on the queue of a stuck one, where the command processor is polling in front of everything queued
+// behind it - a hipStreamSynchronize there never returns.  Which queue a stream gets depends on how many streams the process holds
+// (captured graphs keep some), so the fill is tried on one fresh stream after another, each kept alive so that the next one is
+// given another queue, and every wait here has a deadline: the first fill that completes lets all stuck queues run out.
 PESR_API int pesr_peer_release(void* my_flags, size_t bytes) {
     if (!my_flags || !bytes) return PESR_EINVAL;
-    hipStream_t s;
-    hipError_t e = hipStreamCreateWithFlags(&s, hipStreamNonBlocking);
-    if (e != hipSuccess) { (void)hipGetLastError(); return (int)e; }
-    e = hipMemsetAsync(my_flags, 0xff, bytes, s);
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    (void)hipStreamDestroy(s);
+    constexpr int TRIES = 64;
+    hipStream_t s[TRIES];
+    int n = 0;
+    bool filled = false;
+    hipError_t e = hipSuccess;
+    auto done_within = [](hipStream_t q, double seconds, hipError_t* err) {
+        const auto t0 = std::chrono::steady_clock::now();
+        for (;;) {
+            const hipError_t r = hipStreamQuery(q);
+            if (r == hipSuccess) return true;
+            if (r != hipErrorNotReady) { *err = r; return false; }
+            if (std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count() > seconds) return false;
+            std::this_thread::sleep_for(std::chrono::milliseconds(1));
+        }
+    };
+    while (!filled && n < TRIES && e == hipSuccess) {
+        e = hipStreamCreateWithFlags(&s[n], hipStreamNonBlocking);
+        if (e != hipSuccess) break;
+        ++n;
+        e = hipMemsetAsync(my_flags, 0xff, bytes, s[n - 1]);
+        if (e == hipSuccess) filled = done_within(s[n - 1], 0.1, &e);
+    }
+    // the fills queued behind a stuck stream complete once the first one has landed (they write the same bytes)
+    for (int i = 0; i < n && filled && e == hipSuccess; ++i)
+        if (!done_within(s[i], 10.0, &e) && e == hipSuccess) e = hipErrorNotReady;
+    for (int i = 0; i < n; ++i) (void)hipStreamDestroy(s[i]);
+    if (e == hipSuccess && !filled) e = hipErrorNotReady;
     if (e != hipSuccess) (void)hipGetLastError();
     return (int)e;
 }

@@ -1112,6 +1112,38 @@ def texture_layer(fa, fb, patch=0):
     return TextureLayerFn.apply(fa, fb, patch)
 
 
+# ------------------------------------------------------------------------------------------------
+# contextual loss of one tapped layer    docs/modes.md section 4r
+# ------------------------------------------------------------------------------------------------
+class ContextualLayerFn(Function):
+    """(fa, fb) NHWC [N, H, W, C] -> float64 [N], -log CX: ops.cx_normalize, ops.cx_dist, ops.cx_fwd; only fa gets a gradient (fb is the
+    no_grad hr pass), ops.cx_bwd on what the three stages left, with the selections held fixed.  When fa needs no gradient nothing is
+    saved.  Like TextureLayerFn's, the gradient is NOT masked by fa > 0: the tap's own conv masks the sum of its consumers' gradients."""
+
+    @staticmethod
+    def forward(ctx, fa, fb, h):
+        need = ctx.needs_input_grad[0]
+        fa, fb = _c(fa), _c(fb)
+        xh, yh, inv, _ = ops.cx_normalize(fa, fb)
+        D, m, b = ops.cx_dist(xh, yh)
+        L, CX, S, a, cmax = ops.cx_fwd(D, m, h, fa.shape[3])
+        ctx.h, ctx.shape = float(h), tuple(fa.shape)
+        if need:
+            ctx.save_for_backward(xh, yh, inv, D, m, b, S, a, cmax, CX)
+        return L
+
+    @staticmethod
+    def backward(ctx, g):
+        if not ctx.needs_input_grad[0]:
+            return None, None, None
+        xh, yh, inv, D, m, b, S, a, cmax, CX = ctx.saved_tensors
+        return ops.cx_bwd(_c(g), xh, yh, inv, D, m, b, S, a, cmax, CX, ctx.h, ctx.shape), None, None
+
+
+def contextual_layer(fa, fb, h=0.5):
+    return ContextualLayerFn.apply(fa, fb, h)
+
+
 class VggTailFn(Function):
     """conv4_1 .. conv5_4 (+ pool4) of vgg19 features[:35] (reference model/vgg.py:8-10,19-26) for the sr AND the hr branch in one
     batch: forward on cat(a, b) - one launch per layer over 2B images instead of two over B -, backward on the sr half only (the

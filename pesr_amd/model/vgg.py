@@ -81,14 +81,30 @@ class VGG(nn.Module):
     # all in front of TAIL_START
     TAPS = (1, 6, 11)
 
-    def _run(self, h, lo, hi, prev_relu=False, taps=None):
-        """features[lo:hi].  taps: None, or a list that receives the NHWC outputs of the ReLUs at TAPS.  A tapped output has two
+    def _tap_indices(self, taps):
+        """forward()'s `taps` -> the ascending tuple of `features` indices to tap, or None.  True is TAPS; a tuple names ReLUs in
+        front of TAIL_START (17 = relu3_4, the contextual loss's tap, docs/modes.md section 4r)."""
+        if taps is False or taps is None:
+            return None
+        if taps is True:
+            return self.TAPS
+        which = tuple(sorted({int(t) for t in taps}))
+        mods = list(self.vgg)
+        for t in which:
+            if not (0 < t < self.TAIL_START and isinstance(mods[t], nn.ReLU)):
+                raise ValueError(f"VGG taps: {t} is not the index of a ReLU of vgg19.features in front of {self.TAIL_START}")
+        if not which:
+            raise ValueError("VGG taps: an empty tuple; pass taps=False for none")
+        return which
+
+    def _run(self, h, lo, hi, prev_relu=False, taps=None, which=TAPS):
+        """features[lo:hi].  taps: None, or a list that receives the NHWC outputs of the ReLUs at `which`.  A tapped output has two
         consumers, so its conv masks the sum of their gradients itself (relu_grad_by_consumer = False) and the next layer does not
         (relu_in = False) - the rule of LpipsModel.features_grad; the forward values do not depend on it."""
         i = lo
         for kind, m, has_relu in self._steps(lo, hi):
             if kind == "conv":
-                tap = taps is not None and has_relu and (i + 1) in self.TAPS
+                tap = taps is not None and has_relu and (i + 1) in which
                 by_consumer = has_relu and not tap
                 h = m(h, act=ops.ACT_RELU if has_relu else ops.ACT_NONE, relu_in=prev_relu,
                       relu_grad_by_consumer=by_consumer)   # every other ReLU here feeds a conv or a pool that masks for it
@@ -114,15 +130,18 @@ class VGG(nn.Module):
         (profiles/r04_merge_probe.txt).  The input gradient runs on the sr half only.  Not in the bf16 mode (its oracle mirrors the
         per-pass dispatch), not when the tail's weights are trainable, not for unequal shapes.
         taps=True: -> (features(sr), features(hr), taps_sr, taps_hr), the NHWC outputs of the ReLUs at TAPS of both passes (the hr
-        ones without gradient) from the same two trunk passes; the two feature tensors are the bits of the taps=False call."""
+        ones without gradient) from the same two trunk passes; the two feature tensors are the bits of the taps=False call.
+        taps=(i, ...): the same for the ReLUs at these `features` indices, all in front of TAIL_START, in ascending order."""
         n = len(self.vgg)
         merge = (sr.shape == hr.shape and n > self.TAIL_START and ops.PRECISION == "fp32" and sr.is_cuda
                  and not any(p.requires_grad for p in self.vgg[self.TAIL_START:].parameters()))
+        which = self._tap_indices(taps)
+        taps = which is not None
         taps_sr, taps_hr = ([], []) if taps else (None, None)
         split = self.TAIL_START if merge else n
-        a = self._run(self.sub_mean(sr), 0, split, taps=taps_sr)
+        a = self._run(self.sub_mean(sr), 0, split, taps=taps_sr, which=which)
         with torch.no_grad():
-            b = self._run(self.sub_mean(hr.detach()), 0, split, taps=taps_hr)
+            b = self._run(self.sub_mean(hr.detach()), 0, split, taps=taps_hr, which=which)
         if merge:
             fa, fb = PF.VggTailFn.apply(nhwc(a), nhwc(b), self._steps(self.TAIL_START, n))
             a, b = nchw(fa), nchw(fb)

@@ -1414,6 +1414,127 @@ def gram_bwd(f: torch.Tensor, dg: torch.Tensor, g: torch.Tensor, patch=0) -> tor
 
 
 # ------------------------------------------------------------------------------------------------
+# contextual loss (docs/modes.md section 4r): the stages of pesr_amd/csrc/cx.hip, separately callable
+# ------------------------------------------------------------------------------------------------
+CX_MAX_POINTS = 4096
+
+
+def _chk_cx(what: str, t, shape, dtype=torch.float32):
+    if not torch.is_tensor(t) or not t.is_cuda or t.dtype != dtype or not t.is_contiguous() or (shape is not None and tuple(t.shape) != tuple(shape)):
+        want = "" if shape is None else f" {list(shape)}"
+        raise _lib.PesrHipError(f"{what}: expected a contiguous {str(dtype).replace('torch.', '')} GPU tensor{want} (there is no CPU path)")
+
+
+def _chk_cx_shape(what: str, N: int, P: int, C: int):
+    if C not in GRAM_CHANNELS:
+        raise _lib.PesrHipError(f"{what}: C = {C}, the contextual kernels take C in {GRAM_CHANNELS}")
+    if not 1 <= P <= CX_MAX_POINTS:
+        raise _lib.PesrHipError(f"{what}: P = {P} points per image, the contextual kernels take 1 .. {CX_MAX_POINTS}")
+    if not 1 <= N <= 65535:
+        raise _lib.PesrHipError(f"{what}: N = {N}, the contextual kernels take 1 .. 65535 images")
+
+
+def cx_plan(N: int, P: int, C: int) -> dict:
+    """What the contextual kernels do with N images of P points and C channels (a host-only question): {"row_blocks": the blocks of 64
+    rows of the distance and the row kernels; "col_pieces": the pieces of 64 columns the distance kernel stages; "workspace_bytes": what
+    cx_fwd and cx_bwd want; "saved_bytes": what a forward keeps for its backward}.  ValueError for a shape the kernels do not take."""
+    rb = _memo("pesr_cx_row_blocks", N, P, C)
+    if rb < 1:
+        raise ValueError(f"cx_plan: no contextual kernel for N {N}, P {P}, C {C}")
+    return {"row_blocks": rb, "col_pieces": _memo("pesr_cx_col_pieces", N, P, C),
+            "workspace_bytes": int(_lib.lib().pesr_cx_workspace_bytes(N, P, C)), "saved_bytes": int(_lib.lib().pesr_cx_saved_bytes(N, P, C))}
+
+
+def cx_normalize(fa: torch.Tensor, fb: torch.Tensor):
+    """NHWC features fa (sr), fb (hr) [N, H, W, C] -> (xh, yh, inv, mu): both centred on fb's mean mu [N, C] and scaled to unit length
+    (smooth at 0), fp32 [N, P, C] with P = H W row-major; inv [N, P] = 1 / sqrt(|fa - mu|^2 + 1e-12), what the backward needs."""
+    for name, f in (("fa", fa), ("fb", fb)):
+        if not torch.is_tensor(f) or not f.is_cuda or f.dtype != torch.float32 or f.dim() != 4 or not f.is_contiguous():
+            raise _lib.PesrHipError(f"cx_normalize.{name}: expected contiguous [N, H, W, C] float32 GPU tensors (NHWC features; there is no "
+                                    "CPU path)")
+    if tuple(fa.shape) != tuple(fb.shape):
+        raise _lib.PesrHipError(f"cx_normalize: the two tensors differ in shape: {tuple(fa.shape)} and {tuple(fb.shape)}")
+    N, H, W, C = fa.shape
+    P = H * W
+    _chk_cx_shape("cx_normalize", N, P, C)
+    xh = torch.empty((N, P, C), dtype=torch.float32, device=fa.device)
+    yh, inv, mu = torch.empty_like(xh), xh.new_empty((N, P)), xh.new_empty((N, C))
+    rc = _lib.lib().pesr_cx_normalize(_p(fa), _p(fb), _p(mu), _p(xh), _p(yh), _p(inv), N, P, C, _stream())
+    _lib.check(rc, "pesr_cx_normalize")
+    return xh, yh, inv, mu
+
+
+def cx_dist(xh: torch.Tensor, yh: torch.Tensor):
+    """(xh, yh) fp32 [N, P, C] -> (D fp32 [N, P, P] = (1 - xh_i . yh_j) / 2 on the fp32 MFMA, m fp32 [N, P] = min_k D_ik, b int32 [N, P] its
+    lowest index)."""
+    _chk_cx("cx_dist.xh", xh, None)
+    if xh.dim() != 3:
+        raise _lib.PesrHipError(f"cx_dist.xh: expected [N, P, C], got {tuple(xh.shape)}")
+    _chk_cx("cx_dist.yh", yh, xh.shape)
+    N, P, C = xh.shape
+    _chk_cx_shape("cx_dist", N, P, C)
+    D = torch.empty((N, P, P), dtype=torch.float32, device=xh.device)
+    m = torch.empty((N, P), dtype=torch.float32, device=xh.device)
+    b = torch.empty((N, P), dtype=torch.int32, device=xh.device)
+    rc = _lib.lib().pesr_cx_dist(_p(xh), _p(yh), _p(D), _p(m), _p(b), N, P, C, _stream())
+    _lib.check(rc, "pesr_cx_dist")
+    return D, m, b
+
+
+def cx_fwd(D: torch.Tensor, m: torch.Tensor, h: float = 0.5, C: int = 256):
+    """(D, m) of cx_dist -> (L float64 [N] = -log CX, CX float64 [N], S fp32 [N, P] the row sums of the weights, a int32 [N, P] the arg
+    max over i of c_ij (lowest i), cmax fp32 [N, P] that maximum).  h > 0 is the bandwidth; C only names the plan."""
+    _chk_cx("cx_fwd.D", D, None)
+    if D.dim() != 3 or D.shape[1] != D.shape[2]:
+        raise _lib.PesrHipError(f"cx_fwd.D: expected [N, P, P], got {tuple(D.shape)}")
+    N, P = D.shape[0], D.shape[1]
+    _chk_cx("cx_fwd.m", m, (N, P))
+    _chk_cx_shape("cx_fwd", N, P, C)
+    if not float(h) > 0:
+        raise _lib.PesrHipError(f"cx_fwd: h must be > 0, got {h}")
+    S, cmax = torch.empty_like(m), torch.empty_like(m)
+    a = torch.empty((N, P), dtype=torch.int32, device=D.device)
+    CX = torch.empty(N, dtype=torch.float64, device=D.device)
+    L = torch.empty_like(CX)
+    ws = workspace(cx_plan(N, P, C)["workspace_bytes"], D.device)
+    rc = _lib.lib().pesr_cx_fwd(_p(D), _p(m), float(h), _p(S), _p(a), _p(cmax), _p(CX), _p(L), N, P, C, _p(ws), ws.numel(), _stream())
+    _lib.check(rc, "pesr_cx_fwd")
+    return L, CX, S, a, cmax
+
+
+def cx_bwd(gL: torch.Tensor, xh, yh, inv, D, m, b, S, a, cmax, CX, h: float = 0.5, shape=None, parts: bool = False):
+    """The gradient of sum_n gL[n] L[n] with respect to the sr features, the selections a, b held fixed: fp32 [N, H, W, C] (`shape`;
+    default [N, P, 1, C]).  gL: device double [N]; the rest is what cx_normalize, cx_dist and cx_fwd returned.  Not masked by fa > 0.
+    parts=True: -> (gf, E fp32 [N, P, P] = dL/dD, g_xh fp32 [N, P, C] = -E yh / 2), the two intermediates, for tests."""
+    _chk_cx("cx_bwd.xh", xh, None)
+    if xh.dim() != 3:
+        raise _lib.PesrHipError(f"cx_bwd.xh: expected [N, P, C], got {tuple(xh.shape)}")
+    N, P, C = xh.shape
+    _chk_cx_shape("cx_bwd", N, P, C)
+    _chk_cx("cx_bwd.yh", yh, (N, P, C))
+    _chk_cx("cx_bwd.D", D, (N, P, P))
+    for name, t in (("inv", inv), ("m", m), ("S", S), ("cmax", cmax)):
+        _chk_cx("cx_bwd." + name, t, (N, P))
+    for name, t in (("a", a), ("b", b)):
+        _chk_cx("cx_bwd." + name, t, (N, P), torch.int32)
+    for name, t in (("gL", gL), ("CX", CX)):
+        _chk_cx("cx_bwd." + name, t, (N,), torch.float64)
+    if not float(h) > 0:
+        raise _lib.PesrHipError(f"cx_bwd: h must be > 0, got {h}")
+    shape = (N, P, 1, C) if shape is None else tuple(shape)
+    if len(shape) != 4 or shape[0] != N or shape[1] * shape[2] != P or shape[3] != C:
+        raise _lib.PesrHipError(f"cx_bwd: shape {shape} is not [N, H, W, C] of {N} x {P} points x {C}")
+    gf = torch.empty(shape, dtype=torch.float32, device=xh.device)
+    E = torch.empty_like(D) if parts else None
+    gxh = torch.empty_like(xh) if parts else None
+    ws = workspace(cx_plan(N, P, C)["workspace_bytes"], xh.device)
+    rc = _lib.lib().pesr_cx_bwd(_p(D), _p(m), _p(b), _p(S), _p(a), _p(cmax), _p(CX), _p(gL), _p(xh), _p(yh), _p(inv), float(h), _p(gf),
+                                _p(E), _p(gxh), N, P, C, _p(ws), ws.numel(), _stream())
+    _lib.check(rc, "pesr_cx_bwd")
+    return (gf, E, gxh) if parts else gf
+
+
+# ------------------------------------------------------------------------------------------------
 # tiled inference (docs/modes.md section 4h; the plan and the driver are pesr_amd/tile.py)
 # ------------------------------------------------------------------------------------------------
 def _tile_desc(desc, cols: int, device):

@@ -74,8 +74,16 @@ def _img(x: torch.Tensor) -> torch.Tensor:
 class Trainer:
     def __init__(self, G, D=None, vgg=None, optim_G=None, optim_D=None, *, gan_type="RSGAN", focal_loss=True, fl_gamma=1.0,
                  alpha_vgg=50.0, alpha_gan=1.0, alpha_tv=1e-6, alpha_l1=0.0, world_size=1, gradient_penalty=False,
-                 lpips_model=None, alpha_lpips=0.0, alpha_ssim=0.0, alpha_texture=0.0, texture_patch=16):
+                 lpips_model=None, alpha_lpips=0.0, alpha_ssim=0.0, alpha_texture=0.0, texture_patch=16, alpha_cx=0.0, cx_h=0.5):
         self.G, self.D, self.vgg = G, D, vgg
+        # the contextual loss of the VGG19 tap relu3_4 (docs/modes.md section 4r) as a term of gan_step's generator loss: on only with a
+        # positive weight; off, the VGG is called as without the two arguments.  cx_h: the bandwidth h of the weights
+        self.alpha_cx, self.cx_h = float(alpha_cx), float(cx_h)
+        if not self.alpha_cx >= 0:
+            raise ValueError(f"alpha_cx must be >= 0, got {alpha_cx}")
+        if not self.cx_h > 0:
+            raise ValueError(f"cx_h must be > 0, got {cx_h}")
+        self.use_cx = self.alpha_cx > 0
         # the texture loss, Gram matrices of three VGG19 taps (docs/modes.md section 4q), as a term of gan_step's generator loss: on
         # only with a positive weight; off, the VGG is called without taps and the step launches exactly what it launches without the
         # two arguments.  texture_patch: the side of the patches in each tap's own pixels, 0 = the whole map
@@ -200,8 +208,16 @@ class Trainer:
         # gradients that optim_D.step() has to wait for.  Same graph, same values; only the launch order differs.
         sr_nhwc, hr_nhwc = nhwc(sr), nhwc(hr_cl)
         l1_loss = PF.l1_loss(sr_nhwc, hr_nhwc) * self.alpha_l1
-        texture_loss = None
-        if self.use_texture:     # the taps come out of the same two trunk passes; a batch mean like l1 and vgg: no world_size factor
+        texture_loss = cx_loss = None
+        if self.use_cx:          # one call with the union of the taps; batch means like l1 and vgg: no world_size factor
+            from .contextual import TAP, contextual_from_tap
+            from .texture import TAPS, texture_from_taps
+            which = (TAPS if self.use_texture else ()) + (TAP,)
+            vgg_sr, vgg_hr, taps_sr, taps_hr = self.vgg(sr, hr_cl, taps=which)
+            if self.use_texture:
+                texture_loss = texture_from_taps(taps_sr[:-1], taps_hr[:-1], self.texture_patch).mean().float() * self.alpha_texture
+            cx_loss = contextual_from_tap(taps_sr[-1], taps_hr[-1], self.cx_h).mean().float() * self.alpha_cx
+        elif self.use_texture:   # the taps come out of the same two trunk passes; a batch mean like l1 and vgg: no world_size factor
             from .texture import texture_from_taps
             vgg_sr, vgg_hr, taps_sr, taps_hr = self.vgg(sr, hr_cl, taps=True)
             texture_loss = texture_from_taps(taps_sr, taps_hr, self.texture_patch).mean().float() * self.alpha_texture
@@ -245,6 +261,8 @@ class Trainer:
             total_G_loss = total_G_loss + ssim_loss
         if texture_loss is not None:
             total_G_loss = total_G_loss + texture_loss
+        if cx_loss is not None:
+            total_G_loss = total_G_loss + cx_loss
         total_G_loss.backward()
         self.optim_G.step()
         logs = {"l1": l1_loss.detach(), "vgg": vgg_loss.detach(), "g": G_loss.detach(), "tv": tv_local.detach(),
@@ -257,6 +275,8 @@ class Trainer:
             logs["ssim"] = ssim_loss.detach()
         if texture_loss is not None:
             logs["texture"] = texture_loss.detach()
+        if cx_loss is not None:
+            logs["cx"] = cx_loss.detach()
         return logs
 
     # ---- the GAN step as ONE hipGraph ------------------------------------------------------------------------------------

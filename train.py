@@ -140,6 +140,11 @@ def build_parser():
     p.add_argument("--texture_patch", type=int, default=16,
                    help="side of the texture loss's patches, in each tap's own pixels (EnhanceNet: 16); it must divide the three tap "
                         "sizes (--patch_size * --scale, a half and a quarter of it); 0 = the whole map (Gatys / Johnson)")
+    p.add_argument("--alpha_cx", type=float, default=0.0,
+                   help="weight of the contextual loss of the generator's loss (docs/modes.md section 4r: -log CX of relu3_4 of the "
+                        "VGG19 trunk that --alpha_vgg runs anyway); 0 (default) = off, and the step is then what it is without the "
+                        "flag; > 0 needs --phase train and a (--patch_size * --scale) that is a multiple of 4 and at most 256")
+    p.add_argument("--cx_h", type=float, default=0.5, help="bandwidth h of the contextual loss's weights exp((1 - d / (min d + 1e-5)) / h)")
     p.add_argument("--valid_tile", type=int, default=0,
                    help="validate every image as batches of overlapping tiles (docs/modes.md section 4h): the side of the square of LR "
                         "pixels a tile owns; 0 (default) = off, one Generator call on the whole image")
@@ -441,6 +446,26 @@ def check_alpha_texture(args):
                          f"--scale) = {args.patch_size} * {args.scale} = {side}: {why}; --texture_patch 0 takes the whole map of every tap")
 
 
+def check_alpha_cx(args):
+    """--alpha_cx / --cx_h; SystemExit naming the flag.  No GPU is touched."""
+    if not args.alpha_cx >= 0:
+        raise SystemExit(f"train.py: --alpha_cx {args.alpha_cx} must be >= 0 (0 = off)")
+    if not args.cx_h > 0:
+        raise SystemExit(f"train.py: --alpha_cx {args.alpha_cx}: --cx_h {args.cx_h} must be > 0")
+    if args.alpha_cx == 0:
+        return
+    if args.phase != "train":
+        raise SystemExit(f"train.py: --alpha_cx {args.alpha_cx} needs --phase train: the contextual loss reads a tap of the VGG19 "
+                         f"trunk, and no VGG runs in --phase {args.phase}")
+    from pesr_amd.contextual import check_size, tap_size
+    side = args.patch_size * args.scale
+    why = check_size(side, side)
+    if why:
+        th, tw = tap_size(side, side)
+        raise SystemExit(f"train.py: --alpha_cx {args.alpha_cx}: (--patch_size * --scale) = {args.patch_size} * {args.scale} = {side}, "
+                         f"a relu3_4 tap of {th} x {tw}: {why}")
+
+
 def main(argv=None):
     args = build_parser().parse_args(argv)
     degradation_spec(args)      # (refuses a classical run without its companion flags before anything else starts)
@@ -448,7 +473,8 @@ def main(argv=None):
     lpips_loss_model = lpips_loss_model_of(args, scorer.lpips_model)
     check_alpha_ssim(args)
     check_alpha_texture(args)
-    world = int(os.environ.get("WORLD_SIZE", "1"))
+    check_alpha_cx(args)
+    world =int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
     # TEST HOOK (tests/test_dp_gpu.py): PESR_DP_SHARE_GPU=1 + PESR_DP_BACKEND=gloo lets the ranks time-share cuda:0 over gloo, so
@@ -517,7 +543,8 @@ def main(argv=None):
     trainer = Trainer(G, D, vgg, optim_G, optim_D, gan_type=args.gan_type, focal_loss=args.focal_loss, fl_gamma=args.fl_gamma,
                       alpha_vgg=args.alpha_vgg, alpha_gan=args.alpha_gan, alpha_tv=args.alpha_tv, alpha_l1=args.alpha_l1,
                       world_size=world, gradient_penalty=args.GP, lpips_model=lpips_loss_model, alpha_lpips=args.alpha_lpips,
-                      alpha_ssim=args.alpha_ssim, alpha_texture=args.alpha_texture, texture_patch=args.texture_patch)
+                      alpha_ssim=args.alpha_ssim, alpha_texture=args.alpha_texture, texture_patch=args.texture_patch,
+                      alpha_cx=args.alpha_cx, cx_h=args.cx_h)
 
     check_point = os.path.join(args.check_point, args.phase)
     # what checkpoint.rng_snapshot / rng_restore get besides the process-wide streams: the GPU input pipeline's crop stream, or the
@@ -552,6 +579,8 @@ def main(argv=None):
         keys += ("ssim",)
     if trainer.use_texture:
         keys += ("texture",)
+    if trainer.use_cx:
+        keys += ("cx",)
     graphed, graph_shapes, eager_at_shape = None, None, 0
     use_graph = device.type == "cuda" and (world == 1 if args.hip_graph == "auto" else str2bool(args.hip_graph))
     # data-parallel schedule: fixed by flag, or measured once (inside the first epoch that is long enough for it)
@@ -653,7 +682,7 @@ def main(argv=None):
             if tb is not None:
                 tb.add_scalar("Learning rate", cur_lr, epoch)
                 names = {"l1": "L1 Loss", "vgg": "VGG Loss", "g": "G Loss", "tv": "TV Loss", "d": "D Loss", "lpips": "LPIPS Loss",
-                         "ssim": "SSIM Loss", "texture": "Texture Loss"}
+                         "ssim": "SSIM Loss", "texture": "Texture Loss", "cx": "Contextual Loss"}
                 for k, v in zip(keys, avg):
                     tb.add_scalar(names[k] if gan or k != "l1" else "Pretrain Loss", v, epoch)
 
