@@ -17,6 +17,7 @@ import torch
 import torch.nn.functional as F
 
 from . import functional as PF
+from . import loss_terms
 from .model.basic import nhwc
 from .model.focal_loss import FocalLoss
 from .model.pesr import Discriminator
@@ -74,37 +75,22 @@ def _img(x: torch.Tensor) -> torch.Tensor:
 class Trainer:
     def __init__(self, G, D=None, vgg=None, optim_G=None, optim_D=None, *, gan_type="RSGAN", focal_loss=True, fl_gamma=1.0,
                  alpha_vgg=50.0, alpha_gan=1.0, alpha_tv=1e-6, alpha_l1=0.0, world_size=1, gradient_penalty=False,
-                 lpips_model=None, alpha_lpips=0.0, alpha_ssim=0.0, alpha_texture=0.0, texture_patch=16, alpha_cx=0.0, cx_h=0.5):
+                 lpips_model=None, alpha_lpips=0.0, alpha_ssim=0.0, alpha_texture=0.0, texture_patch=16, alpha_cx=0.0, cx_h=0.5,
+                 **more_terms):
         self.G, self.D, self.vgg = G, D, vgg
-        # the contextual loss of the VGG19 tap relu3_4 (docs/modes.md section 4r) as a term of gan_step's generator loss: on only with a
-        # positive weight; off, the VGG is called as without the two arguments.  cx_h: the bandwidth h of the weights
-        self.alpha_cx, self.cx_h = float(alpha_cx), float(cx_h)
-        if not self.alpha_cx >= 0:
-            raise ValueError(f"alpha_cx must be >= 0, got {alpha_cx}")
-        if not self.cx_h > 0:
-            raise ValueError(f"cx_h must be > 0, got {cx_h}")
-        self.use_cx = self.alpha_cx > 0
-        # the texture loss, Gram matrices of three VGG19 taps (docs/modes.md section 4q), as a term of gan_step's generator loss: on
-        # only with a positive weight; off, the VGG is called without taps and the step launches exactly what it launches without the
-        # two arguments.  texture_patch: the side of the patches in each tap's own pixels, 0 = the whole map
-        self.alpha_texture, self.texture_patch = float(alpha_texture), int(texture_patch)
-        if not self.alpha_texture >= 0:
-            raise ValueError(f"alpha_texture must be >= 0, got {alpha_texture}")
-        if self.texture_patch < 0:
-            raise ValueError(f"texture_patch must be >= 0 (0 = the whole map), got {texture_patch}")
-        self.use_texture = self.alpha_texture > 0
-        # 1 - SSIM-Y as a term of the generator's loss in both phases (docs/modes.md section 4p): on only with a positive weight; off,
-        # both steps launch exactly what they launch without the argument
-        self.alpha_ssim = float(alpha_ssim)
-        if self.alpha_ssim < 0:
-            raise ValueError(f"alpha_ssim must be >= 0, got {alpha_ssim}")
-        self.use_ssim = self.alpha_ssim > 0
-        # LPIPS as a term of the generator's loss (docs/modes.md section 4o): on only with a model AND a positive weight; off, gan_step
-        # launches exactly what it launches without the two arguments
-        self.lpips_model, self.alpha_lpips = lpips_model, float(alpha_lpips)
-        if self.alpha_lpips < 0:
-            raise ValueError(f"alpha_lpips must be >= 0, got {alpha_lpips}")
-        self.use_lpips = lpips_model is not None and self.alpha_lpips > 0
+        # The optional terms of the generator's loss, one record each of loss_terms.TERMS (docs/modes.md section 4s); more_terms: the
+        # keyword arguments of records that joined the table after the ones named above.  self.terms: the ones that are on, in table order;
+        # with none on, both steps launch exactly what they launch without these arguments.  Every record's weight, parameters and switch
+        # stay readable as alpha_<key>, <parameter> and use_<key>.
+        self.terms = []
+        for t in loss_terms.build(dict(lpips_model=lpips_model, alpha_lpips=alpha_lpips, alpha_ssim=alpha_ssim, alpha_texture=alpha_texture,
+                                       texture_patch=texture_patch, alpha_cx=alpha_cx, cx_h=cx_h, **more_terms)):
+            for name in t.params:
+                setattr(self, name, getattr(t, name))
+            setattr(self, t.weight, t.alpha)
+            setattr(self, "use_" + t.key, t.on)
+            if t.on:
+                self.terms.append(t)
         self.optim_G, self.optim_D = optim_G, optim_D
         self.gan_type, self.use_focal = gan_type, focal_loss
         self.pair_classifier = os.environ.get("PESR_PAIR_CLASSIFIER", "1") != "0"   # D's classifier once per phase on [hr; sr] (gan_step)
@@ -131,17 +117,15 @@ class Trainer:
         sr = self.G(lr)
         self.optim_G.zero_grad()
         l1 = PF.l1_loss(nhwc(sr), _img(hr))
-        ssim_loss = self._ssim_term(sr, hr) if self.use_ssim else None
-        (l1 if ssim_loss is None else l1 + ssim_loss).backward()
+        terms = {t.key: t.loss(sr, hr, (), ()) for t in self.terms if "pretrain" in t.phases}
+        total = l1
+        for v in terms.values():
+            total = total + v
+        total.backward()
         self.optim_G.step()
         logs = {"l1": l1.detach()}
-        if ssim_loss is not None:
-            logs["ssim"] = ssim_loss.detach()
+        logs.update((k, v.detach()) for k, v in terms.items())
         return logs
-
-    def _ssim_term(self, sr, hr):
-        """alpha_ssim * (1 - the batch mean of the SSIM-Y score): a batch mean like l1, so no world_size factor (float64 [B] -> fp32 scalar)"""
-        return (1 - PF.ssim_loss(sr, hr).mean()).float() * self.alpha_ssim
 
     # ---- reference train.py:194-259 -----------------------------------------------------------------
     def _gradient_penalty(self, hr_cl, sr, u):
@@ -208,28 +192,18 @@ class Trainer:
         # gradients that optim_D.step() has to wait for.  Same graph, same values; only the launch order differs.
         sr_nhwc, hr_nhwc = nhwc(sr), nhwc(hr_cl)
         l1_loss = PF.l1_loss(sr_nhwc, hr_nhwc) * self.alpha_l1
-        texture_loss = cx_loss = None
-        if self.use_cx:          # one call with the union of the taps; batch means like l1 and vgg: no world_size factor
-            from .contextual import TAP, contextual_from_tap
-            from .texture import TAPS, texture_from_taps
-            which = (TAPS if self.use_texture else ()) + (TAP,)
+        # ONE VGG call, tapped at the union of what the terms read; with no taps it is the call without the argument
+        live = [t for t in self.terms if "train" in t.phases]
+        which = tuple(sorted({i for t in live for i in t.taps}))
+        taps_sr = taps_hr = {}
+        if which:
             vgg_sr, vgg_hr, taps_sr, taps_hr = self.vgg(sr, hr_cl, taps=which)
-            if self.use_texture:
-                texture_loss = texture_from_taps(taps_sr[:-1], taps_hr[:-1], self.texture_patch).mean().float() * self.alpha_texture
-            cx_loss = contextual_from_tap(taps_sr[-1], taps_hr[-1], self.cx_h).mean().float() * self.alpha_cx
-        elif self.use_texture:   # the taps come out of the same two trunk passes; a batch mean like l1 and vgg: no world_size factor
-            from .texture import texture_from_taps
-            vgg_sr, vgg_hr, taps_sr, taps_hr = self.vgg(sr, hr_cl, taps=True)
-            texture_loss = texture_from_taps(taps_sr, taps_hr, self.texture_patch).mean().float() * self.alpha_texture
+            taps_sr, taps_hr = dict(zip(which, taps_sr)), dict(zip(which, taps_hr))
         else:
             vgg_sr, vgg_hr = self.vgg(sr, hr_cl)
         vgg_loss = PF.mse_loss(nhwc(vgg_sr), nhwc(vgg_hr)) * self.alpha_vgg
         tv_local = PF.tv_loss(sr_nhwc) * self.alpha_tv
-        lpips_loss = None
-        if self.use_lpips:       # a batch mean like l1 and vgg: no world_size factor (float64 [B] -> fp32 scalar)
-            from .lpips import lpips_loss as _lpips_loss
-            lpips_loss = _lpips_loss(sr, hr_cl, self.lpips_model).mean().float() * self.alpha_lpips
-        ssim_loss = self._ssim_term(sr, hr_cl) if self.use_ssim else None
+        terms = {t.key: t.loss(sr, hr_cl, [taps_sr[i] for i in t.taps], [taps_hr[i] for i in t.taps]) for t in live}
         self.optim_D.step()
 
         # generator phase
@@ -255,28 +229,15 @@ class Trainer:
                 G_loss = loss_fn(pred_fake if self.gan_type == "SGAN" else pred_fake - pred_real, target_real)
             G_loss = G_loss * self.alpha_gan
         total_G_loss = l1_loss + vgg_loss + G_loss + tv_local * float(self.world_size)
-        if lpips_loss is not None:
-            total_G_loss = total_G_loss + lpips_loss
-        if ssim_loss is not None:
-            total_G_loss = total_G_loss + ssim_loss
-        if texture_loss is not None:
-            total_G_loss = total_G_loss + texture_loss
-        if cx_loss is not None:
-            total_G_loss = total_G_loss + cx_loss
+        for v in terms.values():         # in table order
+            total_G_loss = total_G_loss + v
         total_G_loss.backward()
         self.optim_G.step()
         logs = {"l1": l1_loss.detach(), "vgg": vgg_loss.detach(), "g": G_loss.detach(), "tv": tv_local.detach(),
                 "d": total_D_loss.detach()}
         if gp is not None:
             logs["gp"] = gp.detach()
-        if lpips_loss is not None:
-            logs["lpips"] = lpips_loss.detach()
-        if ssim_loss is not None:
-            logs["ssim"] = ssim_loss.detach()
-        if texture_loss is not None:
-            logs["texture"] = texture_loss.detach()
-        if cx_loss is not None:
-            logs["cx"] = cx_loss.detach()
+        logs.update((k, v.detach()) for k, v in terms.items())
         return logs
 
     # ---- the GAN step as ONE hipGraph ------------------------------------------------------------------------------------

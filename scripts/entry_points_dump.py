@@ -1,13 +1,15 @@
 """What test.py and train.py print and write on a toy data folder, as SHA-256 sums: two trees behave alike iff their sums are equal
 (docs/experiments/entry_points_share.md).
 
-  python scripts/entry_points_dump.py [--tree DIR] [--keep DIR]
+  python scripts/entry_points_dump.py [--tree DIR] [--keep DIR] [--only PREFIX[,PREFIX...]]
 
 In a temporary folder: two seeded 48 x 40 HR PNGs with their x4 LR images (as test, training and validation set), a seeded
 64-channel, 2-block x4 generator, a toy NIQE model of 16-pixel blocks and LpipsModel.random.  Then test.py six times (LR only, with
 --niqe, --from_hr, with every score, the classical degradation with noise, jitter and JPEG, bicubic with JPEG 4:4:4) and train.py
-twice (--synthetic with every --valid_* flag; a folder run with --lr_from_hr, the GPU pipeline and the whole degradation chain), each
-in a process of its own whose torch seed is set first.  --tree DIR takes test.py, train.py, utils.py and pesr_amd from another
+twice (--synthetic with every --valid_* flag; a folder run with --lr_from_hr, the GPU pipeline and the whole degradation chain), then
+train.py on HR patches of 32 with the optional terms of the generator's loss (docs/experiments/loss_terms.md): --phase train eager with
+none, each one alone and all four, --phase pretrain with the SSIM term, and the all-four run captured (--hip_graph true); each
+in a process of its own whose torch seed is set first.  --only runs the runs whose names begin with one of the prefixes.  --tree DIR takes test.py, train.py, utils.py and pesr_amd from another
 checkout (for instance the parent commit's Python files, with PESR_HIP_LIB naming this tree's library); everything else comes from
 this one.  Per run one JSON line: the exit code, the sum of stdout, of every PNG and checkpoint written, and of a checkpoint's tensors.
 --keep DIR also writes every run's stdout there.  A run that fails ends the script.
@@ -24,6 +26,7 @@ HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 ap = argparse.ArgumentParser()
 ap.add_argument("--tree", type=str, default=HERE)
 ap.add_argument("--keep", type=str, default="")
+ap.add_argument("--only", type=str, default="")
 ARGS = ap.parse_args()
 TREE = os.path.abspath(ARGS.tree)
 sys.path.insert(0, HERE)
@@ -37,6 +40,9 @@ NET = ["--num_channels", "64", "--num_blocks", "2"]
 TEST = ["--dataset", "Toy", "--perceptual_model", "g.pt"] + NET
 HR = TEST + ["--from_hr", "true"]
 TRAIN = ["--phase", "pretrain", "--pretrained_model", "g.pt", "--batch_size", "4"] + NET
+TOY32 = ["--pretrained_model", "g.pt", "--batch_size", "4", "--synthetic", "16", "--patch_size", "8", "--num_epochs", "2", "--snapshot_every", "1"] + NET
+GAN = TOY32 + ["--phase", "train", "--hip_graph", "false"]
+LPIPS, SSIM, TEXTURE, CX = ["--alpha_lpips", "1", "--lpips_loss", "w.pt"], ["--alpha_ssim", "1"], ["--alpha_texture", "1", "--texture_patch", "8"], ["--alpha_cx", "1"]
 RUNS = [
     ("test_lr_only", "test.py", TEST),
     ("test_lr_only_niqe", "test.py", TEST + ["--niqe", "m.npz"]),
@@ -50,7 +56,17 @@ RUNS = [
     ("train_folder", "train.py", TRAIN + ["--train_dataset", "Toy", "--valid_dataset", "Toy", "--patch_size", "8", "--num_repeats", "4", "--lr_from_hr", "true",
                                           "--gpu_pipeline", "true", "--degradation", "classical", "--noise_sigma", "10", "--jpeg_quality", "30,95",
                                           "--resize_jitter", "0.5,2", "--max_iters", "2", "--num_epochs", "1"]),
+    ("terms_none", "train.py", GAN),
+    ("terms_lpips", "train.py", GAN + LPIPS),
+    ("terms_ssim", "train.py", GAN + SSIM),
+    ("terms_texture", "train.py", GAN + TEXTURE),
+    ("terms_cx", "train.py", GAN + CX),
+    ("terms_all", "train.py", GAN + LPIPS + SSIM + TEXTURE + CX),
+    ("terms_pretrain_ssim", "train.py", TOY32 + ["--phase", "pretrain", "--hip_graph", "false"] + SSIM),
+    ("terms_all_graph", "train.py", TOY32 + ["--phase", "train", "--hip_graph", "true"] + LPIPS + SSIM + TEXTURE + CX),
 ]
+if ARGS.only:
+    RUNS = [r for r in RUNS if r[0].startswith(tuple(ARGS.only.split(",")))]
 
 
 def make_inputs(root):

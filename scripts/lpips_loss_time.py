@@ -19,29 +19,11 @@ import os
 import sys
 import warnings
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import torch  # noqa: E402
+from _loss_time import HBM_TBS, time_events  # noqa: E402  (puts the repository root on sys.path)
 
-HBM_TBS = 6.29
 CACHE_BYTES = 256 * 2 ** 20
-
-
-def time_events(fn, reps, warmup, calls=1):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    ts = []
-    for _ in range(reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        for _ in range(calls):
-            fn()
-        b.record()
-        b.synchronize()
-        ts.append(a.elapsed_time(b) * 1e3 / calls)
-    ts.sort()
-    return ts[len(ts) // 2], ts[0], ts[-1]
 
 
 def main():
@@ -91,8 +73,8 @@ def main():
                                            ws.numel(), stream), "pesr_lpips_layer2")
 
         nbytes = 3 * n * fh * fw * c * 4
-        med, best, worst = time_events(bwd, args.reps, args.warmup, args.burst)
-        f_med, f_best, f_worst = time_events(fwd, args.reps, args.warmup, args.burst)
+        med, best, worst = time_events(bwd, args.reps, args.warmup, args.burst, digits=None)
+        f_med, f_best, f_worst = time_events(fwd, args.reps, args.warmup, args.burst, digits=None)
         assert torch.equal(ga, ops.lpips_layer_bwd(fa, fb, wt, gout))
         bwd_us += med
         bound = nbytes / HBM_TBS / 1e6
@@ -120,9 +102,9 @@ def main():
     def metric():
         res[0] = LP.lpips(dsr, dhr, model).mean()
 
-    f_med, f_best, f_worst = time_events(forward, args.reps, args.warmup)
-    b_med, b_best, b_worst = time_events(both, args.reps, args.warmup)
-    m_med, m_best, m_worst = time_events(metric, args.reps, args.warmup)
+    f_med, f_best, f_worst = time_events(forward, args.reps, args.warmup, digits=None)
+    b_med, b_best, b_worst = time_events(both, args.reps, args.warmup, digits=None)
+    m_med, m_best, m_worst = time_events(metric, args.reps, args.warmup, digits=None)
     print(json.dumps({"what": "lpips_loss(sr, hr).mean(): forward alone (no graph); forward + backward to sr; lpips() for comparison; one "
                               "call per event pair", "case": [n, h, w],
                       "forward_ms_median": round(f_med / 1e3, 3), "forward_ms_best": round(f_best / 1e3, 3), "forward_ms_worst": round(f_worst / 1e3, 3),

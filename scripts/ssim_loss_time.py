@@ -16,28 +16,9 @@ import json
 import os
 import sys
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import torch  # noqa: E402
-
-HBM_TBS = 6.29
-
-
-def time_events(fn, reps, warmup, calls=1):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    ts = []
-    for _ in range(reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        for _ in range(calls):
-            fn()
-        b.record()
-        b.synchronize()
-        ts.append(a.elapsed_time(b) * 1e3 / calls)
-    ts.sort()
-    return [round(ts[len(ts) // 2], 2), round(ts[0], 2), round(ts[-1], 2)]
+from _loss_time import HBM_TBS, step_ab, time_events  # noqa: E402  (puts the repository root on sys.path)
 
 
 def main():
@@ -104,32 +85,10 @@ def main():
 
 def pretrain_step_times(args, dev):
     """Trainer.pretrain_step of the full-size Generator (256 channels, 32 blocks, batch 16, LR 48 x 48 -> HR 192 x 192) with the term off
-    and on: ms per step, median of --reps single steps after --warmup."""
-    import warnings
-
-    from model import Generator
-    from pesr_amd.optim import FlatAdam
-    from pesr_amd.step import Trainer
-    gen = torch.Generator(device="cpu").manual_seed(7)
-    hr = torch.randint(0, 256, (16, 3, 192, 192), generator=gen).float().to(dev)
-    lr = torch.nn.functional.avg_pool2d(hr, 4)
+    and on: ms per step, median of --reps single steps after --warmup; both twice, alternating (_loss_time.step_ab)."""
     out = {"what": "Trainer.pretrain_step, 256 ch x 32 blocks, batch 16, 48 -> 192: ms per step [median, best, worst]"}
-    for alpha in (0.0, 1.0, 0.0, 1.0):
-        torch.manual_seed(0)
-        with warnings.catch_warnings():
-            warnings.simplefilter("ignore")
-            G = Generator({"num_channels": 256, "depth": 32, "res_scale": 0.1, "scale": 4}).to(dev)
-        tr = Trainer(G, optim_G=FlatAdam([p for p in G.parameters() if p.requires_grad], lr=1e-6), alpha_ssim=alpha)
-        logs = [None]
-
-        def step():
-            logs[0] = tr.pretrain_step(lr, hr)
-
-        t = [round(v / 1e3, 3) for v in time_events(step, args.reps, args.warmup)]
-        key = f"alpha_ssim_{alpha:g}" + ("_again" if f"alpha_ssim_{alpha:g}" in out else "")
-        out[key] = {"ms": t, "logs": {k: round(float(v), 6) for k, v in logs[0].items()}}
-        del tr, G
-        torch.cuda.empty_cache()
+    out.update(step_ab([(f"alpha_ssim_{alpha:g}", {"alpha_ssim": alpha}) for alpha in (0.0, 1.0)], dev, 16, 192, args.reps, args.warmup,
+                       phase="pretrain"))
     print(json.dumps(out), flush=True)
 
 

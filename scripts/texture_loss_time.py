@@ -17,34 +17,10 @@ import argparse
 import json
 import os
 import sys
-import warnings
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import torch  # noqa: E402
-
-HBM_TBS, MFMA_F32_TFLOPS = 6.29, 157.3
-
-
-def time_events(fn, reps, warmup, calls=1):
-    for _ in range(warmup):
-        fn()
-    torch.cuda.synchronize()
-    ts = []
-    for _ in range(reps):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        for _ in range(calls):
-            fn()
-        b.record()
-        b.synchronize()
-        ts.append(a.elapsed_time(b) * 1e3 / calls)
-    ts.sort()
-    return [round(ts[len(ts) // 2], 2), round(ts[0], 2), round(ts[-1], 2)]
-
-
-def floor_us(nbytes, flops):
-    return max(nbytes / HBM_TBS / 1e6, flops / MFMA_F32_TFLOPS / 1e6)
+from _loss_time import floor_us, step_ab, time_events  # noqa: E402  (puts the repository root on sys.path)
 
 
 def main():
@@ -120,36 +96,10 @@ def main():
 
 def gan_step_times(args, dev):
     """Trainer.gan_step of bench.py's networks with the term off, on with patches of 16 and on with the whole map: ms per step, median
-    of --reps single replays of the captured step (the hipGraph of capture_gan_step, as bench.py runs it) after three eager steps and
-    --warmup replays; every variant twice, alternating."""
-    from model import VGG, Discriminator, Generator
-    from pesr_amd.optim import FlatAdam
-    from pesr_amd.step import Trainer
-    gen = torch.Generator(device="cpu").manual_seed(7)
-    hr = torch.randint(0, 256, (args.batch, 3, args.side, args.side), generator=gen).float().to(dev)
-    lr = torch.nn.functional.avg_pool2d(hr, 4)
+    of --reps single replays of the captured step after --warmup replays; every variant twice, alternating (_loss_time.step_ab)."""
     out = {"what": f"Trainer.gan_step, 256 ch x 32 blocks, batch {args.batch}, {args.side // 4} -> {args.side}: ms per step [median, best, worst]"}
-    for alpha, patch in ((0.0, 16), (1.0, 16), (1.0, 0)) * 2:
-        torch.manual_seed(0)
-        opt = {"patch_size": args.side // 4, "num_channels": 256, "depth": 32, "res_scale": 0.1, "spectral_norm": False, "scale": 4}
-        with warnings.catch_warnings():
-            warnings.simplefilter("ignore")
-            G, D, V = Generator(opt).to(dev), Discriminator(opt).to(dev), VGG().to(dev)
-        tr = Trainer(G, D, V, FlatAdam([p for p in G.parameters() if p.requires_grad], lr=1e-6),
-                     FlatAdam(D.parameters(), lr=1e-6), alpha_texture=alpha, texture_patch=patch)
-        logs = [None]
-        for _ in range(3):                                            # first-use work must not happen under capture
-            tr.gan_step(lr, hr)
-        graphed = tr.capture_gan_step(lr, hr)
-
-        def step():
-            logs[0] = graphed(lr, hr)
-
-        t = [round(v / 1e3, 3) for v in time_events(step, args.reps, args.warmup)]
-        key = f"alpha_texture_{alpha:g}" + (f"_patch_{patch}" if alpha else "")
-        out[key + ("_again" if key in out else "")] = {"ms": t, "logs": {k: round(float(v), 6) for k, v in logs[0].items()}}
-        del tr, G, D, V
-        torch.cuda.empty_cache()
+    out.update(step_ab([(f"alpha_texture_{alpha:g}" + (f"_patch_{patch}" if alpha else ""), {"alpha_texture": alpha, "texture_patch": patch})
+                        for alpha, patch in ((0.0, 16), (1.0, 16), (1.0, 0))], dev, args.batch, args.side, args.reps, args.warmup))
     print(json.dumps(out), flush=True)
 
 

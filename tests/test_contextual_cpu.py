@@ -190,8 +190,8 @@ def test_train_flag_default_off_and_refusals(monkeypatch):
     Tr = _load("train")
     d = Tr.build_parser().parse_args([])
     assert d.alpha_cx == 0.0 and d.cx_h == 0.5
-    Tr.check_alpha_cx(d)
-    Tr.check_alpha_cx(Tr.build_parser().parse_args(["--patch_size", "10", "--phase", "pretrain"]))      # off: anything goes
+    Tr.loss_terms_of(d)
+    Tr.loss_terms_of(Tr.build_parser().parse_args(["--patch_size", "10", "--phase", "pretrain"]))      # off: anything goes
     for phase in ("pretrain", "train"):
         with pytest.raises(SystemExit, match=r"^train\.py: --alpha_cx -0\.5 must be >= 0"):
             Tr.main(["--alpha_cx", "-0.5", "--phase", phase, "--synthetic", "16"])
@@ -208,7 +208,7 @@ def test_train_flag_default_off_and_refusals(monkeypatch):
         Tr.main(["--alpha_cx", "1", "--patch_size", "15", "--scale", "2", "--synthetic", "16"])
     for ok in (["--alpha_cx", "1"], ["--alpha_cx", "1", "--patch_size", "48"], ["--alpha_cx", "0.1", "--patch_size", "64", "--cx_h", "0.1"],
                ["--alpha_cx", "1", "--patch_size", "2", "--scale", "2"]):
-        Tr.check_alpha_cx(Tr.build_parser().parse_args(ok))
+        Tr.loss_terms_of(Tr.build_parser().parse_args(ok))
     assert not calls
 
 

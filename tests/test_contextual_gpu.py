@@ -10,7 +10,7 @@ import pytest
 import torch
 
 import contextual_oracle as O
-from helpers import dis_sd, gen_sd, vgg_sd
+import loss_step_harness as HS
 from oracle import detrand
 
 pytestmark = pytest.mark.gpu
@@ -235,12 +235,7 @@ def test_ops_refuse_what_they_do_not_take():
 
 
 # ---- the VGG taps -----------------------------------------------------------------------------------------------------------------------
-def _vgg():
-    if "vgg" not in _SHARED:
-        from model import VGG
-        V = VGG(); V.load_state_dict(vgg_sd()); V.cuda()
-        _SHARED["vgg"] = V
-    return _SHARED["vgg"]
+_vgg = HS.vgg
 
 
 @pytest.mark.parametrize("path", ["merged", "plain"])
@@ -302,76 +297,19 @@ def test_contextual_from_tap_under_the_bf16_modes(mode):
 
 
 # ---- the GAN step ------------------------------------------------------------------------------------------------------------------------
-CH, DEPTH, PS, BATCH, LR, ALPHA = 64, 2, 8, 2, 5e-5, 0.5              # toy networks; the HR side is 32: a tap of 8 x 8 = 64 points
-
-
-def _data():
-    if "data" not in _SHARED:
-        _SHARED["data"] = [(detrand.image_batch((BATCH, 3, PS, PS), 350 + i).cuda(),
-                            detrand.image_batch((BATCH, 3, 4 * PS, 4 * PS), 360 + i).cuda()) for i in range(4)]
-    return _SHARED["data"]
-
-
-def _trainer(**kw):
-    from model import Discriminator, Generator
-    from pesr_amd.optim import FlatAdam
-    from pesr_amd.step import Trainer
-    Gn = Generator({"num_channels": CH, "depth": DEPTH, "res_scale": 0.1, "scale": 4}); Gn.load_state_dict(gen_sd(CH, DEPTH, 0)); Gn.cuda()
-    oG = FlatAdam([p for p in Gn.parameters() if p.requires_grad], lr=LR, betas=(0.9, 0.999))
-    D = Discriminator({"patch_size": PS, "spectral_norm": False}); D.load_state_dict(dis_sd(PS, 1)); D.cuda()
-    return Trainer(Gn, D, _vgg(), oG, FlatAdam(D.parameters(), lr=LR, betas=(0.9, 0.999)), **kw)
-
-
-def _state(tr):
-    return {"G": tr.optim_G.flat.flat_p.clone(), "D": tr.optim_D.flat.flat_p.clone(),
-            **{"D." + k: v.clone() for k, v in tr.D.state_dict().items()}}
-
-
-def _logs(d):
-    return {k: v.item() for k, v in d.items()}
-
-
-def _run(steps, **kw):
-    """-> (the logs of every step, the state after every step, how the VGG was called): eager steps from the same start; cached."""
-    key = ("run", steps, tuple(sorted(kw.items())))
-    if key not in _SHARED:
-        tr = _trainer(**kw)
-        V, calls = tr.vgg, []
-        inner = V.forward
-
-        def spy(*a, **k):
-            calls.append(dict(k))
-            return inner(*a, **k)
-        V.forward = spy
-        try:
-            logs, states = [], []
-            for lr, hr in _data()[:steps]:
-                logs.append(_logs(tr.gan_step(lr, hr)))
-                states.append(_state(tr))
-        finally:
-            del V.forward
-        _SHARED[key] = (logs, states, calls)
-    return _SHARED[key]
-
-
-def test_step_with_the_term_off_is_the_step_without_it():
-    logs0, states0, calls0 = _run(2)
-    logs, states, calls = _run(2, alpha_cx=0.0, cx_h=0.25)
-    assert logs == logs0 and all("cx" not in l for l in logs)
-    assert calls == calls0 == [{}, {}]                                # the VGG is called without taps
-    for s, s0 in zip(states, states0):
-        for k in s0:
-            assert torch.equal(s[k], s0[k]), k
+# (off, on beside the other logs, and captured: tests/test_loss_terms_gpu.py, for every term, on this harness)
+BATCH, ALPHA = 2, 0.5                                                 # toy networks; the HR side is 32: a tap of 8 x 8 = 64 points
+H = HS.harness(350, BATCH)                                            # 64 channels, 2 blocks, LR 8 x 8, lr 5e-5
 
 
 def test_step_with_the_term_on():
     from pesr_amd import contextual
-    logs4, states4, calls = _run(4, alpha_cx=ALPHA)
-    logs0, states0, _ = _run(2)
+    logs4, states4, calls = H.run(4, alpha_cx=ALPHA)
+    logs0, states0, _ = H.run(2)
     assert calls == [{"taps": (contextual.TAP,)}] * 4
     got = logs4[0]["cx"]
-    tr = _trainer(alpha_cx=ALPHA)
-    lr, hr = _data()[0]
+    tr = H.trainer(alpha_cx=ALPHA)
+    lr, hr = H.data()[0]
     with torch.no_grad():                                             # the sr of the first step: G before its update
         _, _, taps_sr, taps_hr = tr.vgg(tr.G(lr), hr, taps=(contextual.TAP,))
     assert tuple(taps_sr[0].shape) == (BATCH, 8, 8, 256)
@@ -382,35 +320,15 @@ def test_step_with_the_term_on():
     print(f"logged cx term {got!r}, restated {want!r}, |difference| {abs(got - want):.3e}, allowed {allowed:.3e}; "
           f"m {float(s['m'].min()):.4f} .. {float(s['m'].max()):.4f}, CX {s['CX'].tolist()}")
     assert np.isfinite(got) and got > 0 and abs(got - want) <= allowed
-    for k in logs0[0]:
-        assert logs4[0][k] == logs0[0][k], k                          # the other terms of the first step are what they were
-    assert not torch.equal(states4[0]["G"], states0[0]["G"])          # sr's gradient differs: G moved otherwise
-    for k in states0[0]:
-        if k != "G":
-            assert torch.equal(states4[0][k], states0[0][k]), k       # D's first step does not see the term
+    HS.assert_only_G_moved(logs4[0], states4[0], logs0[0], states0[0])
 
 
 def test_step_with_texture_and_cx_calls_the_vgg_once_with_the_union():
     from pesr_amd import contextual
-    both, _, calls = _run(2, alpha_cx=ALPHA, alpha_texture=ALPHA, texture_patch=8)
-    tex, _, calls_tex = _run(2, alpha_texture=ALPHA, texture_patch=8)
-    cx, _, _ = _run(4, alpha_cx=ALPHA)
-    assert calls == [{"taps": (1, 6, 11, contextual.TAP)}] * 2 and calls_tex == [{"taps": True}] * 2
+    both, _, calls = H.run(2, alpha_cx=ALPHA, alpha_texture=ALPHA, texture_patch=8)
+    tex, _, calls_tex = H.run(2, alpha_texture=ALPHA, texture_patch=8)
+    cx, _, _ = H.run(4, alpha_cx=ALPHA)
+    assert calls == [{"taps": (1, 6, 11, contextual.TAP)}] * 2 and calls_tex == [{"taps": (1, 6, 11)}] * 2
     assert both[0]["texture"] == tex[0]["texture"] and both[0]["cx"] == cx[0]["cx"]      # the bits of the runs with one term
     for k in tex[0]:
         assert both[0][k] == tex[0][k], k
-
-
-def test_step_with_the_term_on_survives_the_capture():
-    """Two eager steps, a capture, two replays: the bits of four eager steps."""
-    logs4, states4, _ = _run(4, alpha_cx=ALPHA)
-    tr = _trainer(alpha_cx=ALPHA)
-    data = _data()
-    for i in range(2):
-        assert _logs(tr.gan_step(*data[i])) == logs4[i]
-    step = tr.capture_gan_step(*data[0])
-    for i in (2, 3):
-        logs = _logs(step(*data[i]))
-        assert "cx" in logs and logs == logs4[i], (i, logs, logs4[i])
-        for k, v in _state(tr).items():
-            assert torch.equal(v, states4[i][k]), (i, k)

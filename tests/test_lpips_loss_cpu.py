@@ -182,7 +182,7 @@ def test_train_flags_default_off_and_refusals(tmp_path, monkeypatch, gpu_untouch
     Tr = _load("train")
     d = Tr.build_parser().parse_args([])
     assert d.lpips_loss == "" and d.alpha_lpips == 0.0
-    assert Tr.lpips_loss_model_of(d) is None
+    assert Tr.loss_terms_of(d)["lpips_model"] is None
     C.model().save(tmp_path / "w.pt")
     (tmp_path / "junk.pt").write_bytes(b"junk")
     monkeypatch.chdir(tmp_path)
@@ -204,11 +204,11 @@ def test_train_flags_default_off_and_refusals(tmp_path, monkeypatch, gpu_untouch
     # what passes, and the sharing with --valid_lpips
     ok = Tr.build_parser().parse_args(["--alpha_lpips", "0.5", "--lpips_loss", w, "--patch_size", "12", "--valid_lpips", w])
     valid = Tr.lpips_model_of(ok)
-    assert Tr.lpips_loss_model_of(ok, valid) is valid
-    other = Tr.lpips_loss_model_of(ok, None)
+    assert Tr.loss_terms_of(ok, valid)["lpips_model"] is valid
+    other = Tr.loss_terms_of(ok, None)["lpips_model"]
     assert isinstance(other, LP.LpipsModel) and other is not valid
     off = Tr.build_parser().parse_args(["--lpips_loss", w])
-    assert Tr.lpips_loss_model_of(off) is None                       # a weight file alone turns nothing on
+    assert Tr.loss_terms_of(off)["lpips_model"] is None                       # a weight file alone turns nothing on
     assert not gpu_untouched
 
 

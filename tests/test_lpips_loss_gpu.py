@@ -17,8 +17,7 @@ import torch
 import lpips_cases as C
 import lpips_grad_cases as G
 import lpips_trunk_grad as T
-from helpers import dis_sd, gen_sd, vgg_sd
-from oracle import detrand
+import loss_step_harness as HS
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda")
@@ -262,117 +261,28 @@ def test_trunk_gradient_does_not_depend_on_the_mode_at_backward():
 
 
 # ---- the training step -------------------------------------------------------------------------------------------------------------
-CH, DEPTH, PS, BATCH, LR = 64, 2, 8, 4, 5e-5                        # as tests/test_resume_gpu.py; the HR side is 32
-_SHARED = {}
-
-
-def _vgg():
-    if "vgg" not in _SHARED:
-        from model import VGG
-        V = VGG(); V.load_state_dict(vgg_sd()); V.cuda()
-        _SHARED["vgg"] = V
-    return _SHARED["vgg"]
-
-
-def _data():
-    if "data" not in _SHARED:
-        _SHARED["data"] = [(detrand.image_batch((BATCH, 3, PS, PS), 150 + i).cuda(),
-                            detrand.image_batch((BATCH, 3, 4 * PS, 4 * PS), 160 + i).cuda()) for i in range(4)]
-    return _SHARED["data"]
-
-
-def _trainer(**kw):
-    from model import Discriminator, Generator
-    from pesr_amd.optim import FlatAdam
-    from pesr_amd.step import Trainer
-    Gn = Generator({"num_channels": CH, "depth": DEPTH, "res_scale": 0.1, "scale": 4}); Gn.load_state_dict(gen_sd(CH, DEPTH, 0)); Gn.cuda()
-    D = Discriminator({"patch_size": PS, "spectral_norm": False}); D.load_state_dict(dis_sd(PS, 1)); D.cuda()
-    oG = FlatAdam([p for p in Gn.parameters() if p.requires_grad], lr=LR, betas=(0.9, 0.999))
-    oD = FlatAdam(D.parameters(), lr=LR, betas=(0.9, 0.999))
-    return Trainer(Gn, D, _vgg(), oG, oD, **kw)
-
-
-def _state(tr):
-    return {"G": tr.optim_G.flat.flat_p.clone(), "D": tr.optim_D.flat.flat_p.clone(),
-            **{"D." + k: v.clone() for k, v in tr.D.state_dict().items()}}
-
-
-def _logs(d):
-    return {k: v.item() for k, v in d.items()}
-
-
-def _run(steps, **kw):
-    """-> (the trainer, the logs of every step, the state after every step): eager steps from the same start."""
-    tr = _trainer(**kw)
-    logs, states = [], []
-    for lr, hr in _data()[:steps]:
-        logs.append(_logs(tr.gan_step(lr, hr)))
-        states.append(_state(tr))
-    return tr, logs, states
-
-
-def _plain():
-    if "plain" not in _SHARED:
-        _SHARED["plain"] = _run(2)[1:]
-    return _SHARED["plain"]
-
-
-def _with_lpips():
-    if "lpips4" not in _SHARED:
-        _SHARED["lpips4"] = _run(4, lpips_model=C.model(), alpha_lpips=1.0)[1:]
-    return _SHARED["lpips4"]
-
-
-@pytest.mark.parametrize("kw", [{"alpha_lpips": 0.0}, {"lpips_model": "model"}, {"alpha_lpips": 1.0}], ids=["alpha0", "alpha0+model", "no-model"])
-def test_step_with_the_term_off_is_the_step_without_it(kw):
-    kw = dict(kw)
-    if kw.get("lpips_model") == "model":
-        kw = {"lpips_model": C.model(), "alpha_lpips": 0.0}
-    logs0, states0 = _plain()
-    _, logs, states = _run(2, **kw)
-    assert logs == logs0 and all("lpips" not in l for l in logs)
-    for a, b in zip(states, states0):
-        assert sorted(a) == sorted(b)
-        for k in a:
-            assert torch.equal(a[k], b[k]), k
+# (off, on beside the other logs, and captured: tests/test_loss_terms_gpu.py, for every term, on this harness)
+BATCH = 4                                                           # as tests/test_resume_gpu.py; the HR side is 32
+H = HS.harness(150, BATCH)                                          # 64 channels, 2 blocks, LR 8 x 8, lr 5e-5
 
 
 def test_step_with_the_term_on():
     from pesr_amd import lpips as LP
-    model = C.model()
-    lr, hr = _data()[0]
-    tr = _trainer(lpips_model=model, alpha_lpips=1.0)
+    model = HS.lpips_model()                                         # LpipsModel.random(C.MODEL_SEED), as C.model()
+    lr, hr = H.data()[0]
+    tr = H.trainer(lpips_model=model, alpha_lpips=1.0)
     with torch.no_grad():
         sr0 = tr.G(lr)                                               # the sr of the first step: G before its update
         want = LP.lpips(sr0, hr, model).mean().float().item()
-    logs = _logs(tr.gan_step(lr, hr))
+    logs = HS.logs(tr.gan_step(lr, hr))
     assert logs["lpips"] == want and want > 0, (logs["lpips"], want)
-    logs0, states0 = _plain()
-    logs4, states4 = _with_lpips()
+    logs0, states0, _ = H.run(2)
+    logs4, states4, _ = H.run(4, lpips_model=model, alpha_lpips=1.0)
     assert logs4[0]["lpips"] == want
-    for k in ("l1", "vgg", "g", "tv", "d"):
-        assert logs4[0][k] == logs0[0][k], k                         # the other terms of the first step are what they were
-    st = _state(tr)
-    assert not torch.equal(st["G"], states0[0]["G"])                 # G moved otherwise
+    st = HS.state(tr)
+    HS.assert_only_G_moved(logs4[0], st, logs0[0], states0[0])
     assert torch.equal(st["G"], states4[0]["G"])
-    for k in st:
-        if k != "G":
-            assert torch.equal(st[k], states0[0][k]), k              # D's first step does not see the term
     # half the weight: the logged term is half (the same sr), and G moves to yet another place
-    tr_half = _trainer(lpips_model=model, alpha_lpips=0.5)
-    assert _logs(tr_half.gan_step(lr, hr))["lpips"] == 0.5 * want
-    assert not torch.equal(_state(tr_half)["G"], st["G"])
-
-
-def test_step_with_the_term_on_survives_the_capture():
-    """Two eager steps, capture_gan_step, two replays: the bits of four eager steps."""
-    logs4, states4 = _with_lpips()
-    tr = _trainer(lpips_model=C.model(), alpha_lpips=1.0)
-    data = _data()
-    for i in range(2):
-        assert _logs(tr.gan_step(*data[i])) == logs4[i]
-    step = tr.capture_gan_step(*data[0])
-    for i in (2, 3):
-        logs = _logs(step(*data[i]))
-        assert logs["lpips"] == logs4[i]["lpips"] and logs == logs4[i], (i, logs, logs4[i])
-        assert torch.equal(tr.optim_G.flat.flat_p, states4[i]["G"]) and torch.equal(tr.optim_D.flat.flat_p, states4[i]["D"]), i
+    tr_half = H.trainer(lpips_model=model, alpha_lpips=0.5)
+    assert HS.logs(tr_half.gan_step(lr, hr))["lpips"] == 0.5 * want
+    assert not torch.equal(HS.state(tr_half)["G"], st["G"])

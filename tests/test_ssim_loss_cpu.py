@@ -156,8 +156,8 @@ def test_train_flag_default_off_and_refusals(monkeypatch):
     Tr = _load("train")
     d = Tr.build_parser().parse_args([])
     assert d.alpha_ssim == 0.0
-    Tr.check_alpha_ssim(d)
-    Tr.check_alpha_ssim(Tr.build_parser().parse_args(["--patch_size", "2"]))                   # off: any size
+    Tr.loss_terms_of(d)
+    Tr.loss_terms_of(Tr.build_parser().parse_args(["--patch_size", "2"]))                   # off: any size
     for phase in ("pretrain", "train"):
         with pytest.raises(SystemExit, match=r"train\.py: --alpha_ssim -0\.5 must be >= 0"):
             Tr.main(["--alpha_ssim", "-0.5", "--phase", phase, "--synthetic", "16"])
@@ -167,7 +167,7 @@ def test_train_flag_default_off_and_refusals(monkeypatch):
         Tr.main(["--alpha_ssim", "0.25", "--patch_size", "5", "--scale", "2", "--synthetic", "16"])
     with pytest.raises(SystemExit, match=r"--alpha_ssim nan must be >= 0"):
         Tr.main(["--alpha_ssim", "nan", "--synthetic", "16"])
-    Tr.check_alpha_ssim(Tr.build_parser().parse_args(["--alpha_ssim", "1", "--patch_size", "3", "--scale", "4"]))   # 12: a window fits
+    Tr.loss_terms_of(Tr.build_parser().parse_args(["--alpha_ssim", "1", "--patch_size", "3", "--scale", "4"]))   # 12: a window fits
     assert not calls
 
 

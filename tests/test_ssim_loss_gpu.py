@@ -10,8 +10,7 @@ import torch
 
 import ssim_loss_cases as C
 import ssim_loss_oracle as O
-from helpers import dis_sd, gen_sd, vgg_sd
-from oracle import detrand
+import loss_step_harness as HS
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda")
@@ -156,104 +155,23 @@ def test_function_gives_a_gradient_to_sr_only_in_its_layout():
 
 
 # ---- the training steps -----------------------------------------------------------------------------------------------------------------
-CH, DEPTH, PS, BATCH, LR, ALPHA = 64, 2, 8, 4, 5e-5, 0.5              # the toy networks of tests/test_lpips_loss_gpu.py; the HR side is 32
-_SHARED = {}
-
-
-def _data():
-    if "data" not in _SHARED:
-        _SHARED["data"] = [(detrand.image_batch((BATCH, 3, PS, PS), 250 + i).cuda(),
-                            detrand.image_batch((BATCH, 3, 4 * PS, 4 * PS), 260 + i).cuda()) for i in range(4)]
-    return _SHARED["data"]
-
-
-def _trainer(phase, **kw):
-    from model import VGG, Discriminator, Generator
-    from pesr_amd.optim import FlatAdam
-    from pesr_amd.step import Trainer
-    Gn = Generator({"num_channels": CH, "depth": DEPTH, "res_scale": 0.1, "scale": 4}); Gn.load_state_dict(gen_sd(CH, DEPTH, 0)); Gn.cuda()
-    oG = FlatAdam([p for p in Gn.parameters() if p.requires_grad], lr=LR, betas=(0.9, 0.999))
-    if phase == "pretrain":
-        return Trainer(Gn, optim_G=oG, **kw)
-    if "vgg" not in _SHARED:
-        V = VGG(); V.load_state_dict(vgg_sd()); V.cuda()
-        _SHARED["vgg"] = V
-    D = Discriminator({"patch_size": PS, "spectral_norm": False}); D.load_state_dict(dis_sd(PS, 1)); D.cuda()
-    return Trainer(Gn, D, _SHARED["vgg"], oG, FlatAdam(D.parameters(), lr=LR, betas=(0.9, 0.999)), **kw)
-
-
-def _step(tr, phase):
-    return tr.gan_step if phase == "train" else tr.pretrain_step
-
-
-def _state(tr):
-    st = {"G": tr.optim_G.flat.flat_p.clone()}
-    if tr.D is not None:
-        st.update({"D": tr.optim_D.flat.flat_p.clone(), **{"D." + k: v.clone() for k, v in tr.D.state_dict().items()}})
-    return st
-
-
-def _logs(d):
-    return {k: v.item() for k, v in d.items()}
-
-
-def _run(phase, steps, **kw):
-    """-> (the logs of every step, the state after every step): eager steps from the same start; cached per argument set."""
-    key = (phase, steps, tuple(sorted(kw.items())))
-    if key not in _SHARED:
-        tr = _trainer(phase, **kw)
-        logs, states = [], []
-        for lr, hr in _data()[:steps]:
-            logs.append(_logs(_step(tr, phase)(lr, hr)))
-            states.append(_state(tr))
-        _SHARED[key] = (logs, states)
-    return _SHARED[key]
-
-
-@pytest.mark.parametrize("phase", ["pretrain", "train"])
-def test_step_with_the_term_off_is_the_step_without_it(phase):
-    logs0, states0 = _run(phase, 2)
-    logs, states = _run(phase, 2, alpha_ssim=0.0)
-    assert logs == logs0 and all("ssim" not in l for l in logs)
-    for s, s0 in zip(states, states0):
-        assert sorted(s) == sorted(s0)
-        for k in s:
-            assert torch.equal(s[k], s0[k]), k
+# (off, on beside the other logs, and captured: tests/test_loss_terms_gpu.py, for every term, on this harness)
+BATCH, ALPHA = 4, 0.5                                                 # the toy networks of tests/test_lpips_loss_gpu.py; the HR side is 32
+H = HS.harness(250, BATCH)                                            # 64 channels, 2 blocks, LR 8 x 8, lr 5e-5
 
 
 @pytest.mark.parametrize("phase", ["pretrain", "train"])
 def test_step_with_the_term_on(phase):
-    lr, hr = _data()[0]
-    tr = _trainer(phase, alpha_ssim=ALPHA)
+    lr, hr = H.data()[0]
+    tr = H.trainer(phase, alpha_ssim=ALPHA)
     with torch.no_grad():
         sr0 = tr.G(lr)                                                # the sr of the first step: G before its update
     mean = float(np.mean(O.score_ordered(sr0.cpu().numpy(), hr.cpu().numpy())))
     want = float(np.float32(np.float32(1.0 - mean) * np.float32(ALPHA)))
-    logs4, states4 = _run(phase, 4, alpha_ssim=ALPHA)
+    logs4, states4, _ = H.run(4, phase, alpha_ssim=ALPHA)
     got = logs4[0]["ssim"]
     print(f"{phase}: logged ssim term {got!r}, restated {want!r}")
     # to fp32: torch's mean of the four float64 scores may order its sum otherwise, which moves the float32 by one unit at most
     assert np.isfinite(got) and 0 < got < ALPHA and abs(got - want) <= 2.0 ** -23 * want
-    logs0, states0 = _run(phase, 2)
-    for k in logs0[0]:
-        assert logs4[0][k] == logs0[0][k], k                          # the other terms of the first step are what they were
-    assert not torch.equal(states4[0]["G"], states0[0]["G"])          # G moved otherwise
-    for k in states0[0]:
-        if k != "G":
-            assert torch.equal(states4[0][k], states0[0][k]), k       # D's first step does not see the term
-
-
-@pytest.mark.parametrize("phase", ["pretrain", "train"])
-def test_step_with_the_term_on_survives_the_capture(phase):
-    """Two eager steps, a capture, two replays: the bits of four eager steps."""
-    logs4, states4 = _run(phase, 4, alpha_ssim=ALPHA)
-    tr = _trainer(phase, alpha_ssim=ALPHA)
-    data = _data()
-    for i in range(2):
-        assert _logs(_step(tr, phase)(*data[i])) == logs4[i]
-    step = tr.capture_gan_step(*data[0]) if phase == "train" else tr.capture_pretrain_step(*data[0])
-    for i in (2, 3):
-        logs = _logs(step(*data[i]))
-        assert "ssim" in logs and logs == logs4[i], (i, logs, logs4[i])
-        for k, v in _state(tr).items():
-            assert torch.equal(v, states4[i][k]), (i, k)
+    logs0, states0, _ = H.run(2, phase)
+    HS.assert_only_G_moved(logs4[0], states4[0], logs0[0], states0[0])

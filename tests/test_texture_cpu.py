@@ -159,8 +159,8 @@ def test_train_flag_default_off_and_refusals(monkeypatch):
     Tr = _load("train")
     d = Tr.build_parser().parse_args([])
     assert d.alpha_texture == 0.0 and d.texture_patch == 16
-    Tr.check_alpha_texture(d)
-    Tr.check_alpha_texture(Tr.build_parser().parse_args(["--patch_size", "10", "--phase", "pretrain"]))      # off: anything goes
+    Tr.loss_terms_of(d)
+    Tr.loss_terms_of(Tr.build_parser().parse_args(["--patch_size", "10", "--phase", "pretrain"]))      # off: anything goes
     for phase in ("pretrain", "train"):
         with pytest.raises(SystemExit, match=r"^train\.py: --alpha_texture -0\.5 must be >= 0"):
             Tr.main(["--alpha_texture", "-0.5", "--phase", phase, "--synthetic", "16"])
@@ -177,7 +177,7 @@ def test_train_flag_default_off_and_refusals(monkeypatch):
         Tr.main(["--alpha_texture", "1", "--texture_patch", "-1", "--synthetic", "16"])
     for ok in (["--alpha_texture", "1", "--patch_size", "48"], ["--alpha_texture", "1", "--texture_patch", "8"], ["--alpha_texture", "1", "--patch_size", "12", "--texture_patch", "0"],
                ["--alpha_texture", "1", "--patch_size", "12", "--texture_patch", "12"]):
-        Tr.check_alpha_texture(Tr.build_parser().parse_args(ok))
+        Tr.loss_terms_of(Tr.build_parser().parse_args(ok))
     assert not calls
 
 

@@ -391,89 +391,38 @@ def lpips_model_of(args):
     return scorer_of(args).lpips_model
 
 
-def lpips_loss_model_of(args, valid_model=None):
-    """--lpips_loss / --alpha_lpips -> the model of the loss term (None when the term is off); SystemExit naming the flags.  valid_model:
-    the model --valid_lpips loaded; when both flags name one file the object is shared.  No GPU is touched."""
-    if args.alpha_lpips < 0:
-        raise SystemExit(f"train.py: --alpha_lpips {args.alpha_lpips} must be >= 0 (0 = off)")
-    from pesr_amd import lpips as _lpips
-    model = None
-    if args.lpips_loss:
-        if valid_model is not None and os.path.realpath(args.lpips_loss) == os.path.realpath(args.valid_lpips):
-            model = valid_model
-        else:
-            model = _lpips.load_model_flag("train.py", "--lpips_loss", args.lpips_loss)
-    if args.alpha_lpips == 0:
-        return None
-    if model is None:
-        raise SystemExit(f"train.py: --alpha_lpips {args.alpha_lpips} needs --lpips_loss WEIGHTS (an LPIPS weight file; the project ships "
-                         "none)")
-    if args.phase != "train":
-        raise SystemExit(f"train.py: --alpha_lpips {args.alpha_lpips} / --lpips_loss: the LPIPS term belongs to the generator's loss of "
-                         f"--phase train, not --phase {args.phase}")
-    side = args.patch_size * args.scale
-    why = _lpips.check_loss_side(side, side)
-    if why:
-        raise SystemExit(f"train.py: --alpha_lpips / --lpips_loss: (--patch_size * --scale) = {args.patch_size} * {args.scale} = {side}: "
-                         f"{why}")
-    return model
-
-
-def check_alpha_ssim(args):
-    """--alpha_ssim; SystemExit naming the flag.  No GPU is touched."""
-    if not args.alpha_ssim >= 0:
-        raise SystemExit(f"train.py: --alpha_ssim {args.alpha_ssim} must be >= 0 (0 = off)")
-    side = args.patch_size * args.scale
-    if args.alpha_ssim > 0 and side < 11:
-        raise SystemExit(f"train.py: --alpha_ssim {args.alpha_ssim}: (--patch_size * --scale) = {args.patch_size} * {args.scale} = {side} is "
-                         "smaller than the 11 x 11 window of the SSIM")
-
-
-def check_alpha_texture(args):
-    """--alpha_texture / --texture_patch; SystemExit naming the flag.  No GPU is touched."""
-    if not args.alpha_texture >= 0:
-        raise SystemExit(f"train.py: --alpha_texture {args.alpha_texture} must be >= 0 (0 = off)")
-    if args.alpha_texture == 0:
-        return
-    if args.phase != "train":
-        raise SystemExit(f"train.py: --alpha_texture {args.alpha_texture} needs --phase train: the texture loss reads taps of the VGG19 "
-                         f"trunk, and no VGG runs in --phase {args.phase}")
-    from pesr_amd.texture import check_patch
-    side = args.patch_size * args.scale
-    why = check_patch(side, side, args.texture_patch)
-    if why:
-        raise SystemExit(f"train.py: --alpha_texture {args.alpha_texture}: --texture_patch {args.texture_patch} with (--patch_size * "
-                         f"--scale) = {args.patch_size} * {args.scale} = {side}: {why}; --texture_patch 0 takes the whole map of every tap")
-
-
-def check_alpha_cx(args):
-    """--alpha_cx / --cx_h; SystemExit naming the flag.  No GPU is touched."""
-    if not args.alpha_cx >= 0:
-        raise SystemExit(f"train.py: --alpha_cx {args.alpha_cx} must be >= 0 (0 = off)")
-    if not args.cx_h > 0:
-        raise SystemExit(f"train.py: --alpha_cx {args.alpha_cx}: --cx_h {args.cx_h} must be > 0")
-    if args.alpha_cx == 0:
-        return
-    if args.phase != "train":
-        raise SystemExit(f"train.py: --alpha_cx {args.alpha_cx} needs --phase train: the contextual loss reads a tap of the VGG19 "
-                         f"trunk, and no VGG runs in --phase {args.phase}")
-    from pesr_amd.contextual import check_size, tap_size
-    side = args.patch_size * args.scale
-    why = check_size(side, side)
-    if why:
-        th, tw = tap_size(side, side)
-        raise SystemExit(f"train.py: --alpha_cx {args.alpha_cx}: (--patch_size * --scale) = {args.patch_size} * {args.scale} = {side}, "
-                         f"a relu3_4 tap of {th} x {tw}: {why}")
+def loss_terms_of(args, valid_lpips_model=None):
+    """The flags of the optional terms of the generator's loss (pesr_amd/loss_terms.py TERMS) -> their keyword arguments for Trainer;
+    SystemExit naming the flags.  Per term, in table order: the weight rule; the term's own parameters; off: nothing else; the phase;
+    the side of the HR patches.  valid_lpips_model: the model --valid_lpips loaded, for the term that can share it.  No GPU is touched."""
+    from pesr_amd.loss_terms import TERMS
+    side, kw = args.patch_size * args.scale, {}
+    what = f"(--patch_size * --scale) = {args.patch_size} * {args.scale} = {side}"
+    for cls in TERMS:
+        alpha = getattr(args, cls.weight)
+        if not alpha >= 0:
+            raise SystemExit(f"train.py: {cls.flag} {alpha} must be >= 0 (0 = off)")
+        mine = cls.from_flags(args, "train.py", valid_lpips_model)
+        try:
+            term = cls(**mine)
+        except ValueError as e:         # (the text begins with the parameter's name, which is its flag's)
+            raise SystemExit(f"train.py: {cls.flag} {alpha}: --{e}")
+        kw.update(mine)
+        if not term.on:
+            continue
+        if args.phase not in term.phases:
+            raise SystemExit("train.py: " + term.wrong_phase(args.phase))
+        why = term.check(side, what)
+        if why:
+            raise SystemExit("train.py: " + why)
+    return kw
 
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
     degradation_spec(args)      # (refuses a classical run without its companion flags before anything else starts)
     scorer = scorer_of(args)
-    lpips_loss_model = lpips_loss_model_of(args, scorer.lpips_model)
-    check_alpha_ssim(args)
-    check_alpha_texture(args)
-    check_alpha_cx(args)
+    loss_terms = loss_terms_of(args, scorer.lpips_model)
     world =int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local = int(os.environ.get("LOCAL_RANK", "0"))
@@ -542,9 +491,7 @@ def main(argv=None):
     scheduler_D = lr_scheduler.StepLR(optim_D, step_size=args.lr_step, gamma=0.5) if gan else None
     trainer = Trainer(G, D, vgg, optim_G, optim_D, gan_type=args.gan_type, focal_loss=args.focal_loss, fl_gamma=args.fl_gamma,
                       alpha_vgg=args.alpha_vgg, alpha_gan=args.alpha_gan, alpha_tv=args.alpha_tv, alpha_l1=args.alpha_l1,
-                      world_size=world, gradient_penalty=args.GP, lpips_model=lpips_loss_model, alpha_lpips=args.alpha_lpips,
-                      alpha_ssim=args.alpha_ssim, alpha_texture=args.alpha_texture, texture_patch=args.texture_patch,
-                      alpha_cx=args.alpha_cx, cx_h=args.cx_h)
+                      world_size=world, gradient_penalty=args.GP, **loss_terms)
 
     check_point = os.path.join(args.check_point, args.phase)
     # what checkpoint.rng_snapshot / rng_restore get besides the process-wide streams: the GPU input pipeline's crop stream, or the
@@ -572,15 +519,7 @@ def main(argv=None):
     # with --ema_decay the averaged weights are what is validated and saved (the raw ones live in the state file)
     G_eval = optim_G.ema_module(G) if args.ema_decay > 0 else G
     ema_tag = " (EMA)" if args.ema_decay > 0 else ""
-    keys = ("l1", "vgg", "g", "tv", "d") if gan else ("l1",)
-    if trainer.use_lpips:
-        keys += ("lpips",)
-    if trainer.use_ssim:
-        keys += ("ssim",)
-    if trainer.use_texture:
-        keys += ("texture",)
-    if trainer.use_cx:
-        keys += ("cx",)
+    keys = (("l1", "vgg", "g", "tv", "d") if gan else ("l1",)) + tuple(t.key for t in trainer.terms)
     graphed, graph_shapes, eager_at_shape = None, None, 0
     use_graph = device.type == "cuda" and (world == 1 if args.hip_graph == "auto" else str2bool(args.hip_graph))
     # data-parallel schedule: fixed by flag, or measured once (inside the first epoch that is long enough for it)
@@ -681,8 +620,8 @@ def main(argv=None):
             print("Epoch [%d/%d] lr %g  " % (epoch, args.num_epochs, cur_lr) + "  ".join("%s %.4f" % kv for kv in zip(keys, avg)))
             if tb is not None:
                 tb.add_scalar("Learning rate", cur_lr, epoch)
-                names = {"l1": "L1 Loss", "vgg": "VGG Loss", "g": "G Loss", "tv": "TV Loss", "d": "D Loss", "lpips": "LPIPS Loss",
-                         "ssim": "SSIM Loss", "texture": "Texture Loss", "cx": "Contextual Loss"}
+                names = {"l1": "L1 Loss", "vgg": "VGG Loss", "g": "G Loss", "tv": "TV Loss", "d": "D Loss",
+                         **{t.key: t.title for t in trainer.terms}}
                 for k, v in zip(keys, avg):
                     tb.add_scalar(names[k] if gan or k != "l1" else "Pretrain Loss", v, epoch)
 
