@@ -2,7 +2,10 @@
 // (reference model/basic.py:29-30, model/pesr.py:47: eps 1e-5, momentum 0.1, slope 0.2), NHWC fp32.
 //   stats   : per-channel sum and sum of squares  -> per-block partials (no atomics); every thread accumulates in DOUBLE:
 //             dbeta = sum(dz) and the mean are sums of mixed-sign terms that mostly cancel, and an fp32 running sum over
-//             ~100 rows loses the bits the result lives in (these kernels are HBM-bound, the fp64 adds are free)
+//             ~100 rows loses the bits the result lives in (these kernels are HBM-bound, the fp64 adds are free).
+//             The per-block partials stay DOUBLE as well: var = E[x^2] - mean^2 cancels, and a partial rounded to fp32
+//             leaves 2^-24 (mean^2 + var) in it - a relative error of 2^-24 (1 + mean^2 / var) in invstd, 5e-5 at a
+//             channel of mean 100 and std 1 (docs/experiments/bn_tests.md).  The conv epilogues' partials are fp32.
 //   finalize: mean, biased var, invstd in double over the partials (fixed order); running stats
 //             (unbiased var, momentum) and num_batches_tracked updated as nn.BatchNorm2d does
 //   apply   : y = lrelu(gamma * (x - mean) * invstd + beta)         (optionally written NCHW for the
@@ -17,7 +20,7 @@
 template <int WHICH>
 __global__ __launch_bounds__(256) void bn_reduce_kernel(const float* __restrict__ x, const float* __restrict__ dy,
                                                         const float* __restrict__ mean_invstd, const float* __restrict__ gamma,
-                                                        const float* __restrict__ beta, float* __restrict__ part, long M, int C,
+                                                        const float* __restrict__ beta, double* __restrict__ part, long M, int C,
                                                         long rows_per_block, float slope) {
     const int C4 = C >> 2;
     const int cw = C4 < 256 ? C4 : 256;
@@ -56,8 +59,8 @@ __global__ __launch_bounds__(256) void bn_reduce_kernel(const float* __restrict_
         __syncthreads();
         if (tr == 0 && c4 < C4) {
             for (int k = 1; k < rl; ++k) { s0 += red[0][k * cw + tc]; s1 += red[1][k * cw + tc]; }
-            f32x4* p = (f32x4*)part + (size_t)blockIdx.x * 2 * C4;
-            p[c4] = __builtin_convertvector(s0, f32x4); p[C4 + c4] = __builtin_convertvector(s1, f32x4);
+            f64x4* p = (f64x4*)part + (size_t)blockIdx.x * 2 * C4;
+            p[c4] = s0; p[C4 + c4] = s1;
         }
         __syncthreads();
     }
@@ -66,9 +69,10 @@ __global__ __launch_bounds__(256) void bn_reduce_kernel(const float* __restrict_
 // The same fixed-order two-column row reduce for MANY rows (round 6: one row per pixel tile of a conv kernel whose epilogue leaves the
 // sums - up to a few thousand): 1024 threads = CL channel lanes x 1024 / CL row lanes; a thread adds rows rl, rl + RL, ... in increasing
 // order (four loads in flight), the row lanes are combined through LDS in lane order.  CL = 64 is reduce_rows_block2's shape (and
-// arithmetic); CL = 16 gives a layer of 64 channels four blocks of 64 row lanes instead of one block of 16.
-template <int CL>
-__device__ __forceinline__ void bn_rows2(const float* __restrict__ part, int nb, int ncols, int col0, int col1, bool valid, double* red,
+// arithmetic); CL = 16 gives a layer of 64 channels four blocks of 64 row lanes instead of one block of 16.  T: the partials' type -
+// float from a conv kernel's epilogue, double from bn_reduce_kernel.
+template <int CL, typename T>
+__device__ __forceinline__ void bn_rows2(const T* __restrict__ part, int nb, int ncols, int col0, int col1, bool valid, double* red,
                                          double* out0, double* out1) {
     constexpr int RL = 1024 / CL;
     const int cl = threadIdx.x % CL, rl = threadIdx.x / CL;
@@ -76,8 +80,8 @@ __device__ __forceinline__ void bn_rows2(const float* __restrict__ part, int nb,
     if (valid) {
         int k = rl;
         for (; k + 7 * RL < nb; k += 8 * RL) {      // 16 independent loads in flight; the additions stay in row order
-            const float* p0 = part + (size_t)k * ncols;
-            float a[8], b[8];
+            const T* p0 = part + (size_t)k * ncols;
+            T a[8], b[8];
 #pragma unroll
             for (int j = 0; j < 8; ++j) { a[j] = p0[(size_t)j * RL * ncols + col0]; b[j] = p0[(size_t)j * RL * ncols + col1]; }
 #pragma unroll
@@ -98,15 +102,15 @@ __device__ __forceinline__ void bn_rows2(const float* __restrict__ part, int nb,
 
 // second stage of the statistics (fixed-order row reduce of the per-block partials) and the finalize step in
 // ONE launch: block = CL channels; the small layers' BatchNorm is launch-bound, every launch saved is ~4.5 us
-template <int CL>
-__global__ __launch_bounds__(1024) void bn_finalize_kernel(const float* __restrict__ part, int nb, int C, long M, float eps,
+template <int CL, typename T>
+__global__ __launch_bounds__(1024) void bn_finalize_kernel(const T* __restrict__ part, int nb, int C, long M, float eps,
                                                            float momentum, float* __restrict__ mean_invstd,
                                                            float* __restrict__ running_mean, float* __restrict__ running_var,
                                                            long long* __restrict__ num_batches) {
     __shared__ double red[2048];
     const int c = blockIdx.x * CL + (threadIdx.x % CL);
     double s, ss;
-    bn_rows2<CL>(part, nb, 2 * C, c, C + c, c < C, red, &s, &ss);
+    bn_rows2<CL, T>(part, nb, 2 * C, c, C + c, c < C, red, &s, &ss);
     if (blockIdx.x == 0 && threadIdx.x == 0 && num_batches) *num_batches += 1;
     if (c >= C || threadIdx.x / CL != 0) return;
     const double mean = s / (double)M;
@@ -122,13 +126,13 @@ __global__ __launch_bounds__(1024) void bn_finalize_kernel(const float* __restri
 }
 
 // second stage for backward, same fusion: sums[0][c] = sum dz, sums[1][c] = sum dz*xhat (+ dbeta, dgamma)
-template <int CL>
-__global__ __launch_bounds__(1024) void bn_bwd_sums_kernel(const float* __restrict__ part, int nb, int C, float* __restrict__ sums,
+template <int CL, typename T>
+__global__ __launch_bounds__(1024) void bn_bwd_sums_kernel(const T* __restrict__ part, int nb, int C, float* __restrict__ sums,
                                                            float* __restrict__ dbeta, float* __restrict__ dgamma, int accumulate) {
     __shared__ double red[2048];
     const int c = blockIdx.x * CL + (threadIdx.x % CL);
     double s0, s1;
-    bn_rows2<CL>(part, nb, 2 * C, c, C + c, c < C, red, &s0, &s1);
+    bn_rows2<CL, T>(part, nb, 2 * C, c, C + c, c < C, red, &s0, &s1);
     if (c >= C || threadIdx.x / CL != 0) return;
     const float a = (float)s0, b = (float)s1;
     sums[c] = a; sums[C + c] = b;
@@ -207,20 +211,22 @@ __global__ __launch_bounds__(256) void nchw_to_nhwc_kernel(const float* __restri
 namespace {
 // many rows (a conv epilogue's pixel tiles, the 3 -> C kernel's 2048 workgroups): 16-channel blocks of 64 row lanes; few rows (bn_reduce's
 // <= 512 blocks): the 64-channel blocks of 16 row lanes these kernels always had (same order of additions as before round 6)
-static void bn_finalize_launch(const float* part, int rows, int C, long M, float eps, float momentum, float* mean_invstd, float* running_mean,
+template <typename T>
+static void bn_finalize_launch(const T* part, int rows, int C, long M, float eps, float momentum, float* mean_invstd, float* running_mean,
                                float* running_var, long long* num_batches, hipStream_t stream) {
     if (rows > 512)
-        hipLaunchKernelGGL(bn_finalize_kernel<16>, dim3((C + 15) / 16), dim3(1024), 0, stream, part, rows, C, M, eps, momentum, mean_invstd,
+        hipLaunchKernelGGL((bn_finalize_kernel<16, T>), dim3((C + 15) / 16), dim3(1024), 0, stream, part, rows, C, M, eps, momentum, mean_invstd,
                            running_mean, running_var, num_batches);
     else
-        hipLaunchKernelGGL(bn_finalize_kernel<64>, dim3((C + 63) / 64), dim3(1024), 0, stream, part, rows, C, M, eps, momentum, mean_invstd,
+        hipLaunchKernelGGL((bn_finalize_kernel<64, T>), dim3((C + 63) / 64), dim3(1024), 0, stream, part, rows, C, M, eps, momentum, mean_invstd,
                            running_mean, running_var, num_batches);
 }
-static void bn_bwd_sums_launch(const float* part, int rows, int C, float* sums, float* dbeta, float* dgamma, int accumulate, hipStream_t stream) {
+template <typename T>
+static void bn_bwd_sums_launch(const T* part, int rows, int C, float* sums, float* dbeta, float* dgamma, int accumulate, hipStream_t stream) {
     if (rows > 512)
-        hipLaunchKernelGGL(bn_bwd_sums_kernel<16>, dim3((C + 15) / 16), dim3(1024), 0, stream, part, rows, C, sums, dbeta, dgamma, accumulate);
+        hipLaunchKernelGGL((bn_bwd_sums_kernel<16, T>), dim3((C + 15) / 16), dim3(1024), 0, stream, part, rows, C, sums, dbeta, dgamma, accumulate);
     else
-        hipLaunchKernelGGL(bn_bwd_sums_kernel<64>, dim3((C + 63) / 64), dim3(1024), 0, stream, part, rows, C, sums, dbeta, dgamma, accumulate);
+        hipLaunchKernelGGL((bn_bwd_sums_kernel<64, T>), dim3((C + 63) / 64), dim3(1024), 0, stream, part, rows, C, sums, dbeta, dgamma, accumulate);
 }
 static void bn_grid(long M, long* nb, long* rpb) {
     long b = (M + 63) / 64; if (b > 512) b = 512; if (b < 1) b = 1;
@@ -233,22 +239,23 @@ static int bn_elem_grid(long M, int C) {
     return (int)(blocks < 8192 ? blocks : 8192);
 }
 
-// workspace of the stand-alone passes: part [nb][2][C] (bn_reduce_kernel's per-block sums), sums [2][C] (the backward's reduced sums)
-// and dyt, room for an NHWC copy of an NCHW gradient
+// workspace of the stand-alone passes: part [nb][2][C] (bn_reduce_kernel's per-block sums, double), sums [2][C] (the backward's reduced
+// sums) and dyt, room for an NHWC copy of an NCHW gradient
 struct BnWs {
     long nb, rpb;           // bn_grid(M)
-    float *part, *sums;
+    double* part;
+    float* sums;
     float* dyt;             // null where the workspace given ends before the copy
     size_t bytes;           // what pesr_bn_ws_bytes reports
 };
 // false: ws is missing or too small for part and sums
 static bool bn_ws_layout(long M, int C, void* ws, size_t ws_bytes, BnWs* w) {
     bn_grid(M, &w->nb, &w->rpb);
-    const size_t part_bytes = (size_t)w->nb * 2 * C * sizeof(float), sums_bytes = 2 * (size_t)C * sizeof(float);
+    const size_t part_bytes = (size_t)w->nb * 2 * C * sizeof(double), sums_bytes = 2 * (size_t)C * sizeof(float);
     const size_t dyt_off = (part_bytes + sums_bytes + 255) / 256 * 256, copy = (size_t)M * C * sizeof(float);
     w->bytes = dyt_off + copy;
     const bool ok = ws && ws_bytes >= dyt_off;
-    w->part = ok ? (float*)ws : nullptr;
+    w->part = ok ? (double*)ws : nullptr;
     w->sums = ok ? (float*)((char*)ws + part_bytes) : nullptr;
     w->dyt = ok && ws_bytes >= dyt_off + copy ? (float*)((char*)ws + dyt_off) : nullptr;
     return ok;
@@ -271,7 +278,8 @@ static const float* bn_dy_nhwc(const float* dy, int dy_nchw, const BnWs& w, long
     return w.dyt;
 }
 // forward tail: statistics from part [rows][2][C] (mean_invstd, running statistics), then y = lrelu(bn(x))
-static int bn_fwd_tail(const float* part, int rows, const float* x, const float* gamma, const float* beta, float* y, float* mean_invstd,
+template <typename T>
+static int bn_fwd_tail(const T* part, int rows, const float* x, const float* gamma, const float* beta, float* y, float* mean_invstd,
                        float* running_mean, float* running_var, long long* num_batches, long M, int C, long HW, float eps, float momentum,
                        float slope, int y_nchw, hipStream_t stream) {
     bn_finalize_launch(part, rows, C, M, eps, momentum, mean_invstd, running_mean, running_var, num_batches, stream);
@@ -280,7 +288,8 @@ static int bn_fwd_tail(const float* part, int rows, const float* x, const float*
 }
 // backward tail: part [rows][2][C] (null: none wanted) -> sums and dgamma / dbeta; then dx from sums - or, with fixed statistics, from
 // zeros, where the batch-statistics terms of the formula vanish
-static int bn_bwd_tail(const float* part, int rows, const float* x, const float* dy, const float* gamma, const float* beta,
+template <typename T>
+static int bn_bwd_tail(const T* part, int rows, const float* x, const float* dy, const float* gamma, const float* beta,
                        const float* mean_invstd, float* sums, float* dx, float* dgamma, float* dbeta, int accumulate, bool batch_stats, long M,
                        int C, float slope, int premasked, hipStream_t stream) {
     if (part) bn_bwd_sums_launch(part, rows, C, sums, dbeta, dgamma, accumulate, stream);
@@ -388,7 +397,7 @@ int pesr_bn_lrelu_bwd_eval_launch(const float* x, const float* dy, const float* 
     if (want_sums)
         hipLaunchKernelGGL(bn_reduce_kernel<1>, dim3((unsigned)w.nb), dim3(256), 0, stream, x, dy, mean_invstd, gamma, beta, w.part, M, C, w.rpb,
                            slope);
-    return bn_bwd_tail(want_sums ? w.part : nullptr, (int)w.nb, x, dy, gamma, beta, mean_invstd, w.sums, dx, dgamma, dbeta, 0, false, M, C, slope, 0,
+    return bn_bwd_tail(want_sums ? w.part : (double*)nullptr, (int)w.nb, x, dy, gamma, beta, mean_invstd, w.sums, dx, dgamma, dbeta, 0, false, M, C, slope, 0,
                        stream);
 }
 

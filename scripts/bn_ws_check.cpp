@@ -23,7 +23,7 @@ static int check(long M, int C) {
     int bad = 0;
     if (!bn_ws_layout(M, C, ws, bytes, &w) || !w.dyt || w.bytes != bytes) bad = 1;
     if (!bad) {
-        const size_t part_b = (size_t)w.nb * 2 * C * sizeof(float), sums_b = 2 * (size_t)C * sizeof(float), dyt_b = (size_t)M * C * sizeof(float);
+        const size_t part_b = (size_t)w.nb * 2 * C * sizeof(double), sums_b = 2 * (size_t)C * sizeof(float), dyt_b = (size_t)M * C * sizeof(float);
         const size_t part_o = (char*)w.part - ws, sums_o = (char*)w.sums - ws, dyt_o = (char*)w.dyt - ws;
         bad |= part_o % 256 || dyt_o % 256 || sums_o % 16;
         bad |= !(part_o + part_b <= sums_o && sums_o + sums_b <= dyt_o && dyt_o + dyt_b <= bytes);

@@ -619,11 +619,44 @@ def test_discriminator_second_order_forward_equals_forward():
             close(outs[1][2][k], outs[0][2][k], 2e-4, what="grad " + k)
 
 
+def _gv11_float64_step():
+    """The gradient-penalty step of test_gv11 by the CPU oracle (oracle/step.py) in float64, from the same weights and batch.
+    -> (dD/dx at x_both [N, 3, H, W], D's parameter gradients, D's parameters after the Adam step, the number of BatchNorm / LeakyReLU
+    inputs of D(x_both) with |z| < 1e-6)"""
+    c = lambda sd: {k: (v.double() if v.is_floating_point() else v.clone()) for k, v in sd.items()}
+    st = OS.TrainState(c(gen_sd(16, 2)), c(dis_sd(8)), c(vgg_sd()), {"depth": 2, "res_scale": 0.1, "learning_rate": 5e-5, "GP": True})
+    lr = detrand.image_batch((4, 3, 8, 8), 100).double(); hr = detrand.image_batch((4, 3, 32, 32), 200).double()
+    u = detrand.uniform((4, 1, 1, 1), 77, 0.0, 1.0).double()
+    xb = (hr * u + st.G(lr).detach() * (1 - u)).requires_grad_(True)
+    near, real = [0], F.leaky_relu
+
+    def counted(h, slope=0.01, inplace=False):
+        near[0] += int((h.detach().abs() < 1e-6).sum())
+        return real(h, slope)
+    F.leaky_relu = counted
+    try:
+        gx, = torch.autograd.grad(OM.discriminator_forward(dict(st.d), xb, update_running_stats=False).sum(), xb)
+    finally:
+        F.leaky_relu = real
+    OS.gan_step(st, lr, hr, gp_u=u)
+    return gx, {k: v.grad for k, v in st.d.items() if getattr(v, "grad", None) is not None}, {k: v.detach() for k, v in st.d.items()}, near[0]
+
+
 def test_gv11_gradient_penalty_step_vs_reference():
     """--GP true (reference train.py:216-226): one D-phase with the gradient penalty - torch.autograd.grad(D(x_both), x_both,
     create_graph=True) and the backward THROUGH that gradient, all inside D on the HIP kernels - against the run made with the
-    reference's own modules: total D loss, the penalty, dD/dx, D's gradients, post-Adam parameters."""
+    reference's own modules: total D loss, the penalty, dD/dx, D's gradients, post-Adam parameters.
+
+    One BatchNorm output of features.2 is 4.4e-8 at x_both - below what fp32 resolves (u (|gamma xhat| + |beta|) is 1e-7 .. 1e-6 there),
+    so its LeakyReLU branch is a coin toss for any fp32 evaluation.  The reference's fp32 run, which the golden file records, took the
+    negative branch; float64 takes the positive one; dD/dx differs between the two by 2.4e-3 of its maximum and the gradient of
+    features.2.1.bias by 8.6e-4 (docs/experiments/bn_tests.md).  It is the only such input of D(x_both) (asserted), so the golden file
+    and the CPU oracle's float64 step are the two possible outcomes: the kernels must match ONE of them, the same one throughout, to
+    the tolerances this test always had.  The loss and the penalty differ by less than 1e-7 between the two and are held to the
+    golden file alone."""
     g = load_golden("gv11_gradient_penalty_small")
+    gx64, grad64, par64, near = _gv11_float64_step()
+    assert near == 1, near
     tr, G, D = _trainer(16, 2, 8)
     tr.gradient_penalty = True
     lr = detrand.image_batch((4, 3, 8, 8), 100).cuda()
@@ -636,14 +669,19 @@ def test_gv11_gradient_penalty_step_vs_reference():
     import copy
     D2 = copy.deepcopy(D)
     gx = torch.autograd.grad(D2.forward_second_order(x_both).sum(), x_both)[0]
-    close(gx.contiguous().reshape(-1)[torch.from_numpy(g["gx_idx"]).cuda()], g["gx_val"], 0.0, 5e-4 * float(g["gx_max"]), "dD/dx_both")
+    got = gx.contiguous().reshape(-1)[torch.from_numpy(g["gx_idx"]).cuda()].double().cpu().numpy()
+    errs = [float(np.abs(got - g["gx_val"]).max()), float(np.abs(got - gx64.reshape(-1)[torch.from_numpy(g["gx_idx"])].numpy()).max())]
+    print("dD/dx_both: max error against the golden file and against the float64 step:", errs)
+    f64 = int(np.argmin(errs)) == 1                                  # which of the two outcomes the kernels took
+    assert min(errs) <= 5e-4 * float(g["gx_max"]), f"dD/dx_both: max err {errs} against either outcome, scale {float(g['gx_max']):.3e}"
     log = tr.gan_step(lr, hr, gp_u=u)
     close(log["gp"], g["gp"], 5e-5, what="gradient penalty")
     close(log["d"], g["total"], 5e-5, what="total D loss")
     worst = 0.0
     for k, p in D.named_parameters():
         got = p.grad.reshape(-1)[torch.from_numpy(g["gidx." + k]).cuda()].double().cpu().numpy()
-        err = np.abs(got - g["gval." + k]).max() / (float(g["gmax." + k]) + 1e-30)
+        want = grad64[k].reshape(-1)[torch.from_numpy(g["gidx." + k])].numpy() if f64 else g["gval." + k]
+        err = np.abs(got - want).max() / (float(g["gmax." + k]) + 1e-30)
         worst = max(worst, err)
         assert err <= 1e-4, f"grad {k}: {err:.2e} of the maximum"         # measured: 6e-6
     print(f"worst D gradient error with the penalty: {worst:.2e} of a tensor's maximum")
@@ -651,7 +689,8 @@ def test_gv11_gradient_penalty_step_vs_reference():
         if "num_batches" in k:
             assert int(v) == 5
         elif "running" not in k:
-            adam_close(v.reshape(-1)[torch.from_numpy(g["pidx." + k]).cuda()], g["pval." + k], 5e-5, 1, "D." + k)
+            want = par64[k].reshape(-1)[torch.from_numpy(g["pidx." + k])].numpy() if f64 else g["pval." + k]
+            adam_close(v.reshape(-1)[torch.from_numpy(g["pidx." + k]).cuda()], want, 5e-5, 1, "D." + k)
 
 
 def test_gan_step_hipgraph_replay_is_bit_identical_to_eager():
