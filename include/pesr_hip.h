@@ -505,6 +505,31 @@ int pesr_lpips_layer2(const float* fa, const float* fb, const float* w, double* 
 int pesr_lpips_layer_bwd(const float* fa, const float* fb, const float* w, const double* g, float* ga, int N, int H, int W, int C,
                          void* stream);
 
+/* ---- DISTS (docs/modes.md section 4t): the L2 pooling of its VGG16 trunk and the head of one stage ------- */
+/* x: fp32 NHWC [N][H][W][C] -> y [N][ceil(H/2)][ceil(W/2)][C] = sqrt(conv(x * x, g, stride 2, zero padding 1, depthwise) + 1e-12),
+ * g = [1,2,1] (x) [1,2,1] / 16.  Forward only.  fp32, nothing fused, one fixed order inside a window (the header of csrc/dists.hip):
+ * nine squares, eight additions, the + 1e-12 and the square root round (the weights are powers of two).  PESR_EINVAL (nothing
+ * launched): C not a multiple of 64, N, H or W < 1, x or y not on a 16-byte boundary.  64-bit offsets.  pesr_l2pool_blocks: the
+ * workgroups a shape takes (each 256 lanes of four channels of one output pixel), 0 for a shape the kernel does not take; host only. */
+long pesr_l2pool_blocks(int N, int H, int W, int C);
+int pesr_l2pool_fwd(const float* x, float* y, int N, int H, int W, int C, void* stream);
+
+/* The head of one stage.  feat: fp32 NHWC [2N][H][W][C], entries 0 .. N-1 the features of image a, N .. 2N-1 those of image b; C in
+ * {3, 64, 128, 256, 512} (3: stage 0, the image itself as NHWC).  alpha, beta: C device doubles each, the stage's slices of
+ * alpha / w and beta / w.  Per pair and channel over the P = H * W pixels, in float64: mu_a, mu_b = sum / P, var_a = sum((a - mu_a)^2)
+ * / P, var_b likewise, cov = sum((a - mu_a)(b - mu_b)) / P (the centred two-pass form: the features are read twice);
+ * S1 = (2 mu_a mu_b + 1e-6) / (mu_a^2 + mu_b^2 + 1e-6), S2 = (2 cov + 1e-6) / (var_a + var_b + 1e-6);
+ * out: N device doubles, sum_c alpha_c S1_c + beta_c S2_c.  stats_or_null: when non-null [N][C][5] doubles {mu_a, mu_b, var_a, var_b,
+ * cov} are written too; out is the same bits either way.  No fused multiply-add, no atomics, every sum in an order that depends on
+ * (P, C) alone (partials per block of 256 pixels, combined in ascending block order): bit-identical to the ordered float64 host
+ * restatement and on every call.  pesr_dists_pixel_blocks and pesr_dists_workspace_bytes are pure host functions of the shape (P
+ * pixels per image) and return 0 for a shape the kernels do not take; a smaller workspace -> PESR_EWORKSPACE.  PESR_EINVAL (nothing
+ * launched): another C, N < 1 or N > 32767, a side < 1.  64-bit offsets. */
+long pesr_dists_pixel_blocks(int N, long P, int C);
+size_t pesr_dists_workspace_bytes(int N, long P, int C);
+int pesr_dists_layer(const float* feat, const double* alpha, const double* beta, double* out, int N, int H, int W, int C,
+                     double* stats_or_null, void* workspace, size_t ws_bytes, void* stream);
+
 /* ---- backward of the upsampler's tail: conv C -> 4C, PixelShuffle(2), conv C -> 3 (reference model/basic.py:56-60), as the backward
  * of one virtual 3 x 3 conv V from C to 64 channels (48 used) at the resolution of the tail's input h [N][H][W][C]
  * (docs/experiments/upsample_tail.md has the algebra).  w2 OIHW [4C][C][3][3], b2 [4C], w4 OIHW [3][C][3][3], all fp32; C % 16 == 0,

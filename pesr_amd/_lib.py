@@ -116,7 +116,12 @@ SIGNATURES.update({
     "pesr_lpips_layer": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, _P, _P, c_size_t, _P]),
     "pesr_lpips_layer2": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, _P, _P, c_size_t, _P]),
     "pesr_lpips_layer_bwd": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, _P]),
-    "pesr_upsample_tail_gather": (c_int, [_P, _P, c_int, c_int, c_int, _P]),
+    "pesr_l2pool_blocks": (c_long, [c_int, c_int, c_int, c_int]),
+    "pesr_l2pool_fwd": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P]),
+    "pesr_dists_pixel_blocks": (c_long, [c_int, c_long, c_int]),
+    "pesr_dists_workspace_bytes": (c_size_t, [c_int, c_long, c_int]),
+    "pesr_dists_layer": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, _P, _P, c_size_t, _P]),
+    "pesr_upsample_tail_gather":(c_int, [_P, _P, c_int, c_int, c_int, _P]),
     "pesr_upsample_tail_compose": (c_int, [_P, _P, _P, c_int, _P]),
     "pesr_upsample_tail_chain": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, _P]),
     "pesr_tile_gather": (c_int, [_P, c_int, c_int, c_int, _P, _P, _P, c_int, c_int, c_int, _P]),

@@ -463,6 +463,17 @@ PESR_API int pesr_lpips_layer_bwd(const float* fa, const float* fb, const float*
     return pesr_lpips_layer_bwd_launch(fa, fb, w, g, ga, N, H, W, C, (hipStream_t)stream);
 }
 
+PESR_API long pesr_l2pool_blocks(int N, int H, int W, int C) { return pesr_l2pool_blocks_of(N, H, W, C); }
+PESR_API int pesr_l2pool_fwd(const float* x, float* y, int N, int H, int W, int C, void* stream) {
+    return pesr_l2pool_fwd_launch(x, y, N, H, W, C, (hipStream_t)stream);
+}
+PESR_API long pesr_dists_pixel_blocks(int N, long P, int C) { return pesr_dists_pixel_blocks_of(N, P, C); }
+PESR_API size_t pesr_dists_workspace_bytes(int N, long P, int C) { return pesr_dists_ws_bytes(N, P, C); }
+PESR_API int pesr_dists_layer(const float* feat, const double* alpha, const double* beta, double* out, int N, int H, int W, int C,
+                              double* stats_or_null, void* workspace, size_t ws_bytes, void* stream) {
+    return pesr_dists_layer_launch(feat, alpha, beta, out, N, H, W, C, stats_or_null, workspace, ws_bytes, (hipStream_t)stream);
+}
+
 PESR_API int pesr_upsample_tail_gather(const float* g, float* gw, int N, int H, int W, void* stream) {
     return pesr_upsample_tail_gather_launch(g, gw, N, H, W, (hipStream_t)stream);
 }

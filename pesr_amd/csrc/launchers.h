@@ -265,6 +265,14 @@ int pesr_lpips_layer2_launch(const float* fa, const float* fb, const float* w, d
 int pesr_lpips_layer_bwd_launch(const float* fa, const float* fb, const float* w, const double* g, float* ga, int N, int H, int W, int C,
                                 hipStream_t stream);
 
+// DISTS (dists.hip): the L2 pooling of the trunk, and the head of one stage (per-channel statistics of two feature maps -> S1, S2)
+long pesr_l2pool_blocks_of(int N, int H, int W, int C);
+int pesr_l2pool_fwd_launch(const float* x, float* y, int N, int H, int W, int C, hipStream_t stream);
+long pesr_dists_pixel_blocks_of(int N, long P, int C);
+size_t pesr_dists_ws_bytes(int N, long P, int C);
+int pesr_dists_layer_launch(const float* feat, const double* alpha, const double* beta, double* out, int N, int H, int W, int C,
+                            double* stats, void* ws, size_t ws_bytes, hipStream_t stream);
+
 // backward of the upsampler's tail (conv C -> 4C, PixelShuffle(2), conv C -> 3) as one virtual C -> 64 conv (upsample_tail.hip)
 int pesr_upsample_tail_gather_launch(const float* g, float* gw, int N, int H, int W, hipStream_t stream);
 int pesr_upsample_tail_compose_launch(const float* w2, const float* w4, float* weff, int C, hipStream_t stream);

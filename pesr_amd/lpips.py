@@ -53,6 +53,28 @@ def conv_shapes():
     return out
 
 
+def trunk_taps(scaling, convs, pool, x):
+    """The VGG16 trunk of CFG, shared with dists.py: [M, 3, H, W] images in 0..255 through the input affine `scaling`, the 13 `convs`
+    with the fused ReLU and `pool` at every "M" -> the five tapped NHWC feature tensors, always on the fp32 conv kernels."""
+    prev = ops.PRECISION
+    ops.set_precision("fp32")                                       # the metric does not depend on the mode the generator runs in
+    try:
+        with torch.no_grad():
+            h = scaling(x)
+            taps, i = [], 0
+            for v in CFG:
+                if v == "M":
+                    h = pool(h)
+                    continue
+                h = convs[i](h, act=ops.ACT_RELU)
+                if i in TAPS:
+                    taps.append(nhwc(h))
+                i += 1
+    finally:
+        ops.set_precision(prev)
+    return taps
+
+
 class LpipsModel(nn.Module):
     """The 13 conv weights and biases of the VGG16 trunk, the five non-negative "lin" weight vectors, and the input affine."""
 
@@ -140,23 +162,7 @@ class LpipsModel(nn.Module):
     # ---- the trunk ---------------------------------------------------------------------------------------------------------------
     def features(self, x):
         """[M, 3, H, W] images in 0..255 -> the five tapped NHWC feature tensors, always on the fp32 conv kernels."""
-        prev = ops.PRECISION
-        ops.set_precision("fp32")                                   # the metric does not depend on the mode the generator runs in
-        try:
-            with torch.no_grad():
-                h = self.scaling(x)
-                taps, i = [], 0
-                for v in CFG:
-                    if v == "M":
-                        h = self.pool(h, relu_in=True)
-                        continue
-                    h = self.convs[i](h, act=ops.ACT_RELU)
-                    if i in TAPS:
-                        taps.append(nhwc(h))
-                    i += 1
-        finally:
-            ops.set_precision(prev)
-        return taps
+        return trunk_taps(self.scaling, self.convs, lambda h: self.pool(h, relu_in=True), x)
 
 
     def features_grad(self, x):
@@ -266,15 +272,15 @@ def lpips_loss(sr, hr, model, shave=0):
 
 
 # ---- pack: the two published files -> the one file load() reads -----------------------------------------------------------------
-def _read_state_dict(path, flag):
+def _read_state_dict(path, flag, prog="lpips pack"):
     if not os.path.isfile(path):
-        raise SystemExit(f"lpips pack: {flag} {path}: no such file")
+        raise SystemExit(f"{prog}: {flag} {path}: no such file")
     try:
         d = torch.load(path, map_location="cpu", weights_only=True)
     except Exception as e:
-        raise SystemExit(f"lpips pack: {flag} {path}: not readable as a state_dict: {e}")
+        raise SystemExit(f"{prog}: {flag} {path}: not readable as a state_dict: {e}")
     if not isinstance(d, dict):
-        raise SystemExit(f"lpips pack: {flag} {path}: not a state_dict")
+        raise SystemExit(f"{prog}: {flag} {path}: not a state_dict")
     return d
 
 

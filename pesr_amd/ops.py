@@ -1330,6 +1330,77 @@ def lpips_layer_bwd(fa: torch.Tensor, fb: torch.Tensor, w: torch.Tensor, g: torc
 
 
 # ------------------------------------------------------------------------------------------------
+# DISTS (docs/modes.md section 4t): the trunk's L2 pooling and the head of one stage (pesr_amd/csrc/dists.hip)
+# ------------------------------------------------------------------------------------------------
+DISTS_CHANNELS = (3, 64, 128, 256, 512)
+
+
+def l2pool_plan(N: int, H: int, W: int, C: int) -> dict:
+    """What l2pool_fwd does with an NHWC [N, H, W, C] input (a host-only question): {"blocks": its workgroups, "floats_per_block": the
+    output elements one workgroup writes, 1024 / C pixels}.  ValueError for a shape the kernel does not take."""
+    blocks = _memo("pesr_l2pool_blocks", N, H, W, C)
+    if blocks < 1:
+        raise ValueError(f"l2pool_plan: no L2 pooling kernel for N {N}, H {H}, W {W}, C {C}")
+    return {"blocks": blocks, "floats_per_block": 1024}
+
+
+def l2pool_fwd(x: torch.Tensor) -> torch.Tensor:
+    """DISTS's L2 pooling.  x: NHWC [N, H, W, C], C a multiple of 64 -> [N, ceil(H/2), ceil(W/2), C] =
+    sqrt(conv(x * x, [1,2,1] (x) [1,2,1] / 16, stride 2, zero padding 1, depthwise) + 1e-12).  Forward only."""
+    _chk(x, "l2pool_fwd.x")
+    if x.dim() != 4 or min(x.shape) < 1:
+        raise _lib.PesrHipError(f"l2pool_fwd.x: expected a [N, H, W, C] tensor, got {tuple(x.shape)}")
+    N, H, W, C = x.shape
+    if C % 64:
+        raise _lib.PesrHipError(f"l2pool_fwd.x: C = {C}, the L2 pooling kernel takes multiples of 64")
+    y = torch.empty((N, (H + 1) // 2, (W + 1) // 2, C), dtype=torch.float32, device=x.device)
+    _lib.check(_lib.lib().pesr_l2pool_fwd(_p(x), _p(y), N, H, W, C, _stream()), "pesr_l2pool_fwd")
+    return y
+
+
+def dists_plan(N: int, P: int, C: int) -> dict:
+    """What dists_layer does with N image pairs of P pixels and C channels (a host-only question): {"pixel_blocks": the blocks of
+    pixels_per_block = 256 pixels whose partial sums are combined in ascending order; "workspace_bytes"}.  ValueError for a shape the
+    kernels do not take."""
+    nb = _memo("pesr_dists_pixel_blocks", N, P, C)
+    if nb < 1:
+        raise ValueError(f"dists_plan: no DISTS head kernel for N {N}, P {P}, C {C}")
+    return {"pixel_blocks": nb, "pixels_per_block": 256, "workspace_bytes": int(_lib.lib().pesr_dists_workspace_bytes(N, P, C))}
+
+
+def _chk_dists_weights(name: str, t, C: int):
+    if not torch.is_tensor(t) or not t.is_cuda:
+        raise _lib.PesrHipError(f"dists_layer.{name}: pesr_amd ops run only on a GPU (HIP) tensor; there is no CPU fallback")
+    if t.dtype != torch.float64:
+        raise _lib.PesrHipError(f"dists_layer.{name}: expected float64, got {t.dtype}")
+    if t.dim() != 1 or t.shape[0] != C:
+        raise _lib.PesrHipError(f"dists_layer.{name}: expected {C} weights, got {tuple(t.shape)}")
+    if not t.is_contiguous():
+        raise _lib.PesrHipError(f"dists_layer.{name}: expected a contiguous tensor")
+
+
+def dists_layer(feat: torch.Tensor, alpha: torch.Tensor, beta: torch.Tensor, return_stats: bool = False):
+    """The DISTS head of one stage (docs/modes.md section 4t).  feat: NHWC [2N, H, W, C], entries 0 .. N-1 the features of image a and
+    N .. 2N-1 those of image b, C in DISTS_CHANNELS (3: the image itself); alpha, beta: float64 [C], the stage's slices of alpha / w and
+    beta / w -> device double [N], sum_c alpha_c S1_c + beta_c S2_c; with return_stats also the [N, C, 5] doubles (mu_a, mu_b, var_a,
+    var_b, cov).  Contiguous tensors only (_chk): a view raises."""
+    _chk(feat, "dists_layer.feat")
+    if feat.dim() != 4 or feat.shape[0] < 2 or feat.shape[0] % 2 or min(feat.shape) < 1:
+        raise _lib.PesrHipError(f"dists_layer.feat: expected a [2N, H, W, C] tensor (a's features, then b's), got {tuple(feat.shape)}")
+    N, H, W, C = feat.shape[0] // 2, feat.shape[1], feat.shape[2], feat.shape[3]
+    if C not in DISTS_CHANNELS:
+        raise _lib.PesrHipError(f"dists_layer.feat: C = {C}, the DISTS head takes C in {DISTS_CHANNELS}")
+    _chk_dists_weights("alpha", alpha, C)
+    _chk_dists_weights("beta", beta, C)
+    out = torch.empty(N, dtype=torch.float64, device=feat.device)
+    stats = torch.empty((N, C, 5), dtype=torch.float64, device=feat.device) if return_stats else None
+    ws = workspace(int(_lib.lib().pesr_dists_workspace_bytes(N, H * W, C)), feat.device)
+    rc = _lib.lib().pesr_dists_layer(_p(feat), _p(alpha), _p(beta), _p(out), N, H, W, C, _p(stats), _p(ws), ws.numel(), _stream())
+    _lib.check(rc, "pesr_dists_layer")
+    return (out, stats) if return_stats else out
+
+
+# ------------------------------------------------------------------------------------------------
 # texture loss: patch-wise Gram matrices (docs/modes.md section 4q)
 # ------------------------------------------------------------------------------------------------
 GRAM_CHANNELS = (64, 128, 256)

@@ -1,6 +1,6 @@
 """What a run scores and how it prints it, once for test.py and train.py's validation: PSNR-Y always, SSIM-Y (docs/modes.md section 4g),
-NIQE (section 4k) and LPIPS (section 4n) when asked for, in that column order, through utils.compute_PSNR / compute_SSIM /
-compute_NIQE / compute_LPIPS.  One --shave rule and one "the image must hold the model" pre-check serve both programs; what differs
+NIQE (section 4k), LPIPS (section 4n) and DISTS (section 4t) when asked for, in that column order, through utils.compute_PSNR /
+compute_SSIM / compute_NIQE / compute_LPIPS / compute_DISTS.  One --shave rule and one "the image must hold the model" pre-check serve both programs; what differs
 between them (flag names, labels, digits, the tensorboard tag) is in the table below.
 """
 import numpy as np
@@ -11,11 +11,12 @@ _COLUMNS = {
     "SSIM-Y": ("%.10f", "SSIM", "%.6f"),
     "NIQE": ("%.10f", "NIQE", "%.6f"),
     "LPIPS": ("%.10f", "LPIPS", "%.6f"),
+    "DISTS": ("%.10f", "DISTS", "%.6f"),
 }
 
 
 class ScoreError(ValueError):
-    """The ValueError of a score that takes a model (NIQE, LPIPS) for an image it cannot take; `flags` names the model's flag and
+    """The ValueError of a score that takes a model (NIQE, LPIPS, DISTS) for an image it cannot take; `flags` names the model's flag and
     the shave's, for the entry point's own wording of the refusal."""
 
     def __init__(self, flags, err):
@@ -24,15 +25,17 @@ class ScoreError(ValueError):
 
 
 class Scorer:
-    def __init__(self, prog, ssim, shave, niqe="", lpips="", flags=("--niqe", "--lpips", "--shave"), size_flags=None, have_hr=True):
+    def __init__(self, prog, ssim, shave, niqe="", lpips="", flags=("--niqe", "--lpips", "--shave"), size_flags=None, have_hr=True,
+                 dists="", dists_flag="--dists"):
         """prog and flags (of the NIQE model, the LPIPS model and the shave; size_flags: all that decide an image's size after the
-        shave, the shave's alone by default) are quoted in the refusals.  niqe / lpips: a model file (or a loaded model), "" = that
-        column is off.  have_hr false: a run without HR images, which LPIPS refuses.  SystemExit naming the flag for a file that is no
+        shave, the shave's alone by default) and dists_flag (of the DISTS model) are quoted in the refusals.  niqe / lpips / dists: a model
+        file (or a loaded model), "" = that column is off.  have_hr false: a run without HR images, which LPIPS and DISTS refuse.  SystemExit naming the flag for a file that is no
         model.  No GPU is touched."""
         self.prog, self.ssim, self.shave = prog, bool(ssim), int(shave)
         self.niqe_flag, self.lpips_flag, self.shave_flag = flags
         self.size_flags = size_flags or self.shave_flag
-        self.niqe_model = self.lpips_model = None
+        self.dists_flag = dists_flag
+        self.niqe_model = self.lpips_model = self.dists_model = None
         if niqe:
             from . import niqe as _niqe
             self.niqe_model = _niqe.load_model_flag(prog, self.niqe_flag, niqe) if isinstance(niqe, str) else niqe
@@ -42,14 +45,21 @@ class Scorer:
             from . import lpips as _lpips
             self.lpips_model = _lpips.load_model_flag(prog, self.lpips_flag, lpips) if isinstance(lpips, str) else lpips
 
+        if dists:
+            if not have_hr:
+                raise SystemExit(f"{prog}: {self.dists_flag} compares the result with the HR image: it needs --from_hr true")
+            from . import dists as _dists
+            self.dists_model = _dists.load_model_flag(prog, self.dists_flag, dists) if isinstance(dists, str) else dists
+
     def columns(self, hr=True):
         """The names of the values score() returns, in its order; without an HR image only NIQE can be measured."""
-        on = {"PSNR-Y": hr, "SSIM-Y": hr and self.ssim, "NIQE": self.niqe_model is not None, "LPIPS": hr and self.lpips_model is not None}
+        on = {"PSNR-Y": hr, "SSIM-Y": hr and self.ssim, "NIQE": self.niqe_model is not None, "LPIPS": hr and self.lpips_model is not None,
+              "DISTS": hr and self.dists_model is not None}
         return [c for c in _COLUMNS if on[c]]
 
     def check_size(self, h, w, name):
         """SystemExit unless an h x w image (`name` in the message) holds, after the shave, the NIQE model's block twice and LPIPS's
-        16 x 16.  Only the size is needed - a PNG header's, or the synthetic patch's: no GPU is touched."""
+        and DISTS's 16 x 16.  Only the size is needed - a PNG header's, or the synthetic patch's: no GPU is touched."""
         if self.niqe_model is not None:
             from . import niqe as _niqe
             _niqe.check_fits_flag(self.prog, f"{self.niqe_flag} / {self.size_flags}", self.niqe_model, h, w, self.shave, name)
@@ -58,10 +68,15 @@ class Scorer:
             if min(h, w) - 2 * self.shave < MIN_SIDE:
                 raise SystemExit(f"{self.prog}: {self.lpips_flag} / {self.size_flags}: {name}: {max(h - 2 * self.shave, 0)} x "
                                  f"{max(w - 2 * self.shave, 0)} after the shave; LPIPS needs at least {MIN_SIDE} x {MIN_SIDE}")
+        if self.dists_model is not None:
+            from .lpips import MIN_SIDE
+            if min(h, w) - 2 * self.shave < MIN_SIDE:
+                raise SystemExit(f"{self.prog}: {self.dists_flag} / {self.size_flags}: {name}: {max(h - 2 * self.shave, 0)} x "
+                                 f"{max(w - 2 * self.shave, 0)} after the shave; DISTS needs at least {MIN_SIDE} x {MIN_SIDE}")
 
     def score(self, sr, hr=None):
-        """[1,3,H,W] result (and HR image) -> {column: value} in columns(hr is not None)'s order.  LPIPS is taken of the uint8 values
-        the result would be saved as (the identity on an image read back from its file)."""
+        """[1,3,H,W] result (and HR image) -> {column: value} in columns(hr is not None)'s order.  LPIPS and DISTS are taken of the uint8
+        values the result would be saved as (the identity on an image read back from its file)."""
         import utils
         out = {}
         for c in self.columns(hr is not None):
@@ -72,11 +87,14 @@ class Scorer:
                     out[c] = utils.compute_SSIM(sr, hr, self.shave)
                 elif c == "NIQE":
                     out[c] = utils.compute_NIQE(sr, self.niqe_model, self.shave)
-                else:
+                elif c == "LPIPS":
                     out[c] = utils.compute_LPIPS(sr.clamp(0, 255).round(), hr, self.lpips_model, self.shave)
+                else:
+                    out[c] = utils.compute_DISTS(sr.clamp(0, 255).round(), hr, self.dists_model, self.shave)
             except ValueError as e:
-                if c in ("NIQE", "LPIPS"):
-                    raise ScoreError(f"{self.niqe_flag if c == 'NIQE' else self.lpips_flag} / {self.shave_flag}", e) from None
+                flag = {"NIQE": self.niqe_flag, "LPIPS": self.lpips_flag, "DISTS": self.dists_flag}.get(c)
+                if flag:
+                    raise ScoreError(f"{flag} / {self.shave_flag}", e) from None
                 raise
         return out
 

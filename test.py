@@ -4,7 +4,8 @@ self-ensemble, image-space blend `alpha*out + (1-alpha)*out_psnr`, PNG output.  
 (test.py:13-33) plus --precision, --scale and --from_hr (a test set that ships HR images only: LR made on the device, PSNR-Y of the
 result and of the bicubic baseline printed; --ssim adds SSIM-Y, --shave drops a border before both), --niqe (the no-reference NIQE
 of every saved image against a pristine model, with or without --from_hr; docs/modes.md section 4k), --lpips (with --from_hr true:
-the full-reference LPIPS of every saved image and of the bicubic baseline against HR; section 4n) and --tile (every image as
+the full-reference LPIPS of every saved image and of the bicubic baseline against HR; section 4n), --dists (likewise, the
+texture-tolerant DISTS; section 4t) and --tile (every image as
 batches of fixed-size tiles, docs/modes.md section 4h); device-agnostic plumbing; the
 Generator itself runs on the MI355X kernels.
 """
@@ -63,6 +64,10 @@ def build_parser():
                         help="with --from_hr true: an LPIPS weight file (from `python -m pesr_amd.lpips pack`): also print the LPIPS (v0.1, "
                              "VGG variant, measured on the GPU, --shave applied) of every saved image and of the bicubic baseline "
                              "against the HR image")
+    # an addition (not a reference flag): the texture-tolerant full-reference score, docs/modes.md section 4t
+    parser.add_argument("--dists", type=str, default="",
+                        help="with --from_hr true: a DISTS weight file (from `python -m pesr_amd.dists pack`): also print the DISTS "
+                             "(measured on the GPU, --shave applied) of every saved image and of the bicubic baseline against the HR image")
     # additions (not reference flags): tiled inference, docs/modes.md section 4h
     parser.add_argument("--tile", type=int, default=0,
                         help="run every image as batches of overlapping tiles of one fixed shape on the GPU: the side of the square of "
@@ -236,14 +241,14 @@ def main(argv=None):
     jpeg_q = jpeg_quality(args)
     jitter = resize_jitter(args)
     from pesr_amd.quality import Scorer
-    scorer = Scorer("test.py", args.ssim, shave, args.niqe, args.lpips, have_hr=args.from_hr)
+    scorer = Scorer("test.py", args.ssim, shave, args.niqe, args.lpips, have_hr=args.from_hr, dists=args.dists)
     scored = bool(scorer.columns(args.from_hr))     # (an LR-only set has a score only with --niqe)
     from pesr_amd import tile as _tile
     tile_halo = _tile.check_flags("test.py", ("--tile", "--tile_halo", "--tile_batch"), args.tile, args.tile_halo, args.tile_batch,
                                   args.num_blocks, args.scale)
     device = default_device()
     lr_paths = sorted(glob.glob(os.path.join("data/origin/test/", args.dataset, "HR" if args.from_hr else "LR", "*.png")))
-    if scorer.niqe_model is not None or scorer.lpips_model is not None:       # (the size comes from the PNG header: still no GPU)
+    if scorer.niqe_model is not None or scorer.lpips_model is not None or scorer.dists_model is not None:       # (the size comes from the PNG header: still no GPU)
         from PIL import Image
         for path in lr_paths:
             with Image.open(path) as im:

@@ -123,6 +123,10 @@ def build_parser():
                    help="an LPIPS weight file (from `python -m pesr_amd.lpips pack`): validation also averages the LPIPS (v0.1, VGG variant, "
                         "measured on the GPU, docs/modes.md section 4n) of the results against the HR images and prints it in a line of "
                         "its own; the best model is still chosen by PSNR")
+    p.add_argument("--valid_dists", type=str, default="",
+                   help="a DISTS weight file (from `python -m pesr_amd.dists pack`): validation also averages the DISTS (measured on the "
+                        "GPU, docs/modes.md section 4t) of the results against the HR images and prints it in a line of its own; the "
+                        "best model is still chosen by PSNR")
     p.add_argument("--lpips_loss", type=str, default="",
                    help="an LPIPS weight file (from `python -m pesr_amd.lpips pack`) for --alpha_lpips: LPIPS (v0.1, VGG variant) of the "
                         "super-resolved batch against HR as a term of the generator's loss in --phase train (docs/modes.md section 4o)")
@@ -380,7 +384,8 @@ def scorer_of(args):
     """The --valid_* flags -> the Scorer of the validation (pesr_amd/quality.py); SystemExit naming the flags.  No GPU is touched."""
     from pesr_amd.quality import Scorer
     scorer = Scorer("train.py", args.valid_ssim, args.valid_shave, args.valid_niqe, args.valid_lpips,
-                    flags=("--valid_niqe", "--valid_lpips", "--valid_shave"), size_flags="--valid_shave / --patch_size")
+                    flags=("--valid_niqe", "--valid_lpips", "--valid_shave"), size_flags="--valid_shave / --patch_size",
+                    dists=args.valid_dists, dists_flag="--valid_dists")
     if args.synthetic:          # (the synthetic validation images are patch-sized; a folder's sizes are known when it is read)
         scorer.check_size(args.patch_size * args.scale, args.patch_size * args.scale, "the synthetic validation images")
     return scorer

@@ -1,6 +1,6 @@
 """Image <-> tensor helpers, the Y-channel PSNR of the reference (reference utils.py:10-41), the Y-channel SSIM beside it
-(docs/modes.md section 4g) and the no-reference NIQE (section 4k), device-agnostic, and the full-reference LPIPS (section 4n), which
-runs on the GPU only.
+(docs/modes.md section 4g) and the no-reference NIQE (section 4k), device-agnostic, and the full-reference LPIPS (section 4n) and
+DISTS (section 4t), which run on the GPU only.
 
 Tensors carry raw 0..255 values (no /255 anywhere).  Metrics run in numpy on the host exactly as the
 reference does; nothing here is on the hot path.
@@ -139,6 +139,17 @@ def compute_LPIPS(out, lbl, model, shave=0):
     if not isinstance(model, _lpips.LpipsModel):
         model = _lpips.LpipsModel.load(model)
     return float(_lpips.lpips(out, lbl, model, int(shave)).mean())
+
+
+def compute_DISTS(out, lbl, model, shave=0):
+    """DISTS (docs/modes.md section 4t) of N image pairs [N,3,H,W] in 0..255 against a pesr_amd.dists.DistsModel or the path of one, a
+    border of `shave` pixels dropped first -> the mean over the N pairs.  The trunk and the head run on the device and there is no CPU
+    path: anything that is not a float32 GPU tensor raises ValueError, as do images that differ in shape or are smaller than 16 x 16
+    after the shave."""
+    from pesr_amd import dists as _dists
+    if not isinstance(model, _dists.DistsModel):
+        model = _dists.DistsModel.load(model)
+    return float(_dists.dists(out, lbl, model, int(shave)).mean())
 
 
 def update_tensorboard(epoch, tb, img_idx, inp, out, lbl):
