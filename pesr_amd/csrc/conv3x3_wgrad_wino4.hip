@@ -32,8 +32,7 @@
 // pesr_conv3x3_wgrad_wino4_ws_bytes / _side_impl; the same function answers the host-only query pesr_conv3x3_wgrad_kernel, and
 // Python (ops.wgrad_kernel_for, ops._wg4_plan_ok) asks it instead of re-typing the plan.
 #include <mutex>
-#include "common.h"
-#include "launchers.h"
+#include "mfma_f32.h"
 
 struct Wg4Args {
     const float* x;    // [N][H][W][Cin]
@@ -57,7 +56,6 @@ constexpr int G4_VPLANE = G4_K4 * 128, G4_VROW = 6 * G4_VPLANE;       // floats:
 constexpr int G4_DPLANE = G4_K4 * 256, G4_DROW = 6 * G4_DPLANE;       // floats: dM row     [6 xi][3 blocks][4 x-tiles x 64 co]
 constexpr int G4_RING = 6;
 // the two 32x32x2 kernels (below): LDS planes are plain [x-tile][channel] arrays
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 constexpr int X4_VPLANE = G4_TXT * 32, X4_VROW = 6 * X4_VPLANE;       // floats: V row slot [6 xi][12 x-tiles][32 ci]
 constexpr int X4_DPLANE = G4_TXT * 64, X4_DROW = 6 * X4_DPLANE;       // floats: dM row     [6 xi][12 x-tiles][64 co]
 constexpr int X4_RING = 8;                                            // V row slots: four in use, four for the segment behind (a strip start needs all four)
@@ -216,7 +214,7 @@ __device__ __forceinline__ void wg4_epilogue(const Wg4Args& a, const Wg4Block& b
         for (int ky = 0; ky < 3; ++ky)
 #pragma unroll
             for (int j = 0; j < 16; ++j) {
-                const int rw = (j >> 2) * 8 + ks * 4 + (j & 3);          // D layout of the 32x32 tile: row = co, col = lane & 31 = ci
+                const int rw = mfma32_row(j, lane);                      // row = co, col = lane & 31 = ci
                 o[ky * 1024 + rw * 32] = acc[ky][j];
             }
     }

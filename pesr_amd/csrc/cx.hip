@@ -1,12 +1,12 @@
 // Contextual loss (docs/modes.md section 4r): CX of two NHWC feature maps, as P = H W points of C channels per image.  fp32 in, fp32
-// MFMA (v_mfma_f32_32x32x2_f32) for the two GEMMs, double for the sums that decide the value.  No atomics anywhere, every reduction in a
-// fixed order: the same call gives the same bits every time.  All offsets are 64-bit: D is [N][P][P].
+// MFMA for the two GEMMs (mfma_f32.h: its layout, the padded staging, the backward's tiles), double for the sums that decide the value.
+// No atomics anywhere, every reduction in a fixed order: the same call gives the same bits every time.  All offsets are 64-bit: D is [N][P][P].
 //
 //   normalise   mu[n][c] = the mean of the hr points (double sum: rows s, s + 16, ... per wave s, the 16 waves in order; one rounding),
 //               xb = x - mu, r = (float)(1 / sqrt(sum_c xb^2 + 1e-12)) with the sum in double (wave_sum_d's tree), xh = xb r; one wave
 //               per point.  r of the sr points is kept for the backward.
-//   distance    one workgroup of 4 waves per 64 rows i of one image.  Its xh rows stay in LDS ([64][C + 1]: the MFMA operand has the
-//               point on the lane, 32 lanes with an odd stride hit 32 banks), yh is staged in pieces of 64 columns (the next
+//   distance    one workgroup of 4 waves per 64 rows i of one image.  Its xh rows stay in LDS ([64][C + 1], the padded staging: the MFMA
+//               operand has the point on the lane), yh is staged in pieces of 64 columns the same way (the next
 //               piece's global loads are issued before this piece's MFMAs); wave w owns the 32 x 32 tile (w & 1, w >> 1) of the piece,
 //               C / 2 MFMAs.  D = fma(-0.5, s, 0.5) (one rounding) is stored, and every lane keeps the least value and its column of
 //               its 16 rows as it goes (strict <, columns ascending: the lowest column wins among equals); at the end 32 lanes and
@@ -21,10 +21,7 @@
 //               E_ik = q (-c_ik ([a(k) = i] - T_i) / (h (m_i + eps)) + [k = b(i)] U_i), q = -gL / (P CX); the other operand is yh with
 //               the channel on the lane, read coalesced from global (L2).  g_xh = -E yh / 2 goes through LDS once for the per-point
 //               projection (g_xh - xh (xh . g_xh)) r.  Not masked by x > 0: the tap's own conv does that.
-#include "common.h"
-#include "launchers.h"
-
-typedef float cx_f32x16 __attribute__((ext_vector_type(16)));
+#include "mfma_f32.h"
 
 constexpr int CX_THREADS = 256;
 constexpr int CX_MEAN_THREADS = 1024;
@@ -100,26 +97,14 @@ __global__ __launch_bounds__(CX_THREADS) void cx_dist_kernel(const float* __rest
     const float* yn = yh + img * C;
     float* Dn = D + img * P;
 
-    // staged a float4 per lane (the odd row stride makes the LDS writes scalar, four lanes to a bank; one float per lane - coalesced
-    // loads, conflict-free writes - measured slower: 1057 us against 768 at the training shape)
+    // rows r0 .. r0 + 63 of an image's points, zeros past P
+    const auto rows = [=](const float* pts, int r0) {
+        return [=](int r, const float*& src) { return src = pts + (long)(r0 + r) * C, r0 + r < P; };
+    };
     f32x4 v[LOADS];
-#pragma unroll
-    for (int it = 0; it < LOADS; ++it) {
-        const int e = (it * CX_THREADS + tid) * 4, r = i0 + e / C;
-        v[it] = r < P ? *(const f32x4*)(xn + (long)r * C + e % C) : f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-    }
-#pragma unroll
-    for (int it = 0; it < LOADS; ++it) {
-        const int e = (it * CX_THREADS + tid) * 4;
-        float* d = xs + (e / C) * LD + e % C;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) d[i] = v[it][i];
-    }
-#pragma unroll
-    for (int it = 0; it < LOADS; ++it) {
-        const int e = (it * CX_THREADS + tid) * 4, r = e / C;
-        v[it] = r < P ? *(const f32x4*)(yn + (long)r * C + e % C) : f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-    }
+    mfma32_stage_load<C, CX_THREADS>(v, tid, rows(xn, i0));
+    mfma32_stage_store<C, CX_THREADS>(xs, v, tid);
+    mfma32_stage_load<C, CX_THREADS>(v, tid, rows(yn, 0));
 
     float best[16];
     int bidx[16];
@@ -129,31 +114,18 @@ __global__ __launch_bounds__(CX_THREADS) void cx_dist_kernel(const float* __rest
     const float* bb = ys + (ch * 32 + (lane & 31)) * LD + (lane >> 5);
 
     for (int j0 = 0; j0 < P; j0 += CX_COLS) {
-#pragma unroll
-        for (int it = 0; it < LOADS; ++it) {
-            const int e = (it * CX_THREADS + tid) * 4;
-            float* d = ys + (e / C) * LD + e % C;
-#pragma unroll
-            for (int i = 0; i < 4; ++i) d[i] = v[it][i];
-        }
+        mfma32_stage_store<C, CX_THREADS>(ys, v, tid);
         __syncthreads();
-        if (j0 + CX_COLS < P) {
-#pragma unroll
-            for (int it = 0; it < LOADS; ++it) {
-                const int e = (it * CX_THREADS + tid) * 4, r = j0 + CX_COLS + e / C;
-                v[it] = r < P ? *(const f32x4*)(yn + (long)r * C + e % C) : f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-            }
-        }
-        cx_f32x16 acc;
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[r] = 0.0f;
+        if (j0 + CX_COLS < P) mfma32_stage_load<C, CX_THREADS>(v, tid, rows(yn, j0 + CX_COLS));
+        f32x16 acc;
+        mfma32_zero(acc);
 #pragma unroll 8
         for (int kk = 0; kk < C; kk += 2) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[kk], bb[kk], acc, 0, 0, 0);
         const int j = j0 + ch * 32 + (lane & 31);
         if (j < P) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int i = i0 + rh * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+                const int i = mfma32_row(r, lane, i0 + rh * 32);
                 const float d = fmaf(-0.5f, acc[r], 0.5f);
                 if (i < P) {
                     Dn[(long)i * P + j] = d;
@@ -174,7 +146,7 @@ __global__ __launch_bounds__(CX_THREADS) void cx_dist_kernel(const float* __rest
             if (ov < best[r] || (ov == best[r] && oi < bidx[r])) best[r] = ov, bidx[r] = oi;
         }
         if ((lane & 31) == 0) {
-            const int rr = rh * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+            const int rr = mfma32_row(r, lane, rh * 32);
             cand_v[ch][rr] = best[r];
             cand_i[ch][rr] = bidx[r];
         }
@@ -291,9 +263,8 @@ __global__ __launch_bounds__(CX_THREADS) void cx_bwd_kernel(const float* __restr
                                                             const float* __restrict__ yh, const float* __restrict__ inv,
                                                             const float* __restrict__ rows, float* __restrict__ gf,
                                                             float* __restrict__ e_out, float* __restrict__ gxh_out, int P, float hinv) {
-    constexpr int PIX = C == 256 ? 32 : 64, LE = CX_COLS + 1, LG = C + 1;
-    constexpr int NPH = PIX / 32, TILES = (C / 32) * NPH, TPW = TILES / 4, V = C / 64;
-    static_assert(TILES % 4 == 0, "every wave owns the same number of tiles");
+    using Tl = Mfma32Bwd<C>;
+    constexpr int PIX = Tl::PIX, LE = CX_COLS + 1, LG = C + 1, V = C / 64;
     __shared__ float es[PIX * LE];
     __shared__ float gs[PIX * LG];
     __shared__ float p_k[PIX], p_sinv[PIX], p_T[PIX], p_U[PIX];
@@ -322,12 +293,9 @@ __global__ __launch_bounds__(CX_THREADS) void cx_bwd_kernel(const float* __restr
     }
     __syncthreads();
 
-    const int half = wave % NPH;
-    cx_f32x16 acc[TPW];
-#pragma unroll
-    for (int u = 0; u < TPW; ++u)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[u][r] = 0.0f;
+    const int half = Tl::half(wave);
+    f32x16 acc[Tl::TPW];
+    mfma32_zero(acc);
     const float* ap = es + (half * 32 + (lane & 31)) * LE + (lane >> 5);
     const float* yn = yh + img * C + (lane & 31);
 
@@ -352,17 +320,17 @@ __global__ __launch_bounds__(CX_THREADS) void cx_bwd_kernel(const float* __restr
             const int jj = min(j0 + kk + (lane >> 5), P - 1);          // (past P the other operand is 0)
             const float* bp = yn + (long)jj * C;
 #pragma unroll
-            for (int u = 0; u < TPW; ++u)
-                acc[u] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bp[((wave + 4 * u) / NPH) * 32], acc[u], 0, 0, 0);
+            for (int u = 0; u < Tl::TPW; ++u)
+                acc[u] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, bp[Tl::band(wave, u) * 32], acc[u], 0, 0, 0);
         }
         __syncthreads();
     }
 
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-        const int rr = half * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+        const int rr = half * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);      // mfma32_row, written out: see mfma_f32.h
 #pragma unroll
-        for (int u = 0; u < TPW; ++u) gs[rr * LG + ((wave + 4 * u) / NPH) * 32 + (lane & 31)] = -0.5f * acc[u][r];
+        for (int u = 0; u < Tl::TPW; ++u) gs[rr * LG + Tl::band(wave, u) * 32 + (lane & 31)] = -0.5f * acc[u][r];
     }
     __syncthreads();
     for (int rr = wave; rr < nrows; rr += 4) {
@@ -386,7 +354,7 @@ __global__ __launch_bounds__(CX_THREADS) void cx_bwd_kernel(const float* __restr
 
 // ---- host ----------------------------------------------------------------------------------------------------------------------------
 static bool cx_shape_ok(int N, int P, int C) {
-    return N >= 1 && N <= 65535 && P >= 1 && P <= CX_MAX_P && (C == 64 || C == 128 || C == 256);
+    return N >= 1 && N <= 65535 && P >= 1 && P <= CX_MAX_P && mfma32_c_ok(C);
 }
 
 int pesr_cx_row_blocks_host(int N, int P, int C) { return cx_shape_ok(N, P, C) ? (P + CX_ROWS - 1) / CX_ROWS : 0; }
@@ -412,11 +380,9 @@ int pesr_cx_normalize_launch(const float* fa, const float* fb, float* mu, float*
     const long NP = (long)N * P;
     hipLaunchKernelGGL(cx_mean_kernel, dim3(C / 64, N), dim3(CX_MEAN_THREADS), 0, stream, fb, mu, P, C);
     const dim3 grid((unsigned)((2 * NP + 3) / 4)), block(CX_THREADS);
-    switch (C) {
-    case 64: hipLaunchKernelGGL(cx_normalize_kernel<64>, grid, block, 0, stream, fa, fb, (const float*)mu, xh, yh, inv, P, NP); break;
-    case 128: hipLaunchKernelGGL(cx_normalize_kernel<128>, grid, block, 0, stream, fa, fb, (const float*)mu, xh, yh, inv, P, NP); break;
-    default: hipLaunchKernelGGL(cx_normalize_kernel<256>, grid, block, 0, stream, fa, fb, (const float*)mu, xh, yh, inv, P, NP); break;
-    }
+    mfma32_dispatch_c(C, [&](auto c) {
+        hipLaunchKernelGGL(cx_normalize_kernel<c()>, grid, block, 0, stream, fa, fb, (const float*)mu, xh, yh, inv, P, NP);
+    });
     return pesr_launch_status();
 }
 
@@ -427,20 +393,17 @@ int pesr_cx_dist_launch(const float* xh, const float* yh, float* D, float* m, in
     static PesrDeviceOnce once;
     hipError_t attr = hipSuccess;
     once([&] {
-        attr = hipFuncSetAttribute((const void*)cx_dist_kernel<64>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * CX_ROWS * 65 * 4);
-        if (attr == hipSuccess)
-            attr = hipFuncSetAttribute((const void*)cx_dist_kernel<128>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * CX_ROWS * 129 * 4);
-        if (attr == hipSuccess)
-            attr = hipFuncSetAttribute((const void*)cx_dist_kernel<256>, hipFuncAttributeMaxDynamicSharedMemorySize, 2 * CX_ROWS * 257 * 4);
+        for (int ci : {64, 128, 256})
+            mfma32_dispatch_c(ci, [&](auto c) {
+                if (attr == hipSuccess)
+                    attr = hipFuncSetAttribute((const void*)cx_dist_kernel<c()>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                               2 * CX_ROWS * (c() + 1) * 4);
+            });
     });
     if (attr != hipSuccess) return (int)attr;
     const dim3 grid((P + CX_ROWS - 1) / CX_ROWS, N), block(CX_THREADS);
     const size_t lds = (size_t)2 * CX_ROWS * (C + 1) * sizeof(float);
-    switch (C) {
-    case 64: hipLaunchKernelGGL(cx_dist_kernel<64>, grid, block, lds, stream, xh, yh, D, m, b, P); break;
-    case 128: hipLaunchKernelGGL(cx_dist_kernel<128>, grid, block, lds, stream, xh, yh, D, m, b, P); break;
-    default: hipLaunchKernelGGL(cx_dist_kernel<256>, grid, block, lds, stream, xh, yh, D, m, b, P); break;
-    }
+    mfma32_dispatch_c(C, [&](auto c) { hipLaunchKernelGGL(cx_dist_kernel<c()>, grid, block, lds, stream, xh, yh, D, m, b, P); });
     return pesr_launch_status();
 }
 
@@ -471,12 +434,10 @@ int pesr_cx_bwd_launch(const float* D, const float* m, const int* b, const float
     float* rows = (float*)ws;                                          // [N][P][2] <= the forward's workspace
     const float hinv = (float)(1.0 / h);
     hipLaunchKernelGGL(cx_bwd_rows_kernel, dim3((P + 3) / 4, N), dim3(CX_THREADS), 0, stream, D, m, S, a, M, rows, P, hinv);
-    const int pix = C == 256 ? 32 : 64;
-    const dim3 grid((P + pix - 1) / pix, N), block(CX_THREADS);
-    switch (C) {
-    case 64: hipLaunchKernelGGL(cx_bwd_kernel<64>, grid, block, 0, stream, D, m, b, S, a, CX, gL, xh, yh, inv, (const float*)rows, gf, e_out, gxh_out, P, hinv); break;
-    case 128: hipLaunchKernelGGL(cx_bwd_kernel<128>, grid, block, 0, stream, D, m, b, S, a, CX, gL, xh, yh, inv, (const float*)rows, gf, e_out, gxh_out, P, hinv); break;
-    default: hipLaunchKernelGGL(cx_bwd_kernel<256>, grid, block, 0, stream, D, m, b, S, a, CX, gL, xh, yh, inv, (const float*)rows, gf, e_out, gxh_out, P, hinv); break;
-    }
+    mfma32_dispatch_c(C, [&](auto c) {
+        constexpr int pix = Mfma32Bwd<c()>::PIX;
+        hipLaunchKernelGGL(cx_bwd_kernel<c()>, dim3((P + pix - 1) / pix, N), dim3(CX_THREADS), 0, stream, D, m, b, S, a, CX, gL, xh, yh, inv,
+                           (const float*)rows, gf, e_out, gxh_out, P, hinv);
+    });
     return pesr_launch_status();
 }

@@ -1,6 +1,6 @@
 // Texture loss (docs/modes.md section 4q): patch-wise Gram matrices of NHWC feature maps, the squared distance of two of them, and
-// the gradient with respect to the features.  fp32 in, fp32 MFMA (v_mfma_f32_32x32x2_f32: bit for bit a k-ordered fmaf chain), fp32
-// out; the distance in double.  No atomics anywhere: the same call gives the same bits every time.
+// the gradient with respect to the features.  fp32 in, fp32 MFMA (mfma_f32.h: its layout, the padded staging, the backward's tiles),
+// fp32 out; the distance in double.  No atomics anywhere: the same call gives the same bits every time.
 //
 // F [N][H][W][C], patches of ph x pw pixels (ph | H, pw | W), P = (H / ph) (W / pw) of them per image, K = ph pw pixels each; pixel k
 // of a patch is row k / pw, column k % pw of it.  s = 1 / (C K).
@@ -21,13 +21,10 @@
 // workgroup (block_sum_d); reduce.hip's mean_partials_kernel adds an image's partials in its fixed order and divides by P.
 //
 // Backward, gF[k][c] = (float)(g[n] 4 s / P) * sum_c' F[k][c'] dG[c'][c]: one workgroup per (image, patch, run of 64 pixels; 32 at
-// C = 256).  The operand indexed [pixel][c'] has its pixel on the lane, which memory does not give contiguously: the run's rows are
-// staged in LDS with a row stride of C + 1 floats (32 lanes, 32 banks).  The other operand is dG[c'][c] with c on the lane, read
-// coalesced from global (L2: a patch's dG is read by all its pixel runs).  Not masked by F > 0: the tap's own conv does that.
-#include "common.h"
-#include "launchers.h"
-
-typedef float gram_f32x16 __attribute__((ext_vector_type(16)));
+// C = 256: Mfma32Bwd).  The operand indexed [pixel][c'] has its pixel on the lane, which memory does not give contiguously: the run's
+// rows go through the padded staging of mfma_f32.h.  The other operand is dG[c'][c] with c on the lane, read coalesced from global
+// (L2: a patch's dG is read by all its pixel runs).  Not masked by F > 0: the tap's own conv does that.
+#include "mfma_f32.h"
 
 constexpr int GR_THREADS = 256;
 constexpr int GR_CHUNK = 8192;            // floats of one staged piece of the forward: 32 KB
@@ -60,13 +57,12 @@ __global__ __launch_bounds__(GR_THREADS) void gram_fwd_kernel(const float* __res
     const float* base = F + (((long)n * H + (long)py * ph) * W + (long)px * pw) * C;
 
     int ti[TPW], tj[TPW];
-    gram_f32x16 acc[TPW];
+    f32x16 acc[TPW];
+    mfma32_zero(acc);
 #pragma unroll
     for (int u = 0; u < TPW; ++u) {
         ti[u] = tj[u] = 0;
         if (wave + 4 * u < U) gram_tile(blockIdx.y * U + wave + 4 * u, T, ti[u], tj[u]);
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[u][r] = 0.0f;
     }
 
     for (int kc = k0; kc < k1; kc += KC) {
@@ -101,7 +97,7 @@ __global__ __launch_bounds__(GR_THREADS) void gram_fwd_kernel(const float* __res
         if (wave + 4 * u < U) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int gr = ti[u] * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5), gc = tj[u] * 32 + (lane & 31);
+                const int gr = mfma32_row(r, lane, ti[u] * 32), gc = tj[u] * 32 + (lane & 31);
                 const float val = acc[u][r] * scale;
                 if (gr <= gc) {
                     o[gr * C + gc] = val;
@@ -150,9 +146,8 @@ template <int C>
 __global__ __launch_bounds__(GR_THREADS) void gram_bwd_kernel(const float* __restrict__ F, const float* __restrict__ dG,
                                                               const double* __restrict__ g, float* __restrict__ gF, int H, int W, int ph,
                                                               int pw, int npx, int P, int K, int runs, double coef) {
-    constexpr int PIX = C == 256 ? 32 : 64, LD = C + 1;
-    constexpr int NPH = PIX / 32, TILES = (C / 32) * NPH, TPW = TILES / 4;
-    static_assert(TILES % 4 == 0, "every wave owns the same number of tiles");
+    using Tl = Mfma32Bwd<C>;
+    constexpr int PIX = Tl::PIX, LD = C + 1;
     __shared__ float lds[PIX * LD];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int run = (int)(blockIdx.x % (unsigned)runs);
@@ -162,53 +157,36 @@ __global__ __launch_bounds__(GR_THREADS) void gram_bwd_kernel(const float* __res
     const int k0 = run * PIX;
     const long origin = (((long)n * H + (long)py * ph) * W + (long)px * pw) * C;
 
-    constexpr int LOADS = PIX * C / (GR_THREADS * 4);
-    f32x4 v[LOADS];
-#pragma unroll
-    for (int it = 0; it < LOADS; ++it) {
-        const int e = (it * GR_THREADS + tid) * 4;
-        const int k = k0 + e / C, c = e % C;
-        v[it] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-        if (k < K) {
-            const int r = k / pw, q = k - r * pw;
-            v[it] = *(const f32x4*)(F + origin + ((long)r * W + q) * C + c);
-        }
-    }
-#pragma unroll
-    for (int it = 0; it < LOADS; ++it) {
-        const int e = (it * GR_THREADS + tid) * 4;
-        float* d = lds + (e / C) * LD + e % C;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) d[i] = v[it][i];
-    }
+    f32x4 v[PIX * C / (GR_THREADS * 4)];
+    mfma32_stage_load<C, GR_THREADS>(v, tid, [&](int row, const float*& src) {
+        const int k = k0 + row, r = k / pw, q = k - r * pw;
+        return src = F + origin + ((long)r * W + q) * C, k < K;
+    });
+    mfma32_stage_store<C, GR_THREADS>(lds, v, tid);
     __syncthreads();
 
-    // tile t = wave + 4 u: pixel half t % NPH (the same for all of a wave's tiles: 4 % NPH == 0), channel band t / NPH
-    const int half = wave % NPH;
-    gram_f32x16 acc[TPW];
-#pragma unroll
-    for (int u = 0; u < TPW; ++u)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[u][r] = 0.0f;
+    const int half = Tl::half(wave);
+    f32x16 acc[Tl::TPW];
+    mfma32_zero(acc);
     const float* a = lds + (half * 32 + (lane & 31)) * LD + (lane >> 5);
     const float* b = dG + np * ((long)C * C) + (long)(lane >> 5) * C + (lane & 31);
 #pragma unroll 8
     for (int kk = 0; kk < C; kk += 2) {
         const float av = a[kk];
 #pragma unroll
-        for (int u = 0; u < TPW; ++u)
-            acc[u] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, b[(long)kk * C + ((wave + 4 * u) / NPH) * 32], acc[u], 0, 0, 0);
+        for (int u = 0; u < Tl::TPW; ++u)
+            acc[u] = __builtin_amdgcn_mfma_f32_32x32x2f32(av, b[(long)kk * C + Tl::band(wave, u) * 32], acc[u], 0, 0, 0);
     }
 
     const float cf = (float)(g[n] * coef);
 #pragma unroll
     for (int r = 0; r < 16; ++r) {
-        const int k = k0 + half * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+        const int k = mfma32_row(r, lane, k0 + half * 32);
         if (k < K) {
             const int rr = k / pw, q = k - rr * pw;
             float* o = gF + origin + ((long)rr * W + q) * C + (lane & 31);
 #pragma unroll
-            for (int u = 0; u < TPW; ++u) o[((wave + 4 * u) / NPH) * 32] = acc[u][r] * cf;
+            for (int u = 0; u < Tl::TPW; ++u) o[Tl::band(wave, u) * 32] = acc[u][r] * cf;
         }
     }
 }
@@ -222,7 +200,7 @@ struct GramPlan {
 // the shape checks all entry points share; fills the plan
 static int gram_plan(int N, int H, int W, int C, int ph, int pw, GramPlan* pl) {
     if (N < 1 || H < 1 || W < 1 || ph < 1 || pw < 1 || ph > H || pw > W || H % ph || W % pw) return PESR_EINVAL;
-    if (C != 64 && C != 128 && C != 256) return PESR_EINVAL;
+    if (!mfma32_c_ok(C)) return PESR_EINVAL;
     const long hw = (long)H * W;
     if (hw > (1L << 30)) return PESR_EINVAL;
     pl->npx = W / pw;
@@ -260,12 +238,12 @@ int pesr_gram_fwd_launch(const float* f, float* G, int N, int H, int W, int C, i
     const float s = (float)(1.0 / ((double)C * pl.K));
     float* out = pl.S > 1 ? (float*)ws : G;
     const float scale = pl.S > 1 ? 1.0f : s;
-    const dim3 grid((unsigned)(pl.NP * pl.S)), grid3((unsigned)(pl.NP * pl.S), 3), block(GR_THREADS);
-    switch (C) {
-    case 64: hipLaunchKernelGGL((gram_fwd_kernel<64, 1>), grid, block, 0, stream, f, out, H, W, ph, pw, pl.npx, pl.P, pl.K, pl.Ks, pl.S, pl.NP, scale); break;
-    case 128: hipLaunchKernelGGL((gram_fwd_kernel<128, 1>), grid, block, 0, stream, f, out, H, W, ph, pw, pl.npx, pl.P, pl.K, pl.Ks, pl.S, pl.NP, scale); break;
-    default: hipLaunchKernelGGL((gram_fwd_kernel<256, 3>), grid3, block, 0, stream, f, out, H, W, ph, pw, pl.npx, pl.P, pl.K, pl.Ks, pl.S, pl.NP, scale); break;
-    }
+    const dim3 block(GR_THREADS);
+    mfma32_dispatch_c(C, [&](auto c) {
+        constexpr int TG = c() == 256 ? 3 : 1;                         // (gram_fwd_kernel's comment)
+        hipLaunchKernelGGL((gram_fwd_kernel<c(), TG>), dim3((unsigned)(pl.NP * pl.S), TG), block, 0, stream, f, out, H, W, ph, pw, pl.npx,
+                           pl.P, pl.K, pl.Ks, pl.S, pl.NP, scale);
+    });
     if (pl.S > 1)
         hipLaunchKernelGGL(gram_finish_kernel, dim3((unsigned)((total / 4 + GR_THREADS - 1) / GR_THREADS)), block, 0, stream,
                            (const float*)ws, G, total, pl.S, s);
@@ -279,13 +257,13 @@ static int gram_loss_blocks(long per) {
 }
 
 size_t pesr_gram_loss_workspace_bytes_host(int N, int P, int C) {
-    if (N < 1 || P < 1 || (C != 64 && C != 128 && C != 256)) return 0;
+    if (N < 1 || P < 1 || !mfma32_c_ok(C)) return 0;
     return sizeof(double) * (size_t)N * gram_loss_blocks((long)P * C * C);
 }
 
 int pesr_gram_loss_launch(const float* ga, const float* gb, double* t, float* dg, int N, int P, int C, void* ws, size_t ws_bytes,
                           hipStream_t stream) {
-    if (!ga || !gb || !t || N < 1 || N > 65535 || P < 1 || (C != 64 && C != 128 && C != 256)) return PESR_EINVAL;
+    if (!ga || !gb || !t || N < 1 || N > 65535 || P < 1 || !mfma32_c_ok(C)) return PESR_EINVAL;
     if ((long)P * C * C > (1L << 40)) return PESR_EINVAL;
     if ((((uintptr_t)ga | (uintptr_t)gb | (uintptr_t)dg) & 15) || (((uintptr_t)t | (uintptr_t)ws) & 7)) return PESR_EINVAL;
     const long per = (long)P * C * C;
@@ -300,14 +278,12 @@ int pesr_gram_bwd_launch(const float* f, const float* dg, const double* g, float
     GramPlan pl;
     if (!f || !dg || !g || !gf || gram_plan(N, H, W, C, ph, pw, &pl) != PESR_OK) return PESR_EINVAL;
     if ((((uintptr_t)f | (uintptr_t)dg | (uintptr_t)gf) & 15) || ((uintptr_t)g & 7)) return PESR_EINVAL;
-    const int pix = C == 256 ? 32 : 64;
-    const int runs = (pl.K + pix - 1) / pix;
     const double coef = 4.0 * (1.0 / ((double)C * pl.K)) / pl.P;
-    const dim3 grid((unsigned)(pl.NP * runs)), block(GR_THREADS);
-    switch (C) {
-    case 64: hipLaunchKernelGGL(gram_bwd_kernel<64>, grid, block, 0, stream, f, dg, g, gf, H, W, ph, pw, pl.npx, pl.P, pl.K, runs, coef); break;
-    case 128: hipLaunchKernelGGL(gram_bwd_kernel<128>, grid, block, 0, stream, f, dg, g, gf, H, W, ph, pw, pl.npx, pl.P, pl.K, runs, coef); break;
-    default: hipLaunchKernelGGL(gram_bwd_kernel<256>, grid, block, 0, stream, f, dg, g, gf, H, W, ph, pw, pl.npx, pl.P, pl.K, runs, coef); break;
-    }
+    mfma32_dispatch_c(C, [&](auto c) {
+        constexpr int pix = Mfma32Bwd<c()>::PIX;
+        const int runs = (pl.K + pix - 1) / pix;
+        hipLaunchKernelGGL(gram_bwd_kernel<c()>, dim3((unsigned)(pl.NP * runs)), dim3(GR_THREADS), 0, stream, f, dg, g, gf, H, W, ph, pw,
+                           pl.npx, pl.P, pl.K, runs, coef);
+    });
     return pesr_launch_status();
 }

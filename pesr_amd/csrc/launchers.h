@@ -2,6 +2,14 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>
+#include <type_traits>
+
+// Kernels templated on the channel count: calls f(std::integral_constant<int, c>) for the listed c equal to C, as in
+// pesr_dispatch_c<64, 128, 256>(C, [&](auto c) { hipLaunchKernelGGL(kernel<c()>, ...); }).  false: C is not in the list, f was not called.
+template <int... Cs, class F>
+static inline bool pesr_dispatch_c(int C, F&& f) {
+    return ((C == Cs && (f(std::integral_constant<int, Cs>{}), true)) || ...);
+}
 
 int pesr_pack_conv3x3_launch(const float* w, float* out, int O, int I, int mode, int ps, hipStream_t stream);
 int pesr_pack_conv3x3_batched_launch(const long long* desc, int count, hipStream_t stream);

@@ -252,8 +252,12 @@ __global__ __launch_bounds__(LPIPS_THREADS) void lpips_layer_bwd_kernel(const fl
     }
 }
 
+// the channel counts of the five taps
+template <class F>
+static bool lpips_dispatch_c(int C, F&& f) { return pesr_dispatch_c<64, 128, 256, 512>(C, f); }
+
 static bool lpips_shape_ok(int N, int H, int W, int C) {
-    return N >= 1 && N <= 65535 && H >= 1 && W >= 1 && (C == 64 || C == 128 || C == 256 || C == 512);
+    return N >= 1 && N <= 65535 && H >= 1 && W >= 1 && lpips_dispatch_c(C, [](auto) {});
 }
 
 int pesr_lpips_layer2_launch(const float* fa, const float* fb, const float* w, double* out, int N, int H, int W, int C, double* map,
@@ -268,12 +272,7 @@ int pesr_lpips_layer2_launch(const float* fa, const float* fb, const float* w, d
     if (!ws || ws_bytes < (size_t)N * (size_t)groups * sizeof(double)) return PESR_EWORKSPACE;
     const dim3 grid((unsigned)groups, (unsigned)N), block(LPIPS_THREADS);
     double* part = (double*)ws;
-    switch (C) {
-    case 64: hipLaunchKernelGGL(lpips_layer_kernel<64>, grid, block, 0, stream, fa, fb, w, part, map, HW); break;
-    case 128: hipLaunchKernelGGL(lpips_layer_kernel<128>, grid, block, 0, stream, fa, fb, w, part, map, HW); break;
-    case 256: hipLaunchKernelGGL(lpips_layer_kernel<256>, grid, block, 0, stream, fa, fb, w, part, map, HW); break;
-    default: hipLaunchKernelGGL(lpips_layer_kernel<512>, grid, block, 0, stream, fa, fb, w, part, map, HW); break;
-    }
+    lpips_dispatch_c(C, [&](auto c) { hipLaunchKernelGGL(lpips_layer_kernel<c()>, grid, block, 0, stream, fa, fb, w, part, map, HW); });
     return pesr_mean_partials_launch(part, out, N, groups, (double)HW, stream);
 }
 
@@ -293,11 +292,6 @@ int pesr_lpips_layer_bwd_launch(const float* fa, const float* fb, const float* w
     const long groups = (HW + LPIPS_WG_PIX - 1) / LPIPS_WG_PIX;
     if (groups > 2147483647L) return PESR_EINVAL;
     const dim3 grid((unsigned)groups, (unsigned)N), block(LPIPS_THREADS);
-    switch (C) {
-    case 64: hipLaunchKernelGGL(lpips_layer_bwd_kernel<64>, grid, block, 0, stream, fa, fb, w, g, ga, HW); break;
-    case 128: hipLaunchKernelGGL(lpips_layer_bwd_kernel<128>, grid, block, 0, stream, fa, fb, w, g, ga, HW); break;
-    case 256: hipLaunchKernelGGL(lpips_layer_bwd_kernel<256>, grid, block, 0, stream, fa, fb, w, g, ga, HW); break;
-    default: hipLaunchKernelGGL(lpips_layer_bwd_kernel<512>, grid, block, 0, stream, fa, fb, w, g, ga, HW); break;
-    }
+    lpips_dispatch_c(C, [&](auto c) { hipLaunchKernelGGL(lpips_layer_bwd_kernel<c()>, grid, block, 0, stream, fa, fb, w, g, ga, HW); });
     return pesr_launch_status();
 }

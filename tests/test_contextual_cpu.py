@@ -14,7 +14,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 N = 2
 # (C, H, W, regime, seed) of tests/test_contextual_gpu.py; its last case is found by asking ops.cx_plan and is (64, 5, 13): P = 65
 GPU_CASES = [(64, 4, 4, "matched", 100), (64, 5, 7, "unmatched", 110), (128, 8, 8, "matched", 120), (256, 8, 9, "unmatched", 130),
-             (256, 16, 16, "unmatched", 141), (64, 5, 13, "matched", 151)]
+             (256, 16, 16, "unmatched", 141), (128, 5, 7, "unmatched", 166), (64, 5, 13, "matched", 151)]
 
 
 def _load(name):

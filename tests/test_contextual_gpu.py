@@ -20,10 +20,11 @@ H_BAND = 0.5
 G_UP = np.array([0.75, -1.5])
 
 # (C, H, W, regime, seed): P = 16 under one tile; P = 35 odd tails in both GEMM dimensions; exactly one row block; a block and a tail
-# (the cross-block column maximum); several blocks with many-to-one arg maxima; and, appended, the smallest P with two staged column
-# pieces.  The seeds are those whose inputs tests/test_contextual_cpu.py checks.
+# (the cross-block column maximum); several blocks with many-to-one arg maxima; P = 35 again at C = 128 (the tails of that channel
+# count's staging and backward tiles); and, appended, the smallest P with two staged column pieces.  The seeds are those whose inputs
+# tests/test_contextual_cpu.py checks.
 CASES = [(64, 4, 4, "matched", 100), (64, 5, 7, "unmatched", 110), (128, 8, 8, "matched", 120), (256, 8, 9, "unmatched", 130),
-         (256, 16, 16, "unmatched", 141)]
+         (256, 16, 16, "unmatched", 141), (128, 5, 7, "unmatched", 166)]
 LAST = (64, 5, 13, "matched", 151)
 NCASES = len(CASES) + 1
 _SHARED = {}
@@ -73,9 +74,9 @@ def test_the_cases_cover_the_paths():
     assert len(cases) == NCASES
     plans = [_case(i)["plan"] for i in range(NCASES)]
     print("plans:", plans)
-    assert [_case(i)["P"] for i in range(NCASES)] == [16, 35, 64, 72, 256, 65]
-    assert [p["row_blocks"] for p in plans] == [1, 1, 1, 2, 4, 2]     # under a tile, odd, exactly one block, a block and a tail, several
-    assert [p["col_pieces"] for p in plans] == [1, 1, 1, 2, 4, 2]
+    assert [_case(i)["P"] for i in range(NCASES)] == [16, 35, 64, 72, 256, 35, 65]
+    assert [p["row_blocks"] for p in plans] == [1, 1, 1, 2, 4, 1, 2]  # under a tile, odd, exactly one block, a block and a tail, several
+    assert [p["col_pieces"] for p in plans] == [1, 1, 1, 2, 4, 1, 2]
     assert sorted({c[0] for c in cases}) == [64, 128, 256]
     for i, (c, h, w, regime, _) in enumerate(cases):                  # many-to-one arg maxima where the inputs are unmatched
         a = _case(i)["ref"]["a"]
@@ -147,10 +148,10 @@ def test_second_gemm_against_float64_within_the_derived_bound(i):
 
 
 # ---- end to end: the exp chain cannot be bounded tightly, so it is measured ----------------------------------------------------------------
-# Against the float64 oracle on the same fp32 features, on these six cases on the MI355X (docs/modes.md section 4r has every case):
-# the worst |CX - CX64| / CX64 and the worst gradient error relative to the largest gradient entry.  Four times the measured value is
-# allowed, the convention of tests/test_texture_gpu.py, to leave room for other seeds.
-CX_MEASURED, GRAD_MEASURED = 1.052e-7, 3.121e-6
+# Against the float64 oracle on the same fp32 features, on these seven cases on the MI355X (docs/modes.md section 4r has every case):
+# the worst |CX - CX64| / CX64 (128 x 5 x 7; the other six: 1.7e-8 .. 1.052e-7) and the worst gradient error relative to the largest
+# gradient entry.  Four times the measured value is allowed, the convention of tests/test_texture_gpu.py, to leave room for other seeds.
+CX_MEASURED, GRAD_MEASURED = 3.729e-7, 3.121e-6
 CX_ALLOWED, GRAD_ALLOWED = 4 * CX_MEASURED, 4 * GRAD_MEASURED
 
 

@@ -30,15 +30,18 @@ def _smallest_split_shape():
 
 
 # (C, H, W, patch): several patches; an odd K; one patch of one staged piece (C = 128: 64 pixels) ... and of four; C = 256 with two
-# patches of eight pieces; the smallest split shape (appended below) and a split one with an odd K and an uneven last slice
+# patches of eight pieces; the smallest split shape (appended below) and a split one with an odd K and an uneven last slice.  TAILS
+# (behind the split shape, so that every earlier case keeps its index and its seeds): K = 35 at C = 256 (a backward run of 32 and a
+# tail of 3; the forward's tile groups at an odd K) and at C = 128 (one backward run with a tail of 35)
 CASES = [(64, 8, 8, 4), (64, 5, 7, 0), (128, 16, 16, 16), (256, 16, 32, 16), (64, 23, 23, 0)]
+TAILS = [(256, 5, 7, 0), (128, 5, 7, 0)]
 _SHARED = {}
 
 
 def _cases():
     if "cases" not in _SHARED:
         h, w = _smallest_split_shape()
-        _SHARED["cases"] = CASES + [(64, h, w, 0)]
+        _SHARED["cases"] = CASES + [(64, h, w, 0)] + TAILS
     return _SHARED["cases"]
 
 
@@ -61,7 +64,7 @@ def _case(i):
     return _SHARED[key]
 
 
-NCASES = len(CASES) + 1
+NCASES = len(CASES) + 1 + len(TAILS)
 
 
 def test_the_cases_cover_the_paths():
@@ -73,6 +76,7 @@ def test_the_cases_cover_the_paths():
     assert plans[5]["splits"] > 1, plans[5]                           # the smallest shape the launcher splits
     print("smallest split shape with C = 64:", cases[5], plans[5])
     assert plans[1]["pixels"] == 35 and plans[0]["patches"] == 4 and plans[3]["patches"] == 2
+    assert [(c[0], p["pixels"], p["splits"]) for c, p in zip(cases[6:], plans[6:])] == [(256, 35, 1), (128, 35, 1)]
 
 
 # ---- the Gram matrices --------------------------------------------------------------------------------------------------------------------
@@ -147,8 +151,8 @@ def test_backward_against_float64_within_the_derived_bound(i):
 
 # ---- the autograd node end to end ------------------------------------------------------------------------------------------------------
 # Against the float64 oracle on the fp32 features.  These two cannot be derived tightly (dG cancels), so they are measured: on these
-# six cases on the MI355X the worst relative error of T was 5.03e-8 (64 x 23 x 23, whole map) and the worst error of the gradient
-# 6.51e-7 of the largest gradient entry (256 x 16 x 32, patch 16); the other cases: T 3.1e-9 .. 4.5e-8, gradient 2.5e-7 .. 4.4e-7
+# eight cases on the MI355X the worst relative error of T was 5.03e-8 (64 x 23 x 23, whole map) and the worst error of the gradient
+# 6.51e-7 of the largest gradient entry (256 x 16 x 32, patch 16); the other cases: T 3.1e-9 .. 4.5e-8, gradient 2.5e-7 .. 4.7e-7
 # (docs/modes.md section 4q).  Four times the measured value is allowed, to leave room for other seeds.
 T_MEASURED, GRAD_MEASURED = 5.03e-8, 6.51e-7
 T_ALLOWED, GRAD_ALLOWED = 4 * T_MEASURED, 4 * GRAD_MEASURED
