@@ -39,7 +39,8 @@
 //                     per wave at kernel entry, end of prologue, arrival at / release from every chunk barrier, arrival at and release
 //                     from the exchange barrier, last store issued, stores acknowledged, and s_memrealtime (100 MHz) at both ends for
 //                     the clock: kept in LDS behind the exchange slots, copied to g_w4_stamps with vector stores at the end; read back
-//                     by pesr_debug_w4_stamps()
+//                     by pesr_debug_w4_stamps().  TAIL form: slots 40 / 42 / 44 release from the exchange barrier of m-tile group 0 / 1 / 2,
+//                     41 / 43 / 45 that group's last store issued; its last chunk has no barrier of its own (both of its stamps: MFMAs done)
 //   W4_NO_XFORM       no staging transform and no LDS stores (the staged loads are still waited for)
 //   W4_NO_STLOAD      no staging loads
 //   W4_NO_BARRIER     no barrier per chunk
@@ -95,6 +96,30 @@ struct Wino4Args {
 
 constexpr int W4_BN = 64, W4_MG = 9;
 
+// output (m-tile i, k) of lane r of the xi-half wave xt -> (inside the image, element offset of its four channels co ..): the epilogue's
+// out_index, for the TAIL form.  (The epilogue keeps its lambda: routed through this function, hipcc allocates the registers of the sixteen
+// instantiations without TAIL differently, and they are held to the text they compiled to before - docs/experiments/wino4_tail.md.)
+__device__ __forceinline__ bool w4_out_index(const Wino4Args& a, const int TXTv, const int img, const size_t img_out, const int gy0, const int gt0,
+                                             const int xt, const int r, const int co, const int i, const int k, size_t* idx) {
+    const int m = i * 16 + r;
+    const int trow = m / TXTv, txt = m - trow * TXTv;
+    int oy = gy0 + trow;
+    const int ox = 4 * (gt0 + txt) + 2 * xt + k;
+    bool ok = oy < a.H && ox < a.W;
+    if (a.stack) {                                  // virtual row -> row of the [N * H] row space; separator rows are dropped
+        const int im = oy / a.stack, yy = oy - im * a.stack;
+        ok = im < a.stack_n && yy < a.H && ox < a.W;
+        oy = im * a.H + yy;
+    }
+    if (a.ps) {
+        *idx = pesr_ps_out_index(img, oy, ox, co, a.H, a.W, a.Cout);
+    } else {
+        *idx = (img_out + (size_t)oy * a.W + ox) * a.Cout + co;
+    }
+    if (!ok) *idx = 0;
+    return ok;
+}
+
 // Wave w owns the 16 channels w & 3 and HALF of the xi planes (w >> 2: xi 0..2 / 3..5): 27 accumulator tiles, 2 waves per SIMD.
 // (A 12-wave variant - a third of the xi planes per wave, 3 waves per SIMD in the 168-VGPR budget - measured 2 % slower.)
 
@@ -113,10 +138,17 @@ constexpr int W4_BN = 64, W4_MG = 9;
 // LOOP: the chunk loop of wino4_loop.md (docs/experiments): the last chunk peeled off, so that it stages and prefetches nothing, and the
 // first fragment read of a chunk issued in front of its staging loads.  false: the loop as it was before, selected by PESR_WINO4_LOOP=0
 // (same products, same order of additions: tests/test_wino4_loop_gpu.py compares the two with torch.equal).
-template <bool DENSE, int TXTC, bool BNF = false, bool LOOP = true>
+// TAIL: the peeled last chunk of the LOOP form runs its MFMAs group-major (all nine slabs for m-tiles 0..2, then 3..5, then 6..8: each
+// accumulator still gets ky = 0, 1, 2 and kk = 0..3 in that order), and a group's output transform, exchange and stores run as soon as its
+// accumulators are final - under the MFMAs of the groups behind it - instead of all 18 stores of a lane in one burst at the kernel's end
+// (docs/experiments/wino4_tail.md).  For launches of one round of workgroups with the swizzled 12- / 24-x-tile rows, no split-K, no
+// BatchNorm; PESR_WINO4_TAIL=0 selects the LOOP form without it (same bits: tests/test_wino4_tail_gpu.py).
+constexpr int W4_TAIL_SLOTS = 2 * 3 * 2 * 4 * 64 * 16;     // one group's exchange slots: 2 senders x 3 m-tiles x 2 x 4 channel blocks x 64 lanes x 16 B
+template <bool DENSE, int TXTC, bool BNF = false, bool LOOP = true, bool TAIL = false>
 __global__ __launch_bounds__(512) void conv3x3_wino4_kernel(const Wino4Args a, const BnEpi bn_arg) {
     (void)bn_arg;                                          // BatchNorm sums from the epilogue (common.h BnEpi): read through pesr_bn_epi() behind the main loop
     static_assert(!(DENSE && TXTC), "the constant-row-length form is for the non-dense layout");
+    static_assert(!TAIL || (LOOP && TXTC && !BNF), "the TAIL form is for the LOOP form of the constant-row-length kernels without BatchNorm");
     constexpr int NT = 512;                                // threads of the workgroup
     constexpr int NXL = 3;                                 // xi planes per wave
     constexpr int NSLAB = 3 * NXL;                         // weight slabs per wave and chunk: (ky, xl)
@@ -414,10 +446,156 @@ _Pragma("unroll")                                                               
     if (LOOP) {
 #pragma unroll 1
         for (int c = 0; c + 1 < C16; ++c) { W4_CHUNK(c, false) }
-        { const int c = C16 - 1; W4_CHUNK(c, true) }
+        if (!TAIL) { const int c = C16 - 1; W4_CHUNK(c, true) }
     } else {
 #pragma unroll 1
         for (int c = 0; c < C16; ++c) { W4_CHUNK(c, false) }
+    }
+#ifdef W4_STAMPS
+#define W4_STAMPS_OUT()                                                                                                                     \
+    W4_STAMP(36)                                                                                                                            \
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                                                                                        \
+    W4_STAMP(37)                                                                                                                            \
+    W4_STAMP_REAL(39)                                                                                                                       \
+    if (blockIdx.x < W4_ST_WGS && lane < W4_ST_SLOTS) g_w4_stamps[(blockIdx.x * 8 + wave) * W4_ST_SLOTS + lane] = w4_st[lane];
+#else
+#define W4_STAMPS_OUT()
+#endif
+    // ---- the TAIL form's last chunk and epilogue (the epilogue below, a group of three m-tiles at a time; it is described there) ------------
+    if (TAIL) {
+        const int c = C16 - 1;
+        char* const vcur = smem + (c & 1) * v_bytes;
+        // The exchange slots of all three groups are the first W4_TAIL_SLOTS bytes of the V buffer this chunk does NOT read (nothing is staged
+        // for a next chunk, and its last readers passed the barrier of the chunk before), so a group's exchange needs one barrier and the chunk
+        // none at its end.  Group 1 swaps the two senders' halves: a wave then overwrites the slots IT read for group 0 (its own program
+        // order), not slots its partner may still be reading; by group 2 every read of group 0 lies in front of group 1's barrier.
+        char* const xg = smem + ((c & 1) ^ 1) * v_bytes;
+        auto gslot = [&](int half, int il, int k) -> char* { return xg + ((((half * 3 + il) * 2 + k) * 4 + cb) * 64 + lane) * 16; };
+        const size_t img_out = (size_t)img * a.H * a.W;
+        const int co = n0 + cb * 16 + g * 4;
+        // All nine slabs of the chunk in registers before the first store: a wave's vmcnt retires in order, so a weight load waited for
+        // behind a store would wait for that store's acknowledgement (profiles/r04_ab_notes.txt).  Slabs 0 and 1 came with the chunk before
+        // (or from the prologue); the other seven take the free fb slot and the staging registers, which are dead here.
+        f32x4 wq[NSLAB];
+        wq[0] = fb[0]; wq[1] = fb[1];
+        W4_READ_A(fa[0], vcur, 0, 0, 0)
+        W4_FENCE()
+#pragma unroll
+        for (int s = 2; s < NSLAB; ++s) {
+#ifdef W4_NO_WLOAD
+            asm volatile("" : "=v"(wq[s]));
+#endif
+            W4_LDB(wq[s], s / NXL, s % NXL, CB + c)
+        }
+        f32x4 bias4 = {0.f, 0.f, 0.f, 0.f};
+        if (a.bias) bias4 = *(const f32x4*)(a.bias + co);
+        // (the launcher sends a call with BOTH a mask and a skip to the form without TAIL: one set of registers for the loads)
+        const float* const ms = a.mask ? a.mask : a.skip;
+        f32x4 po[6], msk[6];                               // a group's outputs are stored one per slab under the next group's MFMAs
+        size_t pidx[6];
+        bool pok[6];
+#pragma unroll
+        for (int grp = 0; grp < 3; ++grp) {
+#pragma unroll
+            for (int s = 0; s < NSLAB; ++s) {
+                const int ky = s / NXL, xl = s - ky * NXL, cur = (grp * NSLAB + s) & 1;
+                if (s + 1 < NSLAB) W4_READ_A(fa[cur ^ 1], vcur, (s + 1) / NXL, (s + 1) % NXL, grp)
+                else if (grp < 2) W4_READ_A(fa[cur ^ 1], vcur, 0, 0, grp + 1)
+                W4_FENCE()
+                W4_MFMA(fa[cur], wq[s], xl, grp)
+                W4_FENCE()
+                // Six stores back to back fill the store path and stall the wave's MFMAs: one per slab, where the staging blocks sat.  Behind
+                // the last of them this group's output offsets and its skip / mask loads, which have the last three slabs to land.
+                if ((grp > 0 && s < 6) || s == 6) {
+                    __builtin_amdgcn_s_setprio(3);
+                    if (s < 6) {
+                        if (pok[s]) *(f32x4*)(a.y + pidx[s]) = po[s];
+                    } else {
+#pragma unroll
+                        for (int e = 0; e < 6; ++e) {
+                            pok[e] = w4_out_index(a, TXTv, img, img_out, gy0, gt0, xt, r, co, grp * 3 + (e >> 1), e & 1, &pidx[e]);
+                            if (ms) msk[e] = *(const f32x4*)(ms + pidx[e]);
+                        }
+                    }
+                    __builtin_amdgcn_sched_barrier(0);
+                    __builtin_amdgcn_s_setprio(0);
+                    if (grp > 0 && s == 5) { W4_STAMP(39 + 2 * grp) }
+                }
+            }
+            if (grp == 2) { W4_STAMP(2 + 2 * (c < 16 ? c : 15)) W4_STAMP(3 + 2 * (c < 16 ? c : 15)) }
+            // this group's accumulators are final: its half of the output transform, as in the epilogue below
+            const int hs = (grp & 1) ^ xt;                 // the half of the slots this wave sends into; it reads the other
+            f32x4 keep[3][2];
+            if (xt == 0) {
+#pragma unroll
+                for (int il = 0; il < 3; ++il) {
+                    const f32x4 q0 = acc[0][grp * 3 + il], q1 = acc[1][grp * 3 + il], q2 = acc[2][grp * 3 + il];
+                    const f32x4 sm = q1 + q2, df = q1 - q2;
+                    keep[il][0] = q0 + sm; keep[il][1] = df;
+#ifndef W4_NO_EXCHANGE
+                    *(f32x4*)gslot(hs, il, 0) = sm; *(f32x4*)gslot(hs, il, 1) = df;
+#endif
+                }
+            } else {
+#pragma unroll
+                for (int il = 0; il < 3; ++il) {
+                    const f32x4 q0 = acc[0][grp * 3 + il], q1 = acc[1][grp * 3 + il], q2 = acc[2][grp * 3 + il];
+                    const f32x4 sm = q0 + q1, df = q0 - q1;
+                    keep[il][0] = 4.0f * sm; keep[il][1] = 8.0f * df + q2;
+#ifndef W4_NO_EXCHANGE
+                    *(f32x4*)gslot(hs, il, 0) = sm; *(f32x4*)gslot(hs, il, 1) = 2.0f * df;
+#endif
+                }
+            }
+            if (grp == 2) { W4_STAMP(34) }
+#ifndef W4_NO_EXCHANGE
+            // not __syncthreads(): its fence waits vmcnt(0), for the acknowledgement of the stores of the group before
+            __builtin_amdgcn_sched_barrier(0);
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            __builtin_amdgcn_s_barrier();
+            __builtin_amdgcn_sched_barrier(0);
+#endif
+            if (grp == 2) { W4_STAMP(35) }
+            W4_STAMP(40 + 2 * grp)
+            // (xi 0..2 part) + (xi 3..5 part), as the epilogue below adds them: the sum does not depend on which of the two a wave holds
+            f32x4 v[6];
+#pragma unroll
+            for (int e = 0; e < 6; ++e) {
+#ifdef W4_NO_EXCHANGE
+                v[e] = keep[e >> 1][e & 1];
+#else
+                v[e] = keep[e >> 1][e & 1] + *(const f32x4*)gslot(hs ^ 1, e >> 1, e & 1);
+#endif
+            }
+            // (one branch per group on what the call has, not one per output: the six outputs of a form are straight-line code.  In
+            // straight-line code hipcc contracts the multiply by alpha and the sum with the skip into one fma, which the epilogue below -
+            // its skip under a run-time condition - rounds twice: the empty asm keeps the two apart, and the bits the same)
+            auto epi6 = [&](const bool has_mask, const bool has_skip) {
+#pragma unroll
+                for (int e = 0; e < 6; ++e) {
+                    po[e] = pesr_epi4(v[e], a.bias != nullptr, bias4, a.alpha, has_mask, msk[e], false, msk[e], PESR_ACT_NONE, 0.f);
+                    if (has_skip) {
+                        asm volatile("" : "+v"(po[e]));
+                        po[e] = pesr_epi4(po[e], false, bias4, 1.0f, false, msk[e], true, msk[e], PESR_ACT_NONE, 0.f);
+                    }
+                }
+            };
+            auto act6 = [&](const int act) {
+#pragma unroll
+                for (int e = 0; e < 6; ++e) po[e] = pesr_act4(po[e], act, a.slope);
+            };
+            if (a.mask) epi6(true, false);
+            else if (a.skip) epi6(false, true);
+            else epi6(false, false);
+            if (a.act == PESR_ACT_RELU) act6(PESR_ACT_RELU);
+            else if (a.act == PESR_ACT_LRELU) act6(PESR_ACT_LRELU);
+        }
+#pragma unroll
+        for (int e = 0; e < 6; ++e)
+            if (pok[e]) *(f32x4*)(a.y + pidx[e]) = po[e];
+        W4_STAMP(45)
+        W4_STAMPS_OUT()
+        return;
     }
 #undef W4_READ_A
 #undef W4_LDB
@@ -547,13 +725,8 @@ _Pragma("unroll")                                                               
             *(f32x4*)(a.y + idx[e]) = o;
         }
     }
-#ifdef W4_STAMPS
-    W4_STAMP(36)
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    W4_STAMP(37)
-    W4_STAMP_REAL(39)
-    if (blockIdx.x < W4_ST_WGS && lane < W4_ST_SLOTS) g_w4_stamps[(blockIdx.x * 8 + wave) * W4_ST_SLOTS + lane] = w4_st[lane];
-#endif
+    W4_STAMPS_OUT()
+#undef W4_STAMPS_OUT
     if (bn_on) {
         // a lane's 18 outputs are pixels of ITS four channels (co .. co + 3): the 16 r-lanes x 2 xi-half waves of a (cb, g) pair
         // meet through LDS and are added in double, in the fixed order (xt, r)
@@ -723,7 +896,12 @@ int pesr_conv3x3_wino4_launch(const float* x, const float* wp, const float* bias
     lds = (size_t)W4_ST_LDS + 8 * W4_ST_SLOTS * sizeof(unsigned long long);
 #endif
     const dim3 grid((unsigned)(p.tiles * p.ksplit));
-    static PesrDeviceOnce attr_once[16];
+    // PESR_WINO4_TAIL=0: the LOOP form without the TAIL form's last chunk (read at every launch, like PESR_WINO4_LOOP).  The form is for
+    // one round of workgroups: with more, the next workgroup's prologue on the CU already runs under the stores of the one before.
+    const char* const tail_env = getenv("PESR_WINO4_TAIL");
+    const bool tail = loop && !(tail_env && tail_env[0] == '0' && !tail_env[1]) && p.ksplit == 1 && !bn.mode && !p.dense &&
+                      (p.TXT == 12 || p.TXT == 24) && (size_t)(p.TR + 2) * p.v_row >= (size_t)W4_TAIL_SLOTS && p.tiles <= 256 && !(mask && skip);
+    static PesrDeviceOnce attr_once[18];
 #define W4_LAUNCH(ID, ...)                                                                                                  \
     {                                                                                                                       \
         attr_once[ID]([&] { (void)hipFuncSetAttribute((const void*)conv3x3_wino4_kernel<__VA_ARGS__>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); }); \
@@ -735,7 +913,9 @@ int pesr_conv3x3_wino4_launch(const float* x, const float* wp, const float* bias
         else if (p.TXT == 12) W4_LAUNCH_LOOP(1, false, 12, true)
         else if (p.TXT == 24) W4_LAUNCH_LOOP(2, false, 24, true)
         else W4_LAUNCH_LOOP(3, false, 0, true)
-    } else if (p.dense) W4_LAUNCH_LOOP(4, true, 0, false)
+    } else if (tail && p.TXT == 12) W4_LAUNCH(16, false, 12, false, true, true)
+    else if (tail) W4_LAUNCH(17, false, 24, false, true, true)
+    else if (p.dense) W4_LAUNCH_LOOP(4, true, 0, false)
     else if (p.TXT == 12) W4_LAUNCH_LOOP(5, false, 12, false)
     else if (p.TXT == 24) W4_LAUNCH_LOOP(6, false, 24, false)
     else W4_LAUNCH_LOOP(7, false, 0, false)

@@ -1,11 +1,13 @@
 """Where the F(4,3) forward / input-gradient kernel's time goes at the G-body shape ([16,48,48,256] -> 256), per phase and per ablation,
-and the A/B of its two chunk loops (docs/experiments/wino4_loop.md).
+and the A/B of its chunk loops: the loop before (PESR_WINO4_LOOP=0), the new loop (PESR_WINO4_TAIL=0) and the new loop with the TAIL
+form of its last chunk (docs/experiments/wino4_loop.md, wino4_tail.md).
 
     python scripts/wino4_loop.py build            # no GPU needed: conv3x3_wino4.hip once per variant (-DW4_STAMPS, -DW4_NO_*), each linked
                                                   # with the objects of the regular build into a library of its own, exp/libw4_<variant>.so
     python scripts/wino4_loop.py run [--doc F]    # on the GPU: every variant in a child process of its own under `timeout`, stopping at the
-                                                  # first one that fails; then the two tables go into F between its table markers
-    python scripts/wino4_loop.py one LIB OUT.json # what a child does: time LIB in the three forms under both loops (and read its stamps)
+                                                  # first one that fails; then the tables go into F between its table markers
+                                                  # (default: docs/experiments/wino4_tail.md; wino4_loop.md keeps the tables of its change)
+    python scripts/wino4_loop.py one LIB OUT.json # what a child does: time LIB in the three forms under the three loops (and read its stamps)
 
 The variants never go into libpesr_hip.so, and all but `base` and `no_fences` compute wrong results: they are for timing only."""
 import ctypes
@@ -28,6 +30,9 @@ WHAT = {"base": "the product", "stamps": "the product with stamps", "no_xform": 
         "no_exchange": "no epilogue exchange", "mfma_only": "nothing but the MFMAs in the loop", "mfma_only_no_exchange": "the same, and no exchange",
         "no_fences": "no sched_barrier pairs (right results)"}
 FORMS = ("bias + ReLU", "skip", "mask")
+LOOPS = ("old", "new", "tail")
+LOOP_ENV = {"old": {"PESR_WINO4_LOOP": "0"}, "new": {"PESR_WINO4_TAIL": "0"}, "tail": {}}
+LOOP_NAME = {"old": "loop before (`PESR_WINO4_LOOP=0`)", "new": "new loop (`PESR_WINO4_TAIL=0`)", "tail": "new loop with the TAIL form"}
 N, H, W, C = 16, 48, 48, 256
 CHUNKS = C // 16
 BEGIN, END = "<!-- wino4_loop.py: tables -->", "<!-- wino4_loop.py: end of tables -->"
@@ -97,11 +102,10 @@ def one(path, out):
         return statistics.median(us), min(us), max(us)
 
     res = {"lib": os.path.basename(path), "us": {}, "stamps": {}}
-    for loop in ("new", "old"):
-        if loop == "old":
-            os.environ["PESR_WINO4_LOOP"] = "0"
-        else:
-            os.environ.pop("PESR_WINO4_LOOP", None)
+    for loop in ("tail", "new", "old"):
+        for k in ("PESR_WINO4_LOOP", "PESR_WINO4_TAIL"):
+            os.environ.pop(k, None)
+        os.environ.update(LOOP_ENV[loop])
         for form in FORMS:
             res["us"][f"{loop}/{form}"] = timed(form)
             if hasattr(l, "pesr_debug_w4_stamps"):
@@ -129,6 +133,13 @@ def one(path, out):
                       "stores acknowledged": us[:, 37] - us[:, 36],
                       "whole wave (entry -> stores acknowledged)": us[:, 37] - us[:, 0],
                       "shader clock over the wave's life (GHz)": (t[:, 37] - t[:, 0]) / np.maximum(t[:, 39] - t[:, 38], 1) * 0.1}
+                if loop == "tail":                       # slots 40 / 42 / 44: a group's exchange barrier released, 41 / 43 / 45: its last store issued
+                    ph.update({"TAIL: last chunk's start -> group 0's exchange barrier released": us[:, 40] - us[:, rel[-2]],
+                               "TAIL: -> group 1's exchange barrier released": us[:, 42] - us[:, 40],
+                               "TAIL: -> group 2's exchange barrier released": us[:, 44] - us[:, 42],
+                               "TAIL: group 0's last store issued, behind its barrier": us[:, 41] - us[:, 40],
+                               "TAIL: group 1's last store issued, behind its barrier": us[:, 43] - us[:, 42],
+                               "TAIL: group 2's last store issued, behind its barrier": us[:, 45] - us[:, 44]})
                 res["stamps"][f"{loop}/{form}"] = {k: (float(np.median(v)), float(v.min()), float(v.max())) for k, v in ph.items()}
     with open(out, "w") as fh:
         json.dump(res, fh)
@@ -140,26 +151,27 @@ def tables(results):
              "In-kernel stamps (`-DW4_STAMPS`: `s_memtime` shader clocks, turned into us with the median clock that the two `s_memrealtime` stamps",
              "of a wave give), over the 2048 waves of one launch: median (min .. max) in us."]
     st = results.get("stamps", {}).get("stamps", {})
-    for loop in ("old", "new"):
+    for loop in LOOPS:
         keys = [f"{loop}/{f}" for f in FORMS if f"{loop}/{f}" in st]
         if not keys:
             continue
-        lines += ["", f"The {'loop before (`PESR_WINO4_LOOP=0`)' if loop == 'old' else 'new loop'}:", "", "| phase | " + " | ".join(FORMS) + " |", "|---|" + "---|" * len(FORMS)]
+        lines += ["", f"The {LOOP_NAME[loop]}:", "", "| phase | " + " | ".join(FORMS) + " |", "|---|" + "---|" * len(FORMS)]
         for ph in st[keys[0]]:
             lines.append(f"| {ph.strip() if not ph.startswith('  ') else '- ' + ph.strip()} | " + " | ".join("%.2f (%.2f .. %.2f)" % tuple(st[k][ph]) for k in keys) + " |")
     lines += ["", "### Ablations", "",
               "HIP-event time per launch, 100 launches back to back, median of five (us); in brackets the difference to the product under the same loop."]
-    for loop in ("old", "new"):
-        lines += ["", f"The {'loop before (`PESR_WINO4_LOOP=0`)' if loop == 'old' else 'new loop'}:", "", "| build | " + " | ".join(FORMS) + " |", "|---|" + "---|" * len(FORMS)]
+    for loop in LOOPS:
+        lines += ["", f"The {LOOP_NAME[loop]}:", "", "| build | " + " | ".join(FORMS) + " |", "|---|" + "---|" * len(FORMS)]
         for name, _ in VARIANTS:
             if name not in results:
                 continue
             u = results[name]["us"]
             lines.append(f"| `{name}`: {WHAT[name]} | " + " | ".join("%.1f (%+.1f)" % (u[f"{loop}/{f}"][0], u[f"{loop}/{f}"][0] - base[f"{loop}/{f}"][0]) for f in FORMS) + " |")
-    lines += ["", "### The two loops, same library, same process", "", "| form | loop before | new loop | difference | spread of the five (before / new) |", "|---|---|---|---|---|"]
+    lines += ["", "### The three loops, same library, same process", "",
+              "| form | loop before | new loop | with TAIL | new - before | TAIL - new | spread of the five (before / new / TAIL) |", "|---|---|---|---|---|---|---|"]
     for f in FORMS:
-        o, n = base[f"old/{f}"], base[f"new/{f}"]
-        lines.append(f"| {f} | {o[0]:.2f} | {n[0]:.2f} | {n[0] - o[0]:+.2f} | {o[2] - o[1]:.2f} / {n[2] - n[1]:.2f} |")
+        o, n, t = base[f"old/{f}"], base[f"new/{f}"], base[f"tail/{f}"]
+        lines.append(f"| {f} | {o[0]:.2f} | {n[0]:.2f} | {t[0]:.2f} | {n[0] - o[0]:+.2f} | {t[0] - n[0]:+.2f} | {o[2] - o[1]:.2f} / {n[2] - n[1]:.2f} / {t[2] - t[1]:.2f} |")
     return "\n".join(lines) + "\n"
 
 
@@ -196,7 +208,7 @@ if __name__ == "__main__":
     elif cmd == "one":
         one(sys.argv[2], sys.argv[3])
     elif cmd == "run":
-        run(sys.argv[sys.argv.index("--doc") + 1] if "--doc" in sys.argv else os.path.join(R, "docs", "experiments", "wino4_loop.md"),
+        run(sys.argv[sys.argv.index("--doc") + 1] if "--doc" in sys.argv else os.path.join(R, "docs", "experiments", "wino4_tail.md"),
             sys.argv[sys.argv.index("--only") + 1].split(",") if "--only" in sys.argv else ())
     else:
         raise SystemExit(__doc__)
