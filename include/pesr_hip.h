@@ -80,9 +80,8 @@ int pesr_conv3x3_dgrad(const float* dy, const float* w_packed_dgrad, const float
 #define PESR_WGRAD_AUTO 0
 #define PESR_WGRAD_DIRECT 1
 #define PESR_WGRAD_WINO23 2
-#define PESR_WGRAD_WINO4_16X16 3 /* as AUTO, but the F(4,3) kernel in round 2's v_mfma_f32_16x16x4_f32 form (8 waves) instead of the
-                                  * 32x32x2 form AUTO uses since round 3: same transform, same results up to rounding (cross-checks, A/B) */
-#define PESR_WGRAD_WINO4_1D 4    /* (ABI 13) as AUTO, but with round 3's 1-D F(4,3) transform (half the multiplies) on the 12-wave 32x32x2 kernel (cross-checks, A/B) */
+/* algo 3: retired with ABI 20 (was the F(4,3) kernel in its v_mfma_f32_16x16x4_f32 form, 8 waves); the calls return PESR_EINVAL, the workspace query 0 */
+/* algo 4: retired with ABI 20 (was the 1-D F(4,3) transform on the 12-wave 32x32x2 kernel); the calls return PESR_EINVAL, the workspace query 0 */
 #define PESR_WGRAD_WINO4_12W 5   /* (ABI 16) as AUTO, but on round 4's 12-wave kernel (every wave stages and multiplies) instead of the 16-wave one with
                                   * four producer waves AUTO uses since round 5: same transform, same order of additions, bit-identical results */
 size_t pesr_conv3x3_wgrad_workspace_bytes(int N, int H, int W, int Cin, int Cout, int stride, int algo);
@@ -94,9 +93,9 @@ int pesr_conv3x3_wgrad(const float* x, const float* dy, float* dw, float* db, in
  * that plan does not cover the shape (whatever ps_in, algo and accumulate then decide). */
 #define PESR_WGRAD_KERNEL_DIRECT 0         /* conv3x3_wgrad_kernel */
 #define PESR_WGRAD_KERNEL_WINO23 1         /* conv3x3_wgrad_wino_kernel: F(2,3) along x */
-#define PESR_WGRAD_KERNEL_WINO4_16X16 2    /* conv3x3_wgrad_wino4_kernel: F(4,3) along x, 16x16x4 MFMA, 8 waves */
-#define PESR_WGRAD_KERNEL_WINO4_12W_1D 3   /* conv3x3_wgrad_wino4x_kernel: F(4,3) along x, 32x32x2 MFMA, 12 waves */
-#define PESR_WGRAD_KERNEL_WINO4_12W 4      /* the same kernel, F(2,3) along y nested on top */
+/* kernel 2: retired with ABI 20, never answered any more (was conv3x3_wgrad_wino4_kernel: F(4,3) along x, 16x16x4 MFMA, 8 waves) */
+/* kernel 3: retired with ABI 20, never answered any more (was the 1-D transform on conv3x3_wgrad_wino4x_kernel) */
+#define PESR_WGRAD_KERNEL_WINO4_12W 4      /* conv3x3_wgrad_wino4x_kernel: F(4,3) along x with F(2,3) along y nested on top, 32x32x2 MFMA, 12 waves */
 #define PESR_WGRAD_KERNEL_WINO4_PRODUCER 5 /* conv3x3_wgrad_wino4p_kernel: the nested transform, 12 MFMA waves + 4 staging waves (what AUTO runs) */
 int pesr_conv3x3_wgrad_kernel(int N, int H, int W, int Cin, int Cout, int stride, int ps_in, int algo, int accumulate);
 int pesr_conv3x3_wgrad_wino4_side(int N, int H, int W, int Cin, int Cout);

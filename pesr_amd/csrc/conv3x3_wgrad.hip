@@ -471,12 +471,15 @@ int pesr_wgrad_reduce_launch(const float* slab, float* dw, int split, int Cout, 
     return pesr_launch_status();
 }
 
+static bool wgrad_algo_retired(int algo) { return algo == 3 || algo == 4; }     // (ABI 20) the 16x16x4-MFMA and 1-D F(4,3) forms: PESR_EINVAL
+
 // algo: PESR_WGRAD_AUTO (0) = the Winograd F(4,3) form where it applies, else F(2,3), else the direct kernel;
 // PESR_WGRAD_DIRECT (1) = the direct kernel everywhere; PESR_WGRAD_WINO23 (2) = F(2,3) where it applies, else direct (A/B runs,
-// parity cross-checks).  An explicit argument: the library keeps no hidden state.
+// parity cross-checks); PESR_WGRAD_WINO4_12W (5) = as AUTO on the 12-wave F(4,3) kernel; 3 and 4 are retired (0 bytes, as for any
+// algo the call refuses).  An explicit argument: the library keeps no hidden state.
 size_t pesr_conv3x3_wgrad_ws_bytes(int N, int H, int W, int Cin, int Cout, int stride, int algo) {
     WgradPlan p;
-    if (!wgrad_plan(N, H, W, Cin, Cout, stride, &p)) return 0;
+    if (wgrad_algo_retired(algo) || !wgrad_plan(N, H, W, Cin, Cout, stride, &p)) return 0;
     size_t need = p.total_bytes;
     if (stride == 1 && (algo == 0 || algo >= 2)) {
         const size_t ww = pesr_conv3x3_wgrad_wino_ws_bytes(N, H, W, Cin, Cout);
@@ -491,23 +494,22 @@ size_t pesr_conv3x3_wgrad_ws_bytes(int N, int H, int W, int Cin, int Cout, int s
 
 // The ONE dispatch rule of the weight gradient: pesr_conv3x3_wgrad_launch runs the kernel this names, pesr_conv3x3_wgrad_kernel
 // (api.hip) answers with it, so the two cannot disagree.  Host only.  A Winograd form is passed over where its plan rejects the shape,
-// where it has no such mode (side-by-side strips: the 32x32x2 kernels, plain gradients; ps_in: Cout % 256; accumulate: not F(2,3), whose
+// where it has no such mode (side-by-side strips: plain gradients; ps_in: Cout % 256; accumulate: not F(2,3), whose
 // own reduce kernel overwrites) and where the caller's workspace is too small for it.
 int pesr_conv3x3_wgrad_kernel_impl(int N, int H, int W, int Cin, int Cout, int stride, int ps_in, int algo, int accumulate, size_t ws_bytes) {
     // PESR_WGRAD_* -> the F(4,3) kernel it asks for (0: none).  AUTO: the 32x32x2-MFMA form with the transform nested in y (F(2,3)y x
-    // F(4,3)x, 1/3 of the direct form's multiplies), staging on producer waves (round 5); WINO4_12W: round 4's 12-wave kernel of the same
-    // transform; WINO4_1D: round 3's 1-D F(4,3) transform on that kernel; WINO4_16X16: round 2's 16x16x4 form of the 1-D transform - all
-    // three kept as cross-checks
-    static const int wino4_of[6] = {PESR_WGK_WINO4_PRODUCER, 0, 0, PESR_WGK_WINO4_16X16, PESR_WGK_WINO4_12W_1D, PESR_WGK_WINO4_12W};
+    // F(4,3)x, 1/3 of the direct form's multiplies), staging on producer waves; WINO4_12W: the 12-wave kernel of the same transform, kept
+    // as the cross-check the product must equal bit for bit
+    static const int wino4_of[6] = {PESR_WGK_WINO4_PRODUCER, 0, 0, 0, 0, PESR_WGK_WINO4_12W};
     WgradPlan p;
-    if (algo < 0 || algo > 5 || !wgrad_plan(N, H, W, Cin, Cout, stride, &p)) return PESR_EINVAL;
+    if (algo < 0 || algo > 5 || wgrad_algo_retired(algo) || !wgrad_plan(N, H, W, Cin, Cout, stride, &p)) return PESR_EINVAL;
     if (ws_bytes < p.total_bytes) return PESR_EWORKSPACE;       // (every call needs the direct kernel's workspace)
     if (ps_in && (stride != 1 || Cout % 16)) return PESR_EINVAL;
     if (stride != 1 || algo == 1) return PESR_WGK_DIRECT;
     const bool ps_ok = !ps_in || Cout % 256 == 0;
-    if (wino4_of[algo] && ps_ok) {   // F(4,3) where it applies (width % 4 == 0 and >= 48 - the 32x32x2 kernels also 24 / 16 / 12 / 8 -, 64-multiple channels)
+    if (wino4_of[algo] && ps_ok) {   // F(4,3) where it applies (width % 4 == 0 and >= 48 - or 24 / 16 / 12 / 8, images side by side -, 64-multiple channels)
         const int side = pesr_conv3x3_wgrad_wino4_side_impl(N, H, W, Cin, Cout);
-        const bool side_ok = side == 1 || (side > 1 && wino4_of[algo] != PESR_WGK_WINO4_16X16 && !ps_in);
+        const bool side_ok = side == 1 || (side > 1 && !ps_in);
         if (side_ok && ws_bytes >= pesr_conv3x3_wgrad_wino4_ws_bytes(N, H, W, Cin, Cout)) return wino4_of[algo];
     }
     if (ps_ok && !accumulate) {      // F(2,3) where it applies (even width >= 48, 64-multiple channels)
@@ -522,7 +524,7 @@ int pesr_conv3x3_wgrad_launch(const float* x, const float* dy, float* dw, float*
     const int kernel = pesr_conv3x3_wgrad_kernel_impl(N, H, W, Cin, Cout, stride, ps_in, algo, accumulate, ws_bytes);
     if (kernel < 0) return kernel;
     if (!ws) return PESR_EWORKSPACE;
-    if (kernel >= PESR_WGK_WINO4_16X16)
+    if (kernel >= PESR_WGK_WINO4_12W)
         return pesr_conv3x3_wgrad_wino4_launch(x, dy, dw, db, N, H, W, Cin, Cout, alpha, ps_in, accumulate, kernel, ws, ws_bytes, stream);
     if (kernel == PESR_WGK_WINO23) return pesr_conv3x3_wgrad_wino_launch(x, dy, dw, db, N, H, W, Cin, Cout, alpha, ps_in, ws, ws_bytes, stream);
     WgradPlan p;

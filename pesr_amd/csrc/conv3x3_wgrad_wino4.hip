@@ -1,9 +1,9 @@
-// Weight gradient of the stride-1 3x3 conv with the transposed 1-D Winograd F(4,3) along x, fp32-input MFMA, gfx950.
+// Weight gradient of the stride-1 3x3 conv with the transposed Winograd F(4,3) along x (F(2,3) along y nested on top), fp32-input MFMA, gfx950.
 //
 // Same contract as conv3x3_wgrad.hip (ATen convolution_backward's grad_weight for the reference `Conv`,
-// model/basic.py:4-7) for widths that are multiples of 4 (>= 48; the 32x32x2 kernel also 24 / 16 / 12 / 8: images side by side in a strip)
-// and channel counts that are multiples of 64, with HALF of the
-// direct kernel's multiplies.  It is the adjoint of conv3x3_wino4.hip: with V = B^T d of the six input columns of an x-tile
+// model/basic.py:4-7) for widths that are multiples of 4 (>= 48; also 24 / 16 / 12 / 8: images side by side in a strip)
+// and channel counts that are multiples of 64, with HALF of the direct kernel's multiplies along x (a THIRD with the y-nesting
+// below).  It is the adjoint of conv3x3_wino4.hip: with V = B^T d of the six input columns of an x-tile
 // (four output pixels) and dM = A dy of the tile's four output gradients,
 //     dM = [dy0, dy0+dy1+dy2+dy3, dy0-dy1+dy2-dy3, dy0+2dy1+4dy2+8dy3, dy0-2dy1+4dy2-8dy3, dy3]
 //     dU_xi[ky][co][ci] = sum over rows, x-tiles of dM_xi[row][t][co] * V_xi[row + ky - 1][t][ci]          (18 products)
@@ -13,24 +13,23 @@
 // i.e. 18 MFMA accumulator sets over K = x-tiles (pixels / 4) instead of 9 taps over K = pixels.  Measured against fp64 the
 // error is ~1.5e-6 .. 2e-6 of the gradient's maximum (direct / F(2,3): 0.5 .. 1.4e-6).
 //
-// One workgroup owns a 64(co) x 32(ci) x 18 block of dU.  Its 8 waves are 4 pair groups (2 co m-tiles x 1 ci n-tile) x the two
-// halves of the xi planes (xh = wave >> 2: xi 3xh .. 3xh+2): 2 x 9 accumulator tiles = 72 VGPRs per wave - with all 18 (ky, xi)
-// sets of a 64 x 64 block in one wave (144 VGPRs) hipcc spills accumulators inside the loop.  The workgroup sweeps a range of
-// segments (TWO output rows x 12 x-tiles = 96 pixels).  Operands are staged global -> registers -> LDS with the transforms
-// applied on the way: V rows live in a 6-slot ring - a segment needs rows r-1 .. r+2 and the next one adds rows r+3, r+4 -
-// and the two dM rows are double buffered; one barrier per segment.  The LDS image interleaves the four x-tiles of a k-step
-// at 16-float granularity, so the ds_read_b32 fragments are bank-conflict free without padding.  The G^T output transform
-// happens in registers (the two xi halves meet through LDS, fixed order) before the partial block leaves, so the split-K slab
-// has the direct kernel's [split][9][Cout][Cin] layout and its fixed-order reduce kernel (alpha, PixelShuffle channel
-// un-permutation, OIHW store, bias) is shared.  The bias gradient is accumulated on the VALU from the dM_1 fragments
-// (dy0+dy1+dy2+dy3).
+// One workgroup owns a 64(co) x 32(ci) x 18 block of dU: twelve MFMA waves = 2 co halves (32 channels each) x the 6 xi planes, on
+// v_mfma_f32_32x32x2_f32.  The workgroup sweeps a range of segments (TWO output rows x 12 x-tiles = 96 pixels).  Operands are staged
+// global -> registers -> LDS with the transforms applied on the way: V rows live in an 8-slot ring - a segment needs rows r-1 .. r+2,
+// the next one adds rows r+3, r+4, and a strip start needs four free slots - and the two dM rows are double buffered; one barrier per
+// segment.  The LDS planes are plain [x-tile][channel] arrays: a fragment read touches 2 x 32 consecutive floats, an item's staging
+// store 8 lanes x 16 bytes contiguous - conflict-free without any swizzle.  The output transform happens before the partial block
+// leaves (the six xi planes meet through LDS, fixed order), so the split-K slab has the direct kernel's [split][9][Cout][Cin] layout
+// and its fixed-order reduce kernel (alpha, PixelShuffle channel un-permutation, OIHW store, bias) is shared.  The bias gradient is
+// accumulated on the VALU from the dM_1 fragments (dy0+dy1+dy2+dy3).
 //
-// Three generations of the kernel live here, all selectable (PESR_WGRAD_* of include/pesr_hip.h): the 16x16x4 form (round 2), the 12-wave
-// 32x32x2 form (rounds 3 / 4) and the 16-wave form with producer waves (round 5: the product).  What they share - workgroup decode,
-// segment walk, input transforms, k-step arithmetic, epilogue, G4^T - is written once, as the wg4_* device functions below.  Which of
-// them a call runs on is decided in ONE place, pesr_conv3x3_wgrad_kernel_impl (conv3x3_wgrad.hip), from wg4_plan below through
-// pesr_conv3x3_wgrad_wino4_ws_bytes / _side_impl; the same function answers the host-only query pesr_conv3x3_wgrad_kernel, and
-// Python (ops.wgrad_kernel_for, ops._wg4_plan_ok) asks it instead of re-typing the plan.
+// ONE transform lives here - F(4,3) along x with F(2,3) along y nested on top (below) - in TWO schedules: the 12-wave kernel, whose
+// every wave stages and multiplies (PESR_WGRAD_WINO4_12W), and the 16-wave kernel with four producer waves (the product: what
+// PESR_WGRAD_AUTO runs).  The 12-wave kernel is kept because the product must equal it bit for bit (tests/test_conv_gpu.py): what the
+// two share - workgroup decode, segment walk, input transforms, k-step arithmetic, epilogue, G4^T - is written once, as the wg4_*
+// device functions below.  Which kernel a call runs on is decided in ONE place, pesr_conv3x3_wgrad_kernel_impl (conv3x3_wgrad.hip),
+// from wg4_plan below through pesr_conv3x3_wgrad_wino4_ws_bytes / _side_impl; the same function answers the host-only query
+// pesr_conv3x3_wgrad_kernel, and Python (ops.wgrad_kernel_for, ops._wg4_plan_ok) asks it instead of re-typing the plan.
 #include <mutex>
 #include "mfma_f32.h"
 
@@ -46,18 +45,15 @@ struct Wg4Args {
     int co_tiles, ci_tiles;
     int ps_in;
     float* bias_part;  // [split][Cout] partial column sums of dy, or null
-    int side;          // 32x32x2 kernel only: images per strip.  1, or (rows of W / 4 < 12 x-tiles: W = 24 / 16 / 12 ...) 12 / (W / 4) images
+    int side;          // images per strip.  1, or (rows of W / 4 < 12 x-tiles: W = 24 / 16 / 12 ...) 12 / (W / 4) images
                        // laid SIDE BY SIDE in one 12-x-tile strip (x-tile vt = image vt / (W/4), tile vt % (W/4)); `image` indices of the
                        // segment walk are then groups of `side` images, N the real image count
 };
 
-constexpr int G4_NT = 512, G4_TXT = 12, G4_K4 = G4_TXT / 4;
-constexpr int G4_VPLANE = G4_K4 * 128, G4_VROW = 6 * G4_VPLANE;       // floats: V row slot [6 xi][3 blocks][4 x-tiles x 32 ci]
-constexpr int G4_DPLANE = G4_K4 * 256, G4_DROW = 6 * G4_DPLANE;       // floats: dM row     [6 xi][3 blocks][4 x-tiles x 64 co]
-constexpr int G4_RING = 6;
-// the two 32x32x2 kernels (below): LDS planes are plain [x-tile][channel] arrays
-constexpr int X4_VPLANE = G4_TXT * 32, X4_VROW = 6 * X4_VPLANE;       // floats: V row slot [6 xi][12 x-tiles][32 ci]
-constexpr int X4_DPLANE = G4_TXT * 64, X4_DROW = 6 * X4_DPLANE;       // floats: dM row     [6 xi][12 x-tiles][64 co]
+constexpr int WG4_TXT = 12;                                           // x-tiles per strip (48 pixels)
+// LDS planes are plain [x-tile][channel] arrays
+constexpr int X4_VPLANE = WG4_TXT * 32, X4_VROW = 6 * X4_VPLANE;      // floats: V row slot [6 xi][12 x-tiles][32 ci]
+constexpr int X4_DPLANE = WG4_TXT * 64, X4_DROW = 6 * X4_DPLANE;      // floats: dM row     [6 xi][12 x-tiles][64 co]
 constexpr int X4_RING = 8;                                            // V row slots: four in use, four for the segment behind (a strip start needs all four)
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -145,7 +141,7 @@ __device__ __forceinline__ void wg4_gt4_hi(const T u3, const T u4, const T u5, T
     w2 = (1.0f / 6.0f) * s34 + u5;
 }
 
-// ---- the two 32x32x2 kernels: fragment read, k-step, epilogue -----------------------------------------------------------------
+// ---- fragment read, k-step, epilogue ---------------------------------------------------------------------------------------------
 // The fragments of k-step q: three ds_read2st64_b32 - the two dM rows, V rows 0 / 1, V rows 2 / 3.
 __device__ __forceinline__ void wg4_read(float (&fa)[2], float (&fb)[4], const float* db, const float* (&vb)[2], const int q) {
     fa[0] = db[q * 128]; fa[1] = db[X4_DROW + q * 128];
@@ -163,30 +159,19 @@ __device__ __forceinline__ Wg4Nest wg4_nest_terms(const float (&fa)[2], const fl
 __device__ __forceinline__ void wg4_bias_add(float& bsum, const int xi, const float rows01) {
     if (xi == 1) { asm volatile("" : "+v"(bsum)); bsum += rows01; }
 }
-// One whole k-step without staging: the producer kernel's consumers, and the 1-D form of the 12-wave kernel behind its hooks.  (The
-// y-nested form of the 12-wave kernel runs the same terms and MFMAs with a staging hook and two scheduling fences in front of each MFMA:
-// its skeleton stays in that kernel.)
-template <bool NEST>
-__device__ __forceinline__ void wg4_kstep(f32x16 (&acc)[NEST ? 4 : 3], float& bsum, const int xi, const float (&fa)[2], const float (&fb)[4]) {
-    if constexpr (NEST) {
-        const Wg4Nest t = wg4_nest_terms(fa, fb);
-        wg4_bias_add(bsum, xi, t.a[1]);
+// One whole k-step without staging: the producer kernel's consumers.  (The 12-wave kernel runs the same terms and MFMAs with a staging
+// hook and two scheduling fences in front of each MFMA: its skeleton stays in that kernel.)
+__device__ __forceinline__ void wg4_kstep(f32x16 (&acc)[4], float& bsum, const int xi, const float (&fa)[2], const float (&fb)[4]) {
+    const Wg4Nest t = wg4_nest_terms(fa, fb);
+    wg4_bias_add(bsum, xi, t.a[1]);
 #pragma unroll
-        for (int j = 0; j < 4; ++j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(t.a[j], t.b[j], acc[j], 0, 0, 0);
-    } else {
-#pragma unroll
-        for (int ky = 0; ky < 3; ++ky) {
-            acc[ky] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[0], fb[ky], acc[ky], 0, 0, 0);
-            acc[ky] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[1], fb[ky + 1], acc[ky], 0, 0, 0);
-        }
-        wg4_bias_add(bsum, xi, fa[0] + fa[1]);
-    }
+    for (int j = 0; j < 4; ++j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(t.a[j], t.b[j], acc[j], 0, 0, 0);
 }
 
 // Behind the last segment's barrier: bias column sums, G2^T, G4^T and the slab store, by all NT threads of the workgroup (consumer: this wave
 // holds accumulators - every wave of the 12-wave kernel, waves 0..11 of the producer kernel).
-template <bool NEST, int NT>
-__device__ __forceinline__ void wg4_epilogue(const Wg4Args& a, const Wg4Block& b, float* const lds, f32x16 (&acc)[NEST ? 4 : 3], const float bsum,
+template <int NT>
+__device__ __forceinline__ void wg4_epilogue(const Wg4Args& a, const Wg4Block& b, float* const lds, f32x16 (&acc)[4], const float bsum,
                                              const bool consumer, const int tid, const int cot2, const int xi) {
     const int lane = tid & 63, c32 = lane & 31, ks = lane >> 5;
     if (a.bias_part && b.cit == 0) {     // the xi = 1 waves hold column sums of dy: lane pairs (c, c + 32) meet in LDS, fixed order
@@ -202,12 +187,11 @@ __device__ __forceinline__ void wg4_epilogue(const Wg4Args& a, const Wg4Block& b
     // ---- G^T: park the accumulators as ob[cot2][xi][ky][row 32][col 32], then every thread finishes 8 (or 6) (co, ci) positions ------
     float* const ob = lds;
     if (consumer) {
-        if constexpr (NEST) {      // G2^T first, in registers: the four y-planes of this wave's (co half, xi) become its three ky taps
+        // G2^T first, in registers: the four y-planes of this wave's (co half, xi) become its three ky taps
 #pragma unroll
-            for (int j = 0; j < 16; ++j) {
-                const float hs = 0.5f * (acc[1][j] + acc[2][j]), hd = 0.5f * (acc[1][j] - acc[2][j]);
-                acc[0][j] = acc[0][j] + hs; acc[1][j] = hd; acc[2][j] = hs + acc[3][j];
-            }
+        for (int j = 0; j < 16; ++j) {
+            const float hs = 0.5f * (acc[1][j] + acc[2][j]), hd = 0.5f * (acc[1][j] - acc[2][j]);
+            acc[0][j] = acc[0][j] + hs; acc[1][j] = hd; acc[2][j] = hs + acc[3][j];
         }
         float* o = ob + ((cot2 * 6 + xi) * 3) * 1024 + c32;
 #pragma unroll
@@ -232,287 +216,26 @@ __device__ __forceinline__ void wg4_epilogue(const Wg4Args& a, const Wg4Block& b
     }
 }
 
-
-__global__ __launch_bounds__(G4_NT) void conv3x3_wgrad_wino4_kernel(const Wg4Args a) {
-    extern __shared__ __attribute__((aligned(16))) float lds[];
-    float* const vring = lds;                             // [6 slots] V rows
-    float* const dmbuf = lds + G4_RING * G4_VROW;         // [2 buffers][2 rows] dM rows
-
-    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int r = lane & 15, g = lane >> 4;
-    const int xh = wave >> 2, co_half = (wave >> 1) & 1, ci_tile = wave & 1;
-
-    const Wg4Block blk = wg4_decode(a);
-    const int cit = blk.cit, sp = blk.sp, ci0 = blk.ci0, co0 = blk.co0, seg_begin = blk.seg_begin, seg_end = blk.seg_end;
-
-    f32x4 acc[9][2];
-#pragma unroll
-    for (int t = 0; t < 9; ++t)
-#pragma unroll
-        for (int i = 0; i < 2; ++i) acc[t][i] = (f32x4){0.f, 0.f, 0.f, 0.f};
-    float bsum[2] = {0.f, 0.f};
-
-    // ---- staging: per segment 2 V rows x 12 x-tiles x 8 ci-groups = 192 items (threads 0..191: six input columns each) and
-    //      2 dM rows x 12 x-tiles x 16 co-groups = 384 items (threads 128..511: four output-gradient columns each) ------------
-    const bool v_thr = tid < 192, d_thr = tid >= 128;
-    const int vi = v_thr ? tid : 0;
-    const int v_rr = vi / 96, vt = (vi % 96) >> 3, vc4 = vi & 7;          // which of the 2 new rows, x-tile, 4-channel group
-    const int di = d_thr ? tid - 128 : 0;
-    const int d_rr = di / 192, dt = (di % 192) >> 4, dc4 = di & 15;
-    // position of an item inside a plane: block of 4 x-tiles, 16-float groups interleaved over the 4 x-tiles.  The x-tile slot
-    // is rotated by the channel tile (V: by 2 per 16-ci tile, dM: by 1 per 16-co tile): the 16 lanes that write one x-tile's
-    // 64 (32) channels then hit 64 different banks instead of the same 16 four (two) times, and a fragment read - one channel
-    // tile, x-tiles g = 0..3 - still covers 64 consecutive floats.
-    const int v_pos = (vt >> 2) * 128 + (((vc4 >> 2) * 4 + ((vt + 2 * (vc4 >> 2)) & 3)) * 16) + (vc4 & 3) * 4;
-    const int d_pos = (dt >> 2) * 256 + (((dc4 >> 2) * 4 + ((dt + (dc4 >> 2)) & 3)) * 16) + (dc4 & 3) * 4;
-    const int d_C = a.ps_in ? (a.Cout >> 2) : a.Cout;
-    int d_choff;                                          // channel part of a dy address (floats)
-    {
-        const int pch = co0 + dc4 * 4;
-        if (a.ps_in) { const int sub = pch / d_C, cc = pch - sub * d_C; d_choff = ((sub >> 1) * (2 * a.W) + (sub & 1)) * d_C + cc; }
-        else d_choff = pch;
-    }
-
-    // Loads go through a buffer descriptor over ONE tensor row: a column outside the row is fetched at offset 2^31 and a row
-    // outside the image through an empty descriptor - both return zeros, so store_*() transforms what arrived without masking.
-    // Only the waves that own items issue them (V: waves 0..2, dM: waves 2..7).
-    u32x4 vx[6], dd[4];
-    unsigned v_off[6], d_off[4];
-    auto set_strip = [&](int xs) {   // per strip, a thread's column offsets (bytes from the start of a row)
-#pragma unroll
-        for (int j = 0; j < 6; ++j) {
-            const int ix = xs * 48 + 4 * vt - 1 + j;
-            const bool ok = v_thr && ix >= 0 && ix < a.W;
-            v_off[j] = ok ? (unsigned)((ix * a.Cin + ci0 + vc4 * 4) * 4) : 0x80000000u;
-        }
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            const int ox = xs * 48 + 4 * dt + j;
-            const bool ok = d_thr && ox < a.W;
-            d_off[j] = ok ? (unsigned)(((a.ps_in ? 2 * ox * d_C : ox * a.Cout) + d_choff) * 4) : 0x80000000u;
-        }
-    };
-    const unsigned x_row_bytes = (unsigned)a.W * a.Cin * 4;
-    // a dy row of the shuffled tensor spans the two sub-pixel rows 2oy, 2oy+1: 2 * (2W) * (Cout/4) floats = W * Cout as well
-    const unsigned d_row_bytes = (unsigned)a.W * a.Cout * 4;
-    // A wave's descriptor must be wave-uniform - or hipcc wraps every buffer load in a waterfall loop (it did: 62 of them).  The
-    // two new V rows of a segment are spread over threads 0..95 / 96..191, i.e. they MIX inside wave 1: the V descriptor
-    // therefore spans both rows (base = the first one, which may lie outside the image: nothing is fetched through it then) and
-    // a lane adds its row's pitch, or 2^31 when its row is outside the image.  dM rows change at a wave boundary (thread 320).
-    auto uniform_ptr = [](const float* p) -> const float* {
-        const unsigned long long v = (unsigned long long)p;
-        const unsigned lo = __builtin_amdgcn_readfirstlane((unsigned)v), hi = __builtin_amdgcn_readfirstlane((unsigned)(v >> 32));
-        return (const float*)(((unsigned long long)hi << 32) | lo);
-    };
-    auto load_v = [&](int img, int iy0) {                  // input rows iy0 (threads 0..95) and iy0 + 1 (96..191); outside the image: zeros
-        if (wave < 3) {
-            const float* const rowp = a.x + ((long)img * a.H + iy0) * ((long)a.W * a.Cin);
-            const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)uniform_ptr(rowp), 0, 2 * x_row_bytes, 0x00020000);
-            const int iy = iy0 + v_rr;
-            const bool row_ok = iy >= 0 && iy < a.H;
-#pragma unroll
-            for (int j = 0; j < 6; ++j)
-                vx[j] = __builtin_amdgcn_raw_buffer_load_b128(rs, row_ok ? v_off[j] + (unsigned)v_rr * x_row_bytes : 0x80000000u, 0, 0);
-        }
-    };
-    auto store_v = [&](int slot) {
-        if (wave < 3) {
-            float* p = vring + slot * G4_VROW + v_pos;
-            f32x4 tA, tB;
-#pragma unroll
-            for (int n = 0; n < 6; ++n) *(f32x4*)(p + n * G4_VPLANE) = wg4_v_plane(n, vx, tA, tB);
-        }
-    };
-    auto load_d = [&](int img, int oy) {                   // output-gradient row oy (>= H: zeros)
-        if (wave >= 2) {
-            const bool row_ok = oy < a.H;
-            const int ry = row_ok ? oy : 0;
-            const float* const rowp = a.ps_in ? a.dy + ((size_t)img * (2 * a.H) + 2 * ry) * (2 * a.W) * d_C
-                                              : a.dy + ((size_t)img * a.H + ry) * a.W * a.Cout;
-            const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)uniform_ptr(rowp), 0,
-                                                                                __builtin_amdgcn_readfirstlane(row_ok ? d_row_bytes : 0u), 0x00020000);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) dd[j] = __builtin_amdgcn_raw_buffer_load_b128(rs, d_off[j], 0, 0);
-        }
-    };
-    auto store_d = [&](int buf) {
-        if (wave >= 2) {
-            float* p = dmbuf + (buf * 2 + d_rr) * G4_DROW + d_pos;
-            f32x4 tA, tB;
-#pragma unroll
-            for (int n = 0; n < 6; ++n) *(f32x4*)(p + n * G4_DPLANE) = wg4_dm_plane(n, dd, tA, tB);
-        }
-    };
-    auto stage_strip_start = [&](int img, int row, int buf) {   // halo rows row-1 .. row+2 -> slots 0 .. 3; dM(row, row+1) -> buf
-        load_v(img, row - 1); store_v(v_rr);
-        load_v(img, row + 1); store_v(2 + v_rr);
-        load_d(img, row + d_rr); store_d(buf);
-    };
-
-    // ---- fragment addresses (floats): lane (r, g) reads x-tile 4k + g, channel 16*tile + r ------------------------------
-    const int b_lane = (ci_tile * 4 + ((g + 2 * ci_tile) & 3)) * 16 + r + xh * 3 * G4_VPLANE;
-    const int a_lane0 = (co_half * 2 * 4 + ((g + co_half * 2) & 3)) * 16 + r + xh * 3 * G4_DPLANE;        // m-tile 2 co_half
-    const int a_lane1 = ((co_half * 2 + 1) * 4 + ((g + co_half * 2 + 1) & 3)) * 16 + r + xh * 3 * G4_DPLANE;   // m-tile 2 co_half + 1
-
-    if (seg_begin >= seg_end) return;                       // (never: the planner hands every workgroup at least one segment)
-    int img = blk.first.img, xs = blk.first.xs, row = blk.first.row;
-    set_strip(xs);
-    stage_strip_start(img, row, 0);
-    // Staging runs a full segment ahead of its ds_writes: the loads for segment s+1's new rows are issued at the store point
-    // of segment s-1 (or right after a strip start) and land while segment s-1 / s computes; with the loads issued at the top
-    // of segment s they were waited for a third of a segment later - under load an L2 / MALL round trip is longer than that.
-    if (seg_begin + 1 < seg_end && row + 2 < a.H) { load_v(img, row + 3); load_d(img, row + 2 + d_rr); }
-    __syncthreads();
-    int base = 0;                                           // ring slot of the segment's top halo row (row - 1)
-    // One common store point for all waves, two thirds into the segment, with the next loads issued right behind it.  Measured
-    // alternatives: different store points for the two waves of a SIMD 1.4 % slower; the loads spread over three k-steps instead
-    // of one burst 12 % slower (those issued two k-steps before the store have not landed - a loaded L2 round trip is > 1 us).
-    constexpr int store_step = 4;
-
-#pragma unroll 1
-    for (int seg = seg_begin; seg < seg_end; ++seg) {
-        const int par = (seg - seg_begin) & 1;
-        const bool more = seg + 1 < seg_end;
-        const bool cont = more && row + 2 < a.H;            // the next segment is the next row pair of the same strip
-        const bool cont2 = cont && seg + 2 < seg_end && row + 4 < a.H;   // ... and so is the one after it
-
-        const float* const db = dmbuf + (par * 2) * G4_DROW + a_lane0;
-        const float* const db1 = dmbuf + (par * 2) * G4_DROW + a_lane1;
-        const float* vb[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            int sl = base + q; if (sl >= G4_RING) sl -= G4_RING;
-            vb[q] = vring + sl * G4_VROW + b_lane;
-        }
-        // step = (row of the pair rr, k-step k4): 6 A fragments (3 xi x 2 m-tiles) + 9 B fragments (3 ky x 3 xi), 18 MFMAs
-        float av0[6], bv0[9], av1[6], bv1[9];
-#define G4_READ(AV, BV, STEP)                                                                            \
-        {                                                                                                \
-            const int rr_ = (STEP) / G4_K4, k4_ = (STEP) % G4_K4;                                         \
-            _Pragma("unroll") for (int xl = 0; xl < 3; ++xl) {                                           \
-                AV[xl * 2 + 0] = db[rr_ * G4_DROW + xl * G4_DPLANE + k4_ * 256];                         \
-                AV[xl * 2 + 1] = db1[rr_ * G4_DROW + xl * G4_DPLANE + k4_ * 256];                        \
-                _Pragma("unroll") for (int ky = 0; ky < 3; ++ky)                                         \
-                    BV[ky * 3 + xl] = vb[rr_ + ky][xl * G4_VPLANE + k4_ * 128];                          \
-            }                                                                                            \
-        }
-#define G4_MFMA(AV, BV)                                                                                  \
-        _Pragma("unroll") for (int ky = 0; ky < 3; ++ky)                                                 \
-            _Pragma("unroll") for (int xl = 0; xl < 3; ++xl)                                             \
-                _Pragma("unroll") for (int i = 0; i < 2; ++i)                                            \
-                    acc[ky * 3 + xl][i] = __builtin_amdgcn_mfma_f32_16x16x4f32(AV[xl * 2 + i], BV[ky * 3 + xl], acc[ky * 3 + xl][i], 0, 0, 0); \
-        if (xh == 0) { _Pragma("unroll") for (int i = 0; i < 2; ++i) bsum[i] += AV[2 + i]; }   /* dM_1 = dy0+dy1+dy2+dy3 */
-        G4_READ(av0, bv0, 0)
-#pragma unroll
-        for (int stp = 0; stp < 2 * G4_K4; stp += 2) {
-            G4_READ(av1, bv1, stp + 1)
-            __builtin_amdgcn_sched_barrier(0);
-            G4_MFMA(av0, bv0)
-            __builtin_amdgcn_sched_barrier(0);
-            if (stp + 2 < 2 * G4_K4) G4_READ(av0, bv0, stp + 2)
-            if (stp == store_step) {
-                // The staging stores go to LDS that nobody reads in this segment (the two free ring slots, the other dM
-                // buffer); right behind them the loads for the segment after next reuse the staging registers.
-                __builtin_amdgcn_sched_barrier(0);
-                if (cont) {
-                    int sl = base + 4 + v_rr; if (sl >= G4_RING) sl -= G4_RING;
-                    { store_v(sl); store_d(par ^ 1); }
-                    if (cont2) { load_v(img, row + 5); load_d(img, row + 4 + d_rr); }
-                }
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            G4_MFMA(av1, bv1)
-            __builtin_amdgcn_sched_barrier(0);
-        }
-#undef G4_READ
-#undef G4_MFMA
-        if (cont) {                                         // rows +3, +4 went to the slots of rows -1, 0, which the next segment drops
-            __syncthreads();
-            base += 2; if (base >= G4_RING) base -= G4_RING;
-            row += 2;
-        } else if (more) {                                  // new strip / image: its four halo rows are staged from scratch
-            __syncthreads();
-            const Wg4Seg nx = wg4_seg_at(a, seg + 1);
-            img = nx.img; xs = nx.xs; row = nx.row;
-            set_strip(xs);
-            stage_strip_start(img, row, par ^ 1);
-            if (seg + 2 < seg_end && row + 2 < a.H) { load_v(img, row + 3); load_d(img, row + 2 + d_rr); }
-            __syncthreads();
-            base = 0;
-        }
-    }
-    __syncthreads();
-
-    if (a.bias_part && cit == 0) {   // combine the 4 k-slot lane groups through LDS (the staging buffers are free now), fixed order
-        float* red = lds;
-        if (ci_tile == 0 && xh == 0) {
-#pragma unroll
-            for (int i = 0; i < 2; ++i) red[g * 64 + (co_half * 2 + i) * 16 + r] = bsum[i];
-        }
-        __syncthreads();
-        if (tid < 64 && co0 + tid < a.Cout)
-            a.bias_part[(size_t)sp * a.Cout + co0 + tid] = ((red[tid] + red[64 + tid]) + red[128 + tid]) + red[192 + tid];
-        __syncthreads();
-    }
-    // G^T in registers: each xi half contributes a partial dw; the halves meet in LDS [tap 9][co 64][ci 32] (xh = 0 writes,
-    // xh = 1 adds and stores).  slab[sp][ky*3+kx][co][ci]: D tile row = co (= (lane>>4)*4 + reg), col = ci (= lane&15).
-    float* const ob = lds;
-    float* const out = a.slab + (size_t)sp * 9 * a.Cout * a.Cin;
-    const unsigned tap = (unsigned)a.Cout * a.Cin;
-#pragma unroll
-    for (int ph = 0; ph < 2; ++ph) {
-        if (xh == ph) {
-#pragma unroll
-            for (int ky = 0; ky < 3; ++ky)
-#pragma unroll
-                for (int i = 0; i < 2; ++i) {
-                    const f32x4 u0 = acc[ky * 3 + 0][i], u1 = acc[ky * 3 + 1][i], u2 = acc[ky * 3 + 2][i];
-                    f32x4 w0, w1, w2;
-                    if (ph == 0) wg4_gt4_lo(u0, u1, u2, w0, w1, w2);       // U0, U1, U2
-                    else wg4_gt4_hi(u0, u1, u2, w0, w1, w2);               // U3, U4, U5
-#pragma unroll
-                    for (int jj = 0; jj < 4; ++jj) {
-                        const int col = (co_half * 2 + i) * 16 + g * 4 + jj, cil = ci_tile * 16 + r;
-                        float* o = ob + ((ky * 3) * 64 + col) * 32 + cil;
-                        if (ph == 0) { o[0] = w0[jj]; o[64 * 32] = w1[jj]; o[2 * 64 * 32] = w2[jj]; }
-                        else {
-                            const unsigned go = ((unsigned)(ky * 3) * a.Cout + co0 + col) * a.Cin + ci0 + cil;
-                            out[go] = o[0] + w0[jj]; out[go + tap] = o[64 * 32] + w1[jj]; out[go + 2 * tap] = o[2 * 64 * 32] + w2[jj];
-                        }
-                    }
-                }
-        }
-        if (ph == 0) __syncthreads();
-    }
-}
-
 // ---------------------------------------------------------------------------------------------------------------------------
-// Round-3 variant on v_mfma_f32_32x32x2_f32 (PESR_WGRAD_WINO4X): same transform, same 64(co) x 32(ci) x 18 block, same segment
-// sweep, ring, split-K slab and reduce.  What changes is who owns what: TWELVE waves = 2 co halves (32 channels each) x the 6 xi
-// planes; a wave keeps dU_xi[ky = 0..2] of its 32 x 32 tile (3 accumulator tiles = 48 VGPRs) and, per k-step (TWO x-tiles),
-// reads 2 dM fragments (the segment's two rows) and 4 V fragments (input rows r-1 .. r+2) for SIX 64-cycle MFMAs - one
-// ds_read_b32 per MFMA where the 16x16x4 form above needs 15 per 18 32-cycle MFMAs, i.e. 0.4 of the LDS read bytes per flop.
-// The LDS planes are plain [x-tile][channel] arrays: a fragment read touches 2 x 32 consecutive floats, an item's staging store
-// 8 lanes x 16 bytes contiguous - conflict-free without any swizzle.  Three waves per SIMD hide what two could not.
-// G^T needs all six xi of a tap: the waves park their accumulators in LDS (147 KB, the staging buffers are free by then) and all
-// 768 threads finish the nine taps of the block in the same order of additions as the kernel above.
-// ---------------------------------------------------------------------------------------------------------------------------
-constexpr int X4_NT = 768;
-
-// ---------------------------------------------------------------------------------------------------------------------------
-// Round 4, NEST = true (the default): the transform NESTED in y - F(2,3) along y on top of F(4,3) along x - at no cost in staging.
-// A segment is two output rows; per k-step a wave already holds, for its xi plane, the x-transformed gradients D0, D1 of the two
-// rows and the x-transformed inputs X0 .. X3 of the four input rows they touch, and the 1-D form spends SIX MFMAs on
+// The transform is NESTED in y - F(2,3) along y on top of F(4,3) along x - at no cost in staging.  A segment is two output rows; per
+// k-step (TWO x-tiles) a wave reads, for its xi plane, 2 dM fragments - the x-transformed gradients D0, D1 of the two rows - and 4 V
+// fragments - the x-transformed inputs X0 .. X3 of the four input rows r-1 .. r+2 they touch.  The 1-D transform would spend SIX MFMAs on
 //     dU[ky] += D0 * X[ky] + D1 * X[ky + 1],  ky = 0, 1, 2
 // - a 3-tap correlation of 2 against 4 values, i.e. exactly the F(2,3) weight-gradient problem.  Its four products
 //     P0 += D0 * (X0 - X2)    P1 += (D0 + D1) * (X1 + X2)    P2 += (D0 - D1) * (X2 - X1)    P3 += D1 * (X3 - X1)
 // give dU[0] = P0 + (P1 + P2) / 2, dU[1] = (P1 - P2) / 2, dU[2] = (P1 + P2) / 2 + P3 (G2^T, applied once, in registers, in front of
-// the G4^T epilogue): FOUR MFMAs per k-step for the same fragment reads, the same staging, ring and LDS image - five VALU adds per
-// k-step buy a third of the matrix work (24 products per 2 x 4 output pixels: 1/3 of the direct form's 72).  One more accumulator
-// tile per wave (64 VGPRs).  Numerics (scripts/wino2d_wgrad_study.py, fp32 emulation vs fp64 at 16 x 48 x 48 pixels): 2.0 - 2.3e-6
-// of the gradient's maximum against 2.1 - 3.5e-6 for the 1-D form - the F(2,3) matrices are 0, +-1, 1/2.
+// the G4^T epilogue): FOUR 64-cycle MFMAs per k-step - five VALU adds per k-step buy a third of the matrix work (24 products per 2 x 4
+// output pixels: 1/3 of the direct form's 72).  A wave keeps the four P planes of its 32 x 32 tile (4 accumulator tiles = 64 VGPRs).
+// Numerics (scripts/wino2d_wgrad_study.py, fp32 emulation vs fp64 at 16 x 48 x 48 pixels): 2.0 - 2.3e-6 of the gradient's maximum
+// against 2.1 - 3.5e-6 for the 1-D transform - the F(2,3) matrices are 0, +-1, 1/2.
+// G^T needs all six xi of a tap: the waves park their accumulators in LDS (144 KiB, the staging buffers are free by then) and all
+// threads of the workgroup finish the nine taps of the block in one fixed order of additions (wg4_epilogue).
+//
+// The 12-wave kernel (PESR_WGRAD_WINO4_12W): every wave is one of the 2 co halves x 6 xi planes AND stages - three waves per SIMD.  It
+// is the producer kernel's cross-check: the product must equal it in every bit.
 // ---------------------------------------------------------------------------------------------------------------------------
-template <bool NEST>
+constexpr int X4_NT = 768;
+
 __global__ __launch_bounds__(X4_NT) void conv3x3_wgrad_wino4x_kernel(const Wg4Args a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     float* const vring = lds;                             // [8 slots] V rows
@@ -524,10 +247,9 @@ __global__ __launch_bounds__(X4_NT) void conv3x3_wgrad_wino4x_kernel(const Wg4Ar
     const Wg4Block blk = wg4_decode(a);
     const int ci0 = blk.ci0, co0 = blk.co0, seg_begin = blk.seg_begin, seg_end = blk.seg_end;
 
-    constexpr int NACC = NEST ? 4 : 3;
-    f32x16 acc[NACC];
+    f32x16 acc[4];
 #pragma unroll
-    for (int t = 0; t < NACC; ++t)
+    for (int t = 0; t < 4; ++t)
 #pragma unroll
         for (int j = 0; j < 16; ++j) acc[t][j] = 0.f;
     float bsum = 0.f;
@@ -715,7 +437,7 @@ __global__ __launch_bounds__(X4_NT) void conv3x3_wgrad_wino4x_kernel(const Wg4Ar
     n2 = wg4_seg_after(a, n2, seg_begin + 2, seg_end);
     __syncthreads();
     int base = 0, par = 0;                                  // ring slot of the segment's top halo row (row - 1); its dM buffer
-    constexpr int KQ = G4_TXT / 2;                          // k-steps per row
+    constexpr int KQ = WG4_TXT / 2;                          // k-steps per row
     // Static priority for the second-dispatched half (waves 6..11), set once: the two halves run the same program in lockstep
     // behind one barrier per segment, and the younger half loses every arbitration; raised, it pulls ahead and the halves'
     // LDS read bursts and MFMA blocks de-phase (MI355X_MICROARCH.md, "Two waves per SIMD", item 4): 209.6 -> 206.2 us; three
@@ -726,21 +448,18 @@ __global__ __launch_bounds__(X4_NT) void conv3x3_wgrad_wino4x_kernel(const Wg4Ar
     // One k-step (the arithmetic is wg4_kstep's): the y-nesting's VALU work first, then its MFMAs with one hook in front of each (HB < 0:
     // none).  hook(n), n = 0 .. 11 over three consecutive k-steps: staging steps 0 .. 5 (one LDS plane each), then the six loads of the
     // segment after next.
-#define X4_KSTEP(FA, FB, HB)                                                                     \
-        if constexpr (NEST) {                                                                    \
-            const Wg4Nest t_ = wg4_nest_terms(FA, FB);                                           \
-            wg4_bias_add(bsum, xi, t_.a[1]);                                                     \
-            X4_FENCE(); if ((HB) >= 0) hook((HB) + 0); X4_FENCE();                               \
-            acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(t_.a[0], t_.b[0], acc[0], 0, 0, 0);    \
-            X4_FENCE(); if ((HB) >= 0) hook((HB) + 1); X4_FENCE();                               \
-            acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(t_.a[1], t_.b[1], acc[1], 0, 0, 0);    \
-            X4_FENCE(); if ((HB) >= 0) hook((HB) + 2); X4_FENCE();                               \
-            acc[2] = __builtin_amdgcn_mfma_f32_32x32x2f32(t_.a[2], t_.b[2], acc[2], 0, 0, 0);    \
-            X4_FENCE(); if ((HB) >= 0) hook((HB) + 3); X4_FENCE();                               \
-            acc[3] = __builtin_amdgcn_mfma_f32_32x32x2f32(t_.a[3], t_.b[3], acc[3], 0, 0, 0);    \
-        } else {                                                                                 \
-            if ((HB) >= 0) { hook((HB) + 0); hook((HB) + 1); hook((HB) + 2); hook((HB) + 3); }   \
-            wg4_kstep<false>(acc, bsum, xi, FA, FB);                                             \
+#define X4_KSTEP(FA, FB, HB)                                                                 \
+        {                                                                                    \
+            const Wg4Nest t_ = wg4_nest_terms(FA, FB);                                       \
+            wg4_bias_add(bsum, xi, t_.a[1]);                                                 \
+            X4_FENCE(); if ((HB) >= 0) hook((HB) + 0); X4_FENCE();                           \
+            acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(t_.a[0], t_.b[0], acc[0], 0, 0, 0); \
+            X4_FENCE(); if ((HB) >= 0) hook((HB) + 1); X4_FENCE();                           \
+            acc[1] = __builtin_amdgcn_mfma_f32_32x32x2f32(t_.a[1], t_.b[1], acc[1], 0, 0, 0); \
+            X4_FENCE(); if ((HB) >= 0) hook((HB) + 2); X4_FENCE();                           \
+            acc[2] = __builtin_amdgcn_mfma_f32_32x32x2f32(t_.a[2], t_.b[2], acc[2], 0, 0, 0); \
+            X4_FENCE(); if ((HB) >= 0) hook((HB) + 3); X4_FENCE();                           \
+            acc[3] = __builtin_amdgcn_mfma_f32_32x32x2f32(t_.a[3], t_.b[3], acc[3], 0, 0, 0); \
         }
     const float* db = dmbuf + a_lane;
     const float* vb[2] = {vring + b_lane, vring + 2 * X4_VROW + b_lane};     // rows (base, base + 1) and (base + 2, base + 3): the base is even, a pair never wraps
@@ -808,7 +527,7 @@ __global__ __launch_bounds__(X4_NT) void conv3x3_wgrad_wino4x_kernel(const Wg4Ar
 #undef X4_FENCE
     __syncthreads();
 
-    wg4_epilogue<NEST, X4_NT>(a, blk, lds, acc, bsum, true, tid, cot2, xi);
+    wg4_epilogue<X4_NT>(a, blk, lds, acc, bsum, true, tid, cot2, xi);
 }
 
 constexpr int P4_NT = 1024;
@@ -975,7 +694,6 @@ __device__ __forceinline__ void p4_producer(const Wg4Args& a, float* const vring
     }
 }
 
-template <bool NEST>
 __global__ __launch_bounds__(P4_NT) void conv3x3_wgrad_wino4p_kernel(const Wg4Args a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     float* const vring = lds;                             // [8 slots] V rows
@@ -991,10 +709,9 @@ __global__ __launch_bounds__(P4_NT) void conv3x3_wgrad_wino4p_kernel(const Wg4Ar
     if (seg_begin >= seg_end) return;
     const Wg4Seg cur = blk.first;
 
-    constexpr int NACC = NEST ? 4 : 3;
-    f32x16 acc[NACC];
+    f32x16 acc[4];
 #pragma unroll
-    for (int t = 0; t < NACC; ++t)
+    for (int t = 0; t < 4; ++t)
 #pragma unroll
         for (int j = 0; j < 16; ++j) acc[t][j] = 0.f;
     float bsum = 0.f;
@@ -1013,7 +730,7 @@ __global__ __launch_bounds__(P4_NT) void conv3x3_wgrad_wino4p_kernel(const Wg4Ar
         Wg4Seg n1 = wg4_seg_after(a, cur, seg_begin + 1, seg_end);
         __syncthreads();                                       // the first segment is staged
         int base = 0, par = 0;
-        constexpr int KQ = G4_TXT / 2;
+        constexpr int KQ = WG4_TXT / 2;
         float fa0[2], fb0[4], fa1[2], fb1[4];
         const float* db = dmbuf + a_lane;
         const float* vb[2] = {vring + b_lane, vring + 2 * X4_VROW + b_lane};
@@ -1024,12 +741,12 @@ __global__ __launch_bounds__(P4_NT) void conv3x3_wgrad_wino4p_kernel(const Wg4Ar
 #pragma unroll
             for (int q = 0; q < KQ - 2; q += 2) {
                 wg4_read(fa1, fb1, db, vb, q + 1);
-                wg4_kstep<NEST>(acc, bsum, xi, fa0, fb0);
+                wg4_kstep(acc, bsum, xi, fa0, fb0);
                 wg4_read(fa0, fb0, db, vb, q + 2);
-                wg4_kstep<NEST>(acc, bsum, xi, fa1, fb1);
+                wg4_kstep(acc, bsum, xi, fa1, fb1);
             }
             wg4_read(fa1, fb1, db, vb, KQ - 1);
-            wg4_kstep<NEST>(acc, bsum, xi, fa0, fb0);
+            wg4_kstep(acc, bsum, xi, fa0, fb0);
             // the segment's one barrier, in front of its last k-step: this segment's last fragments are in registers, the next
             // segment's rows are stored - its first fragments are read here, under that k-step's MFMAs
             __syncthreads();
@@ -1037,14 +754,14 @@ __global__ __launch_bounds__(P4_NT) void conv3x3_wgrad_wino4p_kernel(const Wg4Ar
             vb[0] = vring + nbase * X4_VROW + b_lane;
             vb[1] = vring + ((nbase + 2) & (X4_RING - 1)) * X4_VROW + b_lane;
             wg4_read(fa0, fb0, db, vb, 0);
-            wg4_kstep<NEST>(acc, bsum, xi, fa1, fb1);
+            wg4_kstep(acc, bsum, xi, fa1, fb1);
             base = nbase; par ^= 1;
             n1 = wg4_seg_after(a, n1, seg + 2, seg_end);
         }
     }
     __syncthreads();
 
-    wg4_epilogue<NEST, P4_NT>(a, blk, lds, acc, bsum, !producer, tid, cot2, xi);
+    wg4_epilogue<P4_NT>(a, blk, lds, acc, bsum, !producer, tid, cot2, xi);
 }
 
 namespace {
@@ -1056,20 +773,20 @@ static bool wg4_plan(int N, int H, int W, int Cin, int Cout, Wg4Plan* p) {
     p->segs_y = (H + 1) / 2;
     p->side = 1;
     if (W < 48) {
-        // Rows shorter than a strip (round 4; the 32x32x2 kernel only): 12 / (W / 4) images side by side in one strip, e.g. two of the
+        // Rows shorter than a strip: 12 / (W / 4) images side by side in one strip, e.g. two of the
         // Discriminator's 24-pixel-wide images (features.6: 194 us on the direct kernel, which issues three times the multiplies).
         const int xtw = W / 4;
-        if (xtw < 2 || G4_TXT % xtw) return false;
-        p->side = G4_TXT / xtw;
+        if (xtw < 2 || WG4_TXT % xtw) return false;
+        p->side = WG4_TXT / xtw;
         if ((size_t)p->side * H * W * (Cin > Cout ? Cin : Cout) * 4 >= ((size_t)1 << 31)) return false;   // 32-bit offsets inside a strip
         const int groups = (N + p->side - 1) / p->side;
-        if ((long)groups * G4_TXT * 8 > (long)N * xtw * 9) return false;          // a mostly empty last group
+        if ((long)groups * WG4_TXT * 8 > (long)N * xtw * 9) return false;          // a mostly empty last group
         p->segs_x = 1;
         p->total_segs = groups * p->segs_y;
     } else {
-        p->segs_x = (W / 4 + G4_TXT - 1) / G4_TXT;
+        p->segs_x = (W / 4 + WG4_TXT - 1) / WG4_TXT;
         // a ragged last strip wastes MFMAs on zeros: accept up to ~1/8
-        if ((long)p->segs_x * G4_TXT * 8 > (long)(W / 4) * 9) return false;
+        if ((long)p->segs_x * WG4_TXT * 8 > (long)(W / 4) * 9) return false;
         p->total_segs = N * p->segs_x * p->segs_y;
     }
     const int tiles = p->co_tiles * p->ci_tiles;
@@ -1098,13 +815,13 @@ int pesr_conv3x3_wgrad_wino4_side_impl(int N, int H, int W, int Cin, int Cout) {
 }
 
 // returns PESR_EINVAL when the shape is not covered (pesr_conv3x3_wgrad_kernel_impl of conv3x3_wgrad.hip sends such calls to the F(2,3)
-// form / the direct kernel).  variant: PESR_WGK_WINO4_16X16 (8 waves), _12W_1D (12 waves, 1-D transform), _12W (the same kernel with the
-// transform nested in y) or _PRODUCER (the y-nested transform with the staging on four producer waves: 16 waves; the product)
+// form / the direct kernel).  variant: PESR_WGK_WINO4_12W (12 waves, every wave stages and multiplies) or _PRODUCER (the staging on four
+// producer waves: 16 waves; the product)
 int pesr_conv3x3_wgrad_wino4_launch(const float* x, const float* dy, float* dw, float* db, int N, int H, int W, int Cin, int Cout,
                                     float alpha, int ps_in, int accumulate, int variant, void* ws, size_t ws_bytes, hipStream_t stream) {
     Wg4Plan p;
-    if (variant < PESR_WGK_WINO4_16X16 || variant > PESR_WGK_WINO4_PRODUCER || !wg4_plan(N, H, W, Cin, Cout, &p)) return PESR_EINVAL;
-    if (p.side > 1 && (variant == PESR_WGK_WINO4_16X16 || ps_in)) return PESR_EINVAL;     // side-by-side strips: the 32x32x2 kernel, plain gradients
+    if ((variant != PESR_WGK_WINO4_12W && variant != PESR_WGK_WINO4_PRODUCER) || !wg4_plan(N, H, W, Cin, Cout, &p)) return PESR_EINVAL;
+    if (p.side > 1 && ps_in) return PESR_EINVAL;     // side-by-side strips: plain gradients
     if (!ws || ws_bytes < p.total_bytes) return PESR_EWORKSPACE;
     if (ps_in && Cout % 256) return PESR_EINVAL;
     Wg4Args a{};
@@ -1113,23 +830,16 @@ int pesr_conv3x3_wgrad_wino4_launch(const float* x, const float* dy, float* dw, 
     a.segs_x = p.segs_x; a.segs_y = p.segs_y; a.total_segs = p.total_segs; a.segs_per_split = p.segs_per_split;
     a.co_tiles = p.co_tiles; a.ci_tiles = p.ci_tiles; a.ps_in = ps_in; a.side = p.side;
     a.bias_part = db ? (float*)((char*)ws + p.slab_bytes + (((size_t)Cout * sizeof(double) + 255) / 256) * 256) : nullptr;
-    constexpr size_t lds = (size_t)(G4_RING * G4_VROW + 4 * G4_DROW) * sizeof(float);
-    static_assert(lds >= (size_t)9 * 64 * 32 * sizeof(float), "epilogue staging fits");
-    static_assert(lds <= 160 * 1024, "wgrad-wino4 LDS budget");
-    constexpr size_t ldsx = (size_t)2 * 6 * 3 * 1024 * sizeof(float);      // the variant's G^T staging (144 KiB) = its eight-slot ring + dM buffers
-    static_assert(ldsx >= (size_t)(X4_RING * X4_VROW + 4 * X4_DROW) * sizeof(float) && ldsx <= 160 * 1024, "wgrad-wino4x LDS budget");
+    constexpr size_t ldsx = (size_t)2 * 6 * 3 * 1024 * sizeof(float);      // the G^T staging (144 KiB) = the eight-slot ring + dM buffers
+    static_assert(ldsx >= (size_t)(X4_RING * X4_VROW + 4 * X4_DROW) * sizeof(float) && ldsx <= 160 * 1024, "wgrad-wino4 LDS budget");
     static PesrDeviceOnce attr_once;
     attr_once([&] {
-        (void)hipFuncSetAttribute((const void*)conv3x3_wgrad_wino4_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void*)conv3x3_wgrad_wino4x_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void*)conv3x3_wgrad_wino4x_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        (void)hipFuncSetAttribute((const void*)conv3x3_wgrad_wino4p_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        (void)hipFuncSetAttribute((const void*)conv3x3_wgrad_wino4x_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        (void)hipFuncSetAttribute((const void*)conv3x3_wgrad_wino4p_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
     });
     const int grid = p.split * p.co_tiles * p.ci_tiles;
-    if (variant == PESR_WGK_WINO4_PRODUCER) hipLaunchKernelGGL(conv3x3_wgrad_wino4p_kernel<true>, dim3(grid), dim3(P4_NT), ldsx, stream, a);
-    else if (variant == PESR_WGK_WINO4_12W) hipLaunchKernelGGL(conv3x3_wgrad_wino4x_kernel<true>, dim3(grid), dim3(X4_NT), ldsx, stream, a);
-    else if (variant == PESR_WGK_WINO4_12W_1D) hipLaunchKernelGGL(conv3x3_wgrad_wino4x_kernel<false>, dim3(grid), dim3(X4_NT), ldsx, stream, a);
-    else hipLaunchKernelGGL(conv3x3_wgrad_wino4_kernel, dim3(grid), dim3(G4_NT), lds, stream, a);
+    if (variant == PESR_WGK_WINO4_PRODUCER) hipLaunchKernelGGL(conv3x3_wgrad_wino4p_kernel, dim3(grid), dim3(P4_NT), ldsx, stream, a);
+    else hipLaunchKernelGGL(conv3x3_wgrad_wino4x_kernel, dim3(grid), dim3(X4_NT), ldsx, stream, a);
     int rc = pesr_launch_status();
     if (rc) return rc;
     // the partial blocks already are dw in tap order: the direct kernel's fixed-order reduce finishes the job

@@ -38,14 +38,13 @@ int pesr_conv3x3_s2_dgrad_launch(const float* dy, const float* wp, const float* 
 
 size_t pesr_conv3x3_wgrad_ws_bytes(int N, int H, int W, int Cin, int Cout, int stride, int algo);
 // The kernel a weight gradient runs on (include/pesr_hip.h PESR_WGRAD_KERNEL_*): the answer of pesr_conv3x3_wgrad_kernel_impl, the rule
-// pesr_conv3x3_wgrad_launch dispatches by, and (the four F(4,3) values) the `variant` of pesr_conv3x3_wgrad_wino4_launch.
+// pesr_conv3x3_wgrad_launch dispatches by, and (the two F(4,3) values) the `variant` of pesr_conv3x3_wgrad_wino4_launch.
 enum PesrWgradKernel {
     PESR_WGK_DIRECT = 0,          // conv3x3_wgrad_kernel
     PESR_WGK_WINO23 = 1,          // conv3x3_wgrad_wino_kernel
-    PESR_WGK_WINO4_16X16 = 2,     // conv3x3_wgrad_wino4_kernel: 16x16x4 MFMA, 8 waves, 1-D transform
-    PESR_WGK_WINO4_12W_1D = 3,    // conv3x3_wgrad_wino4x_kernel<false>: 32x32x2 MFMA, 12 waves, 1-D transform
-    PESR_WGK_WINO4_12W = 4,       // conv3x3_wgrad_wino4x_kernel<true>: the same kernel with the transform nested in y
-    PESR_WGK_WINO4_PRODUCER = 5   // conv3x3_wgrad_wino4p_kernel<true>: the y-nested transform, staging on four producer waves (the product)
+    // 2, 3: retired (the 16x16x4-MFMA kernel, the 1-D transform on the 12-wave kernel); never answered any more
+    PESR_WGK_WINO4_12W = 4,       // conv3x3_wgrad_wino4x_kernel: F(2,3)y x F(4,3)x on 32x32x2 MFMA, 12 waves that stage and multiply
+    PESR_WGK_WINO4_PRODUCER = 5   // conv3x3_wgrad_wino4p_kernel: the same transform, staging on four producer waves (the product)
 };
 // Host only.  A PesrWgradKernel, or the error the launch returns (PESR_EINVAL, PESR_EWORKSPACE).  ws_bytes: the caller's workspace (a Winograd form that
 // needs more than it is passed over, as the launch always did); a query passes SIZE_MAX.

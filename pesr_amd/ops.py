@@ -146,17 +146,12 @@ USE_WGRAD_WINO = os.environ.get("PESR_WGRAD_WINO", "1") != "0"
 USE_WGRAD_WINO4 = os.environ.get("PESR_WGRAD_WINO4", "1") != "0"   # =0: F(2,3) weight gradient instead of F(4,3)
 
 
-WGRAD_AUTO, WGRAD_DIRECT, WGRAD_WINO23, WGRAD_WINO4_16X16, WGRAD_WINO4_1D, WGRAD_WINO4_12W = 0, 1, 2, 3, 4, 5      # include/pesr_hip.h PESR_WGRAD_*
-# PESR_WGRAD_WINO4_16X16=1: round 2's 16x16x4-MFMA form of the F(4,3) weight gradient instead of the 32x32x2 form (A/B switch)
-USE_WGRAD_WINO4_16X16 = os.environ.get("PESR_WGRAD_WINO4_16X16", "0") == "1"
-# PESR_WGRAD_WINO4_1D=1: round 3's 1-D F(4,3) transform on the 32x32x2 kernel instead of the y-nested one (A/B switch)
-USE_WGRAD_WINO4_1D = os.environ.get("PESR_WGRAD_WINO4_1D", "0") == "1"
+WGRAD_AUTO, WGRAD_DIRECT, WGRAD_WINO23, WGRAD_WINO4_12W = 0, 1, 2, 5      # include/pesr_hip.h PESR_WGRAD_* (3 and 4 are retired)
 # include/pesr_hip.h PESR_WGRAD_KERNEL_* (the answer of pesr_conv3x3_wgrad_kernel) -> (kernel name, fraction of the algorithmic flops it
 # issues on the matrix pipe, the key FLOPS.add files them under)
 _WGRAD_KERNELS = (("conv3x3_wgrad_kernel", 1.0, "direct"),
                   ("conv3x3_wgrad_wino_kernel", 2.0 / 3.0, "F(2,3)"),
-                  ("conv3x3_wgrad_wino4_kernel", 0.5, "F(4,3)"),
-                  ("conv3x3_wgrad_wino4x_kernel", 0.5, "F(4,3)"),
+                  None, None,          # 2, 3: retired, never answered any more (the rows below keep their indices)
                   ("conv3x3_wgrad_wino4x_kernel", 1.0 / 3.0, "F(2,3)y x F(4,3)x"),
                   ("conv3x3_wgrad_wino4p_kernel", 1.0 / 3.0, "F(2,3)y x F(4,3)x"))
 
@@ -167,7 +162,7 @@ def _wgrad_algo():
         return WGRAD_DIRECT
     if not (USE_WINO4 and USE_WGRAD_WINO4):
         return WGRAD_WINO23
-    return WGRAD_WINO4_16X16 if USE_WGRAD_WINO4_16X16 else (WGRAD_WINO4_1D if USE_WGRAD_WINO4_1D else WGRAD_AUTO)
+    return WGRAD_AUTO
 
 
 def _wgrad_kernel(N, H, W, Cin, Cout, stride, ps_in, algo, accumulate):

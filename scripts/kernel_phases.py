@@ -1,6 +1,6 @@
-"""Phase breakdown of the two F(4,3) kernels at the K1 shape from in-kernel real-time stamps (100 MHz counter).
+"""Phase breakdown of the forward F(4,3) kernel at the K1 shape from in-kernel real-time stamps (100 MHz counter).
 
-Needs the diagnostic build made by scripts/build_timing.sh (both kernels with -DPESR_TIMING in exp/libtiming.so); the
+Needs the diagnostic build made by scripts/build_timing.sh (the kernel with -DPESR_TIMING in exp/libtiming.so); the
 product library has no stamps.
 usage: bash scripts/build_timing.sh && PESR_HIP_LIB=exp/libtiming.so python scripts/kernel_phases.py
 """
@@ -42,20 +42,12 @@ def main():
     x = torch.rand(N, H, W, C, device="cuda") - 0.5
     w = (torch.rand(C, C, 3, 3, device="cuda") - 0.5) * 0.1
     b = torch.rand(C, device="cuda")
-    dy = torch.rand(N, H, W, C, device="cuda") - 0.5
     w4 = ops.pack_conv3x3_wino4(w, 0)
     for _ in range(20):
         ops.conv3x3_fwd(x, w4, b, C, act=ops.ACT_RELU)
     torch.cuda.synchronize()
     report("conv3x3_wino4_kernel", stamps("pesr_debug_timing_wino4", 256),
            ["entry", "prologue (chunk 0 staged)", "main loop (16 chunks)", "partial exchange", "stores issued"])
-    for _ in range(20):
-        ops.conv3x3_wgrad(x, dy)
-    torch.cuda.synchronize()
-    t = stamps("pesr_debug_timing_wgrad4", 256)
-    report("conv3x3_wgrad_wino4_kernel", t, ["entry", "strip start (4 rows staged)", "main loop (48 segments)", "G^T + slab store"])
-    d = (t[:, 5] - t[:, 4]) / 100.0
-    print(f"   mid-loop strip change: median {np.median(d):.2f} us, max {d.max():.2f}")
 
 
 if __name__ == "__main__":

@@ -1,8 +1,9 @@
 """Writes wgrad_dispatch.json: which kernel ops.wgrad_kernel_for names for the stride-1 weight gradient, and what ops._wg4_plan_ok
-says of the F(4,3) plan, over a grid of problems and under five settings of the USE_WGRAD_* switches - as answered by the commit this
+says of the F(4,3) plan, over a grid of problems and under the settings of the USE_WGRAD_* switches - as answered by the commit this
 script is run at.  It was run at the commit BEFORE the library's own query (pesr_conv3x3_wgrad_kernel) existed, when both functions
 re-typed the planners of csrc/conv3x3_wgrad_wino4.hip / conv3x3_wgrad_wino.hip in Python; tests/test_wgrad_dispatch_cpu.py holds the
-library's answer to that recording.  No GPU.  Run from the repository root: python tests/golden/make_golden_wgrad_dispatch.py
+library's answer to that recording.  (It then had two more switches and settings, for two F(4,3) kernels retired since: their rows
+were filtered out of the recording, the rest of it is as written then - which is why kernel names 2 and 3 are still in its list.)  No GPU.  Run from the repository root: python tests/golden/make_golden_wgrad_dispatch.py
 """
 import itertools
 import json
@@ -22,10 +23,9 @@ GRID = {"N": [1, 2, 3, 5, 12, 13, 16],
         "Cin": [32, 64, 128, 256],
         "Cout": [64, 96, 192, 512]}
 EXTRA = [[6, 22000, 8, 64, 512]]                    # the 32-bit strip-offset rejection of the side-by-side form (planner only)
-SWITCHES = ("USE_WGRAD_WINO", "USE_WGRAD_WINO4", "USE_WGRAD_WINO4_16X16", "USE_WGRAD_WINO4_1D")
-SETTINGS = [("default", {}), ("USE_WGRAD_WINO=0", {"USE_WGRAD_WINO": False}), ("USE_WGRAD_WINO4=0", {"USE_WGRAD_WINO4": False}),
-            ("USE_WGRAD_WINO4_16X16=1", {"USE_WGRAD_WINO4_16X16": True}), ("USE_WGRAD_WINO4_1D=1", {"USE_WGRAD_WINO4_1D": True})]
-DEFAULTS = {"USE_WGRAD_WINO": True, "USE_WGRAD_WINO4": True, "USE_WGRAD_WINO4_16X16": False, "USE_WGRAD_WINO4_1D": False}
+SWITCHES = ("USE_WGRAD_WINO", "USE_WGRAD_WINO4")
+SETTINGS = [("default", {}), ("USE_WGRAD_WINO=0", {"USE_WGRAD_WINO": False}), ("USE_WGRAD_WINO4=0", {"USE_WGRAD_WINO4": False})]
+DEFAULTS = {"USE_WGRAD_WINO": True, "USE_WGRAD_WINO4": True}
 
 
 def points():

@@ -119,7 +119,7 @@ def test_entry_points_are_declared_and_exported():
         assert name in _lib.SIGNATURES and hasattr(lib, name), name
     header = open(os.path.join(ROOT, "include", "pesr_hip.h")).read()
     assert all(f"int {name}(" in header for name in ENTRY_POINTS) and all(f" {name}(int N, int P, int C);" in header for name in PLANNERS)
-    assert lib.pesr_abi_version() == 19
+    assert lib.pesr_abi_version() == 20
 
 
 def test_c_abi_refuses_before_anything_is_launched():
@@ -144,7 +144,7 @@ def test_c_abi_refuses_before_anything_is_launched():
     for planner in PLANNERS:
         fn = getattr(lib, planner)
         assert fn(2, 16, 96) == 0 and fn(2, 0, 64) == 0 and fn(2, 4097, 64) == 0 and fn(2, 4096, 256) > 0
-    assert lib.pesr_abi_version() == 19
+    assert lib.pesr_abi_version() == 20
 
 
 def test_ops_refuse_host_tensors():

@@ -312,7 +312,7 @@ def test_abi_symbols_and_host_side_refusals():
     lib = _lib.lib()
     for name in names:
         assert re.search(rf"\b{name}\s*\(", header) and name in _lib.SIGNATURES and hasattr(lib, name), name
-    assert lib.pesr_abi_version() == 19
+    assert lib.pesr_abi_version() == 20
     p, big = 0x10000, 1 << 40
     pool = lambda N, H, W, Cc, x=p, y=p: lib.pesr_l2pool_fwd(x, y, N, H, W, Cc, None)
     for c in (0, 3, 32, 96, -64):

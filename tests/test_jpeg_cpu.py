@@ -279,7 +279,7 @@ def test_jpeg_symbols_and_the_host_side_workspace_size():
     from pesr_amd import _lib
     from pesr_amd.jpeg import DESC_WORDS, entry_bytes
     L = _lib.lib()
-    assert "pesr_jpeg_u8" in _lib.SIGNATURES and hasattr(L, "pesr_jpeg_u8") and L.pesr_abi_version() == 19
+    assert "pesr_jpeg_u8" in _lib.SIGNATURES and hasattr(L, "pesr_jpeg_u8") and L.pesr_abi_version() == 20
 
     def size(rows, chroma, n=None):
         d = np.array(rows, dtype=np.int64).reshape(-1, DESC_WORDS)

@@ -175,7 +175,7 @@ def test_c_abi_of_the_gradient_refuses_before_anything_is_launched():
     assert bwd(1, 8, 8, 64, ga=p + 8) == -1 and bwd(1, 8, 8, 64, ga=None) == -1 and bwd(1, 8, 8, 64, g=p + 4) == -1
     assert bwd(1, 8, 8, 64, g=None) == -1 and bwd(1, 8, 8, 64, w=p + 2) == -1
     assert fwd(2, 9, 7, 64, nb=8 * 2 * 1 - 1) == -2 and fwd(1, 8, 8, 64, ws=None, nb=0) == -2
-    assert lib.pesr_abi_version() == 19
+    assert lib.pesr_abi_version() == 20
 
 
 def test_train_flags_default_off_and_refusals(tmp_path, monkeypatch, gpu_untouched):

@@ -133,7 +133,7 @@ def test_c_abi_refuses_before_anything_is_launched():
     assert fwd(1, 11, 11, coef=p, nb=7) == -2                          # a single window still needs its one partial
     assert bwd(1, 64, 64, coef=None) == -1 and bwd(1, 64, 64, g=None) == -1 and bwd(1, 64, 64, ga=None) == -1
     assert bwd(1, 64, 64, coef=p + 4) == -1 and bwd(1, 64, 64, g=p + 4) == -1 and bwd(1, 64, 64, ga=p + 2) == -1
-    assert lib.pesr_abi_version() == 19
+    assert lib.pesr_abi_version() == 20
 
 
 def test_ops_refuse_host_tensors():

@@ -87,7 +87,7 @@ def test_entry_points_are_declared_and_exported():
         assert name in _lib.SIGNATURES and hasattr(lib, name), name
     header = open(os.path.join(ROOT, "include", "pesr_hip.h")).read()
     assert all(f"int {name}(" in header for name in ENTRY_POINTS)
-    assert lib.pesr_abi_version() == 19
+    assert lib.pesr_abi_version() == 20
 
 
 def test_c_abi_refuses_before_anything_is_launched():
@@ -123,7 +123,7 @@ def test_c_abi_refuses_before_anything_is_launched():
     assert loss(2, 4, 64, dg=p + 4) == -1 and loss(2, 4, 64, t=p + 4) == -1
     need = lib.pesr_gram_loss_workspace_bytes(2, 4, 64)
     assert need >= 16 and loss(2, 4, 64, nb=need - 1) == -2 and loss(2, 4, 64, ws=None, nb=0) == -2
-    assert lib.pesr_abi_version() == 19
+    assert lib.pesr_abi_version() == 20
 
 
 def test_ops_refuse_host_tensors():

@@ -11,7 +11,7 @@ import os
 import pytest
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "wgrad_dispatch.json")
-SWITCHES = ("USE_WGRAD_WINO", "USE_WGRAD_WINO4", "USE_WGRAD_WINO4_16X16", "USE_WGRAD_WINO4_1D")
+SWITCHES = ("USE_WGRAD_WINO", "USE_WGRAD_WINO4")
 DIRECT, WINO23 = 0, 1        # indices into the recording's kernel list
 
 
@@ -62,8 +62,7 @@ def test_recording_is_the_grid_the_issue_names(golden):
                               "Cin": [32, 64, 128, 256], "Cout": [64, 96, 192, 512]}
     assert golden["extra"] == [[6, 22000, 8, 64, 512]]
     assert len(golden["points"]) == 7 * 6 * 17 * 4 * 4 + 1
-    assert [r["name"] for r in golden["settings"]] == ["default", "USE_WGRAD_WINO=0", "USE_WGRAD_WINO4=0", "USE_WGRAD_WINO4_16X16=1",
-                                                       "USE_WGRAD_WINO4_1D=1"]
+    assert [r["name"] for r in golden["settings"]] == ["default", "USE_WGRAD_WINO=0", "USE_WGRAD_WINO4=0"]
     for r in golden["settings"]:
         assert len(r["kernel"]) == len(r["covered"]) == len(r["side"]) == len(golden["points"])
     default = golden["settings"][0]
@@ -111,6 +110,10 @@ def test_query_knows_the_rules_the_mirror_did_not():
     assert q(16, 48, 48, 64, 192, 1, 1, 0, 0) == 0                       # ps_in, Cout % 256: neither Winograd form
     assert q(16, 48, 94, 64, 64, 1, 0, 0, 0) == 1 and q(16, 48, 94, 64, 64, 1, 0, 0, 1) == 0           # F(2,3) cannot accumulate
     assert q(16, 48, 48, 256, 256, 1, 0, 0, 1) == 5                      # ... the F(4,3) kernels can
-    assert [q(16, 48, 48, 256, 256, 1, 0, a, 0) for a in range(6)] == [5, 0, 1, 2, 3, 4]
-    assert q(16, 24, 24, 256, 256, 1, 0, 3, 0) == 0                      # side by side strips: not on the 16x16x4 kernel (nor F(2,3): W < 48)
+    assert [q(16, 48, 48, 256, 256, 1, 0, a, 0) for a in (0, 1, 2, 5)] == [5, 0, 1, 4]
+    assert q(16, 48, 48, 256, 256, 1, 0, 3, 0) < 0 and q(16, 48, 48, 256, 256, 1, 0, 4, 0) < 0        # the retired algorithms
+    L = _lib.lib()           # ... which the call and the workspace query refuse too (a null workspace: nothing is launched either way)
+    assert [L.pesr_conv3x3_wgrad(None, None, None, None, 16, 48, 48, 256, 256, 1, 1.0, 0, a, 0, None, 1 << 40, None) for a in (3, 4, 5)] == [-1, -1, -2]
+    assert [L.pesr_conv3x3_wgrad_workspace_bytes(16, 48, 48, 256, 256, 1, a) > 0 for a in (3, 4, 5)] == [False, False, True]
+    assert q(16, 24, 24, 256, 256, 1, 0, 5, 0) == 4                      # side by side strips: every F(4,3) kernel that is left does them
     assert q(16, 48, 48, 256, 256, 2, 0, 0, 0) == 0 and q(16, 48, 48, 256, 256, 1, 0, 6, 0) < 0
