@@ -97,7 +97,7 @@ struct Wino4Args {
 constexpr int W4_BN = 64, W4_MG = 9;
 
 // output (m-tile i, k) of lane r of the xi-half wave xt -> (inside the image, element offset of its four channels co ..): the epilogue's
-// out_index, for the TAIL form.  (The epilogue keeps its lambda: routed through this function, hipcc allocates the registers of the sixteen
+// out_index, for the TAIL form.  (The epilogue keeps its lambda: routed through this function, hipcc allocates the registers of the
 // instantiations without TAIL differently, and they are held to the text they compiled to before - docs/experiments/wino4_tail.md.)
 __device__ __forceinline__ bool w4_out_index(const Wino4Args& a, const int TXTv, const int img, const size_t img_out, const int gy0, const int gt0,
                                              const int xt, const int r, const int co, const int i, const int k, size_t* idx) {
@@ -123,7 +123,7 @@ __device__ __forceinline__ bool w4_out_index(const Wino4Args& a, const int TXTv,
 // Wave w owns the 16 channels w & 3 and HALF of the xi planes (w >> 2: xi 0..2 / 3..5): 27 accumulator tiles, 2 waves per SIMD.
 // (A 12-wave variant - a third of the xi planes per wave, 3 waves per SIMD in the 168-VGPR budget - measured 2 % slower.)
 
-// DENSE = false: the swizzle key of the rows of 8 / 12 / 16 / 24 x-tiles (the layers that matter), a_off ^ kxor for odd ky.
+// DENSE = false: the swizzle key of the rows of 8 / 12 / 16 / 24 x-tiles (the layers that matter); for odd ky the row term of 12 flips (a_key).
 // DENSE = true: any row length.  A V row is padded so that the 64-byte entries of consecutive x-tiles m = row * TXT + txt of one
 // xi plane fall into 64-byte slots m mod 4 of the 256-byte bank window, and the 16-byte sub-slot is rotated by (m >> 2) & 3:
 // the 16 lanes of a fragment read (16 consecutive m) then touch every bank once.  The key of the row ky below is a different
@@ -135,20 +135,19 @@ __device__ __forceinline__ bool w4_out_index(const Wino4Args& a, const int TXTv,
 // BNF: the instantiation carries the BatchNorm-sums epilogue (common.h BnEpi; the Discriminator's layers).  false: none of that code -
 // the Generator's / VGG's kernels keep the register allocation they had (with it, the 18 prefetched z values of mode 2 cost the
 // 48-wide instantiation 52 bytes of scratch in its epilogue).
-// LOOP: the chunk loop of wino4_loop.md (docs/experiments): the last chunk peeled off, so that it stages and prefetches nothing, and the
-// first fragment read of a chunk issued in front of its staging loads.  false: the loop as it was before, selected by PESR_WINO4_LOOP=0
-// (same products, same order of additions: tests/test_wino4_loop_gpu.py compares the two with torch.equal).
-// TAIL: the peeled last chunk of the LOOP form runs its MFMAs group-major (all nine slabs for m-tiles 0..2, then 3..5, then 6..8: each
+// The chunk loop (its history and measurements: docs/experiments/wino4_loop.md): the last chunk is peeled off, so that it stages and
+// prefetches nothing, and the first fragment read of a chunk is issued in front of its staging loads.
+// TAIL: the peeled last chunk runs its MFMAs group-major (all nine slabs for m-tiles 0..2, then 3..5, then 6..8: each
 // accumulator still gets ky = 0, 1, 2 and kk = 0..3 in that order), and a group's output transform, exchange and stores run as soon as its
 // accumulators are final - under the MFMAs of the groups behind it - instead of all 18 stores of a lane in one burst at the kernel's end
 // (docs/experiments/wino4_tail.md).  For launches of one round of workgroups with the swizzled 12- / 24-x-tile rows, no split-K, no
-// BatchNorm; PESR_WINO4_TAIL=0 selects the LOOP form without it (same bits: tests/test_wino4_tail_gpu.py).
+// BatchNorm; PESR_WINO4_TAIL=0 selects the form without it (same bits: tests/test_wino4_tail_gpu.py).
 constexpr int W4_TAIL_SLOTS = 2 * 3 * 2 * 4 * 64 * 16;     // one group's exchange slots: 2 senders x 3 m-tiles x 2 x 4 channel blocks x 64 lanes x 16 B
-template <bool DENSE, int TXTC, bool BNF = false, bool LOOP = true, bool TAIL = false>
+template <bool DENSE, int TXTC, bool BNF = false, bool TAIL = false>
 __global__ __launch_bounds__(512) void conv3x3_wino4_kernel(const Wino4Args a, const BnEpi bn_arg) {
     (void)bn_arg;                                          // BatchNorm sums from the epilogue (common.h BnEpi): read through pesr_bn_epi() behind the main loop
     static_assert(!(DENSE && TXTC), "the constant-row-length form is for the non-dense layout");
-    static_assert(!TAIL || (LOOP && TXTC && !BNF), "the TAIL form is for the LOOP form of the constant-row-length kernels without BatchNorm");
+    static_assert(!TAIL || (TXTC && !BNF), "the TAIL form is for the constant-row-length kernels without BatchNorm");
     constexpr int NT = 512;                                // threads of the workgroup
     constexpr int NXL = 3;                                 // xi planes per wave
     constexpr int NSLAB = 3 * NXL;                         // weight slabs per wave and chunk: (ky, xl)
@@ -189,7 +188,7 @@ __global__ __launch_bounds__(512) void conv3x3_wino4_kernel(const Wino4Args a, c
     const int CB = ks * a.chunks_per_split;                // this workgroup's chunk range [CB, CB + C16)
     const int C16 = (C16T - CB) < a.chunks_per_split ? (C16T - CB) : a.chunks_per_split;
 
-    // ---- A fragment offsets: lane (r, g) reads k-group g of x-tile m = 16 i + r (for an even ky; odd ky: ^ kxor) -------------
+    // ---- A fragment offsets: lane (r, g) reads k-group g of x-tile m = 16 i + r (for an even ky; odd ky: a_key below) --------
     const unsigned lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) char*)smem;   // LDS address of the dynamic segment (a multiple of 256)
     int a_off[W4_MG];
     unsigned ktab1 = 0, ktab2 = 0;                         // DENSE: (key(ky) ^ key(0)) << 4 for m-tile i at bits [2i + 4, 2i + 6)
@@ -212,7 +211,6 @@ __global__ __launch_bounds__(512) void conv3x3_wino4_kernel(const Wino4Args a, c
             a_off[i] += (int)lds0;
         }
     };
-    const int kxor = a.row_key * 16;                       // the key's row term flips with the parity of ky
 
     // ---- B: this lane's 16 bytes of slab (ky, xi, chunk): wave-uniform slab base (SGPRs) + one per-lane 32-bit byte offset ----
     // (a buffer load: the slab offset is a scalar operand, so a weight fetch needs no 64-bit vector address arithmetic; the packed
@@ -312,24 +310,22 @@ __global__ __launch_bounds__(512) void conv3x3_wino4_kernel(const Wino4Args a, c
         for (int i = 0; i < W4_MG; ++i) acc[xl][i] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
     f32x4 fa[2][3], fb[3];
-    // The key's row term is there for rows of 12 x-tiles only (row_key: TXT % 8 == 4), and those run on TXTC = 12.  The LOOP form uses
-    // that: no xor at all for the other row lengths, and for 12 the nine offsets of the odd ky live in registers of their own, kept up
-    // with a_off - 27 v_xor fewer per chunk and wave, and hipcc allocates 228 VGPRs instead of 246 (G body 171.1 -> 167.2 us with bias +
-    // ReLU, 173.8 -> 169.7 with the skip, 174.2 -> 169.8 with the mask: docs/experiments/wino4_loop.md).
-    // The form before redoes the xor at every use: hoisted out of ITS loop it cost nine more live registers of the 254.
-    constexpr bool ODD = LOOP && !DENSE;
+    // The key's row term is there for rows of 12 x-tiles only (row_key: TXT % 8 == 4; the launcher refuses any other non-dense row length
+    // with a row term), and those run on TXTC = 12.  So there is no xor at all for the other row lengths, and for 12 the row term flips
+    // with the parity of ky (^ 2 * 16 bytes): the nine offsets of the odd ky live in registers of their own, kept up with a_off.  Against
+    // an xor at every use that is 27 v_xor fewer per chunk and wave, and hipcc allocates 228 VGPRs instead of 246 (G body 171.1 -> 167.2 us
+    // with bias + ReLU, 173.8 -> 169.7 with the skip, 174.2 -> 169.8 with the mask: docs/experiments/wino4_loop.md).
+    constexpr bool ODD = !DENSE;
     constexpr int KX = TXTC == 12 ? 32 : 0;
     static_assert(TXTC == 0 || TXTC == 12 || TXTC == 24, "KX: the row term of the key for a constant row length");
     int a_odd[W4_MG];
-    auto opaque = [](int v) -> int { asm volatile("" : "+s"(v)); return v; };
     auto a_key = [&](const int i, const int ky) -> int {   // fragment offset of m-tile i for the V row ky below the tile row
         if (DENSE) {
             if (ky == 0) return a_off[i];
             const unsigned tab = ky == 1 ? ktab1 : ktab2;
             return a_off[i] ^ (int)((tab >> (2 * i)) & 0x30u);
         }
-        if (ODD) return ((ky & 1) && KX) ? a_odd[i] : a_off[i];
-        return (ky & 1) ? (a_off[i] ^ opaque(kxor)) : a_off[i];
+        return ((ky & 1) && KX) ? a_odd[i] : a_off[i];
     };
     // Fragment reads through 32-bit LDS addresses (a_off carries the dynamic-LDS base, added once): written as `smem + offset`
     // every read paid a v_add_u32 of the base's relocation - a literal 0 hipcc cannot fold (36 per chunk and wave).
@@ -385,18 +381,19 @@ __global__ __launch_bounds__(512) void conv3x3_wino4_kernel(const Wino4Args a, c
     __syncthreads();
     W4_STAMP(1)
 
-    // One chunk, as a macro so that the loop and the peeled copy are the same text (and the LOOP = false kernels the same instructions as
-    // before).  LAST: the peeled last chunk of the LOOP form, which has no successor - it stages nothing and fetches no weights beyond its
-    // own.  The loop itself has no branch: with the prefetch under `if (more)` the staging registers and weight fragments had two
-    // definitions merging at the loop header, and hipcc could not count the outstanding loads exactly.  So the form before (LOOP = false)
-    // lets the last chunk "prefetch" itself again (loads, transforms and LDS stores nobody consumes), and the LOOP form runs the loop over
-    // all chunks but the last and the body once more behind it: the loop waits for vmcnt(8), (8), (2) .. as before, the copy ends on
-    // vmcnt(1), (0) (docs/experiments/wino4_loop.md).  In the body: the weight slab s + 2 (of this chunk, or the first ones of the next)
-    // is fetched at the top of slab s; each group's sched_barrier pair keeps the next group's fragment reads ahead of its 12 MFMAs (hipcc
-    // sinks them next to their use); a third / two thirds in, the staged loads have landed and are transformed into the other V buffer
-    // under the MFMAs, at raised priority - a staging wave's VALU instructions and LDS stores then issue ahead of the other wave's MFMAs
-    // instead of between them (G body 172.0 -> 171.2 us with bias + ReLU, 176.0 -> 174.3 with the skip, 177.3 -> 175.2 with the mask).
-    // LOOP: the chunk's first fragment read goes in front of the six staging loads - every wave comes out of the barrier waiting for it.
+    // One chunk, as a macro so that the loop and the peeled copy are the same text.  LAST: the peeled last chunk, which has no successor -
+    // it stages nothing and fetches no weights beyond its own.  The loop itself has no branch: with the prefetch under `if (more)` the
+    // staging registers and weight fragments had two definitions merging at the loop header, and hipcc could not count the outstanding
+    // loads exactly.  So the loop runs over all chunks but the last, and the body once more behind it (a last chunk inside the loop would
+    // have to "prefetch" itself again: loads, transforms and LDS stores nobody consumes): the loop waits for vmcnt(8), (8), (2) .., the
+    // copy ends on vmcnt(1), (0) (docs/experiments/wino4_loop.md).  In the body: the weight slab s + 2 (of this chunk, or the first ones
+    // of the next) is fetched at the top of slab s; each group's sched_barrier pair keeps the next group's fragment reads ahead of its 12
+    // MFMAs (hipcc sinks them next to their use); a third / two thirds in, the staged loads have landed and are transformed into the
+    // other V buffer under the MFMAs, at raised priority - a staging wave's VALU instructions and LDS stores then issue ahead of the other
+    // wave's MFMAs instead of between them (G body 172.0 -> 171.2 us with bias + ReLU, 176.0 -> 174.3 with the skip, 177.3 -> 175.2 with
+    // the mask).  The chunk's first fragment read goes in front of the six staging loads - every wave comes out of the barrier waiting
+    // for it.  (cn, the next chunk, is CB + (c + 1) in that association: from (CB + c) + 1 hipcc derives the weight slabs' scalar offsets
+    // differently in every instantiation - docs/experiments/wino4_retire.md.)
 #ifdef W4_NO_BARRIER
 #define W4_CHUNK_BARRIER()
 #else
@@ -405,15 +402,10 @@ __global__ __launch_bounds__(512) void conv3x3_wino4_kernel(const Wino4Args a, c
 #define W4_CHUNK(c, LAST)                                                                                                                                                   \
         char* const vcur = smem + (c & 1) * v_bytes;                                                                                                                        \
         char* const vnext = smem + ((c & 1) ^ 1) * v_bytes;                                                                                                                 \
-        const int cn = CB + (LOOP ? c + 1 : (c + 1 < C16 ? c + 1 : c));                                                                                                     \
-        if (LOOP) {                                                                                                                                                         \
-            W4_READ_A(fa[0], vcur, 0, 0, 0)                                                                                                                                 \
-            W4_FENCE()                                                                                                                                                      \
-            if (!LAST) stage_load(0, cn);                                                                                                                                   \
-        } else {                                                                                                                                                            \
-            stage_load(0, cn);                                                                                                                                              \
-            W4_READ_A(fa[0], vcur, 0, 0, 0)                                                                                                                                 \
-        }                                                                                                                                                                   \
+        const int cn = CB + (c + 1);                                                                                                                                        \
+        W4_READ_A(fa[0], vcur, 0, 0, 0)                                                                                                                                     \
+        W4_FENCE()                                                                                                                                                          \
+        if (!LAST) stage_load(0, cn);                                                                                                                                       \
 _Pragma("unroll")                                                                                                                                                           \
         for (int s = 0; s < NSLAB; ++s) {                                                                                                                                   \
             const int ky = s / NXL, xl = s - ky * NXL;                                                                                                                      \
@@ -443,14 +435,9 @@ _Pragma("unroll")                                                               
         W4_STAMP(2 + 2 * (c < 16 ? c : 15))                                                                                                                                 \
         W4_CHUNK_BARRIER()                                                                                                                                                  \
         W4_STAMP(3 + 2 * (c < 16 ? c : 15))
-    if (LOOP) {
 #pragma unroll 1
-        for (int c = 0; c + 1 < C16; ++c) { W4_CHUNK(c, false) }
-        if (!TAIL) { const int c = C16 - 1; W4_CHUNK(c, true) }
-    } else {
-#pragma unroll 1
-        for (int c = 0; c < C16; ++c) { W4_CHUNK(c, false) }
-    }
+    for (int c = 0; c + 1 < C16; ++c) { W4_CHUNK(c, false) }
+    if (!TAIL) { const int c = C16 - 1; W4_CHUNK(c, true) }
 #ifdef W4_STAMPS
 #define W4_STAMPS_OUT()                                                                                                                     \
     W4_STAMP(36)                                                                                                                            \
@@ -682,10 +669,9 @@ _Pragma("unroll")                                                               
     // (Round 4 measured the skip / mask loads issued ONE BATCH AHEAD, the first batch's in front of the exchange barrier: 175.9 vs
     // 172.6 us with bias + ReLU, 179.4 vs 177.1 with the skip, 179.0 vs 177.3 with the mask - slower in every form; and a PERSISTENT
     // launch form for the layers with several rounds of workgroups per CU - 256 workgroups walking their tiles, the next tile's first
-    // chunk staged under the last chunk, the exchange in three batches inside the dead V buffer: bit-identical and 7 - 32 % SLOWER
-    // (scripts/diag/conv3x3_wino4_persist.hip): a wave's vmcnt retires in order, so a persistent wave cannot wait for its next loads
-    // without waiting for its own output stores, while the NEXT workgroup's prologue on the same CU overlaps them for free.
-    // profiles/r04_ab_notes.txt)
+    // chunk staged under the last chunk, the exchange in three batches inside the dead V buffer: bit-identical and 7 - 32 % SLOWER:
+    // a wave's vmcnt retires in order, so a persistent wave cannot wait for its next loads without waiting for its own output stores,
+    // while the NEXT workgroup's prologue on the same CU overlaps them for free.  profiles/r04_ab_notes.txt)
 #pragma unroll
     for (int ib = 0; ib < W4_MG; ib += 3) {
         f32x4 v[6], mkv[6], skv[6];
@@ -877,7 +863,7 @@ int pesr_conv3x3_wino4_launch(const float* x, const float* wp, const float* bias
     a.TR = p.TR; a.TXT = p.TXT; a.HT = p.TR + 2;
     a.tiles_x = p.tiles_x; a.tiles_y = p.tiles_y; a.n_tiles = p.n_tiles;
     a.row_key = (p.TXT % 8 == 4) ? 2 : 0;
-    if (!p.dense && p.TXT != 12 && a.row_key) return PESR_EINVAL;   // the LOOP form relies on it: a row term only on the TXTC = 12 kernels
+    if (!p.dense && p.TXT != 12 && a.row_key) return PESR_EINVAL;   // the chunk loop relies on it (a_key): a row term only on the TXTC = 12 kernels
     a.ksplit = p.ksplit; a.chunks_per_split = p.chunks_per_split; a.slab = (float*)ws;
     a.stack = p.stack; a.stack_n = N; a.v_row = p.v_row;
     if (p.stack) a.N = 1;
@@ -887,39 +873,35 @@ int pesr_conv3x3_wino4_launch(const float* x, const float* wp, const float* bias
         bn.beta = fuse->beta; bn.slope = fuse->slope;
         if (p.ksplit > 1) { bn_fin = bn; bn = BnEpi{}; }      // the conv kernel stores raw partial sums: the finish kernel does the BatchNorm part
     }
-    // PESR_WINO4_LOOP=0: the chunk loop as it was before the LOOP form (read at every launch: an A/B switch, and the bit-identity test's)
-    const char* const loop_env = getenv("PESR_WINO4_LOOP");
-    const bool loop = !(loop_env && loop_env[0] == '0' && !loop_env[1]);
     size_t lds = p.lds;
 #ifdef W4_STAMPS
     if (p.lds > (size_t)W4_ST_LDS) return PESR_EINVAL;
     lds = (size_t)W4_ST_LDS + 8 * W4_ST_SLOTS * sizeof(unsigned long long);
 #endif
     const dim3 grid((unsigned)(p.tiles * p.ksplit));
-    // PESR_WINO4_TAIL=0: the LOOP form without the TAIL form's last chunk (read at every launch, like PESR_WINO4_LOOP).  The form is for
-    // one round of workgroups: with more, the next workgroup's prologue on the CU already runs under the stores of the one before.
+    // PESR_WINO4_TAIL=0: the kernel without the TAIL form's last chunk (read at every launch: an A/B switch, and the bit-identity test's).
+    // The form is for one round of workgroups: with more, the next workgroup's prologue on the CU already runs under the stores of the
+    // one before.
     const char* const tail_env = getenv("PESR_WINO4_TAIL");
-    const bool tail = loop && !(tail_env && tail_env[0] == '0' && !tail_env[1]) && p.ksplit == 1 && !bn.mode && !p.dense &&
+    const bool tail = !(tail_env && tail_env[0] == '0' && !tail_env[1]) && p.ksplit == 1 && !bn.mode && !p.dense &&
                       (p.TXT == 12 || p.TXT == 24) && (size_t)(p.TR + 2) * p.v_row >= (size_t)W4_TAIL_SLOTS && p.tiles <= 256 && !(mask && skip);
-    static PesrDeviceOnce attr_once[18];
+    static PesrDeviceOnce attr_once[10];
 #define W4_LAUNCH(ID, ...)                                                                                                  \
     {                                                                                                                       \
         attr_once[ID]([&] { (void)hipFuncSetAttribute((const void*)conv3x3_wino4_kernel<__VA_ARGS__>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); }); \
         hipLaunchKernelGGL((conv3x3_wino4_kernel<__VA_ARGS__>), grid, dim3(512), lds, stream, a, bn);                        \
     }
-#define W4_LAUNCH_LOOP(ID, ...) { if (loop) W4_LAUNCH(2 * (ID), __VA_ARGS__, true) else W4_LAUNCH(2 * (ID) + 1, __VA_ARGS__, false) }
     if (bn.mode) {
-        if (p.dense) W4_LAUNCH_LOOP(0, true, 0, true)
-        else if (p.TXT == 12) W4_LAUNCH_LOOP(1, false, 12, true)
-        else if (p.TXT == 24) W4_LAUNCH_LOOP(2, false, 24, true)
-        else W4_LAUNCH_LOOP(3, false, 0, true)
-    } else if (tail && p.TXT == 12) W4_LAUNCH(16, false, 12, false, true, true)
-    else if (tail) W4_LAUNCH(17, false, 24, false, true, true)
-    else if (p.dense) W4_LAUNCH_LOOP(4, true, 0, false)
-    else if (p.TXT == 12) W4_LAUNCH_LOOP(5, false, 12, false)
-    else if (p.TXT == 24) W4_LAUNCH_LOOP(6, false, 24, false)
-    else W4_LAUNCH_LOOP(7, false, 0, false)
-#undef W4_LAUNCH_LOOP
+        if (p.dense) W4_LAUNCH(0, true, 0, true)
+        else if (p.TXT == 12) W4_LAUNCH(1, false, 12, true)
+        else if (p.TXT == 24) W4_LAUNCH(2, false, 24, true)
+        else W4_LAUNCH(3, false, 0, true)
+    } else if (tail && p.TXT == 12) W4_LAUNCH(4, false, 12, false, true)
+    else if (tail) W4_LAUNCH(5, false, 24, false, true)
+    else if (p.dense) W4_LAUNCH(6, true, 0, false)
+    else if (p.TXT == 12) W4_LAUNCH(7, false, 12, false)
+    else if (p.TXT == 24) W4_LAUNCH(8, false, 24, false)
+    else W4_LAUNCH(9, false, 0, false)
 #undef W4_LAUNCH
     if (p.ksplit > 1 && bn_fin.mode)
         return pesr_conv_splitk_finish_bn_launch((const float*)ws, bias, y, (long)N * H * W * Cout, Cout, p.ksplit, alpha, bn_fin, stream);

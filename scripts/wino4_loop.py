@@ -1,13 +1,13 @@
 """Where the F(4,3) forward / input-gradient kernel's time goes at the G-body shape ([16,48,48,256] -> 256), per phase and per ablation,
-and the A/B of its chunk loops: the loop before (PESR_WINO4_LOOP=0), the new loop (PESR_WINO4_TAIL=0) and the new loop with the TAIL
-form of its last chunk (docs/experiments/wino4_loop.md, wino4_tail.md).
+and the A/B of its two loops: the chunk loop (PESR_WINO4_TAIL=0) and the same loop with the TAIL form of its last chunk
+(docs/experiments/wino4_loop.md, wino4_tail.md; the loop before them was retired: docs/experiments/wino4_retire.md).
 
     python scripts/wino4_loop.py build            # no GPU needed: conv3x3_wino4.hip once per variant (-DW4_STAMPS, -DW4_NO_*), each linked
                                                   # with the objects of the regular build into a library of its own, exp/libw4_<variant>.so
     python scripts/wino4_loop.py run [--doc F]    # on the GPU: every variant in a child process of its own under `timeout`, stopping at the
                                                   # first one that fails; then the tables go into F between its table markers
                                                   # (default: docs/experiments/wino4_tail.md; wino4_loop.md keeps the tables of its change)
-    python scripts/wino4_loop.py one LIB OUT.json # what a child does: time LIB in the three forms under the three loops (and read its stamps)
+    python scripts/wino4_loop.py one LIB OUT.json # what a child does: time LIB in the three forms under the two loops (and read its stamps)
 
 The variants never go into libpesr_hip.so, and all but `base` and `no_fences` compute wrong results: they are for timing only."""
 import ctypes
@@ -30,9 +30,9 @@ WHAT = {"base": "the product", "stamps": "the product with stamps", "no_xform": 
         "no_exchange": "no epilogue exchange", "mfma_only": "nothing but the MFMAs in the loop", "mfma_only_no_exchange": "the same, and no exchange",
         "no_fences": "no sched_barrier pairs (right results)"}
 FORMS = ("bias + ReLU", "skip", "mask")
-LOOPS = ("old", "new", "tail")
-LOOP_ENV = {"old": {"PESR_WINO4_LOOP": "0"}, "new": {"PESR_WINO4_TAIL": "0"}, "tail": {}}
-LOOP_NAME = {"old": "loop before (`PESR_WINO4_LOOP=0`)", "new": "new loop (`PESR_WINO4_TAIL=0`)", "tail": "new loop with the TAIL form"}
+LOOPS = ("new", "tail")
+LOOP_ENV = {"new": {"PESR_WINO4_TAIL": "0"}, "tail": {}}
+LOOP_NAME = {"new": "loop without the TAIL form (`PESR_WINO4_TAIL=0`)", "tail": "loop with the TAIL form"}
 N, H, W, C = 16, 48, 48, 256
 CHUNKS = C // 16
 BEGIN, END = "<!-- wino4_loop.py: tables -->", "<!-- wino4_loop.py: end of tables -->"
@@ -102,9 +102,8 @@ def one(path, out):
         return statistics.median(us), min(us), max(us)
 
     res = {"lib": os.path.basename(path), "us": {}, "stamps": {}}
-    for loop in ("tail", "new", "old"):
-        for k in ("PESR_WINO4_LOOP", "PESR_WINO4_TAIL"):
-            os.environ.pop(k, None)
+    for loop in ("tail", "new"):
+        os.environ.pop("PESR_WINO4_TAIL", None)
         os.environ.update(LOOP_ENV[loop])
         for form in FORMS:
             res["us"][f"{loop}/{form}"] = timed(form)
@@ -167,11 +166,11 @@ def tables(results):
                 continue
             u = results[name]["us"]
             lines.append(f"| `{name}`: {WHAT[name]} | " + " | ".join("%.1f (%+.1f)" % (u[f"{loop}/{f}"][0], u[f"{loop}/{f}"][0] - base[f"{loop}/{f}"][0]) for f in FORMS) + " |")
-    lines += ["", "### The three loops, same library, same process", "",
-              "| form | loop before | new loop | with TAIL | new - before | TAIL - new | spread of the five (before / new / TAIL) |", "|---|---|---|---|---|---|---|"]
+    lines += ["", "### The two loops, same library, same process", "",
+              "| form | without TAIL | with TAIL | TAIL - without | spread of the five (without / TAIL) |", "|---|---|---|---|---|"]
     for f in FORMS:
-        o, n, t = base[f"old/{f}"], base[f"new/{f}"], base[f"tail/{f}"]
-        lines.append(f"| {f} | {o[0]:.2f} | {n[0]:.2f} | {t[0]:.2f} | {n[0] - o[0]:+.2f} | {t[0] - n[0]:+.2f} | {o[2] - o[1]:.2f} / {n[2] - n[1]:.2f} / {t[2] - t[1]:.2f} |")
+        n, t = base[f"new/{f}"], base[f"tail/{f}"]
+        lines.append(f"| {f} | {n[0]:.2f} | {t[0]:.2f} | {t[0] - n[0]:+.2f} | {n[2] - n[1]:.2f} / {t[2] - t[1]:.2f} |")
     return "\n".join(lines) + "\n"
 
 

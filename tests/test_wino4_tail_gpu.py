@@ -1,12 +1,15 @@
-"""GPU: the TAIL form of the F(4,3) kernel (conv3x3_wino4.hip) - the last chunk run group-major, each group of three m-tiles transformed,
-exchanged and stored under the MFMAs of the groups behind it - against the form without it (PESR_WINO4_TAIL=0) and against the oracle.
+"""GPU: the F(4,3) kernel (conv3x3_wino4.hip) in both forms of its last chunk, against each other and against the oracle: the TAIL form -
+the last chunk run group-major, each group of three m-tiles transformed, exchanged and stored under the MFMAs of the groups behind it - and
+the form without it (PESR_WINO4_TAIL=0), which is also what split-K, the dense layout, BatchNorm and multi-round launches run.
 
 Every case runs the kernel through the C ABI twice, with PESR_WINO4_TAIL unset and set to 0: the two results are the same bits
-(torch.equal: same products, same order of additions), and each is within 1e-5 of the oracle's maximum - the bound
-tests/test_wino4_loop_gpu.py holds this kernel to.  The shapes: one chunk (weight slabs 0 and 1 from the prologue), two and three chunks,
-24-x-tile rows, tile rows past the image (masked stores in every group), several tiles with two n-tiles; with bias + ReLU, skip with
-alpha, mask, and the fused PixelShuffle on either side.  The dense layout, split-K and the BatchNorm epilogue in both modes never take
-the TAIL form: they must run the kernel they ran before and agree all the same."""
+(torch.equal: same products, same order of additions), and each is within 1e-5 of the oracle's maximum - the bound tests/test_conv_gpu.py
+holds this kernel to.  The shapes are the smallest that reach the chunk loop's edges: one chunk (the loop body not at all: weight slabs 0
+and 1 from the prologue), two and three chunks (the body once, twice in front of the peeled chunk), 24-x-tile rows, tile rows past the
+image (masked stores in every group), several tiles with two n-tiles; with bias + ReLU, skip with alpha, mask, and the fused PixelShuffle
+on either side.  Rows of 8 and 16 x-tiles (row length at run time) with and without a ragged edge, the dense layout, split-K, stacked
+images and the BatchNorm epilogue in both modes (all four of its instantiations) never take the TAIL form: they must run the kernel
+they ran before and agree all the same.  A launch refuses BatchNorm sums whose rows are not the rows of `part`."""
 import os
 
 import pytest
@@ -57,8 +60,13 @@ TAIL_SHAPES = [
     (3, 12, 48, 32, 128),     # several tiles and two n-tiles
 ]
 FALLBACK_SHAPES = [
-    (1, 12, 24, 32, 64),      # dense layout
+    (1, 12, 24, 32, 64),      # rows of 8 x-tiles (the row length at run time), six of them and 12 of the 18 tile rows inside the image
+    (1, 12, 20, 48, 64),      # the same with a ragged edge: five x-tiles
     (2, 12, 12, 512, 512),    # split-K
+    (16, 12, 12, 512, 512),   # stacked images (and split-K), in the dense layout: rows of 3 x-tiles
+    (1, 18, 32, 32, 64),      # rows of 8 x-tiles, the 18 x 8 tile full
+    (1, 9, 64, 32, 64),       # rows of 16 x-tiles
+    (1, 16, 36, 32, 64),      # dense layout: rows of 9 x-tiles
 ]
 
 
@@ -80,7 +88,7 @@ def test_forms_of_the_epilogue(monkeypatch, N, H, W, Cin, Cout):
         close(_nchw(old), want[form], TOL, what=f"{form}, PESR_WINO4_TAIL=0")
 
 
-@pytest.mark.parametrize("Cin", [16, 32])
+@pytest.mark.parametrize("Cin", [16, 32, 48])
 def test_pixel_shuffle_on_either_side(monkeypatch, Cin):
     from pesr_amd import ops
     N, H, W, C = 1, 12, 48, 64
@@ -97,9 +105,15 @@ def test_pixel_shuffle_on_either_side(monkeypatch, Cin):
     close(_nchw(new), dx_ref, TOL, what="ps_in, TAIL"); close(_nchw(old), dx_ref, TOL, what="ps_in, PESR_WINO4_TAIL=0")
 
 
-def test_batchnorm_epilogue_both_modes(monkeypatch):
+# H, W, Cin: rows of 12 x-tiles with one, two and three chunks; of 24; of 8 (row length at run time: tile partly, then wholly inside the
+# image); the dense layout (rows of 9)
+BN_SHAPES = [(12, 48, 16), (12, 48, 32), (12, 48, 48), (6, 96, 32), (12, 24, 32), (18, 32, 32), (16, 36, 32)]
+
+
+@pytest.mark.parametrize("H,W,Cin", BN_SHAPES)
+def test_batchnorm_epilogue_both_modes(monkeypatch, H, W, Cin):
     from pesr_amd import ops
-    N, H, W, C, Cin = 1, 12, 48, 64, 32
+    N, C = 1, 64
     # mode 1: z = conv(x) and the sums of z, z^2 per pixel tile
     x = _rand(N, Cin, H, W, seed=1); w = _rand(C, Cin, 3, 3, seed=2, scale=0.1)
     xg = _nhwc(x); wf = ops.pack_conv3x3_wino4(w.cuda(), 0)
@@ -121,3 +135,31 @@ def test_batchnorm_epilogue_both_modes(monkeypatch):
     far = (zz.abs() > 1e-5).float()                       # at the kink the sign of bn(z) is a matter of rounding
     want = torch.where(zz > 0, dx_ref, 0.2 * dx_ref) * far
     close(_nchw(gm) * far, want, TOL, what="g', TAIL"); close(_nchw(gm0) * far, want, TOL, what="g', PESR_WINO4_TAIL=0")
+
+
+def test_bn_rows_must_equal_the_rows_of_part():
+    from pesr_amd import _lib, ops
+    import ctypes
+    N, H, W, Cin, C = 1, 12, 48, 32, 64
+    xg = _nhwc(_rand(N, Cin, H, W, seed=1)); wf = ops.pack_conv3x3_wino4(_rand(C, Cin, 3, 3, seed=2, scale=0.1).cuda(), 0)
+    rows = ops.conv_bn_rows(2, N, H, W, Cin, C, 1)
+    assert rows > 0
+    y = torch.empty((N, H, W, C), device="cuda")
+    L = _lib.lib()
+    for r, want in ((rows, 0), (rows + 1, -1), (rows + 7, -1)):        # -1: PESR_EINVAL
+        part = torch.zeros((r, 2, C), device="cuda")
+        f = ops._fuse_struct(ops.BN_FWD_STATS, part)
+        rc = L.pesr_conv3x3_wino4_bn(ops._p(xg), ops._p(wf.t), None, ops._p(y), N, H, W, Cin, C, None, 0, ctypes.byref(f), ops._stream())
+        assert rc == want, (r, rows, rc)
+    # the direct kernel's twin
+    wp = ops.pack_conv3x3(_rand(C, Cin, 3, 3, seed=2, scale=0.1).cuda(), 0)
+    rows = ops.conv_bn_rows(0, N, H, W, Cin, C, 1)
+    assert rows > 0
+    nws = L.pesr_conv3x3_workspace_bytes(N, H, W, C)
+    ws = ops.workspace(nws, xg.device) if nws else None
+    for r, want in ((rows, 0), (rows + 1, -1)):
+        part = torch.zeros((r, 2, C), device="cuda")
+        f = ops._fuse_struct(ops.BN_FWD_STATS, part)
+        rc = L.pesr_conv3x3_fwd_bn(ops._p(xg), ops._p(wp), None, ops._p(y), N, H, W, Cin, C, 1, ops._p(ws), nws, ctypes.byref(f), ops._stream())
+        assert rc == want, (r, rows, rc)
+    torch.cuda.synchronize()
