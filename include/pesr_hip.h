@@ -529,6 +529,33 @@ size_t pesr_dists_workspace_bytes(int N, long P, int C);
 int pesr_dists_layer(const float* feat, const double* alpha, const double* beta, double* out, int N, int H, int W, int C,
                      double* stats_or_null, void* workspace, size_t ws_bytes, void* stream);
 
+/* ---- channel attention of a residual block (docs/modes.md section 4u; RCAN's RCAB): squeeze, excite, scale ------- */
+/* With t = the block's second conv output, fp32 NHWC [N][HW][C], R = C / reduction hidden units and a = res_scale:
+ *     m[n][c] = (1/HW) sum_p t[n][p][c];  h[n][j] = relu(sum_c w1[j][c] m[n][c] + b1[j]);  s[n][c] = sigmoid(sum_j w2[c][j] h[n][j] + b2[c]);
+ *     y = x + a * t * s[n][c]
+ * backward: ds[n][c] = a sum_p gy * t -> (gate backward) -> dm, dw1, db1, dw2, db2;  gt = a * gy * s + dm / HW;  gx = gy.
+ * w1 [R][C], b1 [R], w2 [C][R], b2 [C], m, s, ds, dm [N][C], h [N][R], all fp32.  Shapes: C % 4 == 0, 4 <= C <= 2048, 1 <= R <= C,
+ * N >= 1, 1 <= HW <= 2^30; anything else, a NULL tensor or an activation tensor off a 16-byte boundary is PESR_EINVAL with nothing
+ * launched, a workspace below pesr_ca_workspace_bytes PESR_EWORKSPACE.  Vector loads and stores only, no atomics, every sum in an
+ * order that depends on the shape alone: the same bits on every call.  64-bit element offsets.
+ * The pixel sums (pesr_ca_pool, pesr_ca_ds) run in two stages: one workgroup per (image, chunk of pixels) adds its pixels in fp32 (for
+ * ds with one fused multiply-add per pixel) and leaves a row in the workspace; the rows are added in double in the fixed order of
+ * the library's second stage, scaled (by 1 / HW, by a) and rounded once.  pesr_ca_pool_partials: the chunks per image of that rule, a
+ * pure host function of the shape (0: a shape the kernels do not take) - at least eight pixels per lane, about 2048 workgroups in all.
+ * In the gate backward the batch sums of the parameter gradients run in increasing n. */
+int pesr_ca_pool_partials(int N, long HW, int C);
+size_t pesr_ca_workspace_bytes(int N, long HW, int C, int R);
+int pesr_ca_pool(const float* t, float* m, int N, long HW, int C, void* workspace, size_t ws_bytes, void* stream);
+int pesr_ca_ds(const float* gy, const float* t, float* ds, int N, long HW, int C, float res_scale, void* workspace, size_t ws_bytes,
+               void* stream);
+int pesr_ca_gate_fwd(const float* m, const float* w1, const float* b1, const float* w2, const float* b2, float* h, float* s, int N,
+                     int C, int R, void* stream);
+int pesr_ca_apply_fwd(const float* x, const float* t, const float* s, float* y, int N, long HW, int C, float res_scale, void* stream);
+int pesr_ca_gate_bwd(const float* ds, const float* s, const float* h, const float* m, const float* w1, const float* w2, float* dm,
+                     float* dw1, float* db1, float* dw2, float* db2, int N, int C, int R, void* workspace, size_t ws_bytes,
+                     void* stream);
+int pesr_ca_apply_bwd(const float* gy, const float* s, const float* dm, float* gt, int N, long HW, int C, float res_scale, void* stream);
+
 /* ---- backward of the upsampler's tail: conv C -> 4C, PixelShuffle(2), conv C -> 3 (reference model/basic.py:56-60), as the backward
  * of one virtual 3 x 3 conv V from C to 64 channels (48 used) at the resolution of the tail's input h [N][H][W][C]
  * (docs/experiments/upsample_tail.md has the algebra).  w2 OIHW [4C][C][3][3], b2 [4C], w4 OIHW [3][C][3][3], all fp32; C % 16 == 0,

@@ -121,6 +121,14 @@ SIGNATURES.update({
     "pesr_dists_pixel_blocks": (c_long, [c_int, c_long, c_int]),
     "pesr_dists_workspace_bytes": (c_size_t, [c_int, c_long, c_int]),
     "pesr_dists_layer": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, _P, _P, c_size_t, _P]),
+    "pesr_ca_pool_partials": (c_int, [c_int, c_long, c_int]),
+    "pesr_ca_workspace_bytes": (c_size_t, [c_int, c_long, c_int, c_int]),
+    "pesr_ca_pool": (c_int, [_P, _P, c_int, c_long, c_int, _P, c_size_t, _P]),
+    "pesr_ca_ds": (c_int, [_P, _P, _P, c_int, c_long, c_int, c_float, _P, c_size_t, _P]),
+    "pesr_ca_gate_fwd": (c_int, [_P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, _P]),
+    "pesr_ca_apply_fwd": (c_int, [_P, _P, _P, _P, c_int, c_long, c_int, c_float, _P]),
+    "pesr_ca_gate_bwd": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, _P, c_size_t, _P]),
+    "pesr_ca_apply_bwd": (c_int, [_P, _P, _P, _P, c_int, c_long, c_int, c_float, _P]),
     "pesr_upsample_tail_gather":(c_int, [_P, _P, c_int, c_int, c_int, _P]),
     "pesr_upsample_tail_compose": (c_int, [_P, _P, _P, c_int, _P]),
     "pesr_upsample_tail_chain": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, _P]),

@@ -2,7 +2,7 @@
 stopped.  The reference keeps torch.save(G.state_dict()) alone ("no true resume"); this is an extension.
 
 One torch.save dict (schema in INTEGRATION.md):
-  format, flags {phase, scale, num_channels, num_blocks, spectral_norm, ema}, epoch, best_psnr, G, D, optim_G, optim_D,
+  format, flags {phase, scale, num_channels, num_blocks, spectral_norm, ema, attention}, epoch, best_psnr, G, D, optim_G, optim_D,
   scheduler_G, scheduler_D, dp {policy, transport}, world, rng [one entry per rank].
 The file is written next to its final name and moved over it, so a run killed while writing leaves the previous file whole.
 """
@@ -17,7 +17,9 @@ import torch
 FORMAT = 1
 STATE_NAME = "train_state.pt"
 # the flags that decide the tensors' shapes and meaning: a state loads only into a run that agrees on all of them
-SHAPE_FLAGS = ("phase", "scale", "num_channels", "num_blocks", "spectral_norm", "ema")
+SHAPE_FLAGS = ("phase", "scale", "num_channels", "num_blocks", "spectral_norm", "ema", "attention")
+# flags that joined later, with what a state written before them stands for (FORMAT stays 1: such a state still loads)
+_LATER_FLAGS = {"attention": 0}
 
 
 def state_path(check_point: str, phase: str) -> str:
@@ -39,7 +41,9 @@ def resolve_resume(resume: str, check_point: str, phase: str):
 
 def shape_flags(args) -> dict:
     return {"phase": args.phase, "scale": args.scale, "num_channels": args.num_channels, "num_blocks": args.num_blocks,
-            "spectral_norm": bool(args.spectral_norm), "ema": args.ema_decay > 0}
+            "spectral_norm": bool(args.spectral_norm), "ema": args.ema_decay > 0,
+            # the reduction of the Generator's channel attention, 0 = none (docs/modes.md section 4u)
+            "attention": args.ca_reduction if getattr(args, "attention", "none") == "ca" else 0}
 
 
 def check_flags(state: dict, args, path: str = "") -> None:
@@ -48,10 +52,10 @@ def check_flags(state: dict, args, path: str = "") -> None:
         raise SystemExit(f"train.py: --resume {path}: state format {state.get('format')!r}, this version reads format {FORMAT}")
     mine = shape_flags(args)
     for k in SHAPE_FLAGS:
-        if state["flags"][k] != mine[k]:
-            flag = "--ema_decay > 0" if k == "ema" else "--" + k
-            raise SystemExit(f"train.py: --resume {path}: the state was saved with {flag} = {state['flags'][k]!r}, this run has "
-                             f"{mine[k]!r}")
+        theirs = state["flags"][k] if k not in _LATER_FLAGS else state["flags"].get(k, _LATER_FLAGS[k])
+        if theirs != mine[k]:
+            flag = {"ema": "--ema_decay > 0", "attention": "--attention / --ca_reduction (the reduction, 0 = none)"}.get(k, "--" + k)
+            raise SystemExit(f"train.py: --resume {path}: the state was saved with {flag} = {theirs!r}, this run has {mine[k]!r}")
 
 
 def rng_snapshot(device=None, gpu_loader=None, shuffle=None) -> dict:

@@ -474,6 +474,36 @@ PESR_API int pesr_dists_layer(const float* feat, const double* alpha, const doub
     return pesr_dists_layer_launch(feat, alpha, beta, out, N, H, W, C, stats_or_null, workspace, ws_bytes, (hipStream_t)stream);
 }
 
+PESR_API int pesr_ca_pool_partials(int N, long HW, int C) { return pesr_ca_pool_partials_of(N, HW, C); }
+PESR_API size_t pesr_ca_workspace_bytes(int N, long HW, int C, int R) { return pesr_ca_ws_bytes(N, HW, C, R); }
+PESR_API int pesr_ca_pool(const float* t, float* m, int N, long HW, int C, void* workspace, size_t ws_bytes, void* stream) {
+    return pesr_ca_sum_launch(t, nullptr, m, N, HW, C, HW > 0 ? 1.0 / (double)HW : 0.0, workspace, ws_bytes, (hipStream_t)stream);
+}
+PESR_API int pesr_ca_ds(const float* gy, const float* t, float* ds, int N, long HW, int C, float res_scale, void* workspace,
+                        size_t ws_bytes, void* stream) {
+    if (!gy) return PESR_EINVAL;
+    return pesr_ca_sum_launch(t, gy, ds, N, HW, C, (double)res_scale, workspace, ws_bytes, (hipStream_t)stream);
+}
+PESR_API int pesr_ca_gate_fwd(const float* m, const float* w1, const float* b1, const float* w2, const float* b2, float* h, float* s,
+                              int N, int C, int R, void* stream) {
+    return pesr_ca_gate_fwd_launch(m, w1, b1, w2, b2, h, s, N, C, R, (hipStream_t)stream);
+}
+PESR_API int pesr_ca_apply_fwd(const float* x, const float* t, const float* s, float* y, int N, long HW, int C, float res_scale,
+                               void* stream) {
+    if (!x) return PESR_EINVAL;
+    return pesr_ca_apply_launch(t, x, s, nullptr, y, N, HW, C, res_scale, (hipStream_t)stream);
+}
+PESR_API int pesr_ca_gate_bwd(const float* ds, const float* s, const float* h, const float* m, const float* w1, const float* w2,
+                              float* dm, float* dw1, float* db1, float* dw2, float* db2, int N, int C, int R, void* workspace,
+                              size_t ws_bytes, void* stream) {
+    return pesr_ca_gate_bwd_launch(ds, s, h, m, w1, w2, dm, dw1, db1, dw2, db2, N, C, R, workspace, ws_bytes, (hipStream_t)stream);
+}
+PESR_API int pesr_ca_apply_bwd(const float* gy, const float* s, const float* dm, float* gt, int N, long HW, int C, float res_scale,
+                               void* stream) {
+    if (!dm) return PESR_EINVAL;
+    return pesr_ca_apply_launch(gy, nullptr, s, dm, gt, N, HW, C, res_scale, (hipStream_t)stream);
+}
+
 PESR_API int pesr_upsample_tail_gather(const float* g, float* gw, int N, int H, int W, void* stream) {
     return pesr_upsample_tail_gather_launch(g, gw, N, H, W, (hipStream_t)stream);
 }

@@ -280,6 +280,20 @@ size_t pesr_dists_ws_bytes(int N, long P, int C);
 int pesr_dists_layer_launch(const float* feat, const double* alpha, const double* beta, double* out, int N, int H, int W, int C,
                             double* stats, void* ws, size_t ws_bytes, hipStream_t stream);
 
+// channel attention of a residual block (channel_attention.hip): the two pixel sums (gy null: of t; else of gy * t) with their fixed-order
+// second stage, the two apply passes (x: forward, dm: backward - exactly one of them), the gate forward and backward
+int pesr_ca_pool_partials_of(int N, long HW, int C);
+size_t pesr_ca_ws_bytes(int N, long HW, int C, int R);
+int pesr_ca_sum_launch(const float* t, const float* gy, float* out, int N, long HW, int C, double scale, void* ws, size_t ws_bytes,
+                       hipStream_t stream);
+int pesr_ca_apply_launch(const float* in, const float* x, const float* s, const float* dm, float* out, int N, long HW, int C, float a,
+                         hipStream_t stream);
+int pesr_ca_gate_fwd_launch(const float* m, const float* W1, const float* B1, const float* W2, const float* B2, float* h, float* s, int N,
+                            int C, int R, hipStream_t stream);
+int pesr_ca_gate_bwd_launch(const float* ds, const float* s, const float* h, const float* m, const float* W1, const float* W2, float* dm,
+                            float* dW1, float* dB1, float* dW2, float* dB2, int N, int C, int R, void* ws, size_t ws_bytes,
+                            hipStream_t stream);
+
 // backward of the upsampler's tail (conv C -> 4C, PixelShuffle(2), conv C -> 3) as one virtual C -> 64 conv (upsample_tail.hip)
 int pesr_upsample_tail_gather_launch(const float* g, float* gw, int N, int H, int W, hipStream_t stream);
 int pesr_upsample_tail_compose_launch(const float* w2, const float* w4, float* weff, int C, hipStream_t stream);

@@ -765,6 +765,32 @@ class ScaleAddFn(Function):
         return ops.relu_mask(gy, None, None, alpha=ctx.alpha), gy, None
 
 
+class ChannelAttentionFn(Function):
+    """y = x + res_scale * t * s, s = sigmoid(W2 relu(W1 mean_pixels(t) + B1) + B2): the tail of a residual channel-attention block
+    (docs/modes.md section 4u), t the output of the block's second conv.  Saves t and the gate's small tensors (s, h, m); x is not
+    needed in backward: gx = gy.  fp32 kernels whatever ops.PRECISION is."""
+
+    @staticmethod
+    def forward(ctx, x, t, w1, b1, w2, b2, res_scale):
+        x, t = _c(x), _c(t)
+        m = ops.ca_pool(t)
+        h, s = ops.ca_gate_fwd(m, w1.detach(), b1.detach(), w2.detach(), b2.detach())
+        ctx.res_scale = res_scale
+        ctx.b1_ref, ctx.b2_ref = b1, b2
+        ctx.save_for_backward(t, s, h, m, w1, w2)
+        return ops.ca_apply_fwd(x, t, s, res_scale)
+
+    @staticmethod
+    def backward(ctx, gy):
+        t, s, h, m, w1, w2 = ctx.saved_tensors
+        gy = _c(gy)
+        ds = ops.ca_ds(gy, t, ctx.res_scale)
+        dm, dw1, db1, dw2, db2 = ops.ca_gate_bwd(ds, s, h, m, w1, w2, grad_out(w1), grad_out(ctx.b1_ref), grad_out(w2),
+                                                 grad_out(ctx.b2_ref))
+        gt = ops.ca_apply_bwd(gy, s, dm, ctx.res_scale) if ctx.needs_input_grad[1] else None
+        return (gy if ctx.needs_input_grad[0] else None), gt, dw1, db1, dw2, db2, None
+
+
 # ------------------------------------------------------------------------------------------------
 # Twice-differentiable building blocks of the Discriminator (gradient penalty, reference train.py:216-226:
 # torch.autograd.grad(D(x_both), x_both, create_graph=True) and then .backward() through that gradient).

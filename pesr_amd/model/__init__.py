@@ -5,10 +5,10 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .basic import BasicBlock, Conv, MeanShift, PixelShuffle, ResBlock, Upsampler
+from .basic import BasicBlock, ChannelAttention, Conv, MeanShift, PixelShuffle, ResBlock, Upsampler
 from .focal_loss import FocalLoss
-from .pesr import Discriminator, Generator, scale_of_state_dict
+from .pesr import Discriminator, Generator, attention_of_state_dict, scale_of_state_dict
 from .vgg import VGG
 
-__all__ = ["Generator", "Discriminator", "VGG", "FocalLoss", "Conv", "MeanShift", "BasicBlock", "ResBlock",
-           "Upsampler", "PixelShuffle", "scale_of_state_dict", "nn", "torch", "F"]
+__all__ = ["Generator", "Discriminator", "VGG", "FocalLoss", "Conv", "MeanShift", "BasicBlock", "ResBlock", "ChannelAttention",
+           "Upsampler", "PixelShuffle", "scale_of_state_dict", "attention_of_state_dict", "nn", "torch", "F"]

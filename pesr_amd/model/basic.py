@@ -222,13 +222,40 @@ class BasicBlock(nn.Sequential):
         return nchw(y)
 
 
+ATTENTIONS = (None, "ca")
+
+
+class ChannelAttention(nn.Module):
+    """RCAN's squeeze-and-excite gate (Zhang et al., ECCV 2018) as the tail of a residual block (an extension, docs/modes.md section
+    4u): forward(x, t, res_scale) = x + res_scale * t * sigmoid(excite(relu(squeeze(mean over the pixels of t)))).  squeeze and excite
+    are 1 x 1 convs n_feats -> n_feats / reduction -> n_feats, initialised like nn.Conv2d, squeeze first; on a pooled [N, C, 1, 1] map
+    they are two small matrix products, which the gate kernels do themselves (the Conv modules hold the parameters)."""
+
+    def __init__(self, n_feats, reduction=16):
+        super().__init__()
+        hidden = ops.ca_check_channels("ChannelAttention", n_feats, reduction)
+        self.squeeze = Conv(n_feats, hidden, 1)
+        self.excite = Conv(hidden, n_feats, 1)
+        self.n_feats, self.reduction = n_feats, reduction
+
+    def forward(self, x_nhwc, t_nhwc, res_scale):
+        return PF.ChannelAttentionFn.apply(x_nhwc, t_nhwc, self.squeeze.weight, self.squeeze.bias, self.excite.weight, self.excite.bias,
+                                           float(res_scale))
+
+    def extra_repr(self):
+        return f"{self.n_feats}, reduction={self.reduction}"
+
+
 class ResBlock(nn.Module):
     """x + res_scale * conv(act(conv(x))) (reference model/basic.py:33-52).  The reference's only configuration (bias, no BN,
     ReLU) is one fused autograd node; the other constructor branches (bn=True, bias=False, LeakyReLU) run un-fused on the
-    same kernels."""
+    same kernels.  attention="ca" (an extension): x + res_scale * t * gate(t) with t = conv(act(conv(x))), the gate a
+    ChannelAttention(n_feats, reduction) constructed and registered after the two convs."""
 
-    def __init__(self, n_feats, kernel_size, bias=True, bn=False, act=nn.ReLU(True), res_scale=1):
+    def __init__(self, n_feats, kernel_size, bias=True, bn=False, act=nn.ReLU(True), res_scale=1, attention=None, reduction=16):
         super().__init__()
+        if attention not in ATTENTIONS:
+            raise ValueError(f"ResBlock: attention = {attention!r}; supported are {ATTENTIONS}")
         _act_slope(act)       # rejects activations the epilogues do not implement
         modules_body = []
         for i in range(2):
@@ -243,8 +270,12 @@ class ResBlock(nn.Module):
         # the fused node runs the 3x3 kernels only: any other (odd) kernel size takes the un-fused path, whose _conv_act
         # routes it to the generic kernels (a [C,C,5,5] weight read by a 3x3 packer would be silently wrong)
         self._fused = kernel_size == 3 and bias and not bn and isinstance(act, nn.ReLU) and not isinstance(act, nn.LeakyReLU)
+        if attention is not None:
+            self.ca = ChannelAttention(n_feats, reduction)
 
     def forward(self, x):
+        if hasattr(self, "ca"):
+            return self._forward_attention(x)
         if self._fused:
             c1, c2 = self.body[0], self.body[2]
             return nchw(PF.ResBlockFn.apply(nhwc(x), c1.weight, c1.bias, c2.weight, c2.bias, c1.packed, c2.packed,
@@ -259,6 +290,22 @@ class ResBlock(nn.Module):
             r = _conv_act(c1, h, act)
             r = _conv_act(c2, r, None)
         return nchw(PF.ScaleAddFn.apply(r, h, float(self.res_scale)))
+
+    def _forward_attention(self, x):
+        """conv + ReLU in one kernel (the ReLU's mask in the second conv's input-gradient epilogue), the second conv plain, then the
+        attention node in place of the scale-and-add; the un-fused variants as in forward()."""
+        h = nhwc(x)
+        if self._fused:
+            c1, c2 = self.body[0], self.body[2]
+            r = PF.conv3x3(h, c1.weight, c1.bias, c1.packed, act=ops.ACT_RELU, relu_grad_by_consumer=True)
+            t = PF.conv3x3(r, c2.weight, c2.bias, c2.packed, relu_in=True)
+        elif self._bn:
+            c1, b1, act, c2, b2 = self.body
+            t = _conv_bn_act(c2, b2, _conv_bn_act(c1, b1, h, act), None)
+        else:
+            c1, act, c2 = self.body
+            t = _conv_act(c2, _conv_act(c1, h, act), None)
+        return nchw(self.ca(h, t, self.res_scale))
 
 
 SCALES = (2, 3, 4)

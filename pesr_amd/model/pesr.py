@@ -42,6 +42,18 @@ def scale_of_state_dict(sd):
     raise ValueError(f"upsampler of unknown scale: upsample.0.weight {tuple(w0.shape)}")
 
 
+def attention_of_state_dict(sd):
+    """-> the reduction of a Generator state_dict's channel attention (docs/modes.md section 4u), 0 for one without: read from the
+    first block's `body.0.ca.squeeze.weight` [C / reduction, C, 1, 1]; ValueError where that tensor is no such weight."""
+    prefix = "module." if any(k.startswith("module.") for k in sd) else ""
+    w = sd.get(prefix + "body.0.ca.squeeze.weight")
+    if w is None:
+        return 0
+    if w.dim() != 4 or w.shape[0] < 1 or w.shape[1] % w.shape[0]:
+        raise ValueError(f"channel attention of unknown shape: body.0.ca.squeeze.weight {tuple(w.shape)}")
+    return w.shape[1] // w.shape[0]
+
+
 class Generator(nn.Module):
     def __init__(self, opt):
         super().__init__()
@@ -50,8 +62,11 @@ class Generator(nn.Module):
         scale = opt.get('scale', 4)        # an extension: the reference's Generator is x4 only (docs/modes.md section 4e)
         if scale not in SCALES:
             raise ValueError(f"Generator: scale {scale}; supported scales are {SCALES}")
+        # an extension: channel attention in the residual blocks (docs/modes.md section 4u); absent or None = the reference's blocks
+        attention, reduction = opt.get('attention'), opt.get('ca_reduction', 16)
+        block_kw = {} if attention is None else {"attention": attention, "reduction": reduction}
         # The reference builds the trunk before everything else (RNG order) but registers it third (state_dict order).
-        trunk = [ResBlock(width, 3, act=nn.ReLU(True), res_scale=res_scale) for _ in range(depth)]
+        trunk = [ResBlock(width, 3, act=nn.ReLU(True), res_scale=res_scale, **block_kw) for _ in range(depth)]
         trunk.append(Conv(width, width, 3))
         self.sub_mean = MeanShift(255, _DIV2K_MEAN, _UNIT_STD)
         self.embed = Conv(3, width, 3)

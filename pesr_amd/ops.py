@@ -1396,6 +1396,134 @@ def dists_layer(feat: torch.Tensor, alpha: torch.Tensor, beta: torch.Tensor, ret
 
 
 # ------------------------------------------------------------------------------------------------
+# channel attention of a residual block (docs/modes.md section 4u; pesr_amd/csrc/channel_attention.hip).  fp32 whatever PRECISION is.
+# ------------------------------------------------------------------------------------------------
+CA_MAX_CHANNELS = 2048
+
+
+def ca_check_channels(what: str, n_feats: int, reduction: int) -> int:
+    """-> R = n_feats / reduction, the hidden units of the gate; ValueError naming the argument the kernels cannot take."""
+    if n_feats < 4 or n_feats % 4 or n_feats > CA_MAX_CHANNELS:
+        raise ValueError(f"{what}: n_feats = {n_feats}; the channel-attention kernels take a multiple of 4 up to {CA_MAX_CHANNELS}")
+    if reduction < 1 or n_feats % reduction:
+        raise ValueError(f"{what}: reduction = {reduction}; it has to be >= 1 and divide n_feats = {n_feats}")
+    return n_feats // reduction
+
+
+def ca_pool_partials(N: int, HW: int, C: int) -> int:
+    """The chunks an image's HW pixels are cut into by the two pixel sums (ca_pool, ca_ds) - one workgroup and one partial row each,
+    combined in ascending order (a host-only question).  ValueError for a shape the kernels do not take."""
+    if C < 4 or C % 4 or C > CA_MAX_CHANNELS:
+        raise ValueError(f"ca_pool_partials: C = {C}; the channel-attention kernels take a multiple of 4 up to {CA_MAX_CHANNELS}")
+    if N < 1:
+        raise ValueError(f"ca_pool_partials: N = {N}")
+    if HW < 1 or HW > 1 << 30:
+        raise ValueError(f"ca_pool_partials: HW = {HW}")
+    return _memo("pesr_ca_pool_partials", N, HW, C)
+
+
+def _ca_map(what: str, t: torch.Tensor):
+    _chk(t, what)
+    if t.dim() != 4 or min(t.shape) < 1:
+        raise ValueError(f"{what}: expected a [N, H, W, C] tensor, got {tuple(t.shape)}")
+    N, H, W, C = t.shape
+    ca_pool_partials(N, H * W, C)
+    return N, H * W, C
+
+
+def _ca_mat(what: str, t: torch.Tensor, shape) -> torch.Tensor:
+    """A gate tensor ([N, C] / [N, R] / a 1 x 1 conv's weight or bias) as the contiguous fp32 matrix the kernels read."""
+    _chk(t, what)
+    if t.numel() != shape[0] * shape[1] or t.shape[0] != shape[0]:
+        raise ValueError(f"{what}: expected {tuple(shape)}, got {tuple(t.shape)}")
+    return t
+
+
+def _ca_ws(N: int, HW: int, C: int, R: int, device):
+    return workspace(int(_lib.lib().pesr_ca_workspace_bytes(N, HW, C, R)), device)
+
+
+def ca_pool(t: torch.Tensor) -> torch.Tensor:
+    """t: NHWC [N, H, W, C] -> m [N, C], the mean over the pixels (fp32 partial sums per chunk, combined in double in a fixed order)."""
+    N, HW, C = _ca_map("ca_pool.t", t)
+    m = torch.empty((N, C), dtype=torch.float32, device=t.device)
+    ws = _ca_ws(N, HW, C, 1, t.device)
+    _lib.check(_lib.lib().pesr_ca_pool(_p(t), _p(m), N, HW, C, _p(ws), ws.numel(), _stream()), "pesr_ca_pool")
+    return m
+
+
+def ca_ds(gy: torch.Tensor, t: torch.Tensor, res_scale: float) -> torch.Tensor:
+    """-> ds [N, C] = res_scale * sum over the pixels of gy * t (the gradient of the gate's output s)."""
+    N, HW, C = _ca_map("ca_ds.t", t)
+    _chk(gy, "ca_ds.gy")
+    if gy.shape != t.shape:
+        raise ValueError(f"ca_ds.gy: expected {tuple(t.shape)}, got {tuple(gy.shape)}")
+    ds = torch.empty((N, C), dtype=torch.float32, device=t.device)
+    ws = _ca_ws(N, HW, C, 1, t.device)
+    _lib.check(_lib.lib().pesr_ca_ds(_p(gy), _p(t), _p(ds), N, HW, C, float(res_scale), _p(ws), ws.numel(), _stream()), "pesr_ca_ds")
+    return ds
+
+
+def ca_gate_fwd(m: torch.Tensor, w1: torch.Tensor, b1: torch.Tensor, w2: torch.Tensor, b2: torch.Tensor):
+    """m [N, C]; w1 [R, C(, 1, 1)], b1 [R], w2 [C, R(, 1, 1)], b2 [C] -> (h [N, R] = relu(w1 m + b1), s [N, C] = sigmoid(w2 h + b2))."""
+    _chk(m, "ca_gate_fwd.m")
+    if m.dim() != 2:
+        raise ValueError(f"ca_gate_fwd.m: expected [N, C], got {tuple(m.shape)}")
+    N, C = m.shape
+    R = w1.shape[0]
+    ca_check_channels("ca_gate_fwd", C, C // R if R and C % R == 0 else 0)
+    _ca_mat("ca_gate_fwd.w1", w1, (R, C)), _ca_mat("ca_gate_fwd.b1", b1, (R, 1))
+    _ca_mat("ca_gate_fwd.w2", w2, (C, R)), _ca_mat("ca_gate_fwd.b2", b2, (C, 1))
+    h = torch.empty((N, R), dtype=torch.float32, device=m.device)
+    s = torch.empty((N, C), dtype=torch.float32, device=m.device)
+    _lib.check(_lib.lib().pesr_ca_gate_fwd(_p(m), _p(w1), _p(b1), _p(w2), _p(b2), _p(h), _p(s), N, C, R, _stream()), "pesr_ca_gate_fwd")
+    return h, s
+
+
+def ca_apply_fwd(x: torch.Tensor, t: torch.Tensor, s: torch.Tensor, res_scale: float) -> torch.Tensor:
+    """y = x + res_scale * t * s[n, c];  x, t: NHWC [N, H, W, C], s [N, C]."""
+    N, HW, C = _ca_map("ca_apply_fwd.t", t)
+    _chk(x, "ca_apply_fwd.x")
+    if x.shape != t.shape:
+        raise ValueError(f"ca_apply_fwd.x: expected {tuple(t.shape)}, got {tuple(x.shape)}")
+    _ca_mat("ca_apply_fwd.s", s, (N, C))
+    y = torch.empty_like(t)
+    _lib.check(_lib.lib().pesr_ca_apply_fwd(_p(x), _p(t), _p(s), _p(y), N, HW, C, float(res_scale), _stream()), "pesr_ca_apply_fwd")
+    return y
+
+
+def ca_gate_bwd(ds, s, h, m, w1, w2, dw1_out=None, db1_out=None, dw2_out=None, db2_out=None):
+    """The gate's backward: ds, s, m [N, C], h [N, R], w1 [R, C(, 1, 1)], w2 [C, R(, 1, 1)] -> (dm [N, C], dw1, db1, dw2, db2), the
+    parameter gradients summed over the batch in increasing n, shaped like w1, [R], like w2, [C]; *_out: where to write them."""
+    _chk(ds, "ca_gate_bwd.ds")
+    if ds.dim() != 2:
+        raise ValueError(f"ca_gate_bwd.ds: expected [N, C], got {tuple(ds.shape)}")
+    N, C = ds.shape
+    R = w1.shape[0]
+    ca_check_channels("ca_gate_bwd", C, C // R if R and C % R == 0 else 0)
+    for name, t, shape in (("s", s, (N, C)), ("h", h, (N, R)), ("m", m, (N, C)), ("w1", w1, (R, C)), ("w2", w2, (C, R))):
+        _ca_mat("ca_gate_bwd." + name, t, shape)
+    dev = ds.device
+    dm = torch.empty((N, C), dtype=torch.float32, device=dev)
+    dw1, db1 = _out(dw1_out, w1.shape, dev), _out(db1_out, (R,), dev)
+    dw2, db2 = _out(dw2_out, w2.shape, dev), _out(db2_out, (C,), dev)
+    ws = _ca_ws(N, 1, C, R, dev)
+    rc = _lib.lib().pesr_ca_gate_bwd(_p(ds), _p(s), _p(h), _p(m), _p(w1), _p(w2), _p(dm), _p(dw1), _p(db1), _p(dw2), _p(db2), N, C, R,
+                                     _p(ws), ws.numel(), _stream())
+    _lib.check(rc, "pesr_ca_gate_bwd")
+    return dm, dw1, db1, dw2, db2
+
+
+def ca_apply_bwd(gy: torch.Tensor, s: torch.Tensor, dm: torch.Tensor, res_scale: float) -> torch.Tensor:
+    """gt = res_scale * gy * s[n, c] + dm[n, c] / HW;  gy: NHWC [N, H, W, C], s, dm [N, C]."""
+    N, HW, C = _ca_map("ca_apply_bwd.gy", gy)
+    _ca_mat("ca_apply_bwd.s", s, (N, C)), _ca_mat("ca_apply_bwd.dm", dm, (N, C))
+    gt = torch.empty_like(gy)
+    _lib.check(_lib.lib().pesr_ca_apply_bwd(_p(gy), _p(s), _p(dm), _p(gt), N, HW, C, float(res_scale), _stream()), "pesr_ca_apply_bwd")
+    return gt
+
+
+# ------------------------------------------------------------------------------------------------
 # texture loss: patch-wise Gram matrices (docs/modes.md section 4q)
 # ------------------------------------------------------------------------------------------------
 GRAM_CHANNELS = (64, 128, 256)

@@ -105,10 +105,16 @@ def tiled_forward(model: Callable, img: torch.Tensor, scale: int, core: int, hal
     return (out_f[None] if f32 else None), out_u
 
 
-def describe(core: int, halo: int, exact: int) -> str:
+def describe(core: int, halo: int, exact: int, attention: bool = False) -> str:
     """The line the entry points print once per run: tile shape, halo, the exact halo, and whether the results are the whole-image
-    forward or an approximation of it.  (Facts of the run only: the number of tiles differs from image to image.)"""
+    forward or an approximation of it.  (Facts of the run only: the number of tiles differs from image to image.)  attention: the
+    Generator pools every block's features over whatever it is given (docs/modes.md section 4u) - a tile's mean is not the image's,
+    so no halo is exact."""
     side = core + 2 * halo
+    if attention:
+        return f"Tiled: tiles of {side} x {side} (an image shorter than that on an axis is taken whole along it), core {core}, halo " \
+               f"{halo}: an APPROXIMATION of the whole-image forward at every halo for every image larger than one tile (the " \
+               f"Generator's channel attention pools over the tile, not over the image; its convs alone reach {exact} pixels)"
     line = f"Tiled: tiles of {side} x {side} (an image shorter than that on an axis is taken whole along it), core {core}, halo {halo}, " \
            f"exact halo {exact}"
     if halo < exact:

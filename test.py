@@ -155,10 +155,26 @@ def check_checkpoint_scale(sd, scale, path):
 
 
 def load_generator(opt, path, scale):
+    """The Generator of a checkpoint: its width, depth and scale are the flags', its channel attention (docs/modes.md section 4u) is
+    read from the checkpoint itself."""
     from model import Generator
+    from pesr_amd.model import attention_of_state_dict
+    sd = check_checkpoint_scale(torch.load(path, map_location="cpu"), scale, path)
+    try:
+        reduction = attention_of_state_dict(sd)
+    except ValueError as e:
+        raise SystemExit(f"test.py: {path}: {e}")
+    if reduction:
+        opt = dict(opt, attention="ca", ca_reduction=reduction)
+        sd = {(k[len("module."):] if k.startswith("module.") else k): v for k, v in sd.items()}     # (saved from an nn.DataParallel)
     model = Generator(dict(opt, scale=scale))
-    model.load_state_dict(check_checkpoint_scale(torch.load(path, map_location="cpu"), scale, path))
+    model.load_state_dict(sd)
     return model
+
+
+def has_attention(*models):
+    from pesr_amd.model.basic import ChannelAttention
+    return any(isinstance(mod, ChannelAttention) for m in models if m is not None for mod in m.modules())
 
 
 # the three generators of the 8-element dihedral group, in the reference's order (test.py:58-60), as tensor ops
@@ -265,7 +281,8 @@ def main(argv=None):
     os.makedirs(save_path, exist_ok=True)
     rows = []           # per image: the scores of what was saved and, with --from_hr, of the bicubic baseline
     if args.tile:
-        print(_tile.describe(args.tile, tile_halo, _tile.receptive_halo(args.num_blocks, args.scale)))
+        print(_tile.describe(args.tile, tile_halo, _tile.receptive_halo(args.num_blocks, args.scale),
+                             attention=has_attention(model, model_psnr)))
     with torch.no_grad():
         for i, lr_path in enumerate(lr_paths):
             if args.from_hr:

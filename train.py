@@ -54,6 +54,11 @@ def build_parser():
     p.add_argument("--alpha_tv", type=float, default=1e-6)
     p.add_argument("--alpha_l1", type=float, default=0)
     # additions
+    p.add_argument("--attention", type=str, default="none", choices=["none", "ca"],
+                   help="ca: RCAN-style channel attention (a squeeze-and-excite gate on the second conv's output) in every residual "
+                        "block of the Generator (docs/modes.md section 4u); none (default): the reference's blocks")
+    p.add_argument("--ca_reduction", type=int, default=16,
+                   help="with --attention ca: the gate's hidden width is --num_channels / this; it has to divide --num_channels")
     p.add_argument("--synthetic", type=int, default=0, help="train on N synthetic samples per epoch instead of a dataset folder")
     p.add_argument("--vgg_weights", type=str, default="",
                    help="state_dict file of torchvision's pretrained vgg19 (torch.save(torchvision.models.vgg19(pretrained=True)"
@@ -356,6 +361,35 @@ def build_vgg(args, device, rank, world):
     return vgg
 
 
+def attention_of(args):
+    """--attention / --ca_reduction -> the reduction of the Generator's channel attention (0: none); SystemExit naming the flag.  No GPU
+    is touched."""
+    if args.ca_reduction < 1:
+        raise SystemExit(f"train.py: --ca_reduction {args.ca_reduction} must be at least 1")
+    # (the default 16 is not held against a run without attention whose width it does not divide)
+    if args.num_channels % args.ca_reduction and (args.attention == "ca" or args.ca_reduction != 16):
+        raise SystemExit(f"train.py: --ca_reduction {args.ca_reduction} does not divide --num_channels {args.num_channels}")
+    if args.attention == "none":
+        return 0
+    if args.num_channels % 4 or args.num_channels > 2048:
+        raise SystemExit(f"train.py: --attention ca needs --num_channels to be a multiple of 4 up to 2048, got {args.num_channels}")
+    return args.ca_reduction
+
+
+def check_pretrained_attention(sd, args, path):
+    """A --pretrained_model whose channel attention is not this run's: SystemExit naming both (instead of load_state_dict's key dump)."""
+    from pesr_amd.model import attention_of_state_dict
+    try:
+        found = attention_of_state_dict(sd)
+    except ValueError as e:
+        raise SystemExit(f"train.py: --pretrained_model {path}: {e}")
+    mine = attention_of(args)
+    if found != mine:
+        say = lambda r: f"--attention ca --ca_reduction {r}" if r else "--attention none"
+        raise SystemExit(f"train.py: --pretrained_model {path} was trained with {say(found)}, this run has {say(mine)}")
+    return sd
+
+
 def check_limits(args, world):
     """Shape limits of the HIP path, checked up front with a clear message instead of a PESR_EINVAL deep inside a step."""
     if args.batch_size % world:
@@ -426,6 +460,7 @@ def loss_terms_of(args, valid_lpips_model=None):
 def main(argv=None):
     args = build_parser().parse_args(argv)
     degradation_spec(args)      # (refuses a classical run without its companion flags before anything else starts)
+    attention = attention_of(args)
     scorer = scorer_of(args)
     loss_terms = loss_terms_of(args, scorer.lpips_model)
     world =int(os.environ.get("WORLD_SIZE", "1"))
@@ -459,7 +494,7 @@ def main(argv=None):
     from pesr_amd.tile import describe, receptive_halo, tiled_forward
     valid_halo = receptive_halo(args.num_blocks, args.scale) if args.valid_tile_halo == -1 else args.valid_tile_halo
     if args.valid_tile and rank == 0:
-        print(describe(args.valid_tile, valid_halo, receptive_halo(args.num_blocks, args.scale)))
+        print(describe(args.valid_tile, valid_halo, receptive_halo(args.num_blocks, args.scale), attention=bool(attention)))
 
     gpu_pipe = args.gpu_pipeline and not args.synthetic
     train_loader, val_loader, sampler = make_loaders(args, rank, world, need_train=not gpu_pipe, device=device)
@@ -467,6 +502,8 @@ def main(argv=None):
         train_loader = sampler = make_gpu_loader(args, rank, world, device)      # (it has set_epoch like a DistributedSampler)
     opt = {"patch_size": args.patch_size, "num_channels": args.num_channels, "depth": args.num_blocks,
            "res_scale": args.res_scale, "spectral_norm": args.spectral_norm, "scale": args.scale}
+    if attention:
+        opt.update(attention="ca", ca_reduction=attention)
     from pesr_amd import checkpoint
     resume_path = checkpoint.resolve_resume(args.resume, args.check_point, args.phase)
     state = None
@@ -477,7 +514,7 @@ def main(argv=None):
         print("resume: no %s yet, starting fresh" % checkpoint.state_path(args.check_point, args.phase))
     G = Generator(opt)
     if args.pretrained_model and state is None:
-        G.load_state_dict(torch.load(args.pretrained_model, map_location="cpu"))
+        G.load_state_dict(check_pretrained_attention(torch.load(args.pretrained_model, map_location="cpu"), args, args.pretrained_model))
     G = G.to(device)
     gan = args.phase != "pretrain"
     D = Discriminator(opt).to(device) if gan else None
