@@ -556,6 +556,32 @@ int pesr_ca_gate_bwd(const float* ds, const float* s, const float* h, const floa
                      void* stream);
 int pesr_ca_apply_bwd(const float* gy, const float* s, const float* dm, float* gt, int N, long HW, int C, float res_scale, void* stream);
 
+/* ---- the U-Net discriminator's own kernels (docs/modes.md section 4v): bilinear x2, the GAN loss of a logit map, conv C -> 1 -------- */
+/* All fp32, no atomics, every sum in an order that depends on the shape alone (the same bits on every call), size_t element offsets;
+ * a bad argument is PESR_EINVAL with nothing launched, a workspace below the stated size PESR_EWORKSPACE.
+ * pesr_bilinear_up2_fwd: NHWC a (and b, or NULL) [N][H][W][C] -> y [N][2H][2W][C] = up2(a + b), up2 = F.interpolate(scale_factor=2,
+ *   mode='bilinear', align_corners=False): per axis out[2i] = 0.25 in[max(i-1,0)] + 0.75 in[i], out[2i+1] = 0.75 in[i] + 0.25 in[min(i+1,n-1)].
+ *   Any N, H, W, C >= 1 (H, W <= 2^29); 16-byte accesses where C % 4 == 0 and the tensors are 16-byte aligned, scalar ones otherwise.
+ * pesr_bilinear_up2_bwd: gy [N][2H][2W][C] -> gx [N][H][W][C], the exact adjoint in gather form: each gx pixel adds its 16 weighted gy
+ *   pixels (rows clamp(2i-1), 2i, 2i+1, clamp(2i+2) with 0.25, 0.75, 0.75, 0.25, the same along x) in a fixed order; the clamp folds
+ *   the border taps onto the edge pixel.  gx is the gradient of both addends.
+ * pesr_gan_loss_map: pesr_gan_loss_fwd_bwd's definitions (gan_type 0 SGAN, 1 RSGAN, 2 RaSGAN; side 0 discriminator, 1 generator; focal
+ *   on side 1 only) on n >= 1 logits: out[0] = scale * mean over the n elements, d_real / d_fake [n] = scale * d/dlogit (either may be
+ *   NULL).  RSGAN pairs the logits of one index; RaSGAN's means run over all n logits.  workspace >= pesr_gan_loss_map_workspace_bytes(n).
+ * pesr_conv3x3_c1_*: the 3 x 3 conv (pad 1, stride 1) from C channels to ONE on the OIHW weights w [1][C][3][3]: x, dx [N][H][W][C],
+ *   y, dy [N][H][W]; C % 4 == 0, 4 <= C <= 1024, N H W < 2^31, x / dx 16-byte aligned.  fwd: bias [1] or NULL.  wgrad: dw [1][C][3][3]
+ *   and db [1] (or NULL), both times alpha; workspace >= pesr_conv3x3_c1_wgrad_workspace_bytes (0: a shape the kernels do not take). */
+int pesr_bilinear_up2_fwd(const float* a, const float* b_or_null, float* y, int N, int H, int W, int C, void* stream);
+int pesr_bilinear_up2_bwd(const float* gy, float* gx, int N, int H, int W, int C, void* stream);
+size_t pesr_gan_loss_map_workspace_bytes(long n);
+int pesr_gan_loss_map(const float* pred_real, const float* pred_fake, long n, int gan_type, int side, int focal, float gamma, float scale,
+                      float* out, float* d_real, float* d_fake, void* workspace, size_t ws_bytes, void* stream);
+size_t pesr_conv3x3_c1_wgrad_workspace_bytes(int N, int H, int W, int C);
+int pesr_conv3x3_c1_fwd(const float* x, const float* w, const float* bias, float* y, int N, int H, int W, int C, void* stream);
+int pesr_conv3x3_c1_dgrad(const float* dy, const float* w, float* dx, int N, int H, int W, int C, void* stream);
+int pesr_conv3x3_c1_wgrad(const float* x, const float* dy, float* dw, float* db, int N, int H, int W, int C, float alpha, void* workspace,
+                          size_t ws_bytes, void* stream);
+
 /* ---- backward of the upsampler's tail: conv C -> 4C, PixelShuffle(2), conv C -> 3 (reference model/basic.py:56-60), as the backward
  * of one virtual 3 x 3 conv V from C to 64 channels (48 used) at the resolution of the tail's input h [N][H][W][C]
  * (docs/experiments/upsample_tail.md has the algebra).  w2 OIHW [4C][C][3][3], b2 [4C], w4 OIHW [3][C][3][3], all fp32; C % 16 == 0,

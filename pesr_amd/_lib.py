@@ -129,6 +129,14 @@ SIGNATURES.update({
     "pesr_ca_apply_fwd": (c_int, [_P, _P, _P, _P, c_int, c_long, c_int, c_float, _P]),
     "pesr_ca_gate_bwd": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, _P, c_size_t, _P]),
     "pesr_ca_apply_bwd": (c_int, [_P, _P, _P, _P, c_int, c_long, c_int, c_float, _P]),
+    "pesr_bilinear_up2_fwd": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, _P]),
+    "pesr_bilinear_up2_bwd": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P]),
+    "pesr_gan_loss_map_workspace_bytes": (c_size_t, [c_long]),
+    "pesr_gan_loss_map": (c_int, [_P, _P, c_long, c_int, c_int, c_int, c_float, c_float, _P, _P, _P, _P, c_size_t, _P]),
+    "pesr_conv3x3_c1_wgrad_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "pesr_conv3x3_c1_fwd": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, _P]),
+    "pesr_conv3x3_c1_dgrad": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, _P]),
+    "pesr_conv3x3_c1_wgrad": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_float, _P, c_size_t, _P]),
     "pesr_upsample_tail_gather":(c_int, [_P, _P, c_int, c_int, c_int, _P]),
     "pesr_upsample_tail_compose": (c_int, [_P, _P, _P, c_int, _P]),
     "pesr_upsample_tail_chain": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, _P]),

@@ -504,6 +504,30 @@ PESR_API int pesr_ca_apply_bwd(const float* gy, const float* s, const float* dm,
     return pesr_ca_apply_launch(gy, nullptr, s, dm, gt, N, HW, C, res_scale, (hipStream_t)stream);
 }
 
+PESR_API int pesr_bilinear_up2_fwd(const float* a, const float* b_or_null, float* y, int N, int H, int W, int C, void* stream) {
+    return pesr_bilinear_up2_fwd_launch(a, b_or_null, y, N, H, W, C, (hipStream_t)stream);
+}
+PESR_API int pesr_bilinear_up2_bwd(const float* gy, float* gx, int N, int H, int W, int C, void* stream) {
+    return pesr_bilinear_up2_bwd_launch(gy, gx, N, H, W, C, (hipStream_t)stream);
+}
+PESR_API size_t pesr_gan_loss_map_workspace_bytes(long n) { return pesr_gan_loss_map_ws_bytes(n); }
+PESR_API int pesr_gan_loss_map(const float* pred_real, const float* pred_fake, long n, int gan_type, int side, int focal, float gamma,
+                               float scale, float* out, float* d_real, float* d_fake, void* workspace, size_t ws_bytes, void* stream) {
+    return pesr_gan_loss_map_launch(pred_real, pred_fake, n, gan_type, side, focal, gamma, scale, out, d_real, d_fake, workspace, ws_bytes,
+                                    (hipStream_t)stream);
+}
+PESR_API size_t pesr_conv3x3_c1_wgrad_workspace_bytes(int N, int H, int W, int C) { return pesr_conv3x3_c1_wgrad_ws_bytes(N, H, W, C); }
+PESR_API int pesr_conv3x3_c1_fwd(const float* x, const float* w, const float* bias, float* y, int N, int H, int W, int C, void* stream) {
+    return pesr_conv3x3_c1_fwd_launch(x, w, bias, y, N, H, W, C, (hipStream_t)stream);
+}
+PESR_API int pesr_conv3x3_c1_dgrad(const float* dy, const float* w, float* dx, int N, int H, int W, int C, void* stream) {
+    return pesr_conv3x3_c1_dgrad_launch(dy, w, dx, N, H, W, C, (hipStream_t)stream);
+}
+PESR_API int pesr_conv3x3_c1_wgrad(const float* x, const float* dy, float* dw, float* db, int N, int H, int W, int C, float alpha,
+                                   void* workspace, size_t ws_bytes, void* stream) {
+    return pesr_conv3x3_c1_wgrad_launch(x, dy, dw, db, N, H, W, C, alpha, workspace, ws_bytes, (hipStream_t)stream);
+}
+
 PESR_API int pesr_upsample_tail_gather(const float* g, float* gw, int N, int H, int W, void* stream) {
     return pesr_upsample_tail_gather_launch(g, gw, N, H, W, (hipStream_t)stream);
 }

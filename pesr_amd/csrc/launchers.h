@@ -294,6 +294,19 @@ int pesr_ca_gate_bwd_launch(const float* ds, const float* s, const float* h, con
                             float* dW1, float* dB1, float* dW2, float* dB2, int N, int C, int R, void* ws, size_t ws_bytes,
                             hipStream_t stream);
 
+// the U-Net discriminator's kernels: bilinear x2 and its adjoint (upsample2x.hip), the GAN loss of a logit map (loss.hip), the 3 x 3 conv
+// from C channels to one (conv_c1.hip)
+int pesr_bilinear_up2_fwd_launch(const float* a, const float* b, float* y, int N, int H, int W, int C, hipStream_t stream);
+int pesr_bilinear_up2_bwd_launch(const float* gy, float* gx, int N, int H, int W, int C, hipStream_t stream);
+size_t pesr_gan_loss_map_ws_bytes(long n);
+int pesr_gan_loss_map_launch(const float* pred_real, const float* pred_fake, long n, int gan, int side, int focal, float gamma, float scale,
+                             float* out, float* d_real, float* d_fake, void* ws, size_t ws_bytes, hipStream_t stream);
+size_t pesr_conv3x3_c1_wgrad_ws_bytes(int N, int H, int W, int C);
+int pesr_conv3x3_c1_fwd_launch(const float* x, const float* w, const float* bias, float* y, int N, int H, int W, int C, hipStream_t stream);
+int pesr_conv3x3_c1_dgrad_launch(const float* dy, const float* w, float* dx, int N, int H, int W, int C, hipStream_t stream);
+int pesr_conv3x3_c1_wgrad_launch(const float* x, const float* dy, float* dw, float* db, int N, int H, int W, int C, float alpha, void* ws,
+                                 size_t ws_bytes, hipStream_t stream);
+
 // backward of the upsampler's tail (conv C -> 4C, PixelShuffle(2), conv C -> 3) as one virtual C -> 64 conv (upsample_tail.hip)
 int pesr_upsample_tail_gather_launch(const float* g, float* gw, int N, int H, int W, hipStream_t stream);
 int pesr_upsample_tail_compose_launch(const float* w2, const float* w4, float* weff, int C, hipStream_t stream);

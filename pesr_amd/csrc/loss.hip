@@ -221,3 +221,136 @@ int pesr_gan_loss_launch(const float* pred_real, const float* pred_fake, int B, 
                        d_fake);
     return pesr_launch_status();
 }
+
+// ------------------------------------------------------------------------------------------------
+// The same losses on a logit MAP (docs/modes.md section 4v: the U-Net discriminator's [B, 1, H, W] output, or any patch-wise D):
+// n = B * H * W logits of any n >= 1, the real and the fake logit of one (b, y, x) paired by their index.  bce_logits / loss_term above
+// are the definitions; every mean runs over all n elements.  No atomics: a 256-lane workgroup owns MAP_PER_BLOCK consecutive logits
+// (past MAP_MAX_BLOCKS workgroups: every MAP_MAX_BLOCKS-th such chunk), a lane adds its elements in increasing order in fp32, the
+// lanes meet in wave_sum's tree and the four waves in order; the workgroups' rows are added in double by reduce_rows.h's second
+// stage - an order that depends on n alone.
+//   RaSGAN:  sums (r, f per workgroup) -> means (mean r, mean f)  -> terms (value, ga, gb per workgroup) -> final (the value; sa, sb)
+//            -> grads (d_real, d_fake, the terms computed again: they are cheaper than a round trip of two more maps)
+//   others:  terms (which also writes the gradients) -> final
+// Workspace: [0, 64) four floats (mean r, mean f, sa, sb), then the [blocks][2] and [blocks][3] rows.
+// ------------------------------------------------------------------------------------------------
+#define MAP_LANES 256
+#define MAP_PER_BLOCK 1024
+#define MAP_MAX_BLOCKS 4096
+
+static int map_blocks(long n) {
+    const long nb = (n + MAP_PER_BLOCK - 1) / MAP_PER_BLOCK;
+    return (int)(nb < MAP_MAX_BLOCKS ? nb : MAP_MAX_BLOCKS);
+}
+size_t pesr_gan_loss_map_ws_bytes(long n) { return n < 1 ? 0 : 64 + (size_t)map_blocks(n) * 5 * sizeof(float); }
+
+namespace {
+// the fixed-order sum of one value per lane over a 256-lane workgroup, to lane 0 (red: [4] floats of LDS)
+__device__ __forceinline__ float map_block_sum(float v, float* red) {
+    const float w = wave_sum(v);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = w;
+    __syncthreads();
+    return ((red[0] + red[1]) + red[2]) + red[3];
+}
+// the per-element terms: val, and d(sum of terms)/d(r_i), d/d(f_i) before the 1/n.  RaSGAN: ga, gb (the caller adds the mean's part)
+__device__ __forceinline__ void map_terms(float r, float f, int gan, int side, int fo, float gamma, float mr, float mf, float* val,
+                                          float* gr, float* gf) {
+    *gr = 0.f; *gf = 0.f;
+    if (gan == 0) {
+        if (side == 0) {
+            float v1, v2;
+            loss_term(r, 1.f, 0, 0.f, &v1, gr); loss_term(f, 0.f, 0, 0.f, &v2, gf);
+            *val = v1 + v2;
+        } else { loss_term(f, 1.f, fo, gamma, val, gf); }
+    } else if (gan == 1) {
+        float g;
+        if (side == 0) { loss_term(r - f, 1.f, 0, 0.f, val, &g); *gr = g; *gf = -g; }
+        else { loss_term(f - r, 1.f, fo, gamma, val, &g); *gf = g; *gr = -g; }
+    } else {
+        float va, vb;
+        loss_term(r - mf, side == 0 ? 1.f : 0.f, fo, gamma, &va, gr);      // ga
+        loss_term(f - mr, side == 0 ? 0.f : 1.f, fo, gamma, &vb, gf);      // gb
+        *val = 0.5f * (va + vb);
+    }
+}
+}  // namespace
+
+__global__ __launch_bounds__(MAP_LANES) void gan_map_sums_kernel(const float* __restrict__ pr, const float* __restrict__ pf, long n,
+                                                                 float* __restrict__ part) {
+    __shared__ float red[4];
+    float sr = 0.f, sf = 0.f;
+    for (long base = (long)blockIdx.x * MAP_PER_BLOCK; base < n; base += (long)gridDim.x * MAP_PER_BLOCK)
+        for (long e = base + threadIdx.x; e < base + MAP_PER_BLOCK && e < n; e += MAP_LANES) { sr += pr[e]; sf += pf[e]; }
+    const float a = map_block_sum(sr, red), b = map_block_sum(sf, red);
+    if (threadIdx.x == 0) { part[blockIdx.x * 2] = a; part[blockIdx.x * 2 + 1] = b; }
+}
+__global__ __launch_bounds__(1024) void gan_map_means_kernel(const float* __restrict__ part, int nb, double inv_n, float* __restrict__ head) {
+    __shared__ double red[16][64];
+    const int cl = threadIdx.x & 63;
+    const double t = reduce_rows_block(part, nb, 2, cl, cl < 2, red);
+    if (threadIdx.x < 2) head[threadIdx.x] = (float)(t * inv_n);
+}
+// GRADS: the RaSGAN gradient pass (head holds the means and sa, sb); else the terms pass, which writes the gradients of SGAN / RSGAN
+template <bool GRADS>
+__global__ __launch_bounds__(MAP_LANES) void gan_map_terms_kernel(const float* __restrict__ pr, const float* __restrict__ pf, long n, int gan,
+                                                                  int side, int focal, float gamma, float gscale,
+                                                                  const float* __restrict__ head, float* __restrict__ part,
+                                                                  float* __restrict__ d_real, float* __restrict__ d_fake, float inv_n) {
+    __shared__ float red[4];
+    const int fo = side == 1 ? focal : 0;
+    float mr = 0.f, mf = 0.f, sa = 0.f, sb = 0.f;
+    if (gan == 2) { mr = head[0]; mf = head[1]; }
+    if (GRADS) { sa = head[2]; sb = head[3]; }
+    float sv = 0.f, sga = 0.f, sgb = 0.f;
+    for (long base = (long)blockIdx.x * MAP_PER_BLOCK; base < n; base += (long)gridDim.x * MAP_PER_BLOCK)
+        for (long e = base + threadIdx.x; e < base + MAP_PER_BLOCK && e < n; e += MAP_LANES) {
+            float val, gr, gf;
+            map_terms(pr[e], pf[e], gan, side, fo, gamma, mr, mf, &val, &gr, &gf);
+            if (GRADS) {                      // r_i also moves every b_j through mean r (and f_i every a_j)
+                if (d_real) d_real[e] = gscale * (0.5f * (gr - sb * inv_n));
+                if (d_fake) d_fake[e] = gscale * (0.5f * (gf - sa * inv_n));
+            } else {
+                sv += val; sga += gr; sgb += gf;
+                if (gan != 2) {
+                    if (d_real) d_real[e] = gscale * gr;
+                    if (d_fake) d_fake[e] = gscale * gf;
+                }
+            }
+        }
+    if (!GRADS) {
+        const float a = map_block_sum(sv, red), b = map_block_sum(sga, red), c = map_block_sum(sgb, red);
+        if (threadIdx.x == 0) { part[blockIdx.x * 3] = a; part[blockIdx.x * 3 + 1] = b; part[blockIdx.x * 3 + 2] = c; }
+    }
+}
+__global__ __launch_bounds__(1024) void gan_map_final_kernel(const float* __restrict__ part, int nb, double inv_n, float scale,
+                                                             float* __restrict__ out, float* __restrict__ head) {
+    __shared__ double red[16][64];
+    const int cl = threadIdx.x & 63;
+    const double t = reduce_rows_block(part, nb, 3, cl, cl < 3, red);
+    if (threadIdx.x == 0) out[0] = scale * (float)(t * inv_n);
+    if (threadIdx.x == 1 || threadIdx.x == 2) head[1 + threadIdx.x] = (float)t;       // sa, sb
+}
+
+int pesr_gan_loss_map_launch(const float* pred_real, const float* pred_fake, long n, int gan, int side, int focal, float gamma, float scale,
+                             float* out, float* d_real, float* d_fake, void* ws, size_t ws_bytes, hipStream_t stream) {
+    if (n < 1 || gan < 0 || gan > 2 || side < 0 || side > 1 || !pred_real || !pred_fake || !out) return PESR_EINVAL;
+    if (!ws || ws_bytes < pesr_gan_loss_map_ws_bytes(n)) return PESR_EWORKSPACE;
+    const int nb = map_blocks(n);
+    float* head = (float*)ws;
+    float* part1 = (float*)((char*)ws + 64);
+    float* part2 = part1 + (size_t)nb * 2;
+    const double inv_n = 1.0 / (double)n;
+    const float gscale = (float)((double)scale * inv_n);
+    if (gan == 2) {
+        hipLaunchKernelGGL(gan_map_sums_kernel, dim3(nb), dim3(MAP_LANES), 0, stream, pred_real, pred_fake, n, part1);
+        hipLaunchKernelGGL(gan_map_means_kernel, dim3(1), dim3(1024), 0, stream, (const float*)part1, nb, inv_n, head);
+    }
+    hipLaunchKernelGGL(gan_map_terms_kernel<false>, dim3(nb), dim3(MAP_LANES), 0, stream, pred_real, pred_fake, n, gan, side, focal, gamma,
+                       gscale, (const float*)head, part2, d_real, d_fake, (float)inv_n);
+    hipLaunchKernelGGL(gan_map_final_kernel, dim3(1), dim3(1024), 0, stream, (const float*)part2, nb, inv_n, scale, out, head);
+    if (gan == 2 && (d_real || d_fake))
+        hipLaunchKernelGGL(gan_map_terms_kernel<true>, dim3(nb), dim3(MAP_LANES), 0, stream, pred_real, pred_fake, n, gan, side, focal, gamma,
+                           gscale, (const float*)head, (float*)nullptr, d_real, d_fake, (float)inv_n);
+    return pesr_launch_status();
+}

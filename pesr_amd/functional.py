@@ -348,7 +348,12 @@ def _conv_wgrad(x, gy, weight, bias_ref, stride, ps, want_w, want_b, *, alpha=1.
     kw = dict(alpha=alpha, want_bias=want_b, dw_out=o_w, db_out=o_b, accumulate=again is not None)
     side = ops.wgrad_rgb_side(x.shape[3], weight.shape[0])
     with _OnSide(gy.device, x, gy, fast=o_w is not None and (o_b is not None or not want_b), where=where):
-        if side is None:
+        if ops.c1_eligible(x.shape[3], weight.shape[0], stride):     # C -> 1: its own kernels (csrc/conv_c1.hip)
+            if again is not None:
+                raise NotImplementedError("the C -> 1 weight gradient has no accumulating form: a node that adds a second use in "
+                                          "place (_second_use) cannot hold a one-channel conv")
+            dw, db = ops.conv3x3_c1_wgrad(x, gy, alpha=alpha, want_bias=want_b, dw_out=o_w, db_out=o_b)
+        elif side is None:
             dw, db = ops.conv3x3_wgrad(x, gy, stride, ps_in=ps, **kw)
         else:
             dw, db = ops.conv3x3_wgrad_rgb(gy, x, 0, **kw) if side == 0 else ops.conv3x3_wgrad_rgb(x, gy, 1, **kw)
@@ -360,7 +365,8 @@ def _dgrad_pack(weight, cache, x_shape, stride, plain=True):
     C -> 3 conv is a 3 -> C conv of dy, dx of a 3 -> C conv a C -> 3 conv of dy (plain: no fused mask / skip / scale, which they lack).
     Nodes that pack before their weight gradient (packing happens on the main stream) call this first and hand the result on."""
     cin, cout = x_shape[3], weight.shape[0]
-    if plain and not cache.ps and (ops.rgb_in_eligible(cout, cin, stride) or ops.rgb_in_dgrad_eligible(cin, cout, stride)):
+    if plain and not cache.ps and (ops.rgb_in_eligible(cout, cin, stride) or ops.rgb_in_dgrad_eligible(cin, cout, stride) or
+                                   ops.c1_eligible(cin, cout, stride)):
         return None
     return cache.for_dgrad(weight, x_shape, stride)
 
@@ -375,6 +381,8 @@ def _conv_dgrad(gy, weight, cache, x_shape, stride=1, *, mask=None, skip=None, a
     x_shape = tuple(x_shape)
     if wpd is _PACK_NOW:
         wpd = _dgrad_pack(weight, cache, x_shape, stride, mask is None and skip is None and alpha == 1.0)
+    if wpd is None and weight.shape[0] == 1:
+        return ops.conv3x3_c1_dgrad(gy, weight.detach(), x_shape)
     if wpd is None:
         return (ops.conv3x3_rgb_in_dgrad if x_shape[3] == 3 else ops.conv3x3_rgb_dgrad)(gy, weight.detach(), x_shape)
     if prev_link is not None and prev_link.z is not None:
@@ -789,6 +797,24 @@ class ChannelAttentionFn(Function):
                                                  grad_out(ctx.b2_ref))
         gt = ops.ca_apply_bwd(gy, s, dm, ctx.res_scale) if ctx.needs_input_grad[1] else None
         return (gy if ctx.needs_input_grad[0] else None), gt, dw1, db1, dw2, db2, None
+
+
+class BilinearUp2Fn(Function):
+    """y = up2(a + b), b optional: bilinear x2 (F.interpolate(scale_factor=2, mode='bilinear', align_corners=False)) of an NHWC map, the
+    decoder step of the U-Net discriminator with the skip addition in front of it folded in (docs/modes.md section 4v).  up2 is linear:
+    the backward is its adjoint, one kernel, and the one tensor is the gradient of both addends.  fp32 whatever ops.PRECISION is."""
+
+    @staticmethod
+    def forward(ctx, a, b=None):
+        return ops.bilinear_up2_fwd(_c(a), None if b is None else _c(b))
+
+    @staticmethod
+    def backward(ctx, gy):
+        need_a, need_b = ctx.needs_input_grad[0], len(ctx.needs_input_grad) > 1 and ctx.needs_input_grad[1]
+        if not (need_a or need_b):
+            return None, None
+        gx = ops.bilinear_up2_bwd(_c(gy))
+        return (gx if need_a else None), (gx if need_b else None)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -1267,8 +1293,11 @@ class GanLossFn(Function):
     @staticmethod
     def forward(ctx, pred_real, pred_fake, gan_type, side, focal, gamma, scale):
         pr, pf = _c(pred_real), _c(pred_fake)
-        out, d_r, d_f = ops.gan_loss(pr, pf, gan_type, side, focal, gamma, scale, need_real=pred_real.requires_grad,
-                                     need_fake=pred_fake.requires_grad)
+        # [B, 1] logits of up to 1024 samples: the one-workgroup kernel, as ever; a logit map ([B, 1, H, W], or a longer vector): the
+        # map kernels (docs/modes.md section 4v)
+        fn = ops.gan_loss if pr.dim() == 2 and pr.shape[1] == 1 and pr.shape[0] <= 1024 else ops.gan_loss_map
+        out, d_r, d_f = fn(pr, pf, gan_type, side, focal, gamma, scale, need_real=pred_real.requires_grad,
+                           need_fake=pred_fake.requires_grad)
         ctx.save_for_backward(d_r, d_f)
         return out[0]
 

@@ -8,7 +8,7 @@ import torch.nn as nn
 
 from .. import functional as PF
 from .. import ops
-from .basic import SCALES, BasicBlock, Conv, MeanShift, ResBlock, Upsampler, nchw, nhwc
+from .basic import SCALES, BasicBlock, Conv, MeanShift, ResBlock, Upsampler, nchw, nhwc, spectral_norm
 
 _DIV2K_MEAN = (0.4488, 0.4371, 0.4040)      # reference model/pesr.py:13
 _UNIT_STD = (1.0, 1.0, 1.0)
@@ -137,6 +137,75 @@ class Discriminator(nn.Module):
 
     def forward(self, x):
         return self.classify(self.forward_features(x))
+
+
+class UNetDiscriminator(nn.Module):
+    """A U-Net discriminator with spectral norm that emits one logit per pixel (an extension, docs/modes.md section 4v): Real-ESRGAN's
+    `UNetDiscriminatorSN` (Wang et al., ICCVW 2021, after Schoenfeld et al., CVPR 2020) with ONE deviation - its three 4 x 4 stride-2
+    convs are 3 x 3 stride-2 here (the MFMA stride-2 kernels are 3 x 3 and Conv refuses even sizes), so its published weights do not load.
+    [B, 3, H, W] with H, W multiples of 8 -> [B, 1, H, W]; independent of opt['patch_size'].  w = opt.get('d_width', 64):
+        conv0 3 -> w (bias)                       lrelu -> x0          conv4 8w -> 4w on up2(x3)   lrelu, + x2 -> x4
+        conv1 w -> 2w, conv2 -> 4w, conv3 -> 8w,                       conv5 4w -> 2w on up2(x4)   lrelu, + x1 -> x5
+              stride 2                            lrelu -> x1, x2, x3  conv6 2w -> w  on up2(x5)   lrelu, + x0 -> x6
+        conv7, conv8 w -> w   lrelu                                    conv9 w -> 1 (bias)         the logits
+    LeakyReLU(0.2), no BatchNorm; conv1 .. conv8 have no bias and, with opt['spectral_norm'], spectral norm (torch's state_dict schema).
+    up2 = bilinear x2; it is linear, so the additions `+ x2`, `+ x1` run inside the upsample kernel that follows them.  The convs are
+    constructed (and draw their nn.Conv2d default initialisation, then u and v) in the order conv0 .. conv9."""
+
+    def __init__(self, opt):
+        super().__init__()
+        w = opt.get('d_width', 64)
+        if w < 4 or w % 4:
+            raise ValueError(f"UNetDiscriminator: d_width = {w}; a positive multiple of 4 (train.py asks for a multiple of 16)")
+        sn = (lambda c: spectral_norm(c)) if opt['spectral_norm'] else (lambda c: c)
+        self.slope = 0.2
+        self.conv0 = Conv(3, w, 3)
+        self.conv1 = sn(Conv(w, 2 * w, 3, stride=2, bias=False))
+        self.conv2 = sn(Conv(2 * w, 4 * w, 3, stride=2, bias=False))
+        self.conv3 = sn(Conv(4 * w, 8 * w, 3, stride=2, bias=False))
+        self.conv4 = sn(Conv(8 * w, 4 * w, 3, bias=False))
+        self.conv5 = sn(Conv(4 * w, 2 * w, 3, bias=False))
+        self.conv6 = sn(Conv(2 * w, w, 3, bias=False))
+        self.conv7 = sn(Conv(w, w, 3, bias=False))
+        self.conv8 = sn(Conv(w, w, 3, bias=False))
+        self.conv9 = Conv(w, 1, 3)
+        self.width = w
+
+    def _act(self, conv, h):
+        return PF.ConvLReluFn.apply(h, conv.effective_weight(), conv.bias, conv.packed, conv.stride, self.slope)
+
+    def forward(self, x):
+        if x.dim() != 4 or x.shape[1] != 3 or x.shape[2] < 8 or x.shape[3] < 8 or x.shape[2] % 8 or x.shape[3] % 8:
+            raise ValueError(f"UNetDiscriminator: input {tuple(x.shape)}; expected [B, 3, H, W] with H and W multiples of 8 (three "
+                             f"stride-2 stages and their x2 upsamplings)")
+        x0 = self._act(self.conv0, nhwc(x))
+        x1 = self._act(self.conv1, x0)
+        x2 = self._act(self.conv2, x1)
+        x3 = self._act(self.conv3, x2)
+        t4 = self._act(self.conv4, PF.BilinearUp2Fn.apply(x3))
+        t5 = self._act(self.conv5, PF.BilinearUp2Fn.apply(t4, x2))        # up2(x4), x4 = t4 + x2
+        t6 = self._act(self.conv6, PF.BilinearUp2Fn.apply(t5, x1))        # up2(x5), x5 = t5 + x1
+        x6 = PF.ScaleAddFn.apply(t6, x0, 1.0)
+        h = self._act(self.conv8, self._act(self.conv7, x6))
+        c9 = self.conv9
+        return nchw(PF.conv3x3(h, c9.weight, c9.bias, c9.packed))
+
+    def forward_features(self, *a, **k):
+        raise TypeError("UNetDiscriminator has no feature / classifier split: call it as a whole (the paired-classifier path of "
+                        "Trainer.gan_step applies to Discriminator only)")
+
+    classify = classify_pair = forward_features
+
+
+D_ARCHS = ("vgg", "unet")
+
+
+def build_discriminator(opt, d_arch="vgg"):
+    """train.py --d_arch: "vgg" - the reference's Discriminator(opt), constructed exactly as without the argument; "unet" - the
+    UNetDiscriminator(opt) (opt['d_width'], docs/modes.md section 4v)."""
+    if d_arch not in D_ARCHS:
+        raise ValueError(f"build_discriminator: d_arch = {d_arch!r}; one of {D_ARCHS}")
+    return UNetDiscriminator(opt) if d_arch == "unet" else Discriminator(opt)
 
 
 def _forward_second_order(self, x):

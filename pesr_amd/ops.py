@@ -504,6 +504,9 @@ def conv3x3_fwd(x: torch.Tensor, wp: torch.Tensor, bias: Optional[torch.Tensor],
         OP_EVENTS.end(br)
         _lib.check(rc, f"pesr_conv3x3_rgb_out_fwd[{N}x{H}x{W}x{Cin}->3]")
         return y
+    if plain and act == ACT_NONE and c1_eligible(Cin, cout, stride):
+        # -> one channel (the U-Net discriminator's logit layer): its own kernels, forward and both gradients
+        return conv3x3_c1_fwd(x, w_oihw, bias)
     if callable(wp):
         wp = wp()
     fam = _conv_family(wp)
@@ -1524,6 +1527,102 @@ def ca_apply_bwd(gy: torch.Tensor, s: torch.Tensor, dm: torch.Tensor, res_scale:
 
 
 # ------------------------------------------------------------------------------------------------
+# the U-Net discriminator's own kernels (docs/modes.md section 4v): bilinear x2 (csrc/upsample2x.hip), the 3 x 3 conv to one channel
+# (csrc/conv_c1.hip); the GAN loss of a logit map stands with gan_loss at the end of this file.  fp32 whatever PRECISION is.
+# ------------------------------------------------------------------------------------------------
+def _up2_map(what: str, t: torch.Tensor):
+    _chk(t, what)
+    if t.dim() != 4 or min(t.shape) < 1:
+        raise ValueError(f"{what}: expected a [N, H, W, C] tensor with no empty axis, got {tuple(t.shape)}")
+    return tuple(t.shape)
+
+
+def bilinear_up2_fwd(a: torch.Tensor, b: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """a (and b, same shape): NHWC [N, H, W, C] -> [N, 2H, 2W, C] = up2(a + b), up2 = F.interpolate(scale_factor=2, mode='bilinear',
+    align_corners=False); a + b is rounded once, as torch's own addition would."""
+    N, H, W, C = _up2_map("bilinear_up2_fwd.a", a)
+    if b is not None:
+        _chk(b, "bilinear_up2_fwd.b")
+        if b.shape != a.shape:
+            raise ValueError(f"bilinear_up2_fwd.b: expected {tuple(a.shape)}, got {tuple(b.shape)}")
+    y = torch.empty((N, 2 * H, 2 * W, C), dtype=torch.float32, device=a.device)
+    rc = _lib.lib().pesr_bilinear_up2_fwd(_p(a), _p(b), _p(y), N, H, W, C, _stream())
+    if rc == -1:
+        raise ValueError(f"bilinear_up2_fwd.a: shape {(N, H, W, C)} is beyond what the kernel indexes")
+    _lib.check(rc, f"pesr_bilinear_up2_fwd[{N}x{H}x{W}x{C}]")
+    return y
+
+
+def bilinear_up2_bwd(gy: torch.Tensor) -> torch.Tensor:
+    """gy: NHWC [N, 2H, 2W, C] -> gx [N, H, W, C], the adjoint of bilinear_up2_fwd (the gradient of a, and of b)."""
+    N, H2, W2, C = _up2_map("bilinear_up2_bwd.gy", gy)
+    if H2 % 2 or W2 % 2:
+        raise ValueError(f"bilinear_up2_bwd.gy: expected even height and width, got {tuple(gy.shape)}")
+    gx = torch.empty((N, H2 // 2, W2 // 2, C), dtype=torch.float32, device=gy.device)
+    rc = _lib.lib().pesr_bilinear_up2_bwd(_p(gy), _p(gx), N, H2 // 2, W2 // 2, C, _stream())
+    if rc == -1:
+        raise ValueError(f"bilinear_up2_bwd.gy: shape {tuple(gy.shape)} is beyond what the kernel indexes")
+    _lib.check(rc, f"pesr_bilinear_up2_bwd[{N}x{H2 // 2}x{W2 // 2}x{C}]")
+    return gx
+
+
+C1_MAX_CHANNELS = 1024
+
+
+def c1_eligible(cin: int, cout: int, stride: int) -> bool:
+    """Shapes of the pesr_conv3x3_c1_* kernels (C -> 1, stride 1): the implicit-GEMM kernels take no one-channel gradient."""
+    return cout == 1 and stride == 1 and cin % 4 == 0 and 4 <= cin <= C1_MAX_CHANNELS
+
+
+def _c1_pair(what: str, x_shape, x: Optional[torch.Tensor], dy: Optional[torch.Tensor], w: Optional[torch.Tensor]):
+    N, H, W, C = x_shape
+    if not c1_eligible(C, 1, 1) or N < 1 or H < 1 or W < 1 or N * H * W >= 1 << 31:
+        raise ValueError(f"{what}.x: shape {tuple(x_shape)}; the C -> 1 kernels take a multiple of 4 channels up to {C1_MAX_CHANNELS} and "
+                         f"fewer than 2^31 pixels")
+    for name, t, shape in (("x", x, (N, H, W, C)), ("dy", dy, (N, H, W, 1)), ("w", w, (1, C, 3, 3))):
+        if t is not None:
+            _chk(t, f"{what}.{name}")
+            if tuple(t.shape) != shape:
+                raise ValueError(f"{what}.{name}: expected {shape}, got {tuple(t.shape)}")
+    return N, H, W, C
+
+
+def conv3x3_c1_fwd(x: torch.Tensor, w_oihw: torch.Tensor, bias: Optional[torch.Tensor]) -> torch.Tensor:
+    """y [N, H, W, 1] = conv(x [N, H, W, C], w OIHW [1, C, 3, 3]) + bias [1]."""
+    N, H, W, C = _c1_pair("conv3x3_c1_fwd", x.shape, x, None, w_oihw)
+    y = torch.empty((N, H, W, 1), dtype=torch.float32, device=x.device)
+    _conv_flops(N, H, W, C, 1, _RGB_VALU)
+    br = OP_EVENTS.begin(f"conv_c1 {C}->1")
+    rc = _lib.lib().pesr_conv3x3_c1_fwd(_p(x), _p(w_oihw), _p(bias), _p(y), N, H, W, C, _stream())
+    OP_EVENTS.end(br)
+    _lib.check(rc, f"pesr_conv3x3_c1_fwd[{N}x{H}x{W}x{C}->1]")
+    return y
+
+
+def conv3x3_c1_dgrad(dy: torch.Tensor, w_oihw: torch.Tensor, in_shape) -> torch.Tensor:
+    """dx [N, H, W, C] of that conv from dy [N, H, W, 1]."""
+    N, H, W, C = _c1_pair("conv3x3_c1_dgrad", tuple(in_shape), None, dy, w_oihw)
+    dx = torch.empty((N, H, W, C), dtype=torch.float32, device=dy.device)
+    _conv_flops(N, H, W, C, 1, _RGB_VALU)
+    rc = _lib.lib().pesr_conv3x3_c1_dgrad(_p(dy), _p(w_oihw), _p(dx), N, H, W, C, _stream())
+    _lib.check(rc, f"pesr_conv3x3_c1_dgrad[{N}x{H}x{W}x{C}<-1]")
+    return dx
+
+
+def conv3x3_c1_wgrad(x: torch.Tensor, dy: torch.Tensor, alpha: float = 1.0, want_bias: bool = True, dw_out=None, db_out=None):
+    """(dw [1, C, 3, 3], db [1] | None) of that conv: per-chunk fp32 rows, added in double in a fixed order."""
+    N, H, W, C = _c1_pair("conv3x3_c1_wgrad", x.shape, x, dy, None)
+    L = _lib.lib()
+    ws = workspace(int(L.pesr_conv3x3_c1_wgrad_workspace_bytes(N, H, W, C)), x.device)
+    dw = _out(dw_out, (1, C, 3, 3), x.device)
+    db = _out(db_out, (1,), x.device) if want_bias else None
+    _conv_flops(N, H, W, C, 1, _RGB_VALU)
+    rc = L.pesr_conv3x3_c1_wgrad(_p(x), _p(dy), _p(dw), _p(db), N, H, W, C, float(alpha), _p(ws), ws.numel(), _stream())
+    _lib.check(rc, f"pesr_conv3x3_c1_wgrad[{N}x{H}x{W}x{C}->1]")
+    return dw, db
+
+
+# ------------------------------------------------------------------------------------------------
 # texture loss: patch-wise Gram matrices (docs/modes.md section 4q)
 # ------------------------------------------------------------------------------------------------
 GRAM_CHANNELS = (64, 128, 256)
@@ -1888,4 +1987,30 @@ def gan_loss(pred_real: torch.Tensor, pred_fake: torch.Tensor, gan_type: str, si
     rc = _lib.lib().pesr_gan_loss_fwd_bwd(_p(pred_real), _p(pred_fake), B, GAN_TYPES[gan_type], side, int(focal), float(gamma), float(scale),
                                           _p(out), _p(d_r), _p(d_f), _stream())
     _lib.check(rc, f"pesr_gan_loss_fwd_bwd[{gan_type}, side {side}]")
+    return out, d_r, d_f
+
+
+def gan_loss_map(pred_real: torch.Tensor, pred_fake: torch.Tensor, gan_type: str, side: int, focal: bool, gamma: float, scale: float = 1.0,
+                 need_real: bool = True, need_fake: bool = True):
+    """The same definitions on a logit map of any shape and size (docs/modes.md section 4v): -> (out [1] = scale * the mean over all
+    elements, d_real | None, d_fake | None shaped like the logits).  RSGAN pairs the logits of one index, RaSGAN's means run over every
+    element.  Two launches (RaSGAN: five), per-workgroup fp32 rows added in double in a fixed order."""
+    _chk(pred_real, "gan_loss_map.pred_real"); _chk(pred_fake, "gan_loss_map.pred_fake")
+    n = pred_real.numel()
+    if n < 1:
+        raise ValueError(f"gan_loss_map.pred_real: an empty tensor {tuple(pred_real.shape)}")
+    if pred_fake.shape != pred_real.shape:
+        raise ValueError(f"gan_loss_map.pred_fake: expected {tuple(pred_real.shape)}, got {tuple(pred_fake.shape)}")
+    if gan_type not in GAN_TYPES:
+        raise ValueError(f"gan_loss_map.gan_type: {gan_type!r}; one of {tuple(GAN_TYPES)}")
+    if side not in (0, 1):
+        raise ValueError(f"gan_loss_map.side: {side!r}; 0 (discriminator) or 1 (generator)")
+    L = _lib.lib()
+    out = torch.empty(1, dtype=torch.float32, device=pred_real.device)
+    d_r = torch.empty_like(pred_real) if need_real else None
+    d_f = torch.empty_like(pred_fake) if need_fake else None
+    ws = workspace(int(L.pesr_gan_loss_map_workspace_bytes(n)), pred_real.device)
+    rc = L.pesr_gan_loss_map(_p(pred_real), _p(pred_fake), n, GAN_TYPES[gan_type], side, int(focal), float(gamma), float(scale), _p(out),
+                             _p(d_r), _p(d_f), _p(ws), ws.numel(), _stream())
+    _lib.check(rc, f"pesr_gan_loss_map[{gan_type}, side {side}, n {n}]")
     return out, d_r, d_f

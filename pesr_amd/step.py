@@ -20,7 +20,7 @@ from . import functional as PF
 from . import loss_terms
 from .model.basic import nhwc
 from .model.focal_loss import FocalLoss
-from .model.pesr import Discriminator
+from .model.pesr import Discriminator, UNetDiscriminator
 
 
 class _GlobalBatchMean(torch.autograd.Function):
@@ -49,7 +49,8 @@ class _GlobalBatchMean(torch.autograd.Function):
 
 
 def batch_mean(x, world=1):
-    return x.mean() if world == 1 else _GlobalBatchMean.apply(x, world)
+    # (a logit map - the U-Net discriminator's [B, 1, H, W] - goes in flattened: the mean runs over every logit of every rank)
+    return x.mean() if world == 1 else _GlobalBatchMean.apply(x.reshape(-1, 1), world)
 
 
 def rasgan_d_loss(pred_real, pred_fake, target_real, target_fake, world=1):
@@ -102,14 +103,18 @@ class Trainer:
         if gradient_penalty and ops.PRECISION != "fp32":
             raise ValueError("the gradient penalty (--GP true) is only built for the fp32 arithmetic: the optional bf16 mode has "
                              "no second-order oracle (use --precision fp32)")
+        if gradient_penalty and isinstance(D, UNetDiscriminator):
+            raise ValueError("gradient_penalty = True with a UNetDiscriminator: the penalty needs a twice-differentiable bilinear "
+                             "upsample node, which is not built (docs/modes.md section 4v); use the VGG-style Discriminator")
         self._targets = {}
         self._graph = None
         self.dp_policy, self.dp_step = "overlap", None
 
     def _target(self, batch, value, device):
+        """batch: the batch size of [B, 1] logits, or the shape of a logit map."""
         key = (batch, value, device)
         if key not in self._targets:
-            self._targets[key] = torch.full((batch, 1), float(value), device=device)
+            self._targets[key] = torch.full((batch, 1) if isinstance(batch, int) else batch, float(value), device=device)
         return self._targets[key]
 
     # ---- reference train.py:164-173 -----------------------------------------------------------------
@@ -166,7 +171,12 @@ class Trainer:
             pred_fake = D(sr.detach())
         if self.gan_type not in ("SGAN", "RSGAN", "RaSGAN"):
             raise ValueError(f"unknown gan_type {self.gan_type}")
-        fused = pred_real.is_cuda and B <= 1024 and not (self.gan_type == "RaSGAN" and self.world_size > 1)
+        # [B, 1] logits: the one-workgroup kernel up to 1024 samples; any other shape (the U-Net discriminator's [B, 1, H, W] map): the
+        # map kernels, which take any size (functional.GanLossFn chooses by the shape)
+        is_map = pred_real.dim() != 2 or pred_real.shape[1] != 1
+        fused = pred_real.is_cuda and (is_map or B <= 1024) and not (self.gan_type == "RaSGAN" and self.world_size > 1)
+        if is_map and not fused:       # the torch paths below build their targets in the logits' shape
+            target_real, target_fake = self._target(tuple(pred_real.shape), 1.0, dev), self._target(tuple(pred_real.shape), 0.0, dev)
         if fused:        # value and both gradients in one kernel (ops.gan_loss) instead of ~25 scalar-sized torch kernels
             total_D_loss = PF.gan_loss(pred_real, pred_fake, self.gan_type, 0)
         elif self.gan_type == "SGAN":

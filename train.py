@@ -59,6 +59,11 @@ def build_parser():
                         "block of the Generator (docs/modes.md section 4u); none (default): the reference's blocks")
     p.add_argument("--ca_reduction", type=int, default=16,
                    help="with --attention ca: the gate's hidden width is --num_channels / this; it has to divide --num_channels")
+    p.add_argument("--d_arch", type=str, default="vgg", choices=["vgg", "unet"],
+                   help="unet: a U-Net discriminator with one logit per pixel (Real-ESRGAN's, with 3 x 3 stride-2 convs; docs/modes.md "
+                        "section 4v), independent of --patch_size; vgg (default): the reference's Discriminator.  Unused in --phase pretrain")
+    p.add_argument("--d_width", type=int, default=64,
+                   help="with --d_arch unet: the channels of its first conv (a positive multiple of 16)")
     p.add_argument("--synthetic", type=int, default=0, help="train on N synthetic samples per epoch instead of a dataset folder")
     p.add_argument("--vgg_weights", type=str, default="",
                    help="state_dict file of torchvision's pretrained vgg19 (torch.save(torchvision.models.vgg19(pretrained=True)"
@@ -376,6 +381,20 @@ def attention_of(args):
     return args.ca_reduction
 
 
+def d_arch_of(args):
+    """--d_arch / --d_width -> "vgg" or "unet"; SystemExit naming the flag.  No GPU is touched."""
+    if args.d_width < 16 or args.d_width % 16:
+        raise SystemExit(f"train.py: --d_width {args.d_width} must be a positive multiple of 16")
+    if args.d_arch == "unet" and args.GP and args.phase != "pretrain":      # (the pretrain phase builds no Discriminator at all)
+        raise SystemExit("train.py: --GP true with --d_arch unet is not built: the gradient penalty needs a twice-differentiable "
+                         "bilinear upsample node (docs/modes.md section 4v); use --d_arch vgg or --GP false")
+    side = args.patch_size * args.scale
+    if args.d_arch == "unet" and args.phase != "pretrain" and (side < 8 or side % 8):
+        raise SystemExit(f"train.py: --d_arch unet needs (--patch_size * --scale) to be a multiple of 8, here {args.patch_size} * "
+                         f"{args.scale} = {side} (three stride-2 stages and their x2 upsamplings)")
+    return args.d_arch
+
+
 def check_pretrained_attention(sd, args, path):
     """A --pretrained_model whose channel attention is not this run's: SystemExit naming both (instead of load_state_dict's key dump)."""
     from pesr_amd.model import attention_of_state_dict
@@ -461,6 +480,7 @@ def main(argv=None):
     args = build_parser().parse_args(argv)
     degradation_spec(args)      # (refuses a classical run without its companion flags before anything else starts)
     attention = attention_of(args)
+    d_arch = d_arch_of(args)
     scorer = scorer_of(args)
     loss_terms = loss_terms_of(args, scorer.lpips_model)
     world =int(os.environ.get("WORLD_SIZE", "1"))
@@ -517,7 +537,8 @@ def main(argv=None):
         G.load_state_dict(check_pretrained_attention(torch.load(args.pretrained_model, map_location="cpu"), args, args.pretrained_model))
     G = G.to(device)
     gan = args.phase != "pretrain"
-    D = Discriminator(opt).to(device) if gan else None
+    from model import build_discriminator
+    D = build_discriminator(dict(opt, d_width=args.d_width) if d_arch == "unet" else opt, d_arch).to(device) if gan else None
     vgg = build_vgg(args, device, rank, world) if gan else None
 
     optim_G = FlatAdam([p for p in G.parameters() if p.requires_grad], lr=args.learning_rate, betas=(0.9, 0.999),
