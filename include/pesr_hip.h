@@ -582,6 +582,18 @@ int pesr_conv3x3_c1_dgrad(const float* dy, const float* w, float* dx, int N, int
 int pesr_conv3x3_c1_wgrad(const float* x, const float* dy, float* dw, float* db, int N, int H, int W, int C, float alpha, void* workspace,
                           size_t ws_bytes, void* stream);
 
+/* ---- window self-attention of the Generator's attention blocks (docs/modes.md section 4w) ---------------------------------------- */
+/* qkv fp32 NHWC [N][H][W][3 D]: channels 0..D-1 q, D..2D-1 k, 2D..3D-1 v, head h the channels 32h..32h+31 of each.  Windows of 8 x 8
+ * pixels on a grid with its origin at (-shift, -shift); positions outside the image are no tokens.  Per window and head, over its
+ * tokens: S = q k^T / sqrt(32), A = softmax over the keys (row maximum subtracted), o = A v -> out [N][H][W][D].
+ * backward: dout [N][H][W][D] -> dqkv [N][H][W][3 D] (dv = A^T do, dA = do v^T, dS = A (dA - rowsum(dA A)), dq = dS k / sqrt(32),
+ * dk = dS^T q / sqrt(32)), every element written once, no zero-fill needed; S and A are recomputed from qkv, nothing else is kept.
+ * fp32 MFMA products, no atomics, fixed summation orders: the same bits on every call.  64-bit element offsets.
+ * PESR_EINVAL with nothing launched (checked before any device call): D < 32, D % 32, D > 1024, shift outside 0..7, N, H or W < 1,
+ * more than 2^31 - 1 windows, a NULL tensor or one off a 16-byte boundary. */
+int pesr_window_attention_fwd(const float* qkv, float* out, int N, int H, int W, int D, int shift, void* stream);
+int pesr_window_attention_bwd(const float* qkv, const float* dout, float* dqkv, int N, int H, int W, int D, int shift, void* stream);
+
 /* ---- backward of the upsampler's tail: conv C -> 4C, PixelShuffle(2), conv C -> 3 (reference model/basic.py:56-60), as the backward
  * of one virtual 3 x 3 conv V from C to 64 channels (48 used) at the resolution of the tail's input h [N][H][W][C]
  * (docs/experiments/upsample_tail.md has the algebra).  w2 OIHW [4C][C][3][3], b2 [4C], w4 OIHW [3][C][3][3], all fp32; C % 16 == 0,

@@ -137,6 +137,8 @@ SIGNATURES.update({
     "pesr_conv3x3_c1_fwd": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, _P]),
     "pesr_conv3x3_c1_dgrad": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, _P]),
     "pesr_conv3x3_c1_wgrad": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_float, _P, c_size_t, _P]),
+    "pesr_window_attention_fwd": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, _P]),
+    "pesr_window_attention_bwd": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P]),
     "pesr_upsample_tail_gather":(c_int, [_P, _P, c_int, c_int, c_int, _P]),
     "pesr_upsample_tail_compose": (c_int, [_P, _P, _P, c_int, _P]),
     "pesr_upsample_tail_chain": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, _P]),

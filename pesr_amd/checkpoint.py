@@ -2,7 +2,7 @@
 stopped.  The reference keeps torch.save(G.state_dict()) alone ("no true resume"); this is an extension.
 
 One torch.save dict (schema in INTEGRATION.md):
-  format, flags {phase, scale, num_channels, num_blocks, spectral_norm, ema, attention, d_arch}, epoch, best_psnr, G, D, optim_G, optim_D,
+  format, flags {phase, scale, num_channels, num_blocks, spectral_norm, ema, attention, d_arch, wattn}, epoch, best_psnr, G, D, optim_G, optim_D,
   scheduler_G, scheduler_D, dp {policy, transport}, world, rng [one entry per rank].
 The file is written next to its final name and moved over it, so a run killed while writing leaves the previous file whole.
 """
@@ -17,9 +17,9 @@ import torch
 FORMAT = 1
 STATE_NAME = "train_state.pt"
 # the flags that decide the tensors' shapes and meaning: a state loads only into a run that agrees on all of them
-SHAPE_FLAGS = ("phase", "scale", "num_channels", "num_blocks", "spectral_norm", "ema", "attention", "d_arch")
+SHAPE_FLAGS = ("phase", "scale", "num_channels", "num_blocks", "spectral_norm", "ema", "attention", "d_arch", "wattn")
 # flags that joined later, with what a state written before them stands for (FORMAT stays 1: such a state still loads)
-_LATER_FLAGS = {"attention": 0, "d_arch": "vgg"}
+_LATER_FLAGS = {"attention": 0, "d_arch": "vgg", "wattn": 0}
 
 
 def state_path(check_point: str, phase: str) -> str:
@@ -45,7 +45,14 @@ def shape_flags(args) -> dict:
             # the reduction of the Generator's channel attention, 0 = none (docs/modes.md section 4u)
             "attention": args.ca_reduction if getattr(args, "attention", "none") == "ca" else 0,
             # the Discriminator's kind (docs/modes.md section 4v); the pretrain phase has none and always says "vgg"
-            "d_arch": getattr(args, "d_arch", "vgg") if args.phase != "pretrain" else "vgg"}
+            "d_arch": getattr(args, "d_arch", "vgg") if args.phase != "pretrain" else "vgg",
+            # the Generator's window-attention blocks (docs/modes.md section 4w): (--wattn_every, their width), 0 = none
+            "wattn": wattn_flag(args)}
+
+
+def wattn_flag(args):
+    every = getattr(args, "wattn_every", 0)
+    return (every, getattr(args, "wattn_dim", 0) or args.num_channels // 2) if every > 0 else 0
 
 
 def check_flags(state: dict, args, path: str = "") -> None:
@@ -56,7 +63,8 @@ def check_flags(state: dict, args, path: str = "") -> None:
     for k in SHAPE_FLAGS:
         theirs = state["flags"][k] if k not in _LATER_FLAGS else state["flags"].get(k, _LATER_FLAGS[k])
         if theirs != mine[k]:
-            flag = {"ema": "--ema_decay > 0", "attention": "--attention / --ca_reduction (the reduction, 0 = none)"}.get(k, "--" + k)
+            flag = {"ema": "--ema_decay > 0", "attention": "--attention / --ca_reduction (the reduction, 0 = none)",
+                    "wattn": "--wattn_every / --wattn_dim (the period and the width, 0 = none)"}.get(k, "--" + k)
             raise SystemExit(f"train.py: --resume {path}: the state was saved with {flag} = {theirs!r}, this run has {mine[k]!r}")
 
 

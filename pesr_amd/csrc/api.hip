@@ -528,6 +528,14 @@ PESR_API int pesr_conv3x3_c1_wgrad(const float* x, const float* dy, float* dw, f
     return pesr_conv3x3_c1_wgrad_launch(x, dy, dw, db, N, H, W, C, alpha, workspace, ws_bytes, (hipStream_t)stream);
 }
 
+PESR_API int pesr_window_attention_fwd(const float* qkv, float* out, int N, int H, int W, int D, int shift, void* stream) {
+    return pesr_window_attention_fwd_launch(qkv, out, N, H, W, D, shift, (hipStream_t)stream);
+}
+PESR_API int pesr_window_attention_bwd(const float* qkv, const float* dout, float* dqkv, int N, int H, int W, int D, int shift,
+                                       void* stream) {
+    return pesr_window_attention_bwd_launch(qkv, dout, dqkv, N, H, W, D, shift, (hipStream_t)stream);
+}
+
 PESR_API int pesr_upsample_tail_gather(const float* g, float* gw, int N, int H, int W, void* stream) {
     return pesr_upsample_tail_gather_launch(g, gw, N, H, W, (hipStream_t)stream);
 }

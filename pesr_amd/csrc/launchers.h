@@ -307,6 +307,11 @@ int pesr_conv3x3_c1_dgrad_launch(const float* dy, const float* w, float* dx, int
 int pesr_conv3x3_c1_wgrad_launch(const float* x, const float* dy, float* dw, float* db, int N, int H, int W, int C, float alpha, void* ws,
                                  size_t ws_bytes, hipStream_t stream);
 
+// window self-attention of the Generator's attention blocks (window_attention.hip): 8 x 8 windows, heads of 32 channels
+int pesr_window_attention_fwd_launch(const float* qkv, float* out, int N, int H, int W, int D, int shift, hipStream_t stream);
+int pesr_window_attention_bwd_launch(const float* qkv, const float* dout, float* dqkv, int N, int H, int W, int D, int shift,
+                                     hipStream_t stream);
+
 // backward of the upsampler's tail (conv C -> 4C, PixelShuffle(2), conv C -> 3) as one virtual C -> 64 conv (upsample_tail.hip)
 int pesr_upsample_tail_gather_launch(const float* g, float* gw, int N, int H, int W, hipStream_t stream);
 int pesr_upsample_tail_compose_launch(const float* w2, const float* w4, float* weff, int C, hipStream_t stream);

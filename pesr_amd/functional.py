@@ -799,6 +799,23 @@ class ChannelAttentionFn(Function):
         return (gy if ctx.needs_input_grad[0] else None), gt, dw1, db1, dw2, db2, None
 
 
+class WindowAttentionFn(Function):
+    """out = softmax(q k^T / sqrt(32)) v per 8 x 8 window and head of 32 channels (docs/modes.md section 4w); qkv: NHWC [N, H, W, 3 D].
+    Saves qkv alone: the backward recomputes the attention matrix.  fp32 kernels whatever ops.PRECISION is."""
+
+    @staticmethod
+    def forward(ctx, qkv, shift):
+        qkv = _c(qkv)
+        ctx.shift = shift
+        ctx.save_for_backward(qkv)
+        return ops.window_attention_fwd(qkv, shift)
+
+    @staticmethod
+    def backward(ctx, gout):
+        qkv, = ctx.saved_tensors
+        return ops.window_attention_bwd(qkv, _c(gout), ctx.shift), None
+
+
 class BilinearUp2Fn(Function):
     """y = up2(a + b), b optional: bilinear x2 (F.interpolate(scale_factor=2, mode='bilinear', align_corners=False)) of an NHWC map, the
     decoder step of the U-Net discriminator with the skip addition in front of it folded in (docs/modes.md section 4v).  up2 is linear:

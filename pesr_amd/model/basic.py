@@ -246,6 +246,32 @@ class ChannelAttention(nn.Module):
         return f"{self.n_feats}, reduction={self.reduction}"
 
 
+class WindowAttention(nn.Module):
+    """A window self-attention block (an extension, docs/modes.md section 4w; the Swin / SwinIR form with conv projections as in CvT):
+    forward(x) = x + proj(attention(qkv(x))).  qkv = Conv(n_feats, 3 dim, 3) gives q | k | v with heads of 32 channels, the attention
+    runs inside 8 x 8 windows of a grid whose origin is (-shift, -shift) over the pixels inside the image, proj = Conv(dim, n_feats, 3)
+    carries the skip addition in its epilogue.  The two convs are constructed in that order and initialised like every Conv; they run
+    on the routed 3 x 3 kernels (and follow --precision), the attention itself is fp32."""
+
+    def __init__(self, n_feats, dim, shift=0):
+        super().__init__()
+        ops.wattn_check_widths("WindowAttention", n_feats, dim)
+        if shift not in range(ops.WATTN_WINDOW):
+            raise ValueError(f"WindowAttention: shift = {shift!r}; expected 0 .. {ops.WATTN_WINDOW - 1}")
+        self.qkv = Conv(n_feats, 3 * dim, 3)
+        self.proj = Conv(dim, n_feats, 3)
+        self.n_feats, self.dim, self.shift = n_feats, dim, shift
+
+    def forward(self, x):
+        h = nhwc(x)
+        u = PF.conv3x3(h, self.qkv.weight, self.qkv.bias, self.qkv.packed)
+        o = PF.WindowAttentionFn.apply(u, self.shift)
+        return nchw(PF.ConvAddFn.apply(o, h, self.proj.weight, self.proj.bias, self.proj.packed))
+
+    def extra_repr(self):
+        return f"{self.n_feats}, dim={self.dim}, shift={self.shift}"
+
+
 class ResBlock(nn.Module):
     """x + res_scale * conv(act(conv(x))) (reference model/basic.py:33-52).  The reference's only configuration (bias, no BN,
     ReLU) is one fused autograd node; the other constructor branches (bn=True, bias=False, LeakyReLU) run un-fused on the

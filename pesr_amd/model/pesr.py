@@ -8,7 +8,7 @@ import torch.nn as nn
 
 from .. import functional as PF
 from .. import ops
-from .basic import SCALES, BasicBlock, Conv, MeanShift, ResBlock, Upsampler, nchw, nhwc, spectral_norm
+from .basic import SCALES, BasicBlock, Conv, MeanShift, ResBlock, Upsampler, WindowAttention, nchw, nhwc, spectral_norm
 
 _DIV2K_MEAN = (0.4488, 0.4371, 0.4040)      # reference model/pesr.py:13
 _UNIT_STD = (1.0, 1.0, 1.0)
@@ -54,6 +54,34 @@ def attention_of_state_dict(sd):
     return w.shape[1] // w.shape[0]
 
 
+def wattn_positions(every, depth):
+    """The body blocks that a window-attention block follows with --wattn_every E: E - 1, 2 E - 1, ... below depth."""
+    return tuple(range(every - 1, depth, every)) if every > 0 else ()
+
+
+def wattn_of_state_dict(sd):
+    """-> (positions, dim) of a Generator state_dict's window-attention blocks (docs/modes.md section 4w): the indices of the body
+    blocks they follow, ascending, and their attention width; ((), 0) for one without.  Read from the `wattn.<i>.qkv.weight` [3 dim,
+    C, 3, 3] and `wattn.<i>.proj.weight` [C, dim, 3, 3]; ValueError where these are no such weights."""
+    prefix = "module." if any(k.startswith("module.") for k in sd) else ""
+    head = prefix + "wattn."
+    positions = sorted({k[len(head):].split(".")[0] for k in sd if k.startswith(head)}, key=lambda i: (len(i), i))
+    if not positions:
+        return (), 0
+    dims = set()
+    for i in positions:
+        qkv, proj = sd.get(f"{head}{i}.qkv.weight"), sd.get(f"{head}{i}.proj.weight")
+        if not i.isdigit() or qkv is None or proj is None or qkv.dim() != 4 or proj.dim() != 4 or qkv.shape[0] % 3 \
+                or tuple(qkv.shape[2:]) != (3, 3) or tuple(proj.shape) != (qkv.shape[1], qkv.shape[0] // 3, 3, 3):
+            raise ValueError(f"window attention of unknown shape: wattn.{i}.qkv.weight "
+                             f"{None if qkv is None else tuple(qkv.shape)}, wattn.{i}.proj.weight "
+                             f"{None if proj is None else tuple(proj.shape)}")
+        dims.add(qkv.shape[0] // 3)
+    if len(dims) != 1:
+        raise ValueError(f"window attention of unknown shape: blocks of different widths {sorted(dims)}")
+    return tuple(int(i) for i in positions), dims.pop()
+
+
 class Generator(nn.Module):
     def __init__(self, opt):
         super().__init__()
@@ -73,12 +101,24 @@ class Generator(nn.Module):
         self.body = nn.Sequential(*trunk)
         self.upsample = Upsampler(width, scale)
         self.add_mean = MeanShift(255, _DIV2K_MEAN, _UNIT_STD, 1)
+        # an extension: a window self-attention block after every wattn_every-th residual block (docs/modes.md section 4w), keyed by the
+        # index of that block, shifted by half a window at every second one.  Constructed and registered after everything else: every
+        # other parameter keeps its initial value and its key.  Absent or 0 = nothing is built.
+        every, dim = opt.get('wattn_every', 0) or 0, opt.get('wattn_dim') or width // 2
+        if every < 0 or every > depth:
+            raise ValueError(f"Generator: wattn_every = {every}; expected 0 (off) .. depth = {depth}")
+        if every:
+            self.wattn = nn.ModuleDict({str(i): WindowAttention(width, dim, shift=4 * (j % 2))
+                                        for j, i in enumerate(wattn_positions(every, depth))})
 
     def forward(self, x):
         feat = self.embed(self.sub_mean(x))
         h = feat
-        for block in self.body[:-1]:
+        wattn = getattr(self, "wattn", None)
+        for i, block in enumerate(self.body[:-1]):
             h = block(h)
+            if wattn is not None and str(i) in wattn:
+                h = wattn[str(i)](h)
         last = self.body[-1]
         # trunk tail conv and the global skip (`res += x`, reference model/pesr.py:32-33) in one kernel
         h = nchw(PF.ConvAddFn.apply(nhwc(h), nhwc(feat), last.weight, last.bias, last.packed))

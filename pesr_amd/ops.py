@@ -1623,6 +1623,66 @@ def conv3x3_c1_wgrad(x: torch.Tensor, dy: torch.Tensor, alpha: float = 1.0, want
 
 
 # ------------------------------------------------------------------------------------------------
+# window self-attention of the Generator's attention blocks (docs/modes.md section 4w; pesr_amd/csrc/window_attention.hip).  fp32
+# whatever PRECISION is.
+# ------------------------------------------------------------------------------------------------
+WATTN_WINDOW = 8          # pixels per window side
+WATTN_HEAD = 32           # channels per head; tau = 1 / sqrt(WATTN_HEAD) is the kernels'
+WATTN_MAX_DIM = 1024      # the kernels' cap on the attention width
+
+
+def routed_3x3_width_ok(c: int) -> bool:
+    """A channel count that the routed 3 x 3 path takes on either side of a conv in all three passes: the forward wants Cin % 16 == 0
+    (it pads Cout to its tile itself), the input gradient is the same kernel with the two exchanged, so Cout % 16 == 0; the weight
+    gradient wants multiples of 4 (tests/test_window_attention_cpu.py asks the library)."""
+    return c >= 16 and c % 16 == 0
+
+
+def wattn_check_widths(what: str, n_feats: int, dim: int) -> int:
+    """-> the heads of an attention block of width dim on n_feats features; ValueError naming the argument that cannot be taken.  (A
+    multiple of 32 and its threefold are multiples of 16: every legal dim suits the projections n_feats -> 3 dim and dim -> n_feats.)"""
+    if dim < WATTN_HEAD or dim % WATTN_HEAD or dim > WATTN_MAX_DIM:
+        raise ValueError(f"{what}: dim = {dim}; the attention width has to be a multiple of {WATTN_HEAD} (the head width) from "
+                         f"{WATTN_HEAD} to {WATTN_MAX_DIM}")
+    if not routed_3x3_width_ok(n_feats):
+        raise ValueError(f"{what}: n_feats = {n_feats}; the 3 x 3 conv kernels take the block's projections forward and backward only "
+                         f"where n_feats is a multiple of 16")
+    return dim // WATTN_HEAD
+
+
+def _wattn_shape(what: str, qkv: torch.Tensor, shift: int):
+    _chk(qkv, what)
+    if qkv.dim() != 4 or min(qkv.shape) < 1 or qkv.shape[3] % (3 * WATTN_HEAD) or qkv.shape[3] > 3 * WATTN_MAX_DIM:
+        raise ValueError(f"{what}: expected [N, H, W, 3 D] with D a multiple of {WATTN_HEAD} up to {WATTN_MAX_DIM}, got {tuple(qkv.shape)}")
+    if not 0 <= shift < WATTN_WINDOW:
+        raise ValueError(f"{what}: shift = {shift}; expected 0 .. {WATTN_WINDOW - 1}")
+    N, H, W, D3 = qkv.shape
+    return N, H, W, D3 // 3
+
+
+def window_attention_fwd(qkv: torch.Tensor, shift: int = 0) -> torch.Tensor:
+    """qkv: NHWC [N, H, W, 3 D] (q | k | v, heads of 32 channels) -> out [N, H, W, D]: softmax(q k^T / sqrt(32)) v per 8 x 8 window of the
+    grid with its origin at (-shift, -shift) and per head, over the window's pixels inside the image."""
+    N, H, W, D = _wattn_shape("window_attention_fwd.qkv", qkv, shift)
+    out = torch.empty((N, H, W, D), dtype=torch.float32, device=qkv.device)
+    _lib.check(_lib.lib().pesr_window_attention_fwd(_p(qkv), _p(out), N, H, W, D, int(shift), _stream()), "pesr_window_attention_fwd")
+    return out
+
+
+def window_attention_bwd(qkv: torch.Tensor, dout: torch.Tensor, shift: int = 0) -> torch.Tensor:
+    """-> dqkv [N, H, W, 3 D], the gradient of window_attention_fwd's input for the gradient dout [N, H, W, D] of its output (the attention
+    matrix is recomputed from qkv)."""
+    N, H, W, D = _wattn_shape("window_attention_bwd.qkv", qkv, shift)
+    _chk(dout, "window_attention_bwd.dout")
+    if tuple(dout.shape) != (N, H, W, D):
+        raise ValueError(f"window_attention_bwd.dout: expected {(N, H, W, D)}, got {tuple(dout.shape)}")
+    dqkv = torch.empty_like(qkv)
+    _lib.check(_lib.lib().pesr_window_attention_bwd(_p(qkv), _p(dout), _p(dqkv), N, H, W, D, int(shift), _stream()),
+               "pesr_window_attention_bwd")
+    return dqkv
+
+
+# ------------------------------------------------------------------------------------------------
 # texture loss: patch-wise Gram matrices (docs/modes.md section 4q)
 # ------------------------------------------------------------------------------------------------
 GRAM_CHANNELS = (64, 128, 256)

@@ -105,11 +105,16 @@ def tiled_forward(model: Callable, img: torch.Tensor, scale: int, core: int, hal
     return (out_f[None] if f32 else None), out_u
 
 
-def describe(core: int, halo: int, exact: int, attention: bool = False) -> str:
+def describe(core: int, halo: int, exact: int, attention: bool = False, wattn: bool = False) -> str:
     """The line the entry points print once per run: tile shape, halo, the exact halo, and whether the results are the whole-image
     forward or an approximation of it.  (Facts of the run only: the number of tiles differs from image to image.)  attention: the
     Generator pools every block's features over whatever it is given (docs/modes.md section 4u) - a tile's mean is not the image's,
-    so no halo is exact."""
+    so no halo is exact.  wattn: the Generator has window-attention blocks (docs/modes.md section 4w), whose window grid starts at the
+    tile's corner and not at the image's - one more sentence says so."""
+    if wattn:
+        return describe(core, halo, exact, attention) + \
+            "; with the Generator's window-attention blocks an APPROXIMATION at every halo (their 8 x 8 window grid starts at the " \
+            "tile, not at the image)"
     side = core + 2 * halo
     if attention:
         return f"Tiled: tiles of {side} x {side} (an image shorter than that on an axis is taken whole along it), core {core}, halo " \

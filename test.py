@@ -155,21 +155,36 @@ def check_checkpoint_scale(sd, scale, path):
 
 
 def load_generator(opt, path, scale):
-    """The Generator of a checkpoint: its width, depth and scale are the flags', its channel attention (docs/modes.md section 4u) is
-    read from the checkpoint itself."""
+    """The Generator of a checkpoint: its width, depth and scale are the flags', its channel attention (docs/modes.md section 4u) and its
+    window-attention blocks (section 4w) are read from the checkpoint itself."""
     from model import Generator
-    from pesr_amd.model import attention_of_state_dict
+    from pesr_amd.model import attention_of_state_dict, wattn_of_state_dict
     sd = check_checkpoint_scale(torch.load(path, map_location="cpu"), scale, path)
     try:
         reduction = attention_of_state_dict(sd)
+        positions, wattn_dim = wattn_of_state_dict(sd)
     except ValueError as e:
         raise SystemExit(f"test.py: {path}: {e}")
     if reduction:
         opt = dict(opt, attention="ca", ca_reduction=reduction)
+    if positions:
+        # (Generator puts a block after every E-th residual block: the first one's index says E, and the others have to follow from it)
+        from pesr_amd.model.pesr import wattn_positions
+        every = positions[0] + 1
+        if wattn_positions(every, opt["depth"]) != positions:
+            raise SystemExit(f"test.py: {path}: its window-attention blocks follow the residual blocks {list(positions)}; a Generator of "
+                             f"--num_blocks {opt['depth']} has them after {list(wattn_positions(every, opt['depth']))} (every "
+                             f"{every}-th block) or not at all")
+        opt = dict(opt, wattn_every=every, wattn_dim=wattn_dim)
+    if reduction or positions:
         sd = {(k[len("module."):] if k.startswith("module.") else k): v for k, v in sd.items()}     # (saved from an nn.DataParallel)
     model = Generator(dict(opt, scale=scale))
     model.load_state_dict(sd)
     return model
+
+
+def has_wattn(*models):
+    return any(getattr(m, "wattn", None) is not None for m in models)
 
 
 def has_attention(*models):
@@ -282,7 +297,7 @@ def main(argv=None):
     rows = []           # per image: the scores of what was saved and, with --from_hr, of the bicubic baseline
     if args.tile:
         print(_tile.describe(args.tile, tile_halo, _tile.receptive_halo(args.num_blocks, args.scale),
-                             attention=has_attention(model, model_psnr)))
+                             attention=has_attention(model, model_psnr), wattn=has_wattn(model, model_psnr)))
     with torch.no_grad():
         for i, lr_path in enumerate(lr_paths):
             if args.from_hr:

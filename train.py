@@ -59,6 +59,12 @@ def build_parser():
                         "block of the Generator (docs/modes.md section 4u); none (default): the reference's blocks")
     p.add_argument("--ca_reduction", type=int, default=16,
                    help="with --attention ca: the gate's hidden width is --num_channels / this; it has to divide --num_channels")
+    p.add_argument("--wattn_every", type=int, default=0,
+                   help="E > 0: a window self-attention block (8 x 8 windows, heads of 32 channels, shifted by half a window at every "
+                        "second block; docs/modes.md section 4w) after every E-th residual block of the Generator; 0 (default): none")
+    p.add_argument("--wattn_dim", type=int, default=0,
+                   help="with --wattn_every: the attention width, a multiple of 32 (the head width) up to 1024; 0 (default): "
+                        "--num_channels / 2")
     p.add_argument("--d_arch", type=str, default="vgg", choices=["vgg", "unet"],
                    help="unet: a U-Net discriminator with one logit per pixel (Real-ESRGAN's, with 3 x 3 stride-2 convs; docs/modes.md "
                         "section 4v), independent of --patch_size; vgg (default): the reference's Discriminator.  Unused in --phase pretrain")
@@ -395,6 +401,45 @@ def d_arch_of(args):
     return args.d_arch
 
 
+def wattn_of(args):
+    """--wattn_every / --wattn_dim -> (E, D) of the Generator's window-attention blocks, (0, 0) for none; SystemExit naming the flag.
+    No GPU is touched."""
+    from pesr_amd import ops as _ops
+    if args.wattn_every < 0:
+        raise SystemExit(f"train.py: --wattn_every {args.wattn_every} must be 0 (off) or positive")
+    if args.wattn_dim < 0:
+        raise SystemExit(f"train.py: --wattn_dim {args.wattn_dim} must be 0 (--num_channels / 2) or a positive multiple of 32")
+    if args.wattn_every == 0:
+        return 0, 0
+    if args.wattn_every > args.num_blocks:
+        raise SystemExit(f"train.py: --wattn_every {args.wattn_every} is above --num_blocks {args.num_blocks}: it would add no block")
+    dim = args.wattn_dim or args.num_channels // 2
+    try:
+        _ops.wattn_check_widths("train.py", args.num_channels, dim)
+    except ValueError as e:
+        flag = "--num_channels" if str(e).startswith("train.py: n_feats") else "--wattn_dim" + ("" if args.wattn_dim else " (0: --num_channels / 2)")
+        raise SystemExit(f"train.py: {flag} with --wattn_every {args.wattn_every}: {e}")
+    return args.wattn_every, dim
+
+
+def check_pretrained_wattn(sd, args, path):
+    """A --pretrained_model whose window-attention blocks are not this run's: SystemExit naming both."""
+    from pesr_amd.model import wattn_of_state_dict
+    from pesr_amd.model.pesr import wattn_positions
+    try:
+        found = wattn_of_state_dict(sd)
+    except ValueError as e:
+        raise SystemExit(f"train.py: --pretrained_model {path}: {e}")
+    every, dim = wattn_of(args)
+    mine = (wattn_positions(every, args.num_blocks), dim)
+    if found != mine:
+        say = lambda w: f"window-attention blocks of width {w[1]} after the residual blocks {list(w[0])}" if w[0] else \
+            "no window-attention blocks"
+        raise SystemExit(f"train.py: --pretrained_model {path} has {say(found)}, this run (--wattn_every {args.wattn_every} --wattn_dim "
+                         f"{args.wattn_dim}) has {say(mine)}")
+    return sd
+
+
 def check_pretrained_attention(sd, args, path):
     """A --pretrained_model whose channel attention is not this run's: SystemExit naming both (instead of load_state_dict's key dump)."""
     from pesr_amd.model import attention_of_state_dict
@@ -480,6 +525,7 @@ def main(argv=None):
     args = build_parser().parse_args(argv)
     degradation_spec(args)      # (refuses a classical run without its companion flags before anything else starts)
     attention = attention_of(args)
+    wattn_every, wattn_dim = wattn_of(args)
     d_arch = d_arch_of(args)
     scorer = scorer_of(args)
     loss_terms = loss_terms_of(args, scorer.lpips_model)
@@ -514,7 +560,8 @@ def main(argv=None):
     from pesr_amd.tile import describe, receptive_halo, tiled_forward
     valid_halo = receptive_halo(args.num_blocks, args.scale) if args.valid_tile_halo == -1 else args.valid_tile_halo
     if args.valid_tile and rank == 0:
-        print(describe(args.valid_tile, valid_halo, receptive_halo(args.num_blocks, args.scale), attention=bool(attention)))
+        print(describe(args.valid_tile, valid_halo, receptive_halo(args.num_blocks, args.scale), attention=bool(attention),
+                       wattn=bool(wattn_every)))
 
     gpu_pipe = args.gpu_pipeline and not args.synthetic
     train_loader, val_loader, sampler = make_loaders(args, rank, world, need_train=not gpu_pipe, device=device)
@@ -524,6 +571,8 @@ def main(argv=None):
            "res_scale": args.res_scale, "spectral_norm": args.spectral_norm, "scale": args.scale}
     if attention:
         opt.update(attention="ca", ca_reduction=attention)
+    if wattn_every:
+        opt.update(wattn_every=wattn_every, wattn_dim=wattn_dim)
     from pesr_amd import checkpoint
     resume_path = checkpoint.resolve_resume(args.resume, args.check_point, args.phase)
     state = None
@@ -534,7 +583,8 @@ def main(argv=None):
         print("resume: no %s yet, starting fresh" % checkpoint.state_path(args.check_point, args.phase))
     G = Generator(opt)
     if args.pretrained_model and state is None:
-        G.load_state_dict(check_pretrained_attention(torch.load(args.pretrained_model, map_location="cpu"), args, args.pretrained_model))
+        sd = check_pretrained_attention(torch.load(args.pretrained_model, map_location="cpu"), args, args.pretrained_model)
+        G.load_state_dict(check_pretrained_wattn(sd, args, args.pretrained_model))
     G = G.to(device)
     gan = args.phase != "pretrain"
     from model import build_discriminator
