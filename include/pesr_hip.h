@@ -594,6 +594,24 @@ int pesr_conv3x3_c1_wgrad(const float* x, const float* dy, float* dw, float* db,
 int pesr_window_attention_fwd(const float* qkv, float* out, int N, int H, int W, int D, int shift, void* stream);
 int pesr_window_attention_bwd(const float* qkv, const float* dout, float* dqkv, int N, int H, int W, int D, int shift, void* stream);
 
+/* ---- LayerNorm over the channels of each pixel, in front of the window attention (docs/modes.md section 4x) ------------------------- */
+/* x fp32 [P][C] (the P = N H W pixels of an NHWC tensor), gamma, beta [C].  Per pixel: mean = (1/C) sum_c x, var = (1/C) sum_c
+ * (x - mean)^2 (centred, from the values held in registers), rstd = 1 / sqrt(var + eps), xh = (x - mean) rstd, y = xh gamma + beta;
+ * stats [P][2] = (mean, rstd) is what the backward keeps.
+ * backward: g = dy gamma, dx = rstd (g - mean_c(g) - xh mean_c(g xh)), dgamma_c = sum_p dy xh, dbeta_c = sum_p dy.  The channel sums
+ * leave one row per workgroup in workspace [pesr_layernorm_partials(P, C)][2 C] (pesr_layernorm_workspace_bytes), added in double in
+ * row order by a second launch of the same call.  dx, dgamma and dbeta are written exactly once, no zero-fill needed; no atomics,
+ * fixed summation orders: the same bits on every call.  The number of workgroups and rows depends on (P, C) alone; 64-bit element
+ * offsets.  pesr_layernorm_partials / _workspace_bytes are host-only and return 0 for a shape the kernels do not take.
+ * PESR_EINVAL with nothing launched (checked before any device call): C no multiple of 4 from 4 to 1024, P < 1, eps not positive and
+ * finite, a NULL pointer or one off a 16-byte boundary (stats and workspace included). */
+int pesr_layernorm_partials(long P, int C);
+size_t pesr_layernorm_workspace_bytes(long P, int C);
+int pesr_layernorm_fwd(const float* x, const float* gamma, const float* beta, float* y, float* stats, long P, int C, float eps,
+                       void* stream);
+int pesr_layernorm_bwd(const float* x, const float* gamma, const float* stats, const float* dy, float* dx, float* dgamma, float* dbeta,
+                       void* workspace, long P, int C, void* stream);
+
 /* ---- backward of the upsampler's tail: conv C -> 4C, PixelShuffle(2), conv C -> 3 (reference model/basic.py:56-60), as the backward
  * of one virtual 3 x 3 conv V from C to 64 channels (48 used) at the resolution of the tail's input h [N][H][W][C]
  * (docs/experiments/upsample_tail.md has the algebra).  w2 OIHW [4C][C][3][3], b2 [4C], w4 OIHW [3][C][3][3], all fp32; C % 16 == 0,

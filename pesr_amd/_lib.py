@@ -139,6 +139,10 @@ SIGNATURES.update({
     "pesr_conv3x3_c1_wgrad": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int, c_float, _P, c_size_t, _P]),
     "pesr_window_attention_fwd": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, _P]),
     "pesr_window_attention_bwd": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, _P]),
+    "pesr_layernorm_partials": (c_int, [c_long, c_int]),
+    "pesr_layernorm_workspace_bytes": (c_size_t, [c_long, c_int]),
+    "pesr_layernorm_fwd": (c_int, [_P, _P, _P, _P, _P, c_long, c_int, c_float, _P]),
+    "pesr_layernorm_bwd": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, c_long, c_int, _P]),
     "pesr_upsample_tail_gather":(c_int, [_P, _P, c_int, c_int, c_int, _P]),
     "pesr_upsample_tail_compose": (c_int, [_P, _P, _P, c_int, _P]),
     "pesr_upsample_tail_chain": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, _P]),

@@ -2,7 +2,7 @@
 stopped.  The reference keeps torch.save(G.state_dict()) alone ("no true resume"); this is an extension.
 
 One torch.save dict (schema in INTEGRATION.md):
-  format, flags {phase, scale, num_channels, num_blocks, spectral_norm, ema, attention, d_arch, wattn}, epoch, best_psnr, G, D, optim_G, optim_D,
+  format, flags {phase, scale, num_channels, num_blocks, spectral_norm, ema, attention, d_arch, wattn, wattn_norm}, epoch, best_psnr, G, D, optim_G, optim_D,
   scheduler_G, scheduler_D, dp {policy, transport}, world, rng [one entry per rank].
 The file is written next to its final name and moved over it, so a run killed while writing leaves the previous file whole.
 """
@@ -17,9 +17,9 @@ import torch
 FORMAT = 1
 STATE_NAME = "train_state.pt"
 # the flags that decide the tensors' shapes and meaning: a state loads only into a run that agrees on all of them
-SHAPE_FLAGS = ("phase", "scale", "num_channels", "num_blocks", "spectral_norm", "ema", "attention", "d_arch", "wattn")
+SHAPE_FLAGS = ("phase", "scale", "num_channels", "num_blocks", "spectral_norm", "ema", "attention", "d_arch", "wattn", "wattn_norm")
 # flags that joined later, with what a state written before them stands for (FORMAT stays 1: such a state still loads)
-_LATER_FLAGS = {"attention": 0, "d_arch": "vgg", "wattn": 0}
+_LATER_FLAGS = {"attention": 0, "d_arch": "vgg", "wattn": 0, "wattn_norm": "none"}
 
 
 def state_path(check_point: str, phase: str) -> str:
@@ -47,7 +47,9 @@ def shape_flags(args) -> dict:
             # the Discriminator's kind (docs/modes.md section 4v); the pretrain phase has none and always says "vgg"
             "d_arch": getattr(args, "d_arch", "vgg") if args.phase != "pretrain" else "vgg",
             # the Generator's window-attention blocks (docs/modes.md section 4w): (--wattn_every, their width), 0 = none
-            "wattn": wattn_flag(args)}
+            "wattn": wattn_flag(args),
+            # the normalisation in front of those blocks' qkv (docs/modes.md section 4x): "ln" or "none"
+            "wattn_norm": getattr(args, "wattn_norm", "none") or "none"}
 
 
 def wattn_flag(args):

@@ -536,6 +536,17 @@ PESR_API int pesr_window_attention_bwd(const float* qkv, const float* dout, floa
     return pesr_window_attention_bwd_launch(qkv, dout, dqkv, N, H, W, D, shift, (hipStream_t)stream);
 }
 
+PESR_API int pesr_layernorm_partials(long P, int C) { return pesr_layernorm_partials_of(P, C); }
+PESR_API size_t pesr_layernorm_workspace_bytes(long P, int C) { return pesr_layernorm_ws_bytes(P, C); }
+PESR_API int pesr_layernorm_fwd(const float* x, const float* gamma, const float* beta, float* y, float* stats, long P, int C, float eps,
+                                void* stream) {
+    return pesr_layernorm_fwd_launch(x, gamma, beta, y, stats, P, C, eps, (hipStream_t)stream);
+}
+PESR_API int pesr_layernorm_bwd(const float* x, const float* gamma, const float* stats, const float* dy, float* dx, float* dgamma,
+                                float* dbeta, void* workspace, long P, int C, void* stream) {
+    return pesr_layernorm_bwd_launch(x, gamma, stats, dy, dx, dgamma, dbeta, workspace, P, C, (hipStream_t)stream);
+}
+
 PESR_API int pesr_upsample_tail_gather(const float* g, float* gw, int N, int H, int W, void* stream) {
     return pesr_upsample_tail_gather_launch(g, gw, N, H, W, (hipStream_t)stream);
 }

@@ -312,6 +312,15 @@ int pesr_window_attention_fwd_launch(const float* qkv, float* out, int N, int H,
 int pesr_window_attention_bwd_launch(const float* qkv, const float* dout, float* dqkv, int N, int H, int W, int D, int shift,
                                      hipStream_t stream);
 
+// LayerNorm over the channels of each pixel (layernorm.hip), x [P][C], stats [P][2] = (mean, rstd); _partials_of: the workgroups of a
+// launch = the rows of the backward's [rows][2 C] workspace (0: a shape the kernels do not take)
+int pesr_layernorm_partials_of(long P, int C);
+size_t pesr_layernorm_ws_bytes(long P, int C);
+int pesr_layernorm_fwd_launch(const float* x, const float* gamma, const float* beta, float* y, float* stats, long P, int C, float eps,
+                              hipStream_t stream);
+int pesr_layernorm_bwd_launch(const float* x, const float* gamma, const float* stats, const float* dy, float* dx, float* dgamma,
+                              float* dbeta, void* ws, long P, int C, hipStream_t stream);
+
 // backward of the upsampler's tail (conv C -> 4C, PixelShuffle(2), conv C -> 3) as one virtual C -> 64 conv (upsample_tail.hip)
 int pesr_upsample_tail_gather_launch(const float* g, float* gw, int N, int H, int W, hipStream_t stream);
 int pesr_upsample_tail_compose_launch(const float* w2, const float* w4, float* weff, int C, hipStream_t stream);

@@ -816,6 +816,25 @@ class WindowAttentionFn(Function):
         return ops.window_attention_bwd(qkv, _c(gout), ctx.shift), None
 
 
+class LayerNormFn(Function):
+    """y = (x - mean) * rstd * gamma + beta over the channels of each pixel of an NHWC map (docs/modes.md section 4x), centred variance,
+    eps = ops.LN_EPS.  Saves x, gamma and the [P, 2] (mean, rstd) the forward leaves.  fp32 kernels whatever ops.PRECISION is."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta):
+        x = _c(x)
+        y, stats = ops.layernorm_fwd(x, gamma.detach(), beta.detach())
+        ctx.beta_ref = beta
+        ctx.save_for_backward(x, gamma, stats)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, gamma, stats = ctx.saved_tensors
+        dx, dgamma, dbeta = ops.layernorm_bwd(x, gamma.detach(), stats, _c(gy), grad_out(gamma), grad_out(ctx.beta_ref))
+        return (dx if ctx.needs_input_grad[0] else None), dgamma, dbeta
+
+
 class BilinearUp2Fn(Function):
     """y = up2(a + b), b optional: bilinear x2 (F.interpolate(scale_factor=2, mode='bilinear', align_corners=False)) of an NHWC map, the
     decoder step of the U-Net discriminator with the skip addition in front of it folded in (docs/modes.md section 4v).  up2 is linear:

@@ -5,11 +5,11 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .basic import BasicBlock, ChannelAttention, Conv, MeanShift, PixelShuffle, ResBlock, Upsampler, WindowAttention
+from .basic import BasicBlock, ChannelAttention, ChannelLayerNorm, Conv, MeanShift, PixelShuffle, ResBlock, Upsampler, WindowAttention
 from .focal_loss import FocalLoss
 from .pesr import Discriminator, Generator, UNetDiscriminator, attention_of_state_dict, build_discriminator, scale_of_state_dict, \
-    wattn_of_state_dict
+    wattn_norm_of_state_dict, wattn_of_state_dict
 from .vgg import VGG
 
-__all__ = ["Generator", "Discriminator", "UNetDiscriminator", "build_discriminator", "VGG", "FocalLoss", "Conv", "MeanShift", "BasicBlock", "ResBlock", "ChannelAttention", "WindowAttention",
-           "Upsampler", "PixelShuffle", "scale_of_state_dict", "attention_of_state_dict", "wattn_of_state_dict", "nn", "torch", "F"]
+__all__ = ["Generator", "Discriminator", "UNetDiscriminator", "build_discriminator", "VGG", "FocalLoss", "Conv", "MeanShift", "BasicBlock", "ResBlock", "ChannelAttention", "WindowAttention", "ChannelLayerNorm",
+           "Upsampler", "PixelShuffle", "scale_of_state_dict", "attention_of_state_dict", "wattn_of_state_dict", "wattn_norm_of_state_dict", "nn", "torch", "F"]

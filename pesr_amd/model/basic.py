@@ -246,30 +246,59 @@ class ChannelAttention(nn.Module):
         return f"{self.n_feats}, reduction={self.reduction}"
 
 
+class ChannelLayerNorm(nn.Module):
+    """LayerNorm over the channels of each pixel (an extension, docs/modes.md section 4x): per pixel of an NHWC map, y = (x - mean) /
+    sqrt(var + 1e-5) * weight + bias with the centred variance.  weight = 1, bias = 0: construction draws nothing from the RNG."""
+
+    def __init__(self, n_feats):
+        super().__init__()
+        ops.ln_check_channels("ChannelLayerNorm", n_feats)
+        self.weight = nn.Parameter(torch.ones(n_feats))
+        self.bias = nn.Parameter(torch.zeros(n_feats))
+        self.n_feats = n_feats
+
+    def forward_nhwc(self, h):
+        return PF.LayerNormFn.apply(h, self.weight, self.bias)
+
+    def forward(self, x):
+        return nchw(self.forward_nhwc(nhwc(x)))
+
+    def extra_repr(self):
+        return f"{self.n_feats}"
+
+
 class WindowAttention(nn.Module):
     """A window self-attention block (an extension, docs/modes.md section 4w; the Swin / SwinIR form with conv projections as in CvT):
     forward(x) = x + proj(attention(qkv(x))).  qkv = Conv(n_feats, 3 dim, 3) gives q | k | v with heads of 32 channels, the attention
     runs inside 8 x 8 windows of a grid whose origin is (-shift, -shift) over the pixels inside the image, proj = Conv(dim, n_feats, 3)
     carries the skip addition in its epilogue.  The two convs are constructed in that order and initialised like every Conv; they run
-    on the routed 3 x 3 kernels (and follow --precision), the attention itself is fp32."""
+    on the routed 3 x 3 kernels (and follow --precision), the attention itself is fp32.
+    norm="ln" (section 4x) puts a ChannelLayerNorm in front of qkv, the pre-norm of every Swin layer: forward(x) = x +
+    proj(attention(qkv(LN(x)))), the skip taking the un-normalised x.  It is registered after the two convs (their initial values and
+    keys are those of the block without it).  norm=None: no such module, what the block was."""
 
-    def __init__(self, n_feats, dim, shift=0):
+    def __init__(self, n_feats, dim, shift=0, norm=None):
         super().__init__()
         ops.wattn_check_widths("WindowAttention", n_feats, dim)
         if shift not in range(ops.WATTN_WINDOW):
             raise ValueError(f"WindowAttention: shift = {shift!r}; expected 0 .. {ops.WATTN_WINDOW - 1}")
+        if norm not in (None, "ln"):
+            raise ValueError(f"WindowAttention: norm = {norm!r}; expected None or 'ln'")
         self.qkv = Conv(n_feats, 3 * dim, 3)
         self.proj = Conv(dim, n_feats, 3)
+        if norm == "ln":
+            self.norm = ChannelLayerNorm(n_feats)
         self.n_feats, self.dim, self.shift = n_feats, dim, shift
 
     def forward(self, x):
         h = nhwc(x)
-        u = PF.conv3x3(h, self.qkv.weight, self.qkv.bias, self.qkv.packed)
+        norm = getattr(self, "norm", None)
+        u = PF.conv3x3(h if norm is None else norm.forward_nhwc(h), self.qkv.weight, self.qkv.bias, self.qkv.packed)
         o = PF.WindowAttentionFn.apply(u, self.shift)
         return nchw(PF.ConvAddFn.apply(o, h, self.proj.weight, self.proj.bias, self.proj.packed))
 
     def extra_repr(self):
-        return f"{self.n_feats}, dim={self.dim}, shift={self.shift}"
+        return f"{self.n_feats}, dim={self.dim}, shift={self.shift}" + (", norm=ln" if hasattr(self, "norm") else "")
 
 
 class ResBlock(nn.Module):

@@ -82,6 +82,28 @@ def wattn_of_state_dict(sd):
     return tuple(int(i) for i in positions), dims.pop()
 
 
+def wattn_norm_of_state_dict(sd):
+    """-> 'ln' where the window-attention blocks of a Generator state_dict carry a LayerNorm in front of qkv (docs/modes.md section 4x:
+    `wattn.<i>.norm.weight` and `.bias`, both [C]), 'none' where they do not (and where there are no blocks).  ValueError where some
+    blocks have one and others not, or where its tensors are not [C], C the blocks' input width."""
+    prefix = "module." if any(k.startswith("module.") for k in sd) else ""
+    head = prefix + "wattn."
+    positions = sorted({k[len(head):].split(".")[0] for k in sd if k.startswith(head)}, key=lambda i: (len(i), i))
+    with_norm = [i for i in positions if any(k.startswith(f"{head}{i}.norm.") for k in sd)]
+    if not with_norm:
+        return 'none'
+    if len(with_norm) != len(positions):
+        raise ValueError(f"window attention of unknown shape: the blocks {with_norm} have a norm, "
+                         f"{[i for i in positions if i not in with_norm]} have none")
+    for i in positions:
+        qkv, w, b = sd.get(f"{head}{i}.qkv.weight"), sd.get(f"{head}{i}.norm.weight"), sd.get(f"{head}{i}.norm.bias")
+        want = None if qkv is None or qkv.dim() != 4 else (qkv.shape[1],)
+        if w is None or b is None or want is None or tuple(w.shape) != want or tuple(b.shape) != want:
+            raise ValueError(f"window attention of unknown shape: wattn.{i}.norm.weight {None if w is None else tuple(w.shape)}, "
+                             f"wattn.{i}.norm.bias {None if b is None else tuple(b.shape)}; expected {want} for both")
+    return 'ln'
+
+
 class Generator(nn.Module):
     def __init__(self, opt):
         super().__init__()
@@ -107,8 +129,15 @@ class Generator(nn.Module):
         every, dim = opt.get('wattn_every', 0) or 0, opt.get('wattn_dim') or width // 2
         if every < 0 or every > depth:
             raise ValueError(f"Generator: wattn_every = {every}; expected 0 (off) .. depth = {depth}")
+        # an extension of that extension: a LayerNorm over each pixel's channels in front of every block's qkv (docs/modes.md section
+        # 4x); absent, None or 'none' = the blocks as they were.  It draws nothing from the RNG.
+        norm = opt.get('wattn_norm')
+        if norm not in (None, 'none', 'ln'):
+            raise ValueError(f"Generator: wattn_norm = {norm!r}; expected None, 'none' or 'ln'")
+        if norm == 'ln' and not every:
+            raise ValueError("Generator: wattn_norm = 'ln' without wattn_every: there is no window-attention block to normalise")
         if every:
-            self.wattn = nn.ModuleDict({str(i): WindowAttention(width, dim, shift=4 * (j % 2))
+            self.wattn = nn.ModuleDict({str(i): WindowAttention(width, dim, shift=4 * (j % 2), norm="ln" if norm == 'ln' else None)
                                         for j, i in enumerate(wattn_positions(every, depth))})
 
     def forward(self, x):

@@ -1683,6 +1683,86 @@ def window_attention_bwd(qkv: torch.Tensor, dout: torch.Tensor, shift: int = 0) 
 
 
 # ------------------------------------------------------------------------------------------------
+# LayerNorm over the channels of each pixel, in front of the window attention (docs/modes.md section 4x; pesr_amd/csrc/layernorm.hip).
+# fp32 whatever PRECISION is.
+# ------------------------------------------------------------------------------------------------
+LN_EPS = 1e-5
+LN_MAX_CHANNELS = 1024    # the kernels' cap on C
+_LN_LANES = 256           # of a workgroup
+
+
+def ln_check_channels(what: str, C: int) -> None:
+    if C < 4 or C % 4 or C > LN_MAX_CHANNELS:
+        raise ValueError(f"{what}: C = {C}; the LayerNorm kernels take a multiple of 4 from 4 to {LN_MAX_CHANNELS}")
+
+
+def layernorm_partials(P: int, C: int) -> int:
+    """The workgroups of a LayerNorm launch over P pixels of C channels = the partial rows of the backward's channel sums, combined in
+    ascending order (a host-only question; a function of the shape alone).  ValueError for a shape the kernels do not take."""
+    ln_check_channels("layernorm_partials", C)
+    if P < 1:
+        raise ValueError(f"layernorm_partials: P = {P}")
+    return _memo("pesr_layernorm_partials", P, C)
+
+
+def layernorm_pass_pixels(P: int, C: int) -> int:
+    """The pixels one step of the whole grid covers: with more than these a workgroup walks on (csrc/layernorm.hip: a group of G lanes per
+    pixel, G the power of two that covers C / 4 up to 64; 4, 2, 1, 1 pixels per group and step at 1, 2, 3, 4 pieces per lane)."""
+    group = 1
+    while group < C // 4 and group < 64:
+        group *= 2
+    pieces = (C // 4 + 63) // 64
+    return layernorm_partials(P, C) * (_LN_LANES // group) * (4, 2, 1, 1)[pieces - 1]
+
+
+def _ln_rows(what: str, x: torch.Tensor):
+    _chk(x, what)
+    if x.dim() < 2 or min(x.shape) < 1:
+        raise ValueError(f"{what}: expected [..., C] with at least one pixel, got {tuple(x.shape)}")
+    C = x.shape[-1]
+    ln_check_channels(what, C)
+    return x.numel() // C, C
+
+
+def _ln_vec(what: str, t: torch.Tensor, C: int) -> None:
+    _chk(t, what)
+    if tuple(t.shape) != (C,):
+        raise ValueError(f"{what}: expected {(C,)}, got {tuple(t.shape)}")
+
+
+def layernorm_fwd(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor):
+    """x: [..., C] (NHWC: every pixel on its own) -> (y, stats): y = (x - mean) * rstd * gamma + beta over the channels of each pixel
+    with the centred variance and eps = LN_EPS; stats [P, 2] = (mean, rstd) is what layernorm_bwd wants back."""
+    P, C = _ln_rows("layernorm_fwd.x", x)
+    _ln_vec("layernorm_fwd.gamma", gamma, C)
+    _ln_vec("layernorm_fwd.beta", beta, C)
+    y = torch.empty_like(x)
+    stats = torch.empty((P, 2), dtype=torch.float32, device=x.device)
+    _lib.check(_lib.lib().pesr_layernorm_fwd(_p(x), _p(gamma), _p(beta), _p(y), _p(stats), P, C, LN_EPS, _stream()), "pesr_layernorm_fwd")
+    return y, stats
+
+
+def layernorm_bwd(x: torch.Tensor, gamma: torch.Tensor, stats: torch.Tensor, dy: torch.Tensor, dgamma_out=None, dbeta_out=None):
+    """-> (dx, dgamma, dbeta) of layernorm_fwd for the gradient dy of its output; every element written once, the channel sums through
+    per-workgroup partial rows in the pooled workspace, added in double in a fixed order.  dgamma_out / dbeta_out: a parameter's
+    flat-gradient view to write into."""
+    P, C = _ln_rows("layernorm_bwd.x", x)
+    _ln_vec("layernorm_bwd.gamma", gamma, C)
+    _chk(stats, "layernorm_bwd.stats")
+    _chk(dy, "layernorm_bwd.dy")
+    if tuple(stats.shape) != (P, 2):
+        raise ValueError(f"layernorm_bwd.stats: expected {(P, 2)}, got {tuple(stats.shape)}")
+    if dy.shape != x.shape:
+        raise ValueError(f"layernorm_bwd.dy: expected {tuple(x.shape)}, got {tuple(dy.shape)}")
+    dx = torch.empty_like(x)
+    dgamma, dbeta = _out(dgamma_out, (C,), x.device), _out(dbeta_out, (C,), x.device)
+    ws = workspace(int(_lib.lib().pesr_layernorm_workspace_bytes(P, C)), x.device)
+    _lib.check(_lib.lib().pesr_layernorm_bwd(_p(x), _p(gamma), _p(stats), _p(dy), _p(dx), _p(dgamma), _p(dbeta), _p(ws), P, C, _stream()),
+               "pesr_layernorm_bwd")
+    return dx, dgamma, dbeta
+
+
+# ------------------------------------------------------------------------------------------------
 # texture loss: patch-wise Gram matrices (docs/modes.md section 4q)
 # ------------------------------------------------------------------------------------------------
 GRAM_CHANNELS = (64, 128, 256)

@@ -156,13 +156,14 @@ def check_checkpoint_scale(sd, scale, path):
 
 def load_generator(opt, path, scale):
     """The Generator of a checkpoint: its width, depth and scale are the flags', its channel attention (docs/modes.md section 4u) and its
-    window-attention blocks (section 4w) are read from the checkpoint itself."""
+    window-attention blocks (section 4w) with or without their LayerNorm (section 4x) are read from the checkpoint itself."""
     from model import Generator
-    from pesr_amd.model import attention_of_state_dict, wattn_of_state_dict
+    from pesr_amd.model import attention_of_state_dict, wattn_norm_of_state_dict, wattn_of_state_dict
     sd = check_checkpoint_scale(torch.load(path, map_location="cpu"), scale, path)
     try:
         reduction = attention_of_state_dict(sd)
         positions, wattn_dim = wattn_of_state_dict(sd)
+        wattn_norm = wattn_norm_of_state_dict(sd)
     except ValueError as e:
         raise SystemExit(f"test.py: {path}: {e}")
     if reduction:
@@ -175,7 +176,7 @@ def load_generator(opt, path, scale):
             raise SystemExit(f"test.py: {path}: its window-attention blocks follow the residual blocks {list(positions)}; a Generator of "
                              f"--num_blocks {opt['depth']} has them after {list(wattn_positions(every, opt['depth']))} (every "
                              f"{every}-th block) or not at all")
-        opt = dict(opt, wattn_every=every, wattn_dim=wattn_dim)
+        opt = dict(opt, wattn_every=every, wattn_dim=wattn_dim, wattn_norm=wattn_norm)
     if reduction or positions:
         sd = {(k[len("module."):] if k.startswith("module.") else k): v for k, v in sd.items()}     # (saved from an nn.DataParallel)
     model = Generator(dict(opt, scale=scale))

@@ -65,6 +65,10 @@ def build_parser():
     p.add_argument("--wattn_dim", type=int, default=0,
                    help="with --wattn_every: the attention width, a multiple of 32 (the head width) up to 1024; 0 (default): "
                         "--num_channels / 2")
+    p.add_argument("--wattn_norm", type=str, default="none", choices=["none", "ln"],
+                   help="with --wattn_every: ln puts a LayerNorm over each pixel's channels in front of every block's qkv (the pre-norm of a "
+                        "Swin layer; docs/modes.md section 4x), so that the attention does not start saturated; none (default): the "
+                        "blocks without it")
     p.add_argument("--d_arch", type=str, default="vgg", choices=["vgg", "unet"],
                    help="unet: a U-Net discriminator with one logit per pixel (Real-ESRGAN's, with 3 x 3 stride-2 convs; docs/modes.md "
                         "section 4v), independent of --patch_size; vgg (default): the reference's Discriminator.  Unused in --phase pretrain")
@@ -422,6 +426,26 @@ def wattn_of(args):
     return args.wattn_every, dim
 
 
+def wattn_norm_of(args):
+    """--wattn_norm -> 'ln' or None; SystemExit naming the flag where there is no block to normalise.  No GPU is touched."""
+    if args.wattn_norm == "ln" and args.wattn_every <= 0:
+        raise SystemExit("train.py: --wattn_norm ln needs --wattn_every E > 0: without window-attention blocks there is nothing to normalise")
+    return "ln" if args.wattn_norm == "ln" else None
+
+
+def check_pretrained_wattn_norm(sd, args, path):
+    """A --pretrained_model whose window-attention blocks have (or lack) the LayerNorm this run lacks (or has): SystemExit naming both."""
+    from pesr_amd.model import wattn_norm_of_state_dict
+    try:
+        found = wattn_norm_of_state_dict(sd)
+    except ValueError as e:
+        raise SystemExit(f"train.py: --pretrained_model {path}: {e}")
+    if found != args.wattn_norm:
+        raise SystemExit(f"train.py: --pretrained_model {path} has window-attention blocks with norm '{found}', this run has "
+                         f"--wattn_norm {args.wattn_norm}")
+    return sd
+
+
 def check_pretrained_wattn(sd, args, path):
     """A --pretrained_model whose window-attention blocks are not this run's: SystemExit naming both."""
     from pesr_amd.model import wattn_of_state_dict
@@ -526,6 +550,7 @@ def main(argv=None):
     degradation_spec(args)      # (refuses a classical run without its companion flags before anything else starts)
     attention = attention_of(args)
     wattn_every, wattn_dim = wattn_of(args)
+    wattn_norm = wattn_norm_of(args)
     d_arch = d_arch_of(args)
     scorer = scorer_of(args)
     loss_terms = loss_terms_of(args, scorer.lpips_model)
@@ -573,6 +598,8 @@ def main(argv=None):
         opt.update(attention="ca", ca_reduction=attention)
     if wattn_every:
         opt.update(wattn_every=wattn_every, wattn_dim=wattn_dim)
+    if wattn_norm:
+        opt.update(wattn_norm=wattn_norm)
     from pesr_amd import checkpoint
     resume_path = checkpoint.resolve_resume(args.resume, args.check_point, args.phase)
     state = None
@@ -584,7 +611,7 @@ def main(argv=None):
     G = Generator(opt)
     if args.pretrained_model and state is None:
         sd = check_pretrained_attention(torch.load(args.pretrained_model, map_location="cpu"), args, args.pretrained_model)
-        G.load_state_dict(check_pretrained_wattn(sd, args, args.pretrained_model))
+        G.load_state_dict(check_pretrained_wattn_norm(check_pretrained_wattn(sd, args, args.pretrained_model), args, args.pretrained_model))
     G = G.to(device)
     gan = args.phase != "pretrain"
     from model import build_discriminator
